@@ -4,19 +4,23 @@
 Default workload = BASELINE.json config C2: HDR merge + propagated uncertainty of a 32-exposure 4096x4096x3 uint16
 stack (LINEAR ICRF, Gaussian weights, sigma = 0.05 * x derived in-kernel), inputs resident in HBM.
 A "step" is one ct_hdr_merge_batch launch over the whole stack.  With --gpus N every rank merges its own C2-sized row
-band of a (4096*N) x 4096 global image (weak scaling, no data-path collective: pixels are independent); a small RCCL
-all_gather of per-band statistics runs once after the timed region.  `--scaling strong` is BASELINE config C5 as
-stated: ONE 8192x8192x3 image cut into N row bands of 8192/N rows, with the per-band statistics all_gather inside
+band of a (4096*N) x 4096 global image (weak scaling, no data-path collective: pixels are independent); with --full a
+small RCCL all_gather of per-band statistics runs once after the timed region.  `--scaling strong` is BASELINE config
+C5 as stated: ONE 8192x8192x3 image cut into N row bands of 8192/N rows, with the per-band statistics all_gather inside
 every timed step (fixed total work: the N-GPU value over the 1-GPU value is the speed-up).
 
   python bench.py --gpus 1 --steps 20 --warmup 3
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
-The JSON carries `roofline` (HBM: algorithmic bytes / mean kernel time from device events on the launch stream, against
-the 8 TB/s spec peak) and `cpu_baseline` (the reference-equivalent eager-PyTorch path of oracle/eager_torch.py timed on
-the host cores over a bounded sample; N = 1, rank 0 only).  Other workloads (--workload linearize|train|flatfield|video) are for
-development and print the same shape of line.
+A plain run sets up, warms up, times the steps and prints the line: `metric`, `value`, `unit`, `ms_per_step`, the
+`roofline` of the timed launches (HBM: algorithmic bytes / mean kernel time from device events on the launch stream,
+against the 8 TB/s spec peak).  `--full` adds what the headline figure does not need: `cpu_baseline` (the
+reference-equivalent eager-PyTorch path of oracle/eager_torch.py timed on the host cores over a bounded sample; N = 1,
+rank 0 only; --no-cpu-baseline drops it again), the merge's steady-state block and finiteness check, the C5 block of a
+multi-GPU line and the extra legs of --streamed / --through-api.  `--dump-outputs DIR` writes what the last timed step
+returned (rank 0) as DIR/<name>.npy.  Other workloads (--workload linearize|train|flatfield|video) are for development
+and print the same shape of line.
 """
 import argparse
 import json
@@ -31,10 +35,32 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy ceiling)
 POWERS = (2.2, 2.4, 2.6)
+# --dump-outputs: an output of more elements than this is written as a fixed sample of them (two float64 + float32
+# outputs of this size are 24 MB, inside the 64 MB a dump may take)
+DUMP_SAMPLES = 1 << 21
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(dirname, arrays):
+    """Write each tensor of `arrays` (name -> tensor or None) as dirname/<name>.npy, float32 / float64.  A tensor of
+    more than DUMP_SAMPLES elements is written flat as the elements at DUMP_SAMPLES sorted flat indices drawn from a
+    generator seeded with 0: the same positions on every run and every build, so two dumps compare element for element."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLES:
+            idx = torch.randint(t.numel(), (DUMP_SAMPLES,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
 
 
 def host_cores():
@@ -49,6 +75,10 @@ def host_cores():
 
 def make_lut(device):
     return torch.stack([torch.linspace(0, 1, 256) ** p for p in POWERS]).to(device)
+
+
+def cpu_baseline_on(args):
+    return args.full and not args.no_cpu_baseline
 
 
 def cpu_baseline_merge(n_exp, stops, seconds=12.0, tile=512):
@@ -217,12 +247,14 @@ def run_merge(args, rank, world, dev):
     elapsed = max_over_ranks(elapsed, world, dev)
     per_launch = sorted(a.elapsed_time(b) for a, b in ev)  # device events on the launch stream (torch's current stream)
     kernel_ms = sum(per_launch) / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"mean": mean, "std": std})
     # The first ~40 launches after any pause run inside a clock / power transient (fast, then 30 % slower, then settling:
     # tools/dvfs_transient.py, profiles/r02_dvfs_transient.log), so a short timed region reads 10-15 % above the steady
-    # state.  The contract's numbers above are what they are; the steady state is measured AFTER the timed region and
-    # reported beside them.
+    # state.  The contract's numbers above are what they are; with --full the steady state is measured AFTER the timed
+    # region and reported beside them.
     steady = None
-    if not strong:
+    if not strong and args.full:
         lead = max(0, 60 - (args.warmup + args.steps))
         for _ in range(lead):
             step()
@@ -234,7 +266,7 @@ def run_merge(args, rank, world, dev):
         torch.cuda.synchronize()
         steady_ms = sum(a.elapsed_time(b) for a, b in ev2) / len(ev2)
         steady = (steady_ms, args.warmup + args.steps + lead)
-    if gathered is None:  # weak mode: per-band statistics gathered once, after the timed region
+    if gathered is None and args.full:  # weak mode: per-band statistics gathered once, after the timed region
         gathered = gather_stats(band_stats(mean, std), world)
     px = h * w
     # stack (+ explicit std) read + float64 mean (+ float32 std) written
@@ -259,8 +291,7 @@ def run_merge(args, rank, world, dev):
                                f"{'' if args.max_code == 65535 else ', Normalize(' + str(args.max_code) + ')'}, Gaussian weights, "
                                f"sigma: {args.std}, float64 mean + float32 std out)"
                                + (", per-band statistics all_gather (RCCL) inside every step" if strong else ""),
-                   "global_image": f"{h_global}x{w}x3 in {world} row band(s)", "kernel": kernel,
-                   "finite": bool(torch.isfinite(gathered).all())},
+                   "global_image": f"{h_global}x{w}x3 in {world} row band(s)", "kernel": kernel},
         "roofline": {"bound": "hbm", "achieved": round(bytes_alg / (kernel_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": round(bytes_alg / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                      "traffic": traffic,
@@ -273,20 +304,22 @@ def run_merge(args, rank, world, dev):
                      "timing": "hipEvent pairs around each launch on the launch stream"
                                + (" (includes the statistics reduction and all_gather)" if strong else "")},
     }
+    if gathered is not None:
+        out["config"]["finite"] = bool(torch.isfinite(gathered).all())
     if steady is not None:
         out["roofline"]["steady_state"] = {
             "kernel_ms": round(steady[0], 4), "frac": round(bytes_alg / (steady[0] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
             "launches": 100, "after_launches": steady[1],
             "note": "same launches, measured after the timed region once the clock transient of the first ~40 launches "
                     "has passed; not part of value / ms_per_step / frac"}
-    if world > 1 and not strong:
+    if world > 1 and not strong and args.full:
         # the driver's multi-GPU line is weak scaling (above); BASELINE's configuration C5 -- one 8192^2 image in N bands,
         # statistics gather inside every step -- rides in the same JSON line
         codes = mean = std = gathered = None   # (the stack is captured by step(): rebind, then release)
         torch.cuda.empty_cache()
         block = c5_strong_block(args, rank, world, dev)
         out["c5_strong"] = block
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if world == 1 and rank == 0 and cpu_baseline_on(args):
         codes = None
         torch.cuda.empty_cache()
         out["cpu_baseline"] = cpu_baseline_merge(n_exp, 0.25, args.cpu_seconds)
@@ -312,11 +345,13 @@ def run_linearize(args, rank, world, dev):
     t0 = time.perf_counter()
     e0.record()
     for _ in range(args.steps):
-        step()
+        lin, sd = step()
     e1.record()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kernel_ms = e0.elapsed_time(e1) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"linearized": lin, "std": sd})
     px = args.frames * 1080 * 1920
     bytes_alg = px * 3 * (2 + 8)
     return {"metric": "frames/s linearized (+uncertainty), 1920x1080x3 uint16, kernel-only", "unit": "frames/s",
@@ -328,7 +363,7 @@ def run_linearize(args, rank, world, dev):
             "roofline": {"bound": "hbm", "achieved": round(bytes_alg / (kernel_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(bytes_alg / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                          "traffic": measured_traffic("linearize_c4") if args.frames == 64 else None},
-            **({} if args.no_cpu_baseline else {"cpu_baseline": cpu_baseline_linearize(min(args.cpu_seconds, 10.0))})}
+            **({"cpu_baseline": cpu_baseline_linearize(min(args.cpu_seconds, 10.0))} if cpu_baseline_on(args) else {})}
 
 
 def run_linearize_streamed(args, dev):
@@ -364,11 +399,47 @@ def run_linearize_streamed(args, dev):
             done += 1
             if done % 256 == 0:
                 checksum += float(lin[0, 0, 0]) + float(sd[0, 0, 0])
-        return done, checksum
+        return done, checksum, (lin, sd)
 
-    # this box's pinned device->host copy rate (warmed up; the same transfer size the pipeline uses) and the kernel-only
-    # rate on resident frames, reported next to the end-to-end figure
+    if args.full:
+        d2h_gbs, kernel_only_fps = _streamed_probes(host, dev)
+    for _ in range(max(1, args.warmup // 3)):
+        stream()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(max(1, args.steps // 10)):
+        t0 = time.perf_counter()
+        done, _, last = stream()
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+        assert done == n
+    if args.dump_outputs:  # of the stream's frames, the last one
+        dump_outputs(args.dump_outputs, {"linearized": last[0], "std": last[1]})
+    best, mean_t = min(times), sum(times) / len(times)
+    out_bytes, in_bytes = 2 * c * h * w * 4, c * h * w * 2
+    floor_spec = out_bytes / 63e9
+    return {"metric": "frames/s linearized (+uncertainty), 1920x1080x3 uint16, streamed host -> MI355X -> host", "unit": "frames/s",
+            "value": round(n / mean_t, 1), "n_gpus": 1, "steps": len(times), "warmup": max(1, args.warmup // 3),
+            "ms_per_step": round(mean_t * 1e3, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"C4 (end to end): {n} frames 1920x1080x3 uint16 from pinned host memory through "
+                                   "linearize_dataset_generator (LINEAR ICRF, sigma = 0.05 x in-kernel), value + std float32 "
+                                   "back on the host",
+                       "best_frames_per_s": round(n / best, 1),
+                       **({"kernel_only_frames_per_s": round(kernel_only_fps, 1)} if args.full else {}),
+                       "bytes_per_frame": {"host_to_device": in_bytes, "device_to_host": out_bytes}},
+            "roofline": {"bound": "pcie", "achieved": round(out_bytes * n / mean_t / 1e9, 2), "peak": 63.0, "unit": "GB/s",
+                         "frac": round(out_bytes * n / mean_t / 1e9 / 63.0, 4), "traffic": None,
+                         "floor_frames_per_s_at_spec": round(1.0 / floor_spec, 1),
+                         **({"measured_pinned_d2h_GBps": round(d2h_gbs, 2),
+                             "frac_of_measured_d2h": round(out_bytes * n / mean_t / 1e9 / d2h_gbs, 4)} if args.full else {})}}
+
+
+def _streamed_probes(host, dev):
+    """This box's pinned device->host copy rate (warmed up; the same transfer size the pipeline uses) and the kernel-only
+    rate on resident frames, reported next to the end-to-end figure."""
     from clair_torch_amd import ops
+    c, h, w = host.shape[1:]
     d_buf = torch.empty((10, c, h, w), dtype=torch.float32, device=dev)
     h_buf = torch.empty((10, c, h, w), dtype=torch.float32, pin_memory=True)
     h_buf.copy_(d_buf, non_blocking=True)
@@ -391,34 +462,7 @@ def run_linearize_streamed(args, dev):
     kernel_only_fps = 10 * resident.shape[0] / (time.perf_counter() - t0)
     del resident
     torch.cuda.empty_cache()
-    for _ in range(max(1, args.warmup // 3)):
-        stream()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(max(1, args.steps // 10)):
-        t0 = time.perf_counter()
-        done, _ = stream()
-        torch.cuda.synchronize()
-        times.append(time.perf_counter() - t0)
-        assert done == n
-    best, mean_t = min(times), sum(times) / len(times)
-    out_bytes, in_bytes = 2 * c * h * w * 4, c * h * w * 2
-    floor_spec = out_bytes / 63e9
-    return {"metric": "frames/s linearized (+uncertainty), 1920x1080x3 uint16, streamed host -> MI355X -> host", "unit": "frames/s",
-            "value": round(n / mean_t, 1), "n_gpus": 1, "steps": len(times), "warmup": max(1, args.warmup // 3),
-            "ms_per_step": round(mean_t * 1e3, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"C4 (end to end): {n} frames 1920x1080x3 uint16 from pinned host memory through "
-                                   "linearize_dataset_generator (LINEAR ICRF, sigma = 0.05 x in-kernel), value + std float32 "
-                                   "back on the host",
-                       "best_frames_per_s": round(n / best, 1),
-                       "kernel_only_frames_per_s": round(kernel_only_fps, 1),
-                       "bytes_per_frame": {"host_to_device": in_bytes, "device_to_host": out_bytes}},
-            "roofline": {"bound": "pcie", "achieved": round(out_bytes * n / mean_t / 1e9, 2), "peak": 63.0, "unit": "GB/s",
-                         "frac": round(out_bytes * n / mean_t / 1e9 / 63.0, 4), "traffic": None,
-                         "floor_frames_per_s_at_spec": round(1.0 / floor_spec, 1),
-                         "measured_pinned_d2h_GBps": round(d2h_gbs, 2),
-                         "frac_of_measured_d2h": round(out_bytes * n / mean_t / 1e9 / d2h_gbs, 4)}}
+    return d2h_gbs, kernel_only_fps
 
 
 def _timed_kernel(step, args):
@@ -457,6 +501,8 @@ def run_flatfield(args, rank, world, dev):
         ops.flatfield_correct(mean, var, flat, flat_std, input_is_variance=True, through_mean=True)
 
     elapsed, kernel_ms = _timed_kernel(step, args)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"mean": mean, "variance": var})
     q = c * h * w
     # sums: value 8 + flat 4 read; apply: value 8 r + 8 w, variance 4 r + 4 w, flat 4, flat std 4
     bytes_alg = q * ((8 + 4) + (16 + 8 + 4 + 4))
@@ -483,6 +529,8 @@ def run_video(args, rank, world, dev):
         seen[0] += b
 
     elapsed, kernel_ms = _timed_kernel(step, args)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"mean": mean, "m2": m2})
     q = c * h * w
     bytes_alg = q * (b * 2 + 16)  # every frame once + (mean, m2) float32 state read and written
     return {"metric": "frames/s video mean/std (WBOMeanVar), 1920x1080x3 uint16, kernel-only", "unit": "frames/s",
@@ -571,16 +619,37 @@ def run_train_through_api(args, rank, world, dev):
     fit(codes, exposures, max(2, args.warmup), dev)  # code objects, pair tables, allocator
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    fit(codes, exposures, args.steps, dev)
+    model = fit(codes, exposures, args.steps, dev)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    # kernel share: the two launches of a step timed back to back without the host loop around them
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"icrf": model.icrf})
     from clair_torch_amd import ops
     from clair_torch_amd.common.general_functions import get_valid_exposure_pairs
-    from clair_torch_amd.training import linearity_loss
     t = torch.tensor(exposures, dtype=torch.float64)
     i, j, r = get_valid_exposure_pairs(t, 0.25)
     pairs = ops.PairList(i, j, r, n_exp, dev)
+    out = {"metric": "ICRF training iterations/s (train_icrf through the public API)", "unit": "iters/s",
+           "value": round(args.steps / elapsed, 3), "n_gpus": 1, "steps": args.steps, "warmup": max(2, args.warmup),
+           "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+           "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "config": {"workload": f"C3 as stated: {args.steps} epochs of train_icrf, {n_exp}-exposure {size}x{size}x3 uint16 stack resident in HBM, "
+                                  f"{pairs.n_pairs} pairs, relative loss, per-channel fused Adam + ReduceLROnPlateau(0.5, 50), "
+                                  "alpha, beta, gamma, delta = 10, 1, 1, 1"},
+           "roofline": _train_roofline(pairs.n_pairs, 3 * size * size, elapsed / args.steps)}
+    if args.full:
+        out["config"].update(_through_api_extras(fit, codes, pairs, elapsed / args.steps * 1e3, dev))
+    if cpu_baseline_on(args):
+        out["cpu_baseline"] = cpu_baseline_train(args.cpu_seconds)
+    return out
+
+
+def _through_api_extras(fit, codes, pairs, step_ms, dev):
+    """--full legs of --through-api: the kernel share of a step (its two launches timed back to back without the host
+    loop around them) and the final LUT against the eager oracle on a down-scaled copy (same optimiser / scheduler
+    recipe on the CPU)."""
+    from clair_torch_amd.datasets import synthetic_exposure_stack
+    from clair_torch_amd.training import linearity_loss
     lut = torch.stack([torch.linspace(0, 1, 256) ** 2.5 for _ in range(3)]).to(dev).requires_grad_(True)
 
     def kernels():
@@ -595,31 +664,18 @@ def run_train_through_api(args, rank, world, dev):
         kernels()
     torch.cuda.synchronize()
     kernel_ms = (time.perf_counter() - k0) / 20 * 1e3
-    del codes
     torch.cuda.empty_cache()
-    # final LUT against the eager oracle on a down-scaled copy (same optimiser / scheduler recipe on the CPU)
     small, exp_s = synthetic_exposure_stack(16, 3, 48, 48, bits=16, stops_per_step=0.5, seed=1241)
     ep = 40
     got = fit(small.to(dev), exp_s, ep, dev).icrf.detach().cpu()
     want = _oracle_training_run(small, exp_s, ep)
-    out = {"metric": "ICRF training iterations/s (train_icrf through the public API)", "unit": "iters/s",
-           "value": round(args.steps / elapsed, 3), "n_gpus": 1, "steps": args.steps, "warmup": max(2, args.warmup),
-           "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-           "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-           "config": {"workload": f"C3 as stated: {args.steps} epochs of train_icrf, {n_exp}-exposure {size}x{size}x3 uint16 stack resident in HBM, "
-                                  f"{pairs.n_pairs} pairs, relative loss, per-channel fused Adam + ReduceLROnPlateau(0.5, 50), "
-                                  "alpha, beta, gamma, delta = 10, 1, 1, 1",
-                      "kernel_ms_per_step": round(kernel_ms, 3),
-                      "host_and_small_kernels_ms_per_step": round(elapsed / args.steps * 1e3 - kernel_ms, 3),
-                      "final_lut_vs_eager_oracle": {"stack": "16x48x48x3 uint16", "epochs": ep,
-                                                    "max_abs_diff": float((got - want).abs().max()),
-                                                    "mean_abs_diff": float((got - want).abs().mean()),
-                                                    "bins_off_by_more_than_1e-4": int(((got - want).abs() > 1e-4).sum()),
-                                                    "max_abs_change_from_start": float((want - torch.stack([torch.linspace(0, 1, 256) ** 2.5] * 3)).abs().max())}},
-           "roofline": _train_roofline(pairs.n_pairs, 3 * size * size, elapsed / args.steps)}
-    if not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline_train(args.cpu_seconds)
-    return out
+    return {"kernel_ms_per_step": round(kernel_ms, 3),
+            "host_and_small_kernels_ms_per_step": round(step_ms - kernel_ms, 3),
+            "final_lut_vs_eager_oracle": {"stack": "16x48x48x3 uint16", "epochs": ep,
+                                          "max_abs_diff": float((got - want).abs().max()),
+                                          "mean_abs_diff": float((got - want).abs().mean()),
+                                          "bins_off_by_more_than_1e-4": int(((got - want).abs() > 1e-4).sum()),
+                                          "max_abs_change_from_start": float((want - torch.stack([torch.linspace(0, 1, 256) ** 2.5] * 3)).abs().max())}}
 
 
 def _oracle_training_run(codes, exposures, epochs):
@@ -685,9 +741,11 @@ def run_train(args, rank, world, dev):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        lin = step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:  # the per-channel loss of the last step and the LUT its Adam step left
+        dump_outputs(args.dump_outputs, {"loss": lin, "icrf": torch.stack(params)})
     return {"metric": "ICRF training iterations/s (linearity term fwd+bwd + Adam)", "unit": "iters/s",
             "value": round(args.steps / elapsed, 3), "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
@@ -697,7 +755,7 @@ def run_train(args, rank, world, dev):
                                    f"{'' if args.max_code == 65535 else f' with codes 0..{args.max_code}'}, "
                                    f"{pairs.n_pairs} pairs, relative loss"},
             "roofline": _train_roofline(pairs.n_pairs, 3 * h * w, elapsed / args.steps),
-            **({} if args.no_cpu_baseline else {"cpu_baseline": cpu_baseline_train(args.cpu_seconds)})}
+            **({"cpu_baseline": cpu_baseline_train(args.cpu_seconds)} if cpu_baseline_on(args) else {})}
 
 
 def _train_roofline(n_pairs, elements, seconds):
@@ -784,7 +842,14 @@ def main():
     ap.add_argument("--train-exposures", type=int, default=64)
     ap.add_argument("--train-size", type=int, default=2048)
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline, the merge's "
+                         "steady-state block and finiteness check, the C5 block of a multi-GPU line, the copy-rate and "
+                         "kernel-only legs of --streamed, the kernel share and oracle comparison of --through-api")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, "
+                         "float32 / float64; an output of more than %d elements as a fixed seeded sample" % DUMP_SAMPLES)
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))

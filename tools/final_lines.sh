@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/final
 rm -rf $O && mkdir -p $O
 cd $R
-run() { name=$1; shift; python3 bench.py "$@" > $O/$name.json 2> $O/$name.err; python3 - <<PY
+run() { name=$1; shift; python3 bench.py "$@" --full > $O/$name.json 2> $O/$name.err; python3 - <<PY
 import json
 d = json.loads(open("$O/$name.json").read().strip().splitlines()[-1])
 r = d.get("roofline") or {}

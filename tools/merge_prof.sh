@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/merge_prof
 rm -rf $O && mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $R
-rocprofv3 --kernel-trace --stats -d $O/m --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/m.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/m --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $O/m.log 2>&1
 grep "^{" $O/m.log > $O/prof_bench_line.json
 cp $(find $O/m -name "*kernel_stats.csv" | head -1) $O/merge_kernel_stats.csv
 # per-dispatch durations of the merge kernel in launch order: the 20 timed launches follow the 3 warm-up ones, the
@@ -27,7 +27,7 @@ print(f"steady-state block (last 100): mean {sum(steady) / len(steady):.1f} us  
 print("all dispatches in order (us):", " ".join(f"{x:.0f}" for x in us))
 PY
 cat $O/trace_summary.txt | head -3
-python3 bench.py > $O/bench_final.json 2>/dev/null
+python3 bench.py --full > $O/bench_final.json 2>/dev/null
 python3 - <<PY
 import csv
 for r in list(csv.DictReader(open("$O/merge_kernel_stats.csv")))[:4]:

@@ -6,11 +6,11 @@ rm -rf $O && mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $R
 for l in nchw nhwc; do
   rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU SQ_WAVES SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR \
-    -d $O/$l.p1 --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --layout $l > $O/$l.p1.log 2>&1
+    -d $O/$l.p1 --output-format csv -- python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --layout $l > $O/$l.p1.log 2>&1
   rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS \
-    -d $O/$l.p2 --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --layout $l > $O/$l.p2.log 2>&1
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/$l.p3 --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --layout $l > $O/$l.p3.log 2>&1
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/$l.p4 --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --layout $l > $O/$l.p4.log 2>&1
+    -d $O/$l.p2 --output-format csv -- python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --layout $l > $O/$l.p2.log 2>&1
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/$l.p3 --output-format csv -- python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --layout $l > $O/$l.p3.log 2>&1
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/$l.p4 --output-format csv -- python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --layout $l > $O/$l.p4.log 2>&1
 done
 python3 - "$O" <<'PY'
 import csv, glob, collections, sys

@@ -7,11 +7,11 @@ O=$R/gpurun_out/pmc_merge
 rm -rf $O && mkdir -p $O
 cd $R
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS \
-  -d $O/p1 --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline > $O/p1.log 2>&1
+  -d $O/p1 --output-format csv -- python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline > $O/p1.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU SQ_WAVES SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VMEM \
-  -d $O/p2 --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline > $O/p2.log 2>&1
+  -d $O/p2 --output-format csv -- python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline > $O/p2.log 2>&1
 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_INSTS_VMEM_WR SQ_WAIT_INST_ANY SQ_ACTIVE_INST_MISC SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_SCA SQ_WAVE_CYCLES SQ_INSTS_SMEM \
-  -d $O/p3 --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline > $O/p3.log 2>&1 || true
+  -d $O/p3 --output-format csv -- python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline > $O/p3.log 2>&1 || true
 python3 - <<PY
 import csv, glob, collections
 for p in ("p1", "p2", "p3"):
