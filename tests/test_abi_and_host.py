@@ -127,6 +127,221 @@ def test_pivot_interval_constants_every_code(lib, max_code, n_points, dtype_max,
         assert np.array_equal(got, np.floor(np.clip(s_ref, 0, top)))
 
 
+# ---- ct_hdr_merge_batch / ct_hdr_merge_batches: every malformed call is refused with the same status before any GPU work ----
+# One valid call (first and only batch(es) of a 3 x 4 x 4 image, LINEAR model, Gaussian weights, constant uncertainty,
+# results written; without streaming state and with it) broken in exactly one way per row.  The pointers are never dereferenced.  The statuses were recorded
+# from the library before the route / validator / argument builder were merged into one of each; they are the contract.
+_FAKE, _FAKE2, _EXPO, _LUT = 0x1000, 0x2000, 0x3000, 0x4000
+_MERGE_DTYPES = {"u8": (0, 255.0), "u16": (1, 65535.0), "f32": (2, 1.0)}
+_MERGE_ROUTE_FLAGS = {"reference_order": 16, "closed_form": 32}
+
+
+def _valid_merge_call():
+    return dict(stack=_FAKE, stacks=[_FAKE, _FAKE2], sizes=[2, 2], n_batches=2, batch=4, std=None, stds=None, geom=True,
+                g=dict(channels=3, h_tile=4, width=4, h_global=4, row_offset=0, image_stride=48, layout=0),
+                icrf=dict(lut_dev=_LUT, n_points=256, interp=1), std_mode=1, weight_mode=1, state=True, mean_out=_FAKE, std_out=_FAKE2,
+                flags=3)
+
+
+def _g(**kw):
+    return lambda c: c["g"].update(kw)
+
+
+def _icrf(**kw):
+    return lambda c: c["icrf"].update(kw)
+
+
+def _set(**kw):
+    return lambda c: c.update(kw)
+
+
+# row -> (mutation, entry points it applies to)
+_MALFORMED = {
+    "null_stack": (_set(stack=None, stacks=None), "both"),
+    "null_geometry": (_set(geom=False), "both"),
+    "batch_not_positive": (_set(batch=0, sizes=[2, 0]), "both"),
+    "h_tile_above_h_global": (_g(h_global=2), "both"),
+    "negative_row_offset": (_g(row_offset=-1), "both"),
+    "layout_out_of_range": (_g(layout=3), "both"),
+    "interp_out_of_range": (_icrf(interp=4), "both"),
+    "lut_missing": (_icrf(lut_dev=None), "both"),
+    "n_points_below_2": (_icrf(n_points=1), "both"),
+    "std_mode_out_of_range": (_set(std_mode=4), "both"),
+    "explicit_without_std_pointer": (_set(std_mode=3), "both"),
+    "weight_mode_out_of_range": (_set(weight_mode=2), "both"),
+    "lookup_no_weight_with_std": (lambda c: (c["icrf"].update(interp=0), c.update(weight_mode=0)), "both"),
+    "no_state_without_first_and_finalize": (_set(flags=1, state=False), "both"),
+    # (several batches on the launch-per-batch route validate FINALIZE with the last batch, after the first has been
+    # launched: those rows are GPU territory and only the one-launch pivot route is listed for ct_hdr_merge_batches)
+    "finalize_without_mean_out": (_set(mean_out=None), "batch+pivot_batches"),
+    "finalize_without_std_out": (_set(std_out=None), "batch+pivot_batches"),
+    "image_stride_too_small": (_g(image_stride=47), "both"),
+    "two_to_the_31_elements": (_g(h_global=1 << 20, width=1 << 10, image_stride=3 * 4 * 1024), "both"),
+    "null_entry_in_stack_devs": (_set(stacks=[_FAKE, None]), "batches"),
+    "n_batches_not_positive": (_set(n_batches=0), "batches"),
+}
+
+
+def _merge_status(lib, nv, fn, dtype, route, state, row):
+    c = _valid_merge_call()
+    _MALFORMED[row][0](c)
+    code, max_code = _MERGE_DTYPES[dtype]
+    g, icrf = nv.Geometry(**c["g"]), nv.Icrf(**c["icrf"])
+    gp = ctypes.byref(g) if c["geom"] else None
+    flags = c["flags"] | _MERGE_ROUTE_FLAGS[route]
+    state = [0x5000, 0x6000, 0x7000] if state == "state" and c["state"] else [None] * 3
+    if fn == "batch":
+        return lib.ct_hdr_merge_batch(c["stack"], code, max_code, c["batch"], gp, c["std"], c["std_mode"], 0.1, _EXPO, ctypes.byref(icrf),
+                                      c["weight_mode"], *state, c["mean_out"], c["std_out"], flags, None)
+    stacks = (ctypes.c_void_p * 2)(*c["stacks"]) if c["stacks"] else None
+    sizes = (ctypes.c_int32 * 2)(*c["sizes"])
+    return lib.ct_hdr_merge_batches(stacks, c["stds"], sizes, c["n_batches"], code, max_code, gp, c["std_mode"], 0.1, _EXPO,
+                                    ctypes.byref(icrf), c["weight_mode"], *state, c["mean_out"], c["std_out"], flags, None)
+
+
+def _malformed_merge_cases():
+    for row, (_, where) in _MALFORMED.items():
+        for dtype in _MERGE_DTYPES:
+            for route in _MERGE_ROUTE_FLAGS:
+                for state in ("no_state", "state"):
+                    if where in ("both", "batch+pivot_batches"):
+                        yield "batch", dtype, route, state, row
+                    if where in ("both", "batches") or (where == "batch+pivot_batches" and dtype != "f32" and route == "closed_form"):
+                        yield "batches", dtype, route, state, row
+
+
+# status of every case: the row's default, then the (entry point, dtype, route, state) cells that differ
+_MALFORMED_STATUS = {'null_stack': (-1, {}),
+ 'null_geometry': (-1, {}),
+ 'batch_not_positive': (-1, {}),
+ 'h_tile_above_h_global': (-1, {}),
+ 'negative_row_offset': (-1, {}),
+ 'layout_out_of_range': (-1, {}),
+ 'interp_out_of_range': (-1, {}),
+ 'lut_missing': (-1, {}),
+ 'n_points_below_2': (-1, {}),
+ 'std_mode_out_of_range': (-1, {}),
+ 'explicit_without_std_pointer': (-1, {}),
+ 'weight_mode_out_of_range': (-1, {}),
+ 'lookup_no_weight_with_std': (-4,
+                               {('batches', 'u8', 'reference_order', 'no_state'): -1,
+                                ('batches', 'u8', 'closed_form', 'no_state'): -1,
+                                ('batches', 'u16', 'reference_order', 'no_state'): -1,
+                                ('batches', 'u16', 'closed_form', 'no_state'): -1,
+                                ('batches', 'f32', 'reference_order', 'no_state'): -1,
+                                ('batches', 'f32', 'closed_form', 'no_state'): -1}),
+ 'no_state_without_first_and_finalize': (-1, {}),
+ 'finalize_without_mean_out': (-1, {}),
+ 'finalize_without_std_out': (-1, {}),
+ 'image_stride_too_small': (-1, {}),
+ 'two_to_the_31_elements': (-5,
+                            {('batches', 'u8', 'reference_order', 'no_state'): -1,
+                             ('batches', 'u16', 'reference_order', 'no_state'): -1,
+                             ('batches', 'f32', 'reference_order', 'no_state'): -1,
+                             ('batches', 'f32', 'closed_form', 'no_state'): -1}),
+ 'null_entry_in_stack_devs': (-1, {}),
+ 'n_batches_not_positive': (-1, {})}
+
+
+@pytest.mark.parametrize("fn,dtype,route,state,row", list(_malformed_merge_cases()))
+def test_malformed_merge_calls_keep_their_status(lib, fn, dtype, route, state, row):
+    from clair_torch_amd import _native as nv
+    default, cells = _MALFORMED_STATUS[row]
+    assert _merge_status(lib, nv, fn, dtype, route, state, row) == cells.get((fn, dtype, route, state), default)
+
+
+# ---- ct_hdr_merge_kernel_name: the route as a pure host function, every combination against the recorded answer ----
+_KERNEL_NAMES = {'a': 'ct::merge_pivot_kernel (float32 moments about the running mean, persistent workgroups, 4 codes per thread, streaming state)',
+ 'b': 'ct::merge_pivot_kernel (float32 moments about a per-pixel pivot, persistent workgroups, 4 codes per thread through typed buffer loads, 7 '
+      'wavefronts per SIMD, first batch)',
+ 'c': 'ct::merge_kernel (float64 moments, integer codes)',
+ 'd': "ct::merge_reference_order_kernel (the reference's float32 autograd order, two passes, float64 exp and divisions)",
+ 'e': 'ct::merge_kernel (float32 moments about a per-pixel pivot, integer codes through the float LUT coordinate)',
+ 'f': 'ct::merge_kernel (float32 moments about a per-pixel pivot, float32 pixels, 4 per thread)',
+ 'g': 'ct::merge_kernel (float64 moments, float32 pixels, 4 per thread)'}
+_NAME_MAX_CODES, _NAME_N_POINTS = (255.0, 1023.0, 4095.0, 65535.0, 300.5), (2, 256, 772, 1024)
+_NAME_FLAG_BITS = (1, 8, 16, 32, 64)  # FIRST_BATCH, F64_MOMENTS, REFERENCE_ORDER, CLOSED_FORM, STD_HINT
+
+
+def _name_flag_sets():
+    return [sum(b for k, b in enumerate(_NAME_FLAG_BITS) if m >> k & 1) for m in range(32)]
+
+
+# (dtype, interp) -> {max_code: {n_points: one letter of _KERNEL_NAMES per flag set, in _name_flag_sets() order}}
+_KERNEL_NAME_TABLE = {(0, 0): {255.0: {'*': 'abccddddabccddddddccddddabccdddd'},
+          1023.0: {'*': 'eeccddddeeccddddddccddddeeccdddd'},
+          4095.0: {'*': 'eeccddddeeccddddddccddddeeccdddd'},
+          65535.0: {'*': 'eeccddddeeccddddddccddddeeccdddd'},
+          300.5: {'*': 'eeccddddeeccddddddccddddeeccdddd'}},
+ (0, 1): {255.0: {'*': 'abccddddabccddddabccddddabccdddd'},
+          1023.0: {'*': 'eeccddddeeccddddeeccddddeeccdddd'},
+          4095.0: {'*': 'eeccddddeeccddddeeccddddeeccdddd'},
+          65535.0: {'*': 'eeccddddeeccddddeeccddddeeccdddd'},
+          300.5: {'*': 'eeccddddeeccddddeeccddddeeccdddd'}},
+ (0, 2): {255.0: {'*': 'abccddddabccddddddccddddabccdddd'},
+          1023.0: {'*': 'eeccddddeeccddddddccddddeeccdddd'},
+          4095.0: {'*': 'eeccddddeeccddddddccddddeeccdddd'},
+          65535.0: {'*': 'eeccddddeeccddddddccddddeeccdddd'},
+          300.5: {'*': 'eeccddddeeccddddddccddddeeccdddd'}},
+ (0, 3): {255.0: {'*': 'abccddddabccddddabccddddabccdddd'},
+          1023.0: {'*': 'eeccddddeeccddddeeccddddeeccdddd'},
+          4095.0: {'*': 'eeccddddeeccddddeeccddddeeccdddd'},
+          65535.0: {'*': 'eeccddddeeccddddeeccddddeeccdddd'},
+          300.5: {'*': 'eeccddddeeccddddeeccddddeeccdddd'}},
+ (1, 0): {255.0: {'*': 'abccddddabccddddddccddddabccdddd'},
+          1023.0: {'*': 'abccddddabccddddddccddddabccdddd'},
+          4095.0: {'*': 'abccddddabccddddddccddddabccdddd'},
+          65535.0: {'*': 'abccddddabccddddddccddddabccdddd', 1024: 'eeccddddeeccddddddccddddeeccdddd'},
+          300.5: {'*': 'eeccddddeeccddddddccddddeeccdddd'}},
+ (1, 1): {255.0: {'*': 'abccddddabccddddabccddddabccdddd'},
+          1023.0: {'*': 'abccddddabccddddabccddddabccdddd'},
+          4095.0: {'*': 'abccddddabccddddabccddddabccdddd'},
+          65535.0: {'*': 'abccddddabccddddabccddddabccdddd', 772: 'eeccddddeeccddddeeccddddeeccdddd'},
+          300.5: {'*': 'eeccddddeeccddddeeccddddeeccdddd'}},
+ (1, 2): {255.0: {'*': 'abccddddabccddddddccddddabccdddd'},
+          1023.0: {'*': 'abccddddabccddddddccddddabccdddd'},
+          4095.0: {'*': 'abccddddabccddddddccddddabccdddd'},
+          65535.0: {'*': 'abccddddabccddddddccddddabccdddd', 772: 'eeccddddeeccddddddccddddeeccdddd'},
+          300.5: {'*': 'eeccddddeeccddddddccddddeeccdddd'}},
+ (1, 3): {255.0: {'*': 'abccddddabccddddabccddddabccdddd'},
+          1023.0: {'*': 'abccddddabccddddabccddddabccdddd'},
+          4095.0: {'*': 'abccddddabccddddabccddddabccdddd'},
+          65535.0: {'*': 'abccddddabccddddabccddddabccdddd'},
+          300.5: {'*': 'eeccddddeeccddddeeccddddeeccdddd'}},
+ (2, 0): {255.0: {'*': 'ffggddddffggddddddggddddffggdddd'},
+          1023.0: {'*': 'ffggddddffggddddddggddddffggdddd'},
+          4095.0: {'*': 'ffggddddffggddddddggddddffggdddd'},
+          65535.0: {'*': 'ffggddddffggddddddggddddffggdddd'},
+          300.5: {'*': 'ffggddddffggddddddggddddffggdddd'}},
+ (2, 1): {255.0: {'*': 'ffggddddffggddddffggddddffggdddd'},
+          1023.0: {'*': 'ffggddddffggddddffggddddffggdddd'},
+          4095.0: {'*': 'ffggddddffggddddffggddddffggdddd'},
+          65535.0: {'*': 'ffggddddffggddddffggddddffggdddd'},
+          300.5: {'*': 'ffggddddffggddddffggddddffggdddd'}},
+ (2, 2): {255.0: {'*': 'ffggddddffggddddddggddddffggdddd'},
+          1023.0: {'*': 'ffggddddffggddddddggddddffggdddd'},
+          4095.0: {'*': 'ffggddddffggddddddggddddffggdddd'},
+          65535.0: {'*': 'ffggddddffggddddddggddddffggdddd'},
+          300.5: {'*': 'ffggddddffggddddddggddddffggdddd'}},
+ (2, 3): {255.0: {'*': 'ffggddddffggddddffggddddffggdddd'},
+          1023.0: {'*': 'ffggddddffggddddffggddddffggdddd'},
+          4095.0: {'*': 'ffggddddffggddddffggddddffggdddd'},
+          65535.0: {'*': 'ffggddddffggddddffggddddffggdddd'},
+          300.5: {'*': 'ffggddddffggddddffggddddffggdddd'}}}
+
+
+@pytest.mark.parametrize("dtype", [0, 1, 2])
+@pytest.mark.parametrize("interp", [0, 1, 2, 3])
+def test_kernel_name_table(lib, dtype, interp):
+    for max_code in _NAME_MAX_CODES:
+        for n_points in _NAME_N_POINTS:
+            by_n = _KERNEL_NAME_TABLE[(dtype, interp)][max_code]
+            letters = by_n.get(n_points, by_n["*"])
+            for letter, flags in zip(letters, _name_flag_sets()):
+                got = lib.ct_hdr_merge_kernel_name(dtype, max_code, interp, n_points, flags).decode()
+                assert got == _KERNEL_NAMES[letter], (dtype, max_code, interp, n_points, flags)
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from clair_torch_amd import _native
     monkeypatch.setattr(_native, "_lib", None)
