@@ -96,3 +96,55 @@ def flatfield_correction(images: torch.Tensor, flatfield: torch.Tensor, flatfiel
         except RuntimeError as exc:
             raise ValueError(f"{name} shape {tuple(other.shape)} is not broadcastable to {tuple(images.shape)}") from exc
     return (images / (flatfield + epsilon)) * flatfield_mean_val
+
+
+def cv_to_torch(x: torch.Tensor) -> torch.Tensor:
+    """OpenCV (H, W) -> (1, H, W); (H, W, 3) BGR -> (3, H, W) RGB (reference general_functions.py:315-335)."""
+    if x.ndim == 2:
+        return x.unsqueeze(0)
+    if x.ndim == 3 and x.shape[2] == 3:
+        return x[:, :, [2, 1, 0]].permute(2, 0, 1)
+    raise ValueError(f"Unexpected image shape: {x.shape}")
+
+
+def torch_to_cv(x: torch.Tensor) -> torch.Tensor:
+    """(3, H, W) RGB -> (H, W, 3) BGR; (1, H, W) -> (H, W); (H, W) unchanged (reference general_functions.py:338-356)."""
+    if x.ndim == 2:
+        return x
+    if x.ndim == 3 and x.shape[0] == 3:
+        return x.permute(1, 2, 0)[:, :, [2, 1, 0]]
+    if x.ndim == 3 and x.shape[0] == 1:
+        return x.squeeze(0)
+    raise ValueError(f"Unexpected tensor shape: {x.shape}")
+
+
+def normalize_tensor(x: torch.Tensor, max_val: Optional[float] = None, min_val: Optional[float] = None,
+                     target_range=(0.0, 1.0)) -> torch.Tensor:
+    """(x - min) / (max - min) scaled to ``target_range``; the tensor's own min / max where none is given (reference
+    general_functions.py:359-388)."""
+    max_val = x.max() if max_val is None else max_val
+    min_val = x.min() if min_val is None else min_val
+    den = max_val - min_val
+    if den == 0:
+        raise ValueError("Normalization range is zero (min == max); cannot normalize.")
+    lo, hi = target_range
+    return (x - min_val) / den * (hi - lo) + lo
+
+
+def clamp_along_dims(x: torch.Tensor, dim, min_max_pairs) -> torch.Tensor:
+    """Clamp ``x`` between one (min, max) pair, or between one pair per slice along ``dim`` (an int or a tuple of ints,
+    negative allowed; the list then has as many pairs as there are slices, in row-major order of those dimensions)
+    (reference general_functions.py:392-436)."""
+    dims = tuple(d % x.ndim for d in ((dim,) if isinstance(dim, int) else dim))
+    if isinstance(min_max_pairs, tuple):
+        return torch.clamp(x, min=min_max_pairs[0], max=min_max_pairs[1])
+    slice_shape = tuple(x.shape[d] for d in dims)
+    n_slices = math.prod(slice_shape)
+    if len(min_max_pairs) != n_slices:
+        raise ValueError(f"Expected 1 or {n_slices} min/max pairs, got {len(min_max_pairs)}")
+    shape = [1] * x.ndim
+    for d, n in zip(dims, slice_shape):
+        shape[d] = n
+    lo = torch.tensor([p[0] for p in min_max_pairs], dtype=x.dtype, device=x.device).reshape(shape)
+    hi = torch.tensor([p[1] for p in min_max_pairs], dtype=x.dtype, device=x.device).reshape(shape)
+    return torch.clamp(x, min=lo, max=hi)

@@ -3,7 +3,8 @@ from typing import Iterable, Optional
 
 import torch
 
-from ..common.transforms import fusable_code_normalisation, fusable_layout
+from .. import ops
+from ..common.transforms import StridedDownscale, fusable_code_normalisation, fusable_downscale, fusable_layout
 
 
 def resolve_device(device) -> torch.device:
@@ -30,8 +31,17 @@ def stage_images(val_batch: torch.Tensor, device: torch.device, transforms: list
     Returns (images, max_code): integer codes with their max_code when the transform list is the
     CastTo(float32)+Normalize(max, 0) pair the kernels ingest directly, else float32 pixels and None.
     With ``want_layout`` a third value is returned: "nhwc_bgr" when the list additionally starts with CvToTorch
-    on raw (B,H,W,3) frames (the kernel then reads the interleaved BGR frames as they are), else "nchw"."""
+    on raw (B,H,W,3) frames (the kernel then reads the interleaved BGR frames as they are), else "nchw".
+    One StridedDownscale in such a list (``fusable_downscale``) keeps the code route: the raw codes are compacted on
+    the device in their own dtype and layout, and the smaller integer stack is returned."""
     images = val_batch.to(device=device, non_blocking=True)  # the ONE host-to-device copy of the batch (a plain DMA when pinned)
+    step, rest = fusable_downscale(transforms)
+    if step is not None and images.ndim == 4:
+        layout, tail = fusable_layout(images, rest) if want_layout else ("nchw", rest)
+        max_code = fusable_code_normalisation(images, tail)
+        if max_code is not None:
+            images = ops.strided_downscale(images, step, layout=layout)
+            return (images, max_code, layout) if want_layout else (images, max_code)
     if want_layout:
         layout, rest = fusable_layout(images, transforms)
         if layout != "nchw":
@@ -49,6 +59,27 @@ def stage_images(val_batch: torch.Tensor, device: torch.device, transforms: list
         raise TypeError("integer images reached the kernel without a Normalize transform; pass "
                         "gpu_transforms=[CastTo('float32'), Normalize(max_val=<max code>, min_val=0)]")
     return images.to(torch.float32).contiguous(), None
+
+
+def restage_planar(val_batch: torch.Tensor, images: torch.Tensor, device: torch.device, transforms: list):
+    """(images, max_code, "nchw") for a batch that ``stage_images`` handed over interleaved but that has to be planar
+    after all (explicit std / dark-field images are planar): the transforms run on the generic route.  ``images`` is
+    what ``stage_images`` returned -- the batch itself, already on the device, unless it was compacted by a
+    StridedDownscale, which must not be applied a second time: then staging starts over from ``val_batch``."""
+    source = val_batch if has_downscale(transforms) else images
+    return stage_images(source, device, transforms) + ("nchw",)
+
+
+def has_downscale(transforms) -> bool:
+    return any(isinstance(t, StridedDownscale) for t in transforms)
+
+
+def refuse_tile_with_downscale(tile, transforms):
+    """Row bands (``tile=``) hold rows [row_offset, row_offset + h) of the global image; which of them a
+    StridedDownscale selects depends on row_offset % step, a phase the staging does not carry."""
+    if tile is not None and has_downscale(transforms):
+        raise ValueError("tile= cannot be combined with a StridedDownscale in gpu_transforms: downscale the row bands "
+                         "before sharding, or run untiled")
 
 
 def std_arguments(std_batch: Optional[torch.Tensor], dataset, device):

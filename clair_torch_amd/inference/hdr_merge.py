@@ -13,7 +13,8 @@ from torch.utils.data import DataLoader
 from .. import ops
 from ..common.typecheck import expect
 from ..models.base import ICRFModelBase
-from ._staging import normalise_transform_list, resolve_device, stage_images, std_arguments
+from ._staging import (normalise_transform_list, refuse_tile_with_downscale, resolve_device, restage_planar, stage_images,
+                       std_arguments)
 
 
 def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFModelBase] = None,
@@ -54,6 +55,7 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
         from .dark_field import DarkField
         dark = DarkField.from_dataset(dark_field_dataset, dataloader.dataset, dev)
     transforms = normalise_transform_list(gpu_transforms)
+    refuse_tile_with_downscale(tile, transforms)
     lut = interp = None
     if icrf_model is not None:
         lut, interp = icrf_model.icrf.detach().to(dev), icrf_model.interp_name
@@ -94,7 +96,7 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
         images, max_code, layout = stage_images(val_batch, dev, transforms, want_layout=True)
         std, std_mode, std_value = std_arguments(std_batch, dataloader.dataset, dev)
         if (std is not None or dark is not None) and layout != "nchw":  # explicit std / dark images are planar
-            images, max_code, layout = stage_images(images, dev, transforms) + ("nchw",)
+            images, max_code, layout = restage_planar(val_batch, images, dev, transforms)
         if dark is not None:
             xb, sig = dark.apply(index_batch, images, max_code, std, std_mode, std_value, tile, group)
             if xb is not None:  # the blurred batch replaces the images; its uncertainty carries both variance terms

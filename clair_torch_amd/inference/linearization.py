@@ -24,7 +24,7 @@ from torch.utils.data import DataLoader
 from .. import ops
 from ..common.typecheck import expect
 from ..models.base import ICRFModelBase
-from ._staging import normalise_transform_list, resolve_device, stage_images, std_arguments
+from ._staging import normalise_transform_list, resolve_device, restage_planar, stage_images, std_arguments
 from ..common.transforms import fusable_code_normalisation, fusable_layout
 
 _GROUP_BYTES = 256 << 20  # device-to-host bytes per group (two float32 planes per frame): ~5 frames of 1080p RGB
@@ -80,7 +80,7 @@ def _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat
         images, max_code, layout = stage_images(val_batch, dev, transforms, want_layout=True)
         std, std_mode, std_value = std_arguments(std_batch, dataloader.dataset, dev)
         if (std is not None or dark is not None) and layout != "nchw":  # explicit std / dark images are planar
-            images, max_code, layout = stage_images(images, dev, transforms) + ("nchw",)
+            images, max_code, layout = restage_planar(val_batch, images, dev, transforms)
         if dark is not None:
             lin, lin_std = dark.linearize(index_batch, images, max_code, std, std_mode, std_value, lut, interp)
         else:

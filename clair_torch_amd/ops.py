@@ -611,6 +611,57 @@ def dark_field_blur(stack: torch.Tensor, dark: torch.Tensor, dark_std: Optional[
     return xb, sig
 
 
+# ---- strided downscale of raw codes (StridedDownscale folded in front of the code-domain kernels) -----------------
+def downscaled_shape(shape, step: int, layout: str = "nchw"):
+    """Shape of ``x[..., ::step, ::step]`` taken on the spatial axes of a 4-D stack in ``layout``."""
+    b, d1, d2, d3 = shape
+    if layout == "nchw":
+        return b, d1, -(-d2 // step), -(-d3 // step)
+    return b, -(-d1 // step), -(-d2 // step), d3
+
+
+def strided_downscale(stack: torch.Tensor, step: int, layout: str = "nchw", out: Optional[torch.Tensor] = None):
+    """ct_strided_downscale: every ``step``-th row and column of a uint8 / uint16 / float32 device stack, compacted in
+    its own dtype and layout -- (B,C,H,W) -> (B,C,ceil(H/step),ceil(W/step)) for "nchw", (B,H,W,C) ->
+    (B,ceil(H/step),ceil(W/step),C) for "nhwc" / "nhwc_bgr" (the channel order is untouched) -- bit-identical to
+    ``x[..., ::step, ::step]`` on the planar view.  ``out``: a contiguous caller tensor of exactly that shape and dtype
+    to write into.  ``step == 1`` returns the stack itself (copied into ``out`` when given)."""
+    _require_device(stack, "stack")
+    if stack.ndim != 4:
+        raise ValueError(f"stack must be 4-dimensional, got shape {tuple(stack.shape)}")
+    if stack.dtype not in _DTYPE:
+        raise TypeError(f"stack dtype {stack.dtype} unsupported (uint8, uint16 codes or float32 pixels)")
+    if layout not in _LAYOUT:
+        raise ValueError(f"unknown layout {layout!r} (nchw, nhwc, nhwc_bgr)")
+    if isinstance(step, bool) or not isinstance(step, int) or step < 1:
+        raise ValueError(f"step must be an int >= 1, got {step!r}")
+    shape = downscaled_shape(stack.shape, step, layout)
+    if out is not None:
+        _require_device(out, "out")
+        if tuple(out.shape) != shape or out.dtype != stack.dtype or out.device != stack.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {stack.dtype} tensor of shape {shape} on {stack.device}")
+    if step == 1:
+        if out is None:
+            return stack
+        alias = torch.int16 if stack.dtype == torch.uint16 else stack.dtype  # torch has no uint16 copy kernel
+        out.view(alias).copy_(stack.view(alias))
+        return out
+    stack = stack.contiguous()
+    if out is None:
+        out = torch.empty(shape, dtype=stack.dtype, device=stack.device)
+    if out.numel() == 0:
+        return out
+    if layout == "nchw":
+        planes, h, w, pixel_elems = stack.shape[0] * stack.shape[1], stack.shape[2], stack.shape[3], 1
+    else:
+        planes, h, w, pixel_elems = stack.shape[0], stack.shape[1], stack.shape[2], stack.shape[3]
+    with torch.cuda.device(stack.device):
+        rc = nv.load().ct_strided_downscale(_ptr(stack), _ptr(out), stack.element_size(), planes, h, w, pixel_elems, step,
+                                            _stream(stack.device))
+    nv.check(rc, "ct_strided_downscale")
+    return out
+
+
 # ---- streaming video statistics -----------------------------------------------------------------------------------
 def video_stats_batch(frames: torch.Tensor, mean_state: torch.Tensor, m2_state: torch.Tensor, frames_before: int, *,
                       lut: Optional[torch.Tensor] = None, interp: Optional[str] = None,

@@ -16,6 +16,8 @@ and pair lists are passed as their component tensors / scalars.
     torch.ops.clair_hip.pair_residual_lut_grad(stack, i_idx, j_idx, ratio, coef, lut, interp, lower, upper, relative,
                                                max_code) -> (C, L) float64
 
+    torch.ops.clair_hip.strided_downscale(stack, step, layout) -> Tensor   (x[..., ::step, ::step], same dtype / layout)
+
 CPU tensors are refused by the kernels' front-end exactly as through ``ops`` (there is no CPU path).
 """
 from typing import Optional, Tuple
@@ -147,3 +149,15 @@ def band_stats(mean: torch.Tensor, std: Optional[torch.Tensor]) -> torch.Tensor:
 def _(mean, std):
     return mean.new_empty((6, mean.shape[0]), dtype=torch.float64)
 
+
+
+@torch.library.custom_op(f"{_LIB}::strided_downscale", mutates_args=())
+def strided_downscale(stack: torch.Tensor, step: int, layout: str = "nchw") -> torch.Tensor:
+    """ct_strided_downscale: every step-th row and column of a code / pixel stack, compacted in its dtype and layout."""
+    out = ops.strided_downscale(stack, step, layout)
+    return out.clone() if out is stack else out  # step 1: an op's result may not alias its input
+
+
+@strided_downscale.register_fake
+def _(stack, step, layout="nchw"):
+    return stack.new_empty(ops.downscaled_shape(stack.shape, step, layout))

@@ -17,7 +17,8 @@ from torch.utils.data import DataLoader
 from .. import ops
 from ..common.general_functions import get_valid_exposure_pairs
 from ..common.typecheck import expect
-from ..inference._staging import normalise_transform_list, resolve_device, stage_images, std_arguments
+from ..inference._staging import (normalise_transform_list, refuse_tile_with_downscale, resolve_device, restage_planar,
+                                  stage_images, std_arguments)
 from ..models.base import ICRFModelBase
 from .linearity import linearity_loss
 from .losses import (compute_endpoint_penalty, compute_monotonicity_penalty, compute_range_penalty,
@@ -56,6 +57,7 @@ def train_icrf(dataloader: DataLoader, batch_size: int, device, icrf_model: ICRF
     if len(schedulers) != len(optimizers):
         raise ValueError(f"Mismatched number of optimizers: {len(optimizers)} and schedulers: {len(schedulers)}.")
     transforms = normalise_transform_list(gpu_transforms)
+    refuse_tile_with_downscale(tile, transforms)
     best_losses = [float("inf")] * channels
     epochs_without_improvement = [0] * channels
     icrf_model.train()
@@ -110,7 +112,7 @@ def train_icrf(dataloader: DataLoader, batch_size: int, device, icrf_model: ICRF
             images, max_code, layout = stage_images(val_batch, dev, transforms, want_layout=True)
             std, std_mode, std_value = std_arguments(std_batch, dataloader.dataset, dev)
             if std is not None and layout != "nchw":  # explicit uncertainty images are planar
-                images, max_code, layout = stage_images(images, dev, transforms) + ("nchw",)
+                images, max_code, layout = restage_planar(val_batch, images, dev, transforms)
             if images.shape[0] < 2:
                 print("Skipped batch due to single image.")
                 continue

@@ -19,7 +19,8 @@ from torch.utils.data import DataLoader
 from .. import ops
 from ..common.general_functions import get_valid_exposure_pairs
 from ..common.typecheck import expect
-from ..inference._staging import resolve_device, stage_images, std_arguments, normalise_transform_list
+from ..inference._staging import (resolve_device, stage_images, std_arguments, normalise_transform_list,
+                                  refuse_tile_with_downscale, restage_planar)
 from ..models.base import ICRFModelBase
 
 
@@ -102,11 +103,12 @@ def measure_linearity(dataloader: DataLoader, device, use_uncertainty_weighting:
     expect(icrf_model, ICRFModelBase, "icrf_model", allow_none=True)
     dev = resolve_device(device)
     transforms = normalise_transform_list(gpu_transforms)
+    refuse_tile_with_downscale(tile, transforms)
     for _, val_batch, std_batch, meta_batch in dataloader:
         images, max_code, layout = stage_images(val_batch, dev, transforms, want_layout=True)
         std, std_mode, std_value = std_arguments(std_batch, dataloader.dataset, dev)
         if std is not None and layout != "nchw":  # explicit uncertainty images are planar
-            images, max_code, layout = stage_images(images, dev, transforms) + ("nchw",)
+            images, max_code, layout = restage_planar(val_batch, images, dev, transforms)
         exposures = meta_batch["exposure_time"].to(torch.float64)
         i_idx, j_idx, ratio = get_valid_exposure_pairs(exposures, 0.2)
         pairs = ops.PairList(i_idx, j_idx, ratio, images.shape[0], dev)

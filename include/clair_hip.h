@@ -321,6 +321,17 @@ int ct_video_stats_batch(const void *frames_dev, int32_t dtype, float max_code, 
                          const ct_icrf *icrf, float frames_before, float *mean_state_dev, float *m2_state_dev,
                          void *stream);
 
+/*
+ * ct_strided_downscale -- StridedDownscale (clair_torch/common/transforms.py:194-216), x[..., ::step, ::step], on a
+ * contiguous stack in its own element type and layout, so that the code-domain kernels above run on the compacted codes:
+ *   dst[p][i][j][e] = src[p][i*step][j*step][e],  i < ceil(h/step), j < ceil(w/step), e < pixel_elems
+ * Planar (B, C, H, W): n_planes = B*C, pixel_elems = 1.  Interleaved (B, H, W, C): n_planes = B, pixel_elems = C (the
+ * channel order is untouched).  elem_bytes 1, 2 or 4; src_dev / dst_dev aligned to it, dst_dev dense
+ * (n_planes, ceil(h/step), ceil(w/step), pixel_elems).  Reads nothing outside src's n_planes*h*w*pixel_elems elements.
+ */
+int ct_strided_downscale(const void *src_dev, void *dst_dev, int32_t elem_bytes, int64_t n_planes, int64_t h, int64_t w,
+                         int32_t pixel_elems, int32_t step, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
