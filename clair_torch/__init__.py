@@ -4,8 +4,8 @@ run_linearity_measurement.py) resolve to the MI355X implementation in ``clair_to
 
 Only the hot-path modules exist here (the table below).  Everything else the scripts import --
 ``clair_torch.common.parameters``, ``.file_settings``, ``clair_torch.datasets.image_dataset``, ``clair_torch.metadata``,
-``save_image`` / ``load_image`` of ``clair_torch.common.data_io`` -- is file I/O, configuration and filename parsing that
-this build does not re-implement.  Those names resolve in exactly one situation: a reference install is importable
+``load_image`` of ``clair_torch.common.data_io`` (``save_image`` is provided) -- is file decoding, configuration and
+filename parsing that this build does not re-implement.  Those names resolve in exactly one situation: a reference install is importable
 further down ``sys.path`` (or named by ``CLAIR_TORCH_REFERENCE``).  Then this package acts as an OVERLAY:
   * a module this package does not provide is loaded from the reference's file of the same dotted name;
   * an attribute missing from a module this package does provide (``load_image`` in ``common.data_io``) is taken from

@@ -25,7 +25,7 @@ EXPORTS = ("ct_abi_version", "ct_error_string", "ct_hdr_merge_batch", "ct_hdr_me
            "ct_flatfield_apply", "ct_video_stats_batch", "ct_dark_field_blur", "ct_hdr_merge_kernel_name",
            "ct_merge_set_retry_counter", "ct_norm_constants", "ct_index_constants", "ct_pivot_index_constants",
            "ct_pivot_floor_constants", "ct_pivot_interval_constants", "ct_band_stats", "ct_band_stats_workspace",
-           "ct_strided_downscale")
+           "ct_strided_downscale", "ct_export_cv")
 
 
 class Geometry(ctypes.Structure):
@@ -106,6 +106,8 @@ def load():
     lib.ct_band_stats.argtypes = [vp, vp, i32, i64, vp, i64, vp, vp]
     lib.ct_strided_downscale.restype = i32
     lib.ct_strided_downscale.argtypes = [vp, vp, i32, i64, i64, i64, i32, i32, vp]
+    lib.ct_export_cv.restype = i32
+    lib.ct_export_cv.argtypes = [vp, i32, vp, i32, i64, i32, i64, i32, vp]
     lib.ct_video_stats_batch.restype = i32
     lib.ct_video_stats_batch.argtypes = [vp, i32, f32, i32, gp, ip, f32, vp, vp, vp]
     if lib.ct_abi_version() != ABI_VERSION:

@@ -34,14 +34,17 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
     ``output_layout`` (extension): "planar" = the reference's (C,H,W); "input" = when the frames are ingested interleaved
     (``gpu_transforms`` starting with CvToTorch on raw (H,W,3) frames), leave mean and uncertainty in that (H,W,C) order and
     channel sequence -- what ``cv2.imwrite`` takes; the kernel then stores dense packets (CT_MERGE_OUT_AS_INPUT).  Not
-    combinable with flat-field / dark-field correction, whose kernels work on planar data.
+    combinable with flat-field / dark-field correction, whose kernels work on planar data.  "cv" = the arrays the
+    reference's ``save_image`` writes, made on the device by ``ops.export_cv`` from the "planar" result after every
+    correction: mean float64 and std float32 as (H,W,C) with a 3-channel image reversed to BGR, (H,W) for one channel;
+    works with every ingest form, with flat-field / dark-field correction and with ``tile`` (a band exports its own rows).
     ``reference_order`` (extension): how the uncertainty is evaluated.  None = the library's default -- LOOKUP and CATMULL
     with uncertainties follow the reference's own float32 autograd order (within 1e-5 of what the reference computes, 4-5x
     the time), LINEAR / no model the closed form; False = the closed-form kernels in every mode (better conditioned than the
     reference, up to 4e-5 away from it on single pixels in those two modes); True = reference order in every mode.
     """
-    if output_layout not in ("planar", "input"):
-        raise ValueError(f"unknown output_layout {output_layout!r} (planar, input)")
+    if output_layout not in ("planar", "input", "cv"):
+        raise ValueError(f"unknown output_layout {output_layout!r} (planar, input, cv)")
     if output_layout == "input" and (flat_field_dataset is not None or dark_field_dataset is not None):
         raise ValueError('output_layout="input" cannot be combined with flat-field / dark-field correction')
     expect(dataloader, DataLoader, "dataloader")
@@ -110,9 +113,19 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
         if last:
             flush(True)
     if flat_field_dataset is not None:
-        return _flat_field_epilogue(state, flat_field_dataset, dataloader.dataset, dev, tile, group)
-    mean, std = result
-    return mean.squeeze(), (std.squeeze() if std is not None else None)
+        mean, std = _flat_field_epilogue(state, flat_field_dataset, dataloader.dataset, dev, tile, group)
+    else:
+        mean, std = result
+        mean, std = mean.squeeze(), (std.squeeze() if std is not None else None)
+    if output_layout == "cv":
+        mean, std = _export_cv(mean), (_export_cv(std) if std is not None else None)
+    return mean, std
+
+
+def _export_cv(planar):
+    """The squeezed planar result in OpenCV order; squeezed to fewer than two axes (a 1-pixel-high image) it has no
+    channel axis left to move and stays as it is."""
+    return ops.export_cv(planar.contiguous()) if planar.ndim in (2, 3) else planar
 
 
 def _flat_field_epilogue(state, flat_field_dataset, main_dataset, dev, tile, group):

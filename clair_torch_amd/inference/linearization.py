@@ -12,6 +12,10 @@ LINEAR / LOOKUP std bit for bit -- but the frames move through a three-stage pip
       -> device-to-host copies of (lin, std) into pinned host tensors on a second copy stream
       -> each frame is yielded once its group's copy event has completed; the next groups are already in flight.
 
+``output_layout="cv"`` (extension): every yielded pair is in the order the reference's ``save_image`` writes -- (H,W,C),
+a 3-channel frame reversed to BGR -- made by two ct_export_cv launches per group before the device-to-host copy, which
+then carries the final bytes.
+
 Ownership: the yielded tensors are CPU tensors (pinned, from PyTorch's caching host allocator) that belong to the caller,
 like the reference's ``.cpu()`` results; the pipeline never writes to them again.
 """
@@ -32,7 +36,9 @@ _SLOTS = 3                # ring slots = groups in flight (copy-in | compute | c
 
 
 def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRFModelBase, flatfield_dataset=None,
-                                gpu_transforms=None, dark_field_dataset=None):
+                                gpu_transforms=None, dark_field_dataset=None, output_layout: str = "planar"):
+    if output_layout not in ("planar", "cv"):
+        raise ValueError(f"unknown output_layout {output_layout!r} (planar, cv)")
     expect(dataloader, DataLoader, "dataloader")
     expect(device, (str, torch.device), "device")
     expect(icrf_model, ICRFModelBase, "icrf_model")
@@ -68,12 +74,13 @@ def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRF
     if first[2] is not None and layout != "nchw":  # explicit uncertainty images are planar: generic route
         streamable = False
     if not streamable:
-        yield from _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat, flat_std, dark)
+        yield from _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat, flat_std, dark,
+                                   output_layout == "cv")
         return
-    yield from _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, max_code, layout)
+    yield from _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, max_code, layout, output_layout == "cv")
 
 
-def _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat, flat_std, dark):
+def _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat, flat_std, dark, cv):
     item = first
     while item is not None:
         index_batch, val_batch, std_batch, meta_batch = item
@@ -88,6 +95,8 @@ def _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat
                                                 max_code=max_code, want_std=True, layout=layout)
         if flat is not None:  # linearization.py:118-130: mean is a constant, the image term is not rescaled
             ops.flatfield_correct(lin, lin_std, flat, flat_std, input_is_variance=False, through_mean=False)
+        if cv:
+            lin, lin_std = ops.export_cv(lin.contiguous()), ops.export_cv(lin_std.contiguous())
         yield lin.squeeze().cpu(), lin_std.squeeze().cpu(), meta_batch
         item = next(items, None)
 
@@ -95,16 +104,19 @@ def _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat
 class _Slot:
     """One ring slot: device buffers for a group of frames and the events that order its three stages."""
 
-    def __init__(self, group, frame_shape, dtype, with_std, chw, dev):
+    def __init__(self, group, frame_shape, dtype, with_std, chw, dev, cv):
         self.frames = torch.empty((group,) + tuple(frame_shape), dtype=dtype, device=dev)
         self.std = torch.empty((group,) + tuple(frame_shape), dtype=torch.float32, device=dev) if with_std else None
         self.lin_out = torch.empty((group,) + tuple(chw), dtype=torch.float32, device=dev)
         self.std_out = torch.empty_like(self.lin_out)
+        # output_layout="cv": the (group, H, W, C) exports the device-to-host copy reads instead
+        self.lin_cv = torch.empty((group, chw[1], chw[2], chw[0]), dtype=torch.float32, device=dev) if cv else None
+        self.std_cv = torch.empty_like(self.lin_cv) if cv else None
         self.copied_in, self.computed, self.copied_out = (torch.cuda.Event() for _ in range(3))
         self.busy = False
 
 
-def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, max_code, layout):
+def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, max_code, layout, cv):
     # Memory note for consumers: the yielded CPU tensors of one group (up to _GROUP_BYTES = 256 MB of output, 5 frames of
     # 1080p RGB) are views of two pinned host tensors, so keeping ONE frame alive keeps its group's pinned pages, and
     # list(generator) page-locks the whole output.  The reference hands out independent pageable .cpu() copies; copying
@@ -117,7 +129,7 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, max_c
     group = max(1, min(16, _GROUP_BYTES // out_bytes))
     std_probe, std_mode, std_value = std_arguments(first[2], dataloader.dataset, torch.device("cpu"))
     with_std = std_probe is not None
-    slots = [_Slot(group, frame_shape, probe.dtype, with_std, chw, dev) for _ in range(_SLOTS)]
+    slots = [_Slot(group, frame_shape, probe.dtype, with_std, chw, dev, cv) for _ in range(_SLOTS)]
     compute = torch.cuda.current_stream(dev)
     h2d, d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
     in_flight = deque()  # (slot, n frames, pinned lin, pinned std, metas)
@@ -161,6 +173,9 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, max_c
                                             layout=layout, out=(slot.lin_out[:k], slot.std_out[:k]))
         if flat is not None:  # linearization.py:118-130
             ops.flatfield_correct(lin, lin_std, flat, flat_std, input_is_variance=False, through_mean=False)
+        if cv:
+            lin = ops.export_cv(lin, out=slot.lin_cv[:k])
+            lin_std = ops.export_cv(lin_std, out=slot.std_cv[:k])
         slot.computed.record(compute)
         with torch.cuda.stream(d2h):
             d2h.wait_event(slot.computed)

@@ -662,6 +662,57 @@ def strided_downscale(stack: torch.Tensor, step: int, layout: str = "nchw", out:
     return out
 
 
+# ---- export of planar results in OpenCV order (the device half of save_image) ------------------------------------
+_EXPORT_DTYPES = (torch.float32, torch.float64)
+
+
+def export_shape(shape):
+    """Shape ``export_cv`` gives for an input of ``shape``: (H,W) -> (H,W), (C,H,W) -> (H,W,C), (F,C,H,W) -> (F,H,W,C)."""
+    if len(shape) == 2:
+        return tuple(shape)
+    if len(shape) == 3:
+        return shape[1], shape[2], shape[0]
+    if len(shape) == 4:
+        return shape[0], shape[2], shape[3], shape[1]
+    raise ValueError(f"x must be (H, W), (C, H, W) or (F, C, H, W), got shape {tuple(shape)}")
+
+
+def export_cv(x: torch.Tensor, dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None):
+    """ct_export_cv: the array the reference's ``save_image`` hands to ``cv.imwrite`` (data_io.py:228-234), made on the
+    device.  ``x``: a contiguous float32 / float64 device tensor (H,W), (C,H,W) or (F,C,H,W); the result is (H,W) (a cast
+    only), (H,W,C) or (F,H,W,C) in ``dtype`` (float32, float64, None = that of ``x``), with the channels reversed iff
+    C == 3 (RGB -> BGR).  Casts are numpy's ``astype``; the same dtype is a bit copy.  ``out``: a contiguous caller tensor
+    of exactly that shape and dtype to write into."""
+    _require_device(x, "x")
+    if x.dtype not in _EXPORT_DTYPES:
+        raise TypeError(f"x dtype {x.dtype} unsupported (float32 or float64)")
+    if dtype is None:
+        dtype = x.dtype
+    if dtype not in _EXPORT_DTYPES:
+        raise TypeError(f"dtype {dtype} unsupported (torch.float32, torch.float64 or None)")
+    shape = export_shape(tuple(x.shape))
+    if not x.is_contiguous():
+        raise ValueError("x must be contiguous")
+    if out is not None:
+        _require_device(out, "out")
+        if tuple(out.shape) != shape or out.dtype != dtype or out.device != x.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {dtype} tensor of shape {shape} on {x.device}")
+    else:
+        out = torch.empty(shape, dtype=dtype, device=x.device)
+    if out.numel() == 0:
+        return out
+    if x.ndim == 2:
+        images, channels, plane = 1, 1, x.numel()
+    else:
+        channels, plane = x.shape[-3], x.shape[-2] * x.shape[-1]
+        images = x.shape[0] if x.ndim == 4 else 1
+    with torch.cuda.device(x.device):
+        rc = nv.load().ct_export_cv(_ptr(x), int(x.dtype == torch.float64), _ptr(out), int(dtype == torch.float64), images,
+                                    channels, plane, int(channels == 3), _stream(x.device))
+    nv.check(rc, "ct_export_cv")
+    return out
+
+
 # ---- streaming video statistics -----------------------------------------------------------------------------------
 def video_stats_batch(frames: torch.Tensor, mean_state: torch.Tensor, m2_state: torch.Tensor, frames_before: int, *,
                       lut: Optional[torch.Tensor] = None, interp: Optional[str] = None,

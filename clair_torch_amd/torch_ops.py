@@ -17,6 +17,7 @@ and pair lists are passed as their component tensors / scalars.
                                                max_code) -> (C, L) float64
 
     torch.ops.clair_hip.strided_downscale(stack, step, layout) -> Tensor   (x[..., ::step, ::step], same dtype / layout)
+    torch.ops.clair_hip.export_cv(x, to_f64) -> Tensor   (planar result -> the (H,W,C) BGR array save_image writes)
 
 CPU tensors are refused by the kernels' front-end exactly as through ``ops`` (there is no CPU path).
 """
@@ -161,3 +162,14 @@ def strided_downscale(stack: torch.Tensor, step: int, layout: str = "nchw") -> t
 @strided_downscale.register_fake
 def _(stack, step, layout="nchw"):
     return stack.new_empty(ops.downscaled_shape(stack.shape, step, layout))
+
+
+@torch.library.custom_op(f"{_LIB}::export_cv", mutates_args=())
+def export_cv(x: torch.Tensor, to_f64: bool) -> torch.Tensor:
+    """ct_export_cv: a planar (H,W) / (C,H,W) / (F,C,H,W) result in OpenCV order, float64 or float32."""
+    return ops.export_cv(x, torch.float64 if to_f64 else torch.float32)
+
+
+@export_cv.register_fake
+def _(x, to_f64):
+    return x.new_empty(ops.export_shape(tuple(x.shape)), dtype=torch.float64 if to_f64 else torch.float32)

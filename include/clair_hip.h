@@ -332,6 +332,18 @@ int ct_video_stats_batch(const void *frames_dev, int32_t dtype, float max_code, 
 int ct_strided_downscale(const void *src_dev, void *dst_dev, int32_t elem_bytes, int64_t n_planes, int64_t h, int64_t w,
                          int32_t pixel_elems, int32_t step, void *stream);
 
+/*
+ * ct_export_cv -- the array save_image hands to cv.imwrite (clair_torch/common/data_io.py:228-234: astype, transpose to
+ * (H, W, C), channel reversal of a 3-channel image), made on the device from planar results:
+ *   dst[f][p][c'] = (dst type) src[f][c][p],  p < plane = H*W,  c' = channels-1-c when reverse_channels, else c
+ *   src_dev (n_images, channels, plane), dst_dev (n_images, plane, channels), float32 or float64 each (*_is_f64), dense,
+ *   aligned to their element only (an interior slice of a larger buffer is fine).
+ * Casts round to nearest even and keep subnormals (float64 -> float32 as numpy's astype); the same type is a bit copy.
+ * Touches nothing outside n_images*channels*plane elements of either side; an empty input is CT_OK without a launch.
+ */
+int ct_export_cv(const void *src_dev, int32_t src_is_f64, void *dst_dev, int32_t dst_is_f64, int64_t n_images,
+                 int32_t channels, int64_t plane, int32_t reverse_channels, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
