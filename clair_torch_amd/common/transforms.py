@@ -1,12 +1,22 @@
 """The reference's transform classes (clair_torch/common/transforms.py:68-216; ``to_config`` / ``from_config`` and the
 YAML registry are not part of this build).
 
-``compute_hdr_image`` / ``linearize_dataset_generator`` recognise the pair ``[CastTo(float32), Normalize(max, 0)]`` in
-``gpu_transforms`` applied to integer codes and fold it into the kernels' load stage -- optionally behind a leading
-``CvToTorch`` (raw OpenCV frames, folded into the kernels' addressing) and with one ``StridedDownscale`` anywhere after
-that (the raw codes are compacted by ct_strided_downscale first); any other transform list is executed with these
-classes' ``__call__`` (plain PyTorch ops on the device) before the float32 kernel variant runs.
+The entry points stage a batch through one of three routes (inference/_staging.py):
+
+- code route: ``[CastTo(float32), Normalize(max, 0)]`` applied to integer codes is folded into the kernels' load stage --
+  optionally behind a leading ``CvToTorch`` (raw OpenCV frames, folded into the kernels' addressing) and with one
+  ``StridedDownscale`` anywhere after that (the raw codes are compacted by ct_strided_downscale first);
+- fused ingest (``fusable_ingest``): any other chain of ``CastTo(float32)``, up to four ``Normalize(max, min, range)`` /
+  ``ClampAlongDims`` (one pair, or one per channel) stages, an optional leading ``CvToTorch`` and at most one
+  ``StridedDownscale`` is evaluated by ct_ingest_transform in one pass, bit for bit what these classes give on the CPU,
+  and the float32 kernel variant runs on its planar result;
+- torch route: everything else -- a data-dependent ``Normalize`` (``max_val`` or ``min_val`` None), casts to another
+  dtype or device, clamps over a non-channel dim, more than four stages, other transform classes, non-contiguous or
+  non-4-D batches -- is executed with these classes' ``__call__`` (plain PyTorch ops on the device) before the float32
+  kernel variant runs.
 """
+import ctypes
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
@@ -47,8 +57,9 @@ class TorchToCv(BaseTransform):
 
 class ClampAlongDims(BaseTransform):
     """Clamp between one (min, max) pair, or one pair per slice along ``dim`` (reference transforms.py:137-157).  A clamp
-    bound is in general not a representable code / max_code, so a list holding this transform runs on the generic
-    route (torch ops, float32 kernel variant) and is never folded."""
+    bound is in general not a representable code / max_code, so a list holding this transform never takes the code
+    route; with one pair, or one pair per channel (``dim`` 1 / -3 of the planar view, at most 4 channels), it is a stage
+    of the fused ingest (``fusable_ingest``), otherwise it runs as a torch op."""
 
     def __init__(self, dim, min_max_pairs):
         expect(dim, (int, tuple), "dim")
@@ -91,7 +102,8 @@ class Normalize(BaseTransform):
     """(x - min) / (max - min) * span + min_t (reference general_functions.py:359-388).  Executed as a torch op on a
     GPU tensor the division by a scalar is a multiplication by its reciprocal (torch's GPU kernels), 1 ulp away from
     the CPU result for some codes; when the kernels fold this transform (integer codes, see
-    ``fusable_code_normalisation``) they reproduce the CPU reference's correctly rounded division instead."""
+    ``fusable_code_normalisation``) or the fused ingest evaluates it (``max_val`` and ``min_val`` both given, see
+    ``fusable_ingest``) the CPU reference's correctly rounded division is reproduced instead."""
 
     def __init__(self, max_val: Optional[float] = None, min_val: Optional[float] = None, target_range=(0.0, 1.0)):
         self.max_val, self.min_val, self.target_range = max_val, min_val, tuple(target_range)
@@ -163,3 +175,83 @@ def fusable_downscale(transforms, images: Optional[torch.Tensor] = None):
     if fusable_code_normalisation(probe, tail) is None:
         return None, ts
     return ts[k].step_size, rest
+
+
+@dataclass(frozen=True)
+class IngestPlan:
+    """What ``fusable_ingest`` recognised: the stack's memory ``layout`` ("nchw", or "nhwc_bgr" for raw frames behind a
+    leading CvToTorch), the StridedDownscale ``step`` to apply to the raw stack first (1 = none) and the arithmetic
+    ``stages`` in list order, as ``ops.ingest_transform`` takes them: ("affine", sub, div, mul, add) for a Normalize,
+    ("clamp", [(lo, hi), ...]) with one pair or one per channel for a ClampAlongDims."""
+    layout: str
+    step: int
+    stages: tuple
+
+
+INGEST_MAX_STAGES, INGEST_MAX_CHANNELS = 4, 4
+
+
+def _is_number(v) -> bool:
+    return isinstance(v, (int, float)) and not isinstance(v, bool)
+
+
+def _clamp_stage(t: ClampAlongDims, channels: int):
+    pairs = t.min_max_pairs
+    if isinstance(pairs, tuple):  # one pair for every element, whatever dim says (clamp_along_dims)
+        if len(pairs) != 2 or not all(_is_number(v) for v in pairs):
+            return None
+        return "clamp", [(pairs[0], pairs[1])]
+    dim = t.dim[0] if isinstance(t.dim, tuple) and len(t.dim) == 1 else t.dim
+    if isinstance(dim, bool) or not isinstance(dim, int) or dim not in (1, -3):
+        return None
+    if len(pairs) != channels or channels > INGEST_MAX_CHANNELS:  # a wrong count raises on the torch route, as ever
+        return None
+    if not all(isinstance(p, (tuple, list)) and len(p) == 2 and all(_is_number(v) for v in p) for p in pairs):
+        return None
+    return "clamp", [(p[0], p[1]) for p in pairs]
+
+
+def fusable_ingest(images: torch.Tensor, transforms) -> Optional[IngestPlan]:
+    """An ``IngestPlan`` when ct_ingest_transform can evaluate ``transforms`` on the 4-D batch ``images`` in one pass,
+    else None (the list then runs as torch ops).  Recognised: an optional leading CvToTorch on (B,H,W,3) uint8 / uint16
+    frames (``fusable_layout``); at most one StridedDownscale(step >= 1) anywhere after it (selecting pixels commutes
+    with per-pixel stages, so the raw stack is compacted first); CastTo(float32, device=None), required before the first
+    arithmetic stage of an integer batch and the identity afterwards; and one to four arithmetic stages, each a
+    Normalize with ``max_val`` and ``min_val`` given (a zero range is left to the torch route, which raises) or a
+    ClampAlongDims with a single (min, max) tuple or a list of C <= 4 pairs along the channel axis (``dim`` 1 or -3).
+    The constants are formed as ``Normalize.__call__`` forms them (``max - min`` and ``hi - lo`` in Python's own
+    arithmetic); the kernel rounds them to float32 as torch does a Python scalar."""
+    if images.ndim != 4 or images.dtype not in (torch.uint8, torch.uint16, torch.float32) or not images.is_contiguous():
+        return None
+    layout, ts = fusable_layout(images, transforms)
+    channels = images.shape[1] if layout == "nchw" else 3
+    is_float, step, stages = images.dtype == torch.float32, None, []
+    for t in ts:
+        if type(t) is StridedDownscale:
+            if step is not None or t.step_size < 1:
+                return None
+            step = t.step_size
+        elif type(t) is CastTo:
+            if t.data_type != torch.float32 or t.device is not None:
+                return None
+            is_float = True
+        elif type(t) is Normalize:
+            if not is_float or not _is_number(t.max_val) or not _is_number(t.min_val):
+                return None
+            lo, hi = t.target_range if len(t.target_range) == 2 else (None, None)
+            if not _is_number(lo) or not _is_number(hi):
+                return None
+            den = t.max_val - t.min_val
+            if den == 0 or ctypes.c_float(den).value == 0.0:  # (a range that only float32 rounds to zero divides by it)
+                return None
+            stages.append(("affine", t.min_val, den, hi - lo, lo))
+        elif type(t) is ClampAlongDims:
+            stage = _clamp_stage(t, channels) if is_float else None
+            if stage is None:
+                return None
+            stages.append(stage)
+        else:
+            return None
+    if not is_float or not 1 <= len(stages) <= INGEST_MAX_STAGES:
+        return None
+    return IngestPlan(layout, 1 if step is None else step, tuple(stages))

@@ -4,7 +4,8 @@ from typing import Iterable, Optional
 import torch
 
 from .. import ops
-from ..common.transforms import StridedDownscale, fusable_code_normalisation, fusable_downscale, fusable_layout
+from ..common.transforms import (StridedDownscale, fusable_code_normalisation, fusable_downscale, fusable_ingest,
+                                 fusable_layout)
 
 
 def resolve_device(device) -> torch.device:
@@ -33,7 +34,10 @@ def stage_images(val_batch: torch.Tensor, device: torch.device, transforms: list
     With ``want_layout`` a third value is returned: "nhwc_bgr" when the list additionally starts with CvToTorch
     on raw (B,H,W,3) frames (the kernel then reads the interleaved BGR frames as they are), else "nchw".
     One StridedDownscale in such a list (``fusable_downscale``) keeps the code route: the raw codes are compacted on
-    the device in their own dtype and layout, and the smaller integer stack is returned."""
+    the device in their own dtype and layout, and the smaller integer stack is returned.
+    Any other list that ``fusable_ingest`` recognises (a black level, a target range, clamps, ...) is evaluated by
+    ct_ingest_transform in one pass with the reference's CPU arithmetic; the rest runs as torch ops.  Both give
+    float32 planar pixels."""
     images = val_batch.to(device=device, non_blocking=True)  # the ONE host-to-device copy of the batch (a plain DMA when pinned)
     step, rest = fusable_downscale(transforms)
     if step is not None and images.ndim == 4:
@@ -53,6 +57,10 @@ def stage_images(val_batch: torch.Tensor, device: torch.device, transforms: list
     max_code = fusable_code_normalisation(images, transforms)
     if max_code is not None:
         return images, max_code
+    plan = fusable_ingest(images, transforms)
+    if plan is not None:
+        images = ops.strided_downscale(images, plan.step, layout=plan.layout)
+        return ops.ingest_transform(images, plan.stages, layout=plan.layout), None
     for t in transforms:
         images = t(images)
     if images.dtype in (torch.uint8, torch.uint16):

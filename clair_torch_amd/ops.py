@@ -713,6 +713,89 @@ def export_cv(x: torch.Tensor, dtype: Optional[torch.dtype] = None, out: Optiona
     return out
 
 
+# ---- a recognised gpu_transforms chain in one pass (CastTo / Normalize / ClampAlongDims) --------------------------
+def ingest_shape(shape, layout: str = "nchw"):
+    """Shape of the planar (B,C,H,W) stack ``ingest_transform`` gives for a 4-D stack of ``shape`` in ``layout``."""
+    b, d1, d2, d3 = shape
+    return (b, d1, d2, d3) if layout == "nchw" else (b, d3, d1, d2)
+
+
+def _number(v, what):
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise TypeError(f"{what} must be an int or a float, got {v!r}")
+    return float(v)
+
+
+def _ingest_stages(stages, channels: int):
+    """The ct_ingest_stage array of ``stages``: ("affine", sub, div, mul, add) | ("clamp", [(lo, hi)] * (1 or C))."""
+    stages = list(stages)
+    if len(stages) > nv.INGEST_MAX_STAGES:
+        raise ValueError(f"at most {nv.INGEST_MAX_STAGES} stages, got {len(stages)}")
+    arr = (nv.IngestStage * max(len(stages), 1))()
+    for k, st in enumerate(stages):
+        if not isinstance(st, (tuple, list)) or not st or st[0] not in ("affine", "clamp"):
+            raise ValueError(f"stage {k}: expected ('affine', sub, div, mul, add) or ('clamp', pairs), got {st!r}")
+        if st[0] == "affine":
+            if len(st) != 5:
+                raise ValueError(f"stage {k}: ('affine', sub, div, mul, add) takes four constants")
+            sub, div, mul, add = (_number(v, f"stage {k}") for v in st[1:])
+            arr[k].kind, arr[k].sub, arr[k].div, arr[k].mul, arr[k].add = nv.INGEST_AFFINE, sub, div, mul, add
+            if arr[k].div == 0.0:
+                raise ValueError("Normalization range is zero (min == max); cannot normalize.")
+            continue
+        if len(st) != 2 or not isinstance(st[1], (tuple, list)):
+            raise ValueError(f"stage {k}: ('clamp', pairs) takes a list of (lo, hi) pairs")
+        pairs = list(st[1])
+        if len(pairs) not in (1, channels) or (len(pairs) > 1 and channels > nv.INGEST_MAX_CHANNELS):
+            raise ValueError(f"stage {k}: expected 1 or {channels} min/max pairs (at most {nv.INGEST_MAX_CHANNELS} "
+                             f"channels with one pair each), got {len(pairs)}")
+        if len(pairs) == 1:
+            pairs = pairs * nv.INGEST_MAX_CHANNELS
+        pairs += [pairs[-1]] * (nv.INGEST_MAX_CHANNELS - len(pairs))  # unused entries
+        arr[k].kind = nv.INGEST_CLAMP
+        for c, pair in enumerate(pairs):
+            if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+                raise ValueError(f"stage {k}: a clamp pair is (lo, hi), got {pair!r}")
+            arr[k].lo[c], arr[k].hi[c] = _number(pair[0], f"stage {k}"), _number(pair[1], f"stage {k}")
+    return arr, len(stages)
+
+
+def ingest_transform(stack: torch.Tensor, stages, layout: str = "nchw", out: Optional[torch.Tensor] = None):
+    """ct_ingest_transform: the chain CastTo(float32), Normalize(max, min, range), ClampAlongDims evaluated in one pass
+    with the reference's float32 arithmetic (every operation rounded on its own, a correctly rounded division).
+    ``stack``: a contiguous uint8 / uint16 / float32 device stack, (B,C,H,W) for "nchw" or (B,H,W,3) for "nhwc" /
+    "nhwc_bgr"; the result is the planar float32 (B,C,H,W) stack (RGB planes for "nhwc_bgr").  ``stages``: up to 4 of
+    ("affine", sub, div, mul, add) -- ((x - sub) / div) * mul + add, the constants rounded to float32 -- and
+    ("clamp", pairs) with one (lo, hi) pair, or one per channel of the result (C <= 4).  ``out``: a contiguous float32
+    caller tensor of exactly the result's shape to write into."""
+    _require_device(stack, "stack")
+    if stack.ndim != 4:
+        raise ValueError(f"stack must be 4-dimensional, got shape {tuple(stack.shape)}")
+    if stack.dtype not in _DTYPE:
+        raise TypeError(f"stack dtype {stack.dtype} unsupported (uint8, uint16 codes or float32 pixels)")
+    if layout not in _LAYOUT:
+        raise ValueError(f"unknown layout {layout!r} (nchw, nhwc, nhwc_bgr)")
+    if layout != "nchw" and stack.shape[3] != 3:
+        raise ValueError(f"layout {layout!r} takes (B, H, W, 3) frames, got shape {tuple(stack.shape)}")
+    if not stack.is_contiguous():
+        raise ValueError("stack must be contiguous")
+    shape = ingest_shape(tuple(stack.shape), layout)
+    arr, n_stages = _ingest_stages(stages, shape[1])
+    if out is not None:
+        _require_device(out, "out")
+        if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != stack.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on {stack.device}")
+    else:
+        out = torch.empty(shape, dtype=torch.float32, device=stack.device)
+    if out.numel() == 0:
+        return out
+    with torch.cuda.device(stack.device):
+        rc = nv.load().ct_ingest_transform(_ptr(stack), _DTYPE[stack.dtype], _LAYOUT[layout], shape[0], shape[1],
+                                           shape[2] * shape[3], arr, n_stages, _ptr(out), _stream(stack.device))
+    nv.check(rc, "ct_ingest_transform")
+    return out
+
+
 # ---- streaming video statistics -----------------------------------------------------------------------------------
 def video_stats_batch(frames: torch.Tensor, mean_state: torch.Tensor, m2_state: torch.Tensor, frames_before: int, *,
                       lut: Optional[torch.Tensor] = None, interp: Optional[str] = None,

@@ -18,10 +18,12 @@ and pair lists are passed as their component tensors / scalars.
 
     torch.ops.clair_hip.strided_downscale(stack, step, layout) -> Tensor   (x[..., ::step, ::step], same dtype / layout)
     torch.ops.clair_hip.export_cv(x, to_f64) -> Tensor   (planar result -> the (H,W,C) BGR array save_image writes)
+    torch.ops.clair_hip.ingest_transform(stack, stages, layout) -> Tensor   (CastTo / Normalize / ClampAlongDims chain in
+                                  one pass; stages = 13 floats each: kind, sub, div, mul, add, lo[0..3], hi[0..3])
 
 CPU tensors are refused by the kernels' front-end exactly as through ``ops`` (there is no CPU path).
 """
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -173,3 +175,42 @@ def export_cv(x: torch.Tensor, to_f64: bool) -> torch.Tensor:
 @export_cv.register_fake
 def _(x, to_f64):
     return x.new_empty(ops.export_shape(tuple(x.shape)), dtype=torch.float64 if to_f64 else torch.float32)
+
+
+_STAGE_FLOATS = 13  # kind (0 affine, 1 clamp), sub, div, mul, add, lo[0..3], hi[0..3]: ct_ingest_stage, flattened
+
+
+def flatten_ingest_stages(stages, channels: int):
+    """``ops.ingest_transform``'s stage list as the flat float list the custom op takes."""
+    flat = []
+    for st in stages:
+        if st[0] == "affine":
+            flat += [0.0] + [float(v) for v in st[1:5]] + [0.0] * 8
+        else:
+            pairs = list(st[1]) * (4 if len(st[1]) == 1 else 1)
+            pairs += [pairs[-1]] * (4 - len(pairs))
+            flat += [1.0] + [0.0] * 4 + [float(p[0]) for p in pairs[:4]] + [float(p[1]) for p in pairs[:4]]
+    return flat
+
+
+@torch.library.custom_op(f"{_LIB}::ingest_transform", mutates_args=())
+def ingest_transform(stack: torch.Tensor, stages: Sequence[float], layout: str = "nchw") -> torch.Tensor:
+    """ct_ingest_transform: a CastTo(float32) / Normalize / ClampAlongDims chain in one pass, planar float32 result."""
+    if len(stages) % _STAGE_FLOATS != 0:
+        raise ValueError(f"stages holds {_STAGE_FLOATS} floats per stage, got {len(stages)}")
+    channels = ops.ingest_shape(tuple(stack.shape), layout)[1]
+    listed = []
+    for k in range(0, len(stages), _STAGE_FLOATS):
+        kind, sub, div, mul, add = stages[k:k + 5]
+        lo, hi = stages[k + 5:k + 9], stages[k + 9:k + 13]
+        if kind == 0:
+            listed.append(("affine", sub, div, mul, add))
+        else:
+            n = channels if channels <= 4 else 1
+            listed.append(("clamp", [(lo[c], hi[c]) for c in range(n)]))
+    return ops.ingest_transform(stack, listed, layout)
+
+
+@ingest_transform.register_fake
+def _(stack, stages, layout="nchw"):
+    return stack.new_empty(ops.ingest_shape(tuple(stack.shape), layout), dtype=torch.float32)

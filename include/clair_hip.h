@@ -333,6 +333,36 @@ int ct_strided_downscale(const void *src_dev, void *dst_dev, int32_t elem_bytes,
                          int32_t pixel_elems, int32_t step, void *stream);
 
 /*
+ * ct_ingest_transform -- a gpu_transforms chain CastTo(float32), Normalize(max, min, range), ClampAlongDims in one pass
+ * (normalize_tensor, clair_torch/common/general_functions.py:359-388; clamp_along_dims, general_functions.py:392-436; the
+ * transform classes, clair_torch/common/transforms.py:108-157): raw codes or pixels to the planar float32 stack the
+ * float32 kernels above take, bit for bit what those classes give on the CPU.  Up to CT_INGEST_MAX_STAGES stages, in
+ * order, float32, every operation rounded on its own:
+ *   CT_INGEST_AFFINE  t = x - sub; t = t / div; t = t * mul; t = t + add   (sub = fl32(min), div = fl32(max - min),
+ *                     mul = fl32(hi - lo), add = fl32(lo); correctly rounded division; all four always run)
+ *   CT_INGEST_CLAMP   t = min(max(x, lo[c]), hi[c]) as torch.clamp (NaN stays NaN), c = channel of the planar result;
+ *                     one pair for all channels is that pair in all CT_INGEST_MAX_CHANNELS entries
+ *   src_dev  CT_DTYPE_U8 / U16 / F32, dense, aligned to its element: (n_images, channels, plane) for CT_LAYOUT_NCHW,
+ *            (n_images, plane, 3) for CT_LAYOUT_NHWC / NHWC_BGR (BGR: memory channel 2 - c feeds plane c)
+ *   dst_dev  (n_images, channels, plane) float32, dense, aligned to 4 bytes (an interior slice of a buffer is fine)
+ * n_stages = 0 is the cast alone.  CT_ERR_UNSUPPORTED: an interleaved layout with channels != 3; clamp pairs that differ
+ * between channels with channels > CT_INGEST_MAX_CHANNELS.  Touches nothing outside n_images*channels*plane elements of
+ * either side and never writes src; an empty input is CT_OK without a launch.
+ */
+#define CT_INGEST_AFFINE 0
+#define CT_INGEST_CLAMP 1
+#define CT_INGEST_MAX_STAGES 4
+#define CT_INGEST_MAX_CHANNELS 4
+typedef struct {
+    int32_t kind;                       /* CT_INGEST_* */
+    float sub, div, mul, add;           /* AFFINE */
+    float lo[CT_INGEST_MAX_CHANNELS];   /* CLAMP, per channel */
+    float hi[CT_INGEST_MAX_CHANNELS];
+} ct_ingest_stage;
+int ct_ingest_transform(const void *src_dev, int32_t dtype, int32_t layout, int64_t n_images, int32_t channels,
+                        int64_t plane, const ct_ingest_stage *stages, int32_t n_stages, float *dst_dev, void *stream);
+
+/*
  * ct_export_cv -- the array save_image hands to cv.imwrite (clair_torch/common/data_io.py:228-234: astype, transpose to
  * (H, W, C), channel reversal of a 3-channel image), made on the device from planar results:
  *   dst[f][p][c'] = (dst type) src[f][c][p],  p < plane = H*W,  c' = channels-1-c when reverse_channels, else c

@@ -1,0 +1,384 @@
+"""The fused ingest on the device: ct_ingest_transform evaluates CastTo(float32) / Normalize(max, min, range) /
+ClampAlongDims chains in one pass (clair_torch/common/general_functions.py:359-436, transforms.py:108-157).  Its
+specification is the float32 arithmetic of those classes on the CPU, so every comparison here is exact: the bit pattern
+of the kernel's result against the same chain run with the project's classes on the CPU (which
+tests/test_ingest_host.py pins to the reference's recorded output)."""
+import numpy as np
+import pytest
+import torch
+from torch.utils.data import DataLoader
+
+from _util import golden
+
+pytestmark = pytest.mark.gpu
+
+_NP = {torch.uint8: np.uint8, torch.uint16: np.uint16}
+PAIRS = {1: [(0.05, 0.9)], 2: [(0.0, 1.0), (0.125, 0.7)], 3: [(0.0, 1.0), (0.125, 0.7), (-0.25, 0.3333)]}
+# (max, min, target range): the parameter sets of tests/golden/ingest.npz
+PARAMS = {"u8_255_16": (255, 16, (0.0, 1.0)), "u16_65535_256": (65535, 256, (0.0, 1.0)), "u16_4095_64_pm1": (4095, 64, (-1.0, 1.0))}
+CLAMPS3 = [[(0.0, 1.0), (0.125, 0.7), (-0.25, 0.3333)], [(-0.5, 0.5), (0.0, 0.0625), (0.9, 2.0)],
+           [(1e-3, 0.999), (-1.0, -0.5), (0.25, 0.75)]]
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    from clair_torch_amd import _native
+    _native.load()
+    return torch.device("cuda:0")
+
+
+def _T():
+    from clair_torch_amd.common import transforms
+    return transforms
+
+
+def _random(rng, shape, dtype, top=None):
+    if dtype == torch.float32:
+        return torch.from_numpy((rng.random(shape, dtype=np.float32) * 5000.0 - 200.0).astype(np.float32))
+    top = np.iinfo(_NP[dtype]).max if top is None else top
+    return torch.from_numpy(rng.integers(0, top + 1, size=shape).astype(_NP[dtype]))
+
+
+def _bgr_frames(planar):
+    """(B,3,H,W) RGB planes -> the (B,H,W,3) BGR frames an OpenCV reader hands over."""
+    return torch.from_numpy(np.ascontiguousarray(planar.numpy()[:, ::-1].transpose(0, 2, 3, 1)))
+
+
+def _rgb_frames(planar):
+    return torch.from_numpy(np.ascontiguousarray(planar.numpy().transpose(0, 2, 3, 1)))
+
+
+def _cpu_chain(host, transforms):
+    x = host
+    for t in transforms:
+        x = t(x)
+    assert x.dtype == torch.float32 and not x.is_cuda
+    return x.contiguous()
+
+
+def _same_bits(got, want):
+    got = got.cpu() if got.is_cuda else got
+    return got.dtype == want.dtype == torch.float32 and tuple(got.shape) == tuple(want.shape) and \
+        torch.equal(got.contiguous().view(torch.int32), want.contiguous().view(torch.int32))
+
+
+def _plan(images, transforms):
+    plan = _T().fusable_ingest(images, transforms)
+    assert plan is not None, "the list must take the fused route"
+    return plan
+
+
+def _run(dev, host, transforms, layout=None, planar=None):
+    """ops.ingest_transform on ``host`` with the stages the recogniser makes of ``transforms`` -- for ``host`` itself, or,
+    with an explicit ``layout`` the recogniser has no list for (RGB frames), for the ``planar`` form of the same stack."""
+    from clair_torch_amd import ops
+    plan = _plan(host if planar is None else planar, transforms)
+    assert plan.step == 1
+    return ops.ingest_transform(host.to(dev), plan.stages, layout=plan.layout if layout is None else layout)
+
+
+def _chain(params, pairs=None):
+    T = _T()
+    mx, mn, rng = params
+    ts = [T.CastTo("float32"), T.Normalize(mx, mn, rng)]
+    return ts + ([T.ClampAlongDims(1, pairs)] if pairs is not None else [])
+
+
+# ---- every code ------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def all_codes():
+    """uint16 (1,3,128,512): each plane holds all 65 536 codes (plane 0 in order); uint8 (1,3,16,16) likewise."""
+    rng = np.random.default_rng(5)
+    c16 = np.arange(65536, dtype=np.uint16)
+    c8 = np.arange(256, dtype=np.uint8)
+    u16 = np.stack([c16, rng.permutation(c16), c16[::-1]]).reshape(1, 3, 128, 512)
+    u8 = np.stack([c8, rng.permutation(c8), c8[::-1]]).reshape(1, 3, 16, 16)
+    return {torch.uint16: torch.from_numpy(np.ascontiguousarray(u16)), torch.uint8: torch.from_numpy(np.ascontiguousarray(u8))}
+
+
+@pytest.mark.parametrize("layout", ["nchw", "nhwc_bgr"])
+@pytest.mark.parametrize("dtype", [torch.uint8, torch.uint16])
+def test_every_code_is_the_cpu_result(dev, all_codes, dtype, layout):
+    T = _T()
+    planar = all_codes[dtype]
+    host = planar if layout == "nchw" else _bgr_frames(planar)
+    lead = [] if layout == "nchw" else [T.CvToTorch()]
+    g = golden("ingest")
+    for name, params in PARAMS.items():
+        # the division alone, against the CPU classes and against the reference's recorded output
+        ts = _chain(params)
+        got = _run(dev, host, lead + ts)
+        assert _same_bits(got, _cpu_chain(planar, ts)), (name, "normalize")
+        if name.startswith("u8") == (dtype == torch.uint8):
+            want = torch.from_numpy(g[name])
+            assert _same_bits(got[0, 0].reshape(-1), want), (name, "fixture")
+            assert _same_bits(got[0, 2].reshape(-1), want.flip(0)), (name, "fixture, reversed plane")
+        for k, pairs in enumerate(CLAMPS3):
+            ts = _chain(params, pairs)
+            assert _same_bits(_run(dev, host, lead + ts), _cpu_chain(planar, ts)), (name, "clamps", k)
+
+
+# ---- shapes ----------------------------------------------------------------------------------------------------------
+# H*W = 1, 2, 3 (mod 4); planes that are not 16-byte aligned; a packet crossing a plane boundary (2 x 3 x 1 x 3 without a
+# per-channel stage is one plane of 18); widths below one packet; whole packets only (16 x 64); more than one workgroup
+SHAPES = [(1, 1, 1, 1), (2, 3, 1, 3), (2, 3, 5, 7), (1, 2, 3, 6), (3, 3, 16, 64), (1, 3, 9, 131), (2, 3, 37, 53)]
+
+
+@pytest.mark.parametrize("dtype", [torch.uint8, torch.uint16, torch.float32])
+def test_shapes_and_layouts(dev, dtype):
+    T = _T()
+    rng = np.random.default_rng(11)
+    params = (4095, 64, (0.0, 1.0)) if dtype != torch.uint8 else (255, 16, (0.0, 1.0))
+    for shape in SHAPES:
+        planar = _random(rng, shape, dtype)
+        c = shape[1]
+        for ts in (_chain(params, PAIRS[c]), _chain(params), _chain(params) + [T.ClampAlongDims(2, (0.1, 0.8))]):
+            want = _cpu_chain(planar, ts)
+            assert _same_bits(_run(dev, planar, ts), want), (shape, "nchw", len(ts))
+            if c == 3:
+                assert _same_bits(_run(dev, _rgb_frames(planar), ts, "nhwc", planar), want), (shape, "nhwc", len(ts))
+                assert _same_bits(_run(dev, _bgr_frames(planar), ts, "nhwc_bgr", planar), want), (shape, "nhwc_bgr", len(ts))
+                if dtype != torch.float32:  # raw frames through the recogniser
+                    assert _same_bits(_run(dev, _bgr_frames(planar), [T.CvToTorch()] + ts), want), (shape, "CvToTorch")
+
+
+@pytest.mark.parametrize("layout", ["nchw", "nhwc_bgr"])
+@pytest.mark.parametrize("dtype", [torch.uint8, torch.uint16, torch.float32])
+def test_out_is_an_unaligned_interior_slice(dev, dtype, layout):
+    from clair_torch_amd import ops
+    rng = np.random.default_rng(3)
+    params = (4095, 64, (0.0, 1.0)) if dtype != torch.uint8 else (255, 16, (0.0, 1.0))
+    ts = _chain(params, PAIRS[3])
+    sentinel = -7.25
+    for shape in [(2, 3, 5, 7), (3, 3, 16, 64), (1, 3, 9, 131)]:
+        planar = _random(rng, shape, dtype)
+        host = planar if layout == "nchw" else _bgr_frames(planar)
+        want = _cpu_chain(planar, ts)
+        stages = _plan(planar, ts).stages
+        x = host.to(dev)
+        n, trail = want.numel(), 37
+        for lead in (1, 2, 3, 5):
+            buf = torch.full((lead + n + trail,), sentinel, dtype=torch.float32, device=dev)
+            out = buf[lead:lead + n].view(shape)
+            assert ops.ingest_transform(x, stages, layout=layout, out=out) is out
+            flat = buf.cpu()
+            assert _same_bits(flat[lead:lead + n].view(shape), want), (shape, lead)
+            assert bool((flat[:lead] == sentinel).all()) and bool((flat[lead + n:] == sentinel).all()), (shape, lead)
+        back = x.cpu()
+        same = back.view(torch.int16) == host.view(torch.int16) if dtype == torch.uint16 else back == host
+        assert bool(same.all()), "the source stack was written to"
+
+
+# ---- float32 inputs --------------------------------------------------------------------------------------------------
+def test_float32_special_values(dev):
+    T = _T()
+    tiny = np.float32(1e-45)
+    special = np.array([0.0, -0.0, tiny, -tiny, 1.1754942e-38, -1.1754942e-38, 1.17549435e-38, np.inf, -np.inf, np.nan,
+                        -np.nan, 3.4028235e38, -3.4028235e38, 0.5, -0.5, 1.0, 2.0, 0.125, 0.7, 64.0, 4095.0, 1e-30, 16.0],
+                       dtype=np.float32)
+    rng = np.random.default_rng(9)
+    body = (rng.standard_normal(3 * 7 * 23 - 3 * special.size) * 10.0 ** rng.integers(-42, 6, size=3 * 7 * 23 - 3 * special.size))
+    vals = np.concatenate([special, special[::-1], special, body.astype(np.float32)])
+    planar = torch.from_numpy(rng.permutation(vals).astype(np.float32).reshape(1, 3, 7, 23))
+    assert bool(torch.isnan(planar).any()) and bool(torch.isinf(planar).any())
+    lists = [[T.ClampAlongDims(1, PAIRS[3])], [T.ClampAlongDims(0, (0.0, 1.0))], [T.ClampAlongDims(0, (-0.0, 0.0))],
+             [T.Normalize(1.0, 0.0)], [T.Normalize(4095, 64)], [T.Normalize(1e-38, 0.0)], [T.Normalize(3e38, 0.0)],
+             [T.Normalize(2.0, 1e-40, (-1.0, 1.0)), T.ClampAlongDims(1, PAIRS[3])],
+             [T.CastTo("float32"), T.ClampAlongDims(-3, PAIRS[3]), T.Normalize(0.5, 0.0, (0.0, 1e-38))]]
+    for k, ts in enumerate(lists):
+        want = _cpu_chain(planar, ts)
+        for layout, host in (("nchw", planar), ("nhwc", _rgb_frames(planar)), ("nhwc_bgr", _bgr_frames(planar))):
+            got = _run(dev, host, ts, layout, planar).cpu()
+            nan = torch.isnan(want)
+            assert torch.equal(torch.isnan(got), nan), (k, layout, "NaN positions")
+            assert _same_bits(torch.where(nan, torch.zeros_like(got), got), torch.where(nan, torch.zeros_like(want), want)), (k, layout)
+
+
+# ---- stage order and count, through the recogniser and stage_images ------------------------------------------------------
+def _staged(dev, host, transforms, want_layout=False):
+    from clair_torch_amd.inference._staging import stage_images
+    out = stage_images(host, dev, transforms, want_layout=want_layout)
+    assert out[1] is None and out[0].dtype == torch.float32 and out[0].is_contiguous() and out[0].is_cuda
+    assert not want_layout or out[2] == "nchw"
+    return out[0]
+
+
+def test_stage_order_and_count(dev):
+    T = _T()
+    rng = np.random.default_rng(13)
+    planar = _random(rng, (2, 3, 9, 21), torch.uint16, top=5000)
+    cast = T.CastTo("float32")
+    n1, n2 = T.Normalize(4095, 64), T.Normalize(0.9, 0.1, (-1.0, 1.0))
+    code_clamp = T.ClampAlongDims(1, [(64.0, 4095.0), (100.0, 3000.5), (0.0, 2047.0)])
+    lists = [[cast, code_clamp, n1, T.ClampAlongDims(1, PAIRS[3])],          # clamp -> normalize -> clamp
+             [cast, n1, n2],                                                  # two normalizes
+             [cast, code_clamp, n1, T.ClampAlongDims((1,), PAIRS[3]), n2],    # four stages
+             [cast, n1, T.ClampAlongDims(0, (0.25, 0.75))],                   # a single pair, dim 0
+             [cast, n1, cast, T.ClampAlongDims(-3, PAIRS[3])]]
+    for k, ts in enumerate(lists):
+        _plan(planar, ts)
+        want = _cpu_chain(planar, ts)
+        assert _same_bits(_staged(dev, planar, ts), want), k
+        assert _same_bits(_staged(dev, planar, ts, want_layout=True), want), k
+    # five stages: the torch route, as before.  No bit-exactness is promised there: each of its 12 float32 operations is
+    # within 1 ulp (6e-8 of a magnitude below 8) of the CPU's, and the two trailing normalizes amplify by 2.5 each
+    five = [cast, code_clamp, n1, T.ClampAlongDims(1, PAIRS[3]), n2, n2]
+    assert T.fusable_ingest(planar, five) is None
+    assert torch.allclose(_staged(dev, planar, five).cpu(), _cpu_chain(planar, five), rtol=0, atol=12 * 8 * 6e-8 * 6.25)
+
+
+@pytest.mark.parametrize("s", [2, 3])
+def test_with_strided_downscale(dev, s):
+    T = _T()
+    from clair_torch_amd.inference._staging import restage_planar
+    rng = np.random.default_rng(17 + s)
+    planar = _random(rng, (3, 3, 18, 34), torch.uint16, top=5000)
+    raw = _bgr_frames(planar)
+    cast, norm, clamp, sd, cv = T.CastTo("float32"), T.Normalize(4095, 64), T.ClampAlongDims(1, PAIRS[3]), T.StridedDownscale(s), T.CvToTorch()
+    want = _cpu_chain(planar, [cast, norm, clamp])[..., ::s, ::s].contiguous()
+    for k, ts in enumerate([[sd, cast, norm, clamp], [cast, sd, norm, clamp], [cast, norm, sd, clamp], [cast, norm, clamp, sd]]):
+        assert _plan(planar, ts).step == s and _plan(raw, [cv] + ts).layout == "nhwc_bgr"
+        assert _same_bits(_cpu_chain(planar, ts), want)
+        assert _same_bits(_staged(dev, planar, ts), want), (k, "planar")
+        assert _same_bits(_staged(dev, raw, [cv] + ts), want), (k, "raw")
+        assert _same_bits(_staged(dev, raw, [cv] + ts, want_layout=True), want), (k, "raw, want_layout")
+        again, max_code, layout = restage_planar(raw, raw.to(dev), dev, [cv] + ts)
+        assert max_code is None and layout == "nchw" and _same_bits(again, want), (k, "restaged")
+
+
+# ---- end to end -------------------------------------------------------------------------------------------------------
+def _raw_frames_dataset(frames, times, std_hint):
+    """(H,W,3) BGR frames as an OpenCV reader hands them over (StackDataset itself insists on (N,C,H,W))."""
+    from clair_torch_amd.common.enums import MissingStdMode
+    from clair_torch_amd.datasets import StackDataset
+
+    class RawFrames(StackDataset):
+        def __init__(self):
+            self.values, self.stds, self.exposure_times = frames, None, times
+            self.files, self.std_hint = list(range(len(times))), std_hint
+            self.missing_std_mode = MissingStdMode.MULTIPLIER if std_hint else MissingStdMode.NONE
+            self.materialize_std = False
+
+        def __len__(self):
+            return len(self.exposure_times)
+
+    return RawFrames()
+
+
+def _tensors(item):
+    return [t for t in (item if isinstance(item, (tuple, list)) else (item,)) if isinstance(t, torch.Tensor)]
+
+
+def test_entry_points_equal_the_cpu_staged_float_stack(dev):
+    T = _T()
+    from clair_torch_amd.common.enums import InterpMode, MissingStdMode
+    from clair_torch_amd.datasets import StackDataset, custom_collate
+    from clair_torch_amd.inference import compute_hdr_image, linearize_dataset_generator
+    from clair_torch_amd.models import ICRFModelDirect
+    from clair_torch_amd.training.losses import gaussian_value_weights
+    rng = np.random.default_rng(23)
+    ts = [T.CastTo("float32"), T.Normalize(4095, 64), T.ClampAlongDims(1, [(0.0, 1.0), (0.01, 0.95), (0.0, 0.9)])]
+    codes = _random(rng, (8, 3, 16, 24), torch.uint16, top=4500)
+    pixels = _cpu_chain(codes, ts)
+    t = [0.002 * 2.0 ** k for k in range(8)]
+    model = ICRFModelDirect(icrf=torch.stack([torch.linspace(0, 1, 256) ** p for p in (2.2, 2.4, 2.6)]),
+                            interpolation_mode=InterpMode.LINEAR).to(dev)
+    std = dict(missing_std_mode=MissingStdMode.MULTIPLIER, missing_std_value=0.05, materialize_std=False)
+
+    def merge(dataset, transforms):
+        return compute_hdr_image(DataLoader(dataset, batch_size=4, collate_fn=custom_collate), "cuda", model,
+                                 weight_fn=gaussian_value_weights, gpu_transforms=transforms)
+
+    want = merge(StackDataset(pixels, t, **std), None)
+    got = merge(StackDataset(codes, t, **std), ts)
+    assert want[1] is not None and tuple(got[0].shape) == (3, 16, 24)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    got = merge(_raw_frames_dataset(_bgr_frames(codes), t, ("multiplier", 0.05)), [T.CvToTorch()] + ts)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+
+    def linearize(stack, transforms):
+        loader = DataLoader(StackDataset(stack, t[:3], **std), batch_size=1, collate_fn=custom_collate)
+        return list(linearize_dataset_generator(loader, "cuda", model, gpu_transforms=transforms))
+
+    want = linearize(pixels[:3], None)
+    got = linearize(codes[:3], ts)
+    assert len(got) == len(want) == 3
+    for a, b in zip(got, want):
+        ta, tb = _tensors(a), _tensors(b)
+        assert len(ta) == len(tb) >= 2 and all(torch.equal(x, y) for x, y in zip(ta, tb))
+
+    # stage_images itself: planar, and raw (B,H,W,3) frames behind CvToTorch
+    assert _same_bits(_staged(dev, codes, ts), pixels)
+    assert _same_bits(_staged(dev, codes, ts, want_layout=True), pixels)
+    assert _same_bits(_staged(dev, _bgr_frames(codes), [T.CvToTorch()] + ts), pixels)
+    assert _same_bits(_staged(dev, _bgr_frames(codes), [T.CvToTorch()] + ts, want_layout=True), pixels)
+
+
+# ---- front-end checks, the custom op, graph capture ------------------------------------------------------------------------
+def test_front_end_checks_and_custom_op(dev):
+    from clair_torch_amd import ops, torch_ops
+    rng = np.random.default_rng(29)
+    planar = _random(rng, (2, 3, 6, 10), torch.uint16, top=5000)
+    x = planar.to(dev)
+    stages = [("affine", 64, 4031, 1.0, 0.0), ("clamp", PAIRS[3])]
+    want = _cpu_chain(planar, _chain((4095, 64, (0.0, 1.0)), PAIRS[3]))
+    assert _same_bits(ops.ingest_transform(x, stages), want)
+    flat = torch_ops.flatten_ingest_stages(stages, 3)
+    assert _same_bits(torch.ops.clair_hip.ingest_transform(x, flat, "nchw"), want)
+    frames = _bgr_frames(planar).to(dev)
+    assert _same_bits(torch.ops.clair_hip.ingest_transform(frames, flat, "nhwc_bgr"), want)
+    assert _same_bits(ops.ingest_transform(x, []), planar.to(torch.float32))  # no stage: the cast alone
+    empty = ops.ingest_transform(x[:0], stages)
+    assert tuple(empty.shape) == (0, 3, 6, 10) and empty.dtype == torch.float32
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        ops.ingest_transform(planar, stages)
+    with pytest.raises(TypeError):
+        ops.ingest_transform(x.to(torch.float64), stages)
+    with pytest.raises(TypeError):
+        ops.ingest_transform(x.view(torch.int16), stages)
+    with pytest.raises(ValueError):
+        ops.ingest_transform(x[0], stages)
+    with pytest.raises(ValueError):
+        ops.ingest_transform(x, stages, layout="nhwc")              # (B,H,W,3) expected
+    with pytest.raises(ValueError):
+        ops.ingest_transform(x, stages, layout="chwn")
+    with pytest.raises(ValueError):
+        ops.ingest_transform(x.permute(0, 1, 3, 2), stages)          # not contiguous
+    with pytest.raises(ValueError):
+        ops.ingest_transform(x, stages * 3)                          # six stages
+    with pytest.raises(ValueError):
+        ops.ingest_transform(x, [("clamp", PAIRS[2])])               # two pairs for three channels
+    with pytest.raises(ValueError, match="range is zero"):
+        ops.ingest_transform(x, [("affine", 64, 0, 1.0, 0.0)])
+    with pytest.raises(ValueError):
+        ops.ingest_transform(x, [("scale", 2.0)])
+    for bad in (torch.zeros((2, 3, 6, 9), device=dev), torch.zeros((2, 3, 6, 10), device=dev, dtype=torch.float64),
+                torch.zeros((2, 3, 10, 6), device=dev).permute(0, 1, 3, 2)):
+        with pytest.raises(ValueError):
+            ops.ingest_transform(x, stages, out=bad)
+    with pytest.raises(RuntimeError):
+        ops.ingest_transform(x, stages, out=torch.zeros((2, 3, 6, 10)))
+
+
+def test_graph_capture_replays_bit_identically(dev):
+    from clair_torch_amd import ops
+    rng = np.random.default_rng(31)
+    planar = _random(rng, (2, 3, 17, 33), torch.uint16, top=5000)
+    frames = _bgr_frames(planar).to(dev)
+    stages = [("affine", 64, 4031, 2.0, -1.0), ("clamp", PAIRS[3])]
+    eager = ops.ingest_transform(frames, stages, layout="nhwc_bgr")
+    out = torch.empty_like(eager)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream(device=dev)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+        ops.ingest_transform(frames, stages, layout="nhwc_bgr", out=out)  # warm-up on the capture stream
+    side.synchronize()
+    with torch.cuda.graph(graph, stream=side):  # one launch, one stream
+        ops.ingest_transform(frames, stages, layout="nhwc_bgr", out=out)
+    out.zero_()
+    graph.replay()
+    torch.cuda.synchronize()
+    assert _same_bits(out, eager.cpu())
+    assert _same_bits(out, _cpu_chain(planar, [_T().CastTo("float32"), _T().Normalize(4095, 64, (-1.0, 1.0)), _T().ClampAlongDims(1, PAIRS[3])]))
