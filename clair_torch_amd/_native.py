@@ -18,6 +18,7 @@ LAYOUT_NCHW, LAYOUT_NHWC, LAYOUT_NHWC_BGR = 0, 1, 2
 MERGE_FIRST_BATCH, MERGE_FINALIZE, MERGE_MEAN_OUT_F32, MERGE_F64_MOMENTS = 1, 2, 4, 8
 MERGE_REFERENCE_ORDER, MERGE_CLOSED_FORM, MERGE_STD_HINT, MERGE_REQUIRE_ONE_LAUNCH, MERGE_OUT_AS_INPUT = 16, 32, 64, 128, 256
 INGEST_AFFINE, INGEST_CLAMP, INGEST_MAX_STAGES, INGEST_MAX_CHANNELS = 0, 1, 4, 4
+INGEST_AFFINE_DATA, EXTREMA_MIN, EXTREMA_MAX, EXTREMA_MAX_PREFIX = 2, 1, 2, 3
 ERR_NO_GRADIENT_PATH = -4
 
 ABI_VERSION = 3
@@ -26,7 +27,8 @@ EXPORTS = ("ct_abi_version", "ct_error_string", "ct_hdr_merge_batch", "ct_hdr_me
            "ct_flatfield_apply", "ct_video_stats_batch", "ct_dark_field_blur", "ct_hdr_merge_kernel_name",
            "ct_merge_set_retry_counter", "ct_norm_constants", "ct_index_constants", "ct_pivot_index_constants",
            "ct_pivot_floor_constants", "ct_pivot_interval_constants", "ct_band_stats", "ct_band_stats_workspace",
-           "ct_strided_downscale", "ct_export_cv", "ct_ingest_transform")
+           "ct_strided_downscale", "ct_export_cv", "ct_ingest_transform", "ct_ingest_extrema_workspace", "ct_ingest_extrema",
+           "ct_ingest_transform_data")
 
 
 class Geometry(ctypes.Structure):
@@ -116,6 +118,12 @@ def load():
     lib.ct_export_cv.argtypes = [vp, i32, vp, i32, i64, i32, i64, i32, vp]
     lib.ct_ingest_transform.restype = i32
     lib.ct_ingest_transform.argtypes = [vp, i32, i32, i64, i32, i64, ctypes.POINTER(IngestStage), i32, vp, vp]
+    lib.ct_ingest_extrema_workspace.restype = i64
+    lib.ct_ingest_extrema_workspace.argtypes = []
+    lib.ct_ingest_extrema.restype = i32
+    lib.ct_ingest_extrema.argtypes = [vp, i32, i32, i64, i32, i64, ctypes.POINTER(IngestStage), i32, i32, f32, f32, vp, i64, vp, vp]
+    lib.ct_ingest_transform_data.restype = i32
+    lib.ct_ingest_transform_data.argtypes = [vp, i32, i32, i64, i32, i64, ctypes.POINTER(IngestStage), i32, vp, vp, vp]
     lib.ct_video_stats_batch.restype = i32
     lib.ct_video_stats_batch.argtypes = [vp, i32, f32, i32, gp, ip, f32, vp, vp, vp]
     if lib.ct_abi_version() != ABI_VERSION:

@@ -10,10 +10,13 @@ The entry points stage a batch through one of three routes (inference/_staging.p
   ``ClampAlongDims`` (one pair, or one per channel) stages, an optional leading ``CvToTorch`` and at most one
   ``StridedDownscale`` is evaluated by ct_ingest_transform in one pass, bit for bit what these classes give on the CPU,
   and the float32 kernel variant runs on its planar result;
-- torch route: everything else -- a data-dependent ``Normalize`` (``max_val`` or ``min_val`` None), casts to another
-  dtype or device, clamps over a non-channel dim, more than four stages, other transform classes, non-contiguous or
-  non-4-D batches -- is executed with these classes' ``__call__`` (plain PyTorch ops on the device) before the float32
-  kernel variant runs.
+- fused ingest with device-side extrema (``fusable_ingest_data``): the same grammar with exactly one data-dependent
+  ``Normalize`` (``max_val`` and / or ``min_val`` None, e.g. ``[CastTo("float32"), Normalize()]``): ct_ingest_extrema
+  reduces the batch's own minimum / maximum behind the constant stages in front of it in one streaming pass, and
+  ct_ingest_transform_data evaluates the chain with those constants, again bit for bit the CPU classes;
+- torch route: everything else -- two data-dependent ``Normalize``s, casts to another dtype or device, clamps over a
+  non-channel dim, more than four stages, other transform classes, non-contiguous or non-4-D batches -- is executed
+  with these classes' ``__call__`` (plain PyTorch ops on the device) before the float32 kernel variant runs.
 """
 import ctypes
 from dataclasses import dataclass
@@ -103,7 +106,8 @@ class Normalize(BaseTransform):
     GPU tensor the division by a scalar is a multiplication by its reciprocal (torch's GPU kernels), 1 ulp away from
     the CPU result for some codes; when the kernels fold this transform (integer codes, see
     ``fusable_code_normalisation``) or the fused ingest evaluates it (``max_val`` and ``min_val`` both given, see
-    ``fusable_ingest``) the CPU reference's correctly rounded division is reproduced instead."""
+    ``fusable_ingest``; one of them or both None -- the batch's own extrema, taken over everything the transform
+    receives -- see ``fusable_ingest_data``) the CPU reference's correctly rounded division is reproduced instead."""
 
     def __init__(self, max_val: Optional[float] = None, min_val: Optional[float] = None, target_range=(0.0, 1.0)):
         self.max_val, self.min_val, self.target_range = max_val, min_val, tuple(target_range)
@@ -211,35 +215,37 @@ def _clamp_stage(t: ClampAlongDims, channels: int):
     return "clamp", [(p[0], p[1]) for p in pairs]
 
 
-def fusable_ingest(images: torch.Tensor, transforms) -> Optional[IngestPlan]:
-    """An ``IngestPlan`` when ct_ingest_transform can evaluate ``transforms`` on the 4-D batch ``images`` in one pass,
-    else None (the list then runs as torch ops).  Recognised: an optional leading CvToTorch on (B,H,W,3) uint8 / uint16
-    frames (``fusable_layout``); at most one StridedDownscale(step >= 1) anywhere after it (selecting pixels commutes
-    with per-pixel stages, so the raw stack is compacted first); CastTo(float32, device=None), required before the first
-    arithmetic stage of an integer batch and the identity afterwards; and one to four arithmetic stages, each a
-    Normalize with ``max_val`` and ``min_val`` given (a zero range is left to the torch route, which raises) or a
-    ClampAlongDims with a single (min, max) tuple or a list of C <= 4 pairs along the channel axis (``dim`` 1 or -3).
-    The constants are formed as ``Normalize.__call__`` forms them (``max - min`` and ``hi - lo`` in Python's own
-    arithmetic); the kernel rounds them to float32 as torch does a Python scalar."""
+def _recognise_ingest(images: torch.Tensor, transforms, allow_data: bool):
+    """(layout, step, step_first, stages, index of the data-dependent stage or None), or None: the grammar that
+    ``fusable_ingest`` and ``fusable_ingest_data`` share.  Without ``allow_data`` a Normalize bound of None declines."""
     if images.ndim != 4 or images.dtype not in (torch.uint8, torch.uint16, torch.float32) or not images.is_contiguous():
         return None
     layout, ts = fusable_layout(images, transforms)
     channels = images.shape[1] if layout == "nchw" else 3
-    is_float, step, stages = images.dtype == torch.float32, None, []
+    is_float, step, stages, data_at, step_first = images.dtype == torch.float32, None, [], None, False
     for t in ts:
         if type(t) is StridedDownscale:
             if step is not None or t.step_size < 1:
                 return None
-            step = t.step_size
+            step, step_first = t.step_size, data_at is None
         elif type(t) is CastTo:
             if t.data_type != torch.float32 or t.device is not None:
                 return None
             is_float = True
         elif type(t) is Normalize:
-            if not is_float or not _is_number(t.max_val) or not _is_number(t.min_val):
+            if not is_float:
                 return None
             lo, hi = t.target_range if len(t.target_range) == 2 else (None, None)
             if not _is_number(lo) or not _is_number(hi):
+                return None
+            if allow_data and (t.max_val is None or t.min_val is None):
+                given = t.min_val if t.max_val is None else t.max_val
+                if data_at is not None or not (given is None or _is_number(given)):
+                    return None
+                data_at = len(stages)
+                stages.append(("affine_data", hi - lo, lo))
+                continue
+            if not _is_number(t.max_val) or not _is_number(t.min_val):
                 return None
             den = t.max_val - t.min_val
             if den == 0 or ctypes.c_float(den).value == 0.0:  # (a range that only float32 rounds to zero divides by it)
@@ -254,4 +260,51 @@ def fusable_ingest(images: torch.Tensor, transforms) -> Optional[IngestPlan]:
             return None
     if not is_float or not 1 <= len(stages) <= INGEST_MAX_STAGES:
         return None
-    return IngestPlan(layout, 1 if step is None else step, tuple(stages))
+    return layout, 1 if step is None else step, step is not None and step_first, tuple(stages), data_at
+
+
+def fusable_ingest(images: torch.Tensor, transforms) -> Optional[IngestPlan]:
+    """An ``IngestPlan`` when ct_ingest_transform can evaluate ``transforms`` on the 4-D batch ``images`` in one pass,
+    else None (the list then runs as torch ops).  Recognised: an optional leading CvToTorch on (B,H,W,3) uint8 / uint16
+    frames (``fusable_layout``); at most one StridedDownscale(step >= 1) anywhere after it (selecting pixels commutes
+    with per-pixel stages, so the raw stack is compacted first); CastTo(float32, device=None), required before the first
+    arithmetic stage of an integer batch and the identity afterwards; and one to four arithmetic stages, each a
+    Normalize with ``max_val`` and ``min_val`` given (a zero range is left to the torch route, which raises) or a
+    ClampAlongDims with a single (min, max) tuple or a list of C <= 4 pairs along the channel axis (``dim`` 1 or -3).
+    The constants are formed as ``Normalize.__call__`` forms them (``max - min`` and ``hi - lo`` in Python's own
+    arithmetic); the kernel rounds them to float32 as torch does a Python scalar."""
+    found = _recognise_ingest(images, transforms, allow_data=False)
+    if found is None:
+        return None
+    return IngestPlan(found[0], found[1], found[3])
+
+
+@dataclass(frozen=True)
+class DataIngestPlan:
+    """What ``fusable_ingest_data`` recognised: ``layout`` and ``step`` as in ``IngestPlan``; ``step_first``: the
+    StridedDownscale stands in front of the data-dependent Normalize, whose extrema are then those of the selected
+    pixels (behind it they are those of the full-resolution batch: the two do not commute); ``stages`` in list order with
+    one ("affine_data", mul, add) entry for that Normalize; ``prefix``: the constant stages in front of it, which
+    ct_ingest_extrema evaluates; ``min_val`` / ``max_val``: the bound that was given, None for one taken from the data."""
+    layout: str
+    step: int
+    step_first: bool
+    stages: tuple
+    prefix: tuple
+    min_val: Optional[float]
+    max_val: Optional[float]
+
+
+def fusable_ingest_data(images: torch.Tensor, transforms) -> Optional[DataIngestPlan]:
+    """A ``DataIngestPlan`` when ``transforms`` is a list of ``fusable_ingest``'s grammar that holds exactly ONE
+    data-dependent Normalize -- ``max_val`` and / or ``min_val`` None (the reference's default,
+    clair_torch/common/transforms.py:108-133), the other bound, if given, a plain number -- among its one to four
+    arithmetic stages; else None.  Lists without such a Normalize belong to ``fusable_ingest``; two of them, subclasses
+    and everything ``fusable_ingest`` declines stay on the torch route.  A zero range cannot be seen here: the staging
+    checks the constants the device formed and raises as the reference does."""
+    found = _recognise_ingest(images, transforms, allow_data=True)
+    if found is None or found[4] is None:
+        return None
+    layout, step, step_first, stages, at = found
+    ts = [t for t in fusable_layout(images, transforms)[1] if type(t) is Normalize and (t.max_val is None or t.min_val is None)]
+    return DataIngestPlan(layout, step, step_first, stages, stages[:at], ts[0].min_val, ts[0].max_val)

@@ -26,9 +26,12 @@
 // What precedes the first aligned packet of a plane / image (slot 0) and what follows the last whole one goes element by
 // element.  Every load is that of an element of the thread's own pixels, every store lies in the thread's own [p0, p0+n).
 // The stage list travels by value in the kernel arguments; the stage loop is wave-uniform.
-#include <string.h>
-
-#include "ct_device.hpp"
+//
+// AFFINE_DATA (ct_ingest_transform_data) is AFFINE whose sub and div are not known when the launch is queued: a
+// data-dependent Normalize (max_val and / or min_val None) takes them from the batch, and ct_ingest_extrema leaves them in
+// consts_dev[0..1].  The *_data_kernel twins read the two floats once per thread through a wave-uniform load; the kernels
+// of the constant chains take no such pointer and are the code they were.
+#include "ct_ingest_stages.hpp"
 
 namespace ct {
 
@@ -45,31 +48,6 @@ struct IngestArgs {
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 constexpr int kGroup = 4;        // output elements per packet
 constexpr uint32_t kMaxRows = 65535;
-
-template <int N>
-__device__ __forceinline__ void ingest_stages(float (&v)[N], const IngestArgs &a, uint32_t c)
-{
-    for (uint32_t s = 0; s < a.n_stages; ++s) {
-        const ct_ingest_stage &st = a.stage[s];
-        if (st.kind == CT_INGEST_AFFINE) {
-            const float sub = st.sub, div = st.div, mul = st.mul, add = st.add;
-#pragma unroll
-            for (int k = 0; k < N; ++k) {
-                float t = v[k] - sub;
-                t = t / div;
-                t = t * mul;
-                v[k] = t + add;
-            }
-        } else {
-            const float lo = st.lo[c], hi = st.hi[c];
-#pragma unroll
-            for (int k = 0; k < N; ++k) {
-                const float t = v[k] < lo ? lo : v[k];
-                v[k] = t > hi ? hi : t;
-            }
-        }
-    }
-}
 
 // slot 0 -> the elements in front of the first aligned packet, slot s >= 1 -> packet s - 1; false when there is nothing
 __device__ __forceinline__ bool ingest_span(const float *dst, int64_t plane, int64_t &p0, int64_t &n, bool &whole)
@@ -96,9 +74,10 @@ __device__ __forceinline__ void ingest_store_packet(float *dp, const float (&v)[
     *reinterpret_cast<u32x4_t *>(dp) = w;
 }
 
-template <typename T>
-__global__ __launch_bounds__(kBlock) void ingest_planar_kernel(const IngestArgs a)
+template <typename T, bool DATA>
+__device__ __forceinline__ void ingest_planar(const IngestArgs &a, const float *consts)
 {
+    const float dsub = DATA ? consts[0] : 0.0f, ddiv = DATA ? consts[1] : 1.0f;
     const uint32_t q = a.first + blockIdx.y;
     const uint32_t c = q % a.channels;
     const T *src = static_cast<const T *>(a.src) + (int64_t)q * a.plane;
@@ -112,21 +91,22 @@ __global__ __launch_bounds__(kBlock) void ingest_planar_kernel(const IngestArgs 
         float v[kGroup];
 #pragma unroll
         for (int k = 0; k < kGroup; ++k) v[k] = (float)in[k];
-        ingest_stages(v, a, c);
+        ingest_stages<DATA>(v, a, c, dsub, ddiv);
         ingest_store_packet(dst + p0, v);
         return;
     }
     for (int64_t k = 0; k < n; ++k) {
         float v[1] = {(float)src[p0 + k]};
-        ingest_stages(v, a, c);
+        ingest_stages<DATA>(v, a, c, dsub, ddiv);
         dst[p0 + k] = v[0];
     }
 }
 
-template <typename T, bool REV>
-__global__ __launch_bounds__(kBlock) void ingest_packed3_kernel(const IngestArgs a)
+template <typename T, bool REV, bool DATA>
+__device__ __forceinline__ void ingest_packed3(const IngestArgs &a, const float *consts)
 {
     constexpr int C = 3;
+    const float dsub = DATA ? consts[0] : 0.0f, ddiv = DATA ? consts[1] : 1.0f;
     const uint32_t f = a.first + blockIdx.y;
     const T *src = static_cast<const T *>(a.src) + (int64_t)f * C * a.plane;
     float *dst = a.dst + (int64_t)f * C * a.plane;
@@ -141,7 +121,7 @@ __global__ __launch_bounds__(kBlock) void ingest_packed3_kernel(const IngestArgs
             float v[kGroup];
 #pragma unroll
             for (int k = 0; k < kGroup; ++k) v[k] = (float)in[k * C + (REV ? C - 1 - c : c)];
-            ingest_stages(v, a, (uint32_t)c);
+            ingest_stages<DATA>(v, a, (uint32_t)c, dsub, ddiv);
             float *dp = dst + c * a.plane + p0;
             if ((reinterpret_cast<uintptr_t>(dp) & 15u) == 0) {  // plane 0 always; the others iff plane % 4 == 0
                 ingest_store_packet(dp, v);
@@ -156,21 +136,52 @@ __global__ __launch_bounds__(kBlock) void ingest_packed3_kernel(const IngestArgs
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             float v[1] = {(float)src[(p0 + k) * C + (REV ? C - 1 - c : c)]};
-            ingest_stages(v, a, (uint32_t)c);
+            ingest_stages<DATA>(v, a, (uint32_t)c, dsub, ddiv);
             dst[c * a.plane + p0 + k] = v[0];
         }
     }
 }
 
 template <typename T>
-static int launch_ingest(IngestArgs a, int32_t layout, int64_t rows, hipStream_t s)
+__global__ __launch_bounds__(kBlock) void ingest_planar_kernel(const IngestArgs a)
+{
+    ingest_planar<T, false>(a, nullptr);
+}
+
+template <typename T, bool REV>
+__global__ __launch_bounds__(kBlock) void ingest_packed3_kernel(const IngestArgs a)
+{
+    ingest_packed3<T, REV, false>(a, nullptr);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void ingest_planar_data_kernel(const IngestArgs a, const float *__restrict__ consts)
+{
+    ingest_planar<T, true>(a, consts);
+}
+
+template <typename T, bool REV>
+__global__ __launch_bounds__(kBlock) void ingest_packed3_data_kernel(const IngestArgs a, const float *__restrict__ consts)
+{
+    ingest_packed3<T, REV, true>(a, consts);
+}
+
+template <typename T>
+static int launch_ingest(IngestArgs a, int32_t layout, int64_t rows, const float *consts, hipStream_t s)
 {
     const int64_t slots = 1 + (a.plane + kGroup - 1) / kGroup;
     const dim3 block(kBlock);
     for (int64_t first = 0; first < rows; first += kMaxRows) {
         a.first = (uint32_t)first;
         const dim3 grid((uint32_t)((slots + kBlock - 1) / kBlock), (uint32_t)(rows - first < kMaxRows ? rows - first : kMaxRows));
-        if (layout == CT_LAYOUT_NCHW)
+        if (consts) {
+            if (layout == CT_LAYOUT_NCHW)
+                hipLaunchKernelGGL((ingest_planar_data_kernel<T>), grid, block, 0, s, a, consts);
+            else if (layout == CT_LAYOUT_NHWC_BGR)
+                hipLaunchKernelGGL((ingest_packed3_data_kernel<T, true>), grid, block, 0, s, a, consts);
+            else
+                hipLaunchKernelGGL((ingest_packed3_data_kernel<T, false>), grid, block, 0, s, a, consts);
+        } else if (layout == CT_LAYOUT_NCHW)
             hipLaunchKernelGGL((ingest_planar_kernel<T>), grid, block, 0, s, a);
         else if (layout == CT_LAYOUT_NHWC_BGR)
             hipLaunchKernelGGL((ingest_packed3_kernel<T, true>), grid, block, 0, s, a);
@@ -181,27 +192,16 @@ static int launch_ingest(IngestArgs a, int32_t layout, int64_t rows, hipStream_t
     return CT_OK;
 }
 
-}  // namespace ct
-
-extern "C" int ct_ingest_transform(const void *src_dev, int32_t dtype, int32_t layout, int64_t n_images, int32_t channels,
-                                   int64_t plane, const ct_ingest_stage *stages, int32_t n_stages, float *dst_dev,
-                                   void *stream)
+// consts_dev NULL: the constant chains of ct_ingest_transform (no AFFINE_DATA stage); else ct_ingest_transform_data
+static int ingest_transform(const void *src_dev, int32_t dtype, int32_t layout, int64_t n_images, int32_t channels, int64_t plane,
+                            const ct_ingest_stage *stages, int32_t n_stages, float *dst_dev, const float *consts_dev, bool data,
+                            void *stream)
 {
-    using namespace ct;
-    if (dtype != CT_DTYPE_U8 && dtype != CT_DTYPE_U16 && dtype != CT_DTYPE_F32) return CT_ERR_INVALID_ARGUMENT;
-    if (layout != CT_LAYOUT_NCHW && layout != CT_LAYOUT_NHWC && layout != CT_LAYOUT_NHWC_BGR) return CT_ERR_INVALID_ARGUMENT;
-    if (channels < 1 || n_images < 0 || plane < 0) return CT_ERR_INVALID_ARGUMENT;
-    if (n_stages < 0 || n_stages > CT_INGEST_MAX_STAGES || (n_stages > 0 && !stages)) return CT_ERR_INVALID_ARGUMENT;
-    bool by_channel = false;  // does a clamp hold different pairs for different channels?
-    for (int32_t k = 0; k < n_stages; ++k) {
-        if (stages[k].kind != CT_INGEST_AFFINE && stages[k].kind != CT_INGEST_CLAMP) return CT_ERR_INVALID_ARGUMENT;
-        if (stages[k].kind == CT_INGEST_CLAMP)
-            for (int c = 1; c < CT_INGEST_MAX_CHANNELS; ++c)
-                by_channel |= memcmp(&stages[k].lo[c], &stages[k].lo[0], sizeof(float)) != 0 ||
-                              memcmp(&stages[k].hi[c], &stages[k].hi[0], sizeof(float)) != 0;
-    }
-    if (layout != CT_LAYOUT_NCHW && channels != 3) return CT_ERR_UNSUPPORTED;
-    if (by_channel && channels > CT_INGEST_MAX_CHANNELS) return CT_ERR_UNSUPPORTED;
+    bool by_channel = false;
+    const int rc = ingest_validate(dtype, layout, n_images, channels, plane, stages, n_stages, CT_INGEST_MAX_STAGES, data ? 1 : 0,
+                                   by_channel);
+    if (rc != CT_OK) return rc;
+    if (data && (!consts_dev || reinterpret_cast<uintptr_t>(consts_dev) % sizeof(float) != 0)) return CT_ERR_INVALID_ARGUMENT;
     if (n_images == 0 || plane == 0) return CT_OK;
     const uintptr_t src_align = dtype == CT_DTYPE_U8 ? 1 : (dtype == CT_DTYPE_U16 ? 2 : 4);
     if (!src_dev || !dst_dev || reinterpret_cast<uintptr_t>(src_dev) % src_align != 0 ||
@@ -231,7 +231,23 @@ extern "C" int ct_ingest_transform(const void *src_dev, int32_t dtype, int32_t l
     }
     if (a.plane / kGroup / kBlock + 2 > 0x7fffffff) return CT_ERR_TOO_LARGE;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == CT_DTYPE_U8) return launch_ingest<uint8_t>(a, layout, rows, s);
-    if (dtype == CT_DTYPE_U16) return launch_ingest<uint16_t>(a, layout, rows, s);
-    return launch_ingest<float>(a, layout, rows, s);
+    if (dtype == CT_DTYPE_U8) return launch_ingest<uint8_t>(a, layout, rows, consts_dev, s);
+    if (dtype == CT_DTYPE_U16) return launch_ingest<uint16_t>(a, layout, rows, consts_dev, s);
+    return launch_ingest<float>(a, layout, rows, consts_dev, s);
+}
+
+}  // namespace ct
+
+extern "C" int ct_ingest_transform(const void *src_dev, int32_t dtype, int32_t layout, int64_t n_images, int32_t channels,
+                                   int64_t plane, const ct_ingest_stage *stages, int32_t n_stages, float *dst_dev,
+                                   void *stream)
+{
+    return ct::ingest_transform(src_dev, dtype, layout, n_images, channels, plane, stages, n_stages, dst_dev, nullptr, false, stream);
+}
+
+extern "C" int ct_ingest_transform_data(const void *src_dev, int32_t dtype, int32_t layout, int64_t n_images, int32_t channels,
+                                        int64_t plane, const ct_ingest_stage *stages, int32_t n_stages, float *dst_dev,
+                                        const float *consts_dev, void *stream)
+{
+    return ct::ingest_transform(src_dev, dtype, layout, n_images, channels, plane, stages, n_stages, dst_dev, consts_dev, true, stream);
 }

@@ -5,7 +5,7 @@ import torch
 
 from .. import ops
 from ..common.transforms import (StridedDownscale, fusable_code_normalisation, fusable_downscale, fusable_ingest,
-                                 fusable_layout)
+                                 fusable_ingest_data, fusable_layout)
 
 
 def resolve_device(device) -> torch.device:
@@ -36,8 +36,11 @@ def stage_images(val_batch: torch.Tensor, device: torch.device, transforms: list
     One StridedDownscale in such a list (``fusable_downscale``) keeps the code route: the raw codes are compacted on
     the device in their own dtype and layout, and the smaller integer stack is returned.
     Any other list that ``fusable_ingest`` recognises (a black level, a target range, clamps, ...) is evaluated by
-    ct_ingest_transform in one pass with the reference's CPU arithmetic; the rest runs as torch ops.  Both give
-    float32 planar pixels."""
+    ct_ingest_transform in one pass with the reference's CPU arithmetic.  A list of that grammar with one data-dependent
+    Normalize (``max_val`` / ``min_val`` None, ``fusable_ingest_data``) first has the batch's extrema reduced on the
+    device (ct_ingest_extrema) -- of the compacted stack when the StridedDownscale stands in front of that Normalize, of
+    the full-resolution one when it stands behind -- and costs one 16-byte readback per batch for the reference's
+    zero-range error.  The rest runs as torch ops.  All of these give float32 planar pixels."""
     images = val_batch.to(device=device, non_blocking=True)  # the ONE host-to-device copy of the batch (a plain DMA when pinned)
     step, rest = fusable_downscale(transforms)
     if step is not None and images.ndim == 4:
@@ -61,6 +64,16 @@ def stage_images(val_batch: torch.Tensor, device: torch.device, transforms: list
     if plan is not None:
         images = ops.strided_downscale(images, plan.step, layout=plan.layout)
         return ops.ingest_transform(images, plan.stages, layout=plan.layout), None
+    plan = fusable_ingest_data(images, transforms) if images.is_cuda else None  # on a CPU "device" the classes run
+    if plan is not None:
+        if plan.step_first:
+            images = ops.strided_downscale(images, plan.step, layout=plan.layout)
+        consts = ops.ingest_extrema(images, plan.prefix, plan.layout, plan.min_val, plan.max_val)
+        if not plan.step_first:
+            images = ops.strided_downscale(images, plan.step, layout=plan.layout)
+        out = ops.ingest_transform(images, plan.stages, layout=plan.layout, consts=consts)
+        ops.check_ingest_consts(consts)
+        return out, None
     for t in transforms:
         images = t(images)
     if images.dtype in (torch.uint8, torch.uint16):

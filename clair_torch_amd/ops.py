@@ -726,15 +726,25 @@ def _number(v, what):
     return float(v)
 
 
-def _ingest_stages(stages, channels: int):
-    """The ct_ingest_stage array of ``stages``: ("affine", sub, div, mul, add) | ("clamp", [(lo, hi)] * (1 or C))."""
+def _ingest_stages(stages, channels: int, data: bool = False, limit: int = nv.INGEST_MAX_STAGES):
+    """The ct_ingest_stage array of ``stages``: ("affine", sub, div, mul, add) | ("clamp", [(lo, hi)] * (1 or C)) and,
+    with ``data``, at most one ("affine_data", mul, add) whose sub / div the device supplies."""
     stages = list(stages)
-    if len(stages) > nv.INGEST_MAX_STAGES:
-        raise ValueError(f"at most {nv.INGEST_MAX_STAGES} stages, got {len(stages)}")
+    if len(stages) > limit:
+        raise ValueError(f"at most {limit} stages, got {len(stages)}")
+    kinds = ("affine", "clamp", "affine_data") if data else ("affine", "clamp")
     arr = (nv.IngestStage * max(len(stages), 1))()
+    n_data = 0
     for k, st in enumerate(stages):
-        if not isinstance(st, (tuple, list)) or not st or st[0] not in ("affine", "clamp"):
-            raise ValueError(f"stage {k}: expected ('affine', sub, div, mul, add) or ('clamp', pairs), got {st!r}")
+        if not isinstance(st, (tuple, list)) or not st or st[0] not in kinds:
+            extra = " or ('affine_data', mul, add)" if data else ""
+            raise ValueError(f"stage {k}: expected ('affine', sub, div, mul, add) or ('clamp', pairs){extra}, got {st!r}")
+        if st[0] == "affine_data":
+            n_data += 1
+            if len(st) != 3 or n_data > 1:
+                raise ValueError(f"stage {k}: one ('affine_data', mul, add) stage with two constants at most")
+            arr[k].kind, arr[k].mul, arr[k].add = nv.INGEST_AFFINE_DATA, _number(st[1], f"stage {k}"), _number(st[2], f"stage {k}")
+            continue
         if st[0] == "affine":
             if len(st) != 5:
                 raise ValueError(f"stage {k}: ('affine', sub, div, mul, add) takes four constants")
@@ -760,14 +770,7 @@ def _ingest_stages(stages, channels: int):
     return arr, len(stages)
 
 
-def ingest_transform(stack: torch.Tensor, stages, layout: str = "nchw", out: Optional[torch.Tensor] = None):
-    """ct_ingest_transform: the chain CastTo(float32), Normalize(max, min, range), ClampAlongDims evaluated in one pass
-    with the reference's float32 arithmetic (every operation rounded on its own, a correctly rounded division).
-    ``stack``: a contiguous uint8 / uint16 / float32 device stack, (B,C,H,W) for "nchw" or (B,H,W,3) for "nhwc" /
-    "nhwc_bgr"; the result is the planar float32 (B,C,H,W) stack (RGB planes for "nhwc_bgr").  ``stages``: up to 4 of
-    ("affine", sub, div, mul, add) -- ((x - sub) / div) * mul + add, the constants rounded to float32 -- and
-    ("clamp", pairs) with one (lo, hi) pair, or one per channel of the result (C <= 4).  ``out``: a contiguous float32
-    caller tensor of exactly the result's shape to write into."""
+def _check_ingest_stack(stack: torch.Tensor, layout: str):
     _require_device(stack, "stack")
     if stack.ndim != 4:
         raise ValueError(f"stack must be 4-dimensional, got shape {tuple(stack.shape)}")
@@ -779,8 +782,31 @@ def ingest_transform(stack: torch.Tensor, stages, layout: str = "nchw", out: Opt
         raise ValueError(f"layout {layout!r} takes (B, H, W, 3) frames, got shape {tuple(stack.shape)}")
     if not stack.is_contiguous():
         raise ValueError("stack must be contiguous")
+
+
+def _check_consts(consts, device):
+    _require_device(consts, "consts")
+    if consts.dtype != torch.float32 or tuple(consts.shape) != (4,) or consts.device != device or not consts.is_contiguous():
+        raise ValueError(f"consts must be the 4-element float32 tensor of ingest_extrema on {device}")
+
+
+def ingest_transform(stack: torch.Tensor, stages, layout: str = "nchw", out: Optional[torch.Tensor] = None,
+                     consts: Optional[torch.Tensor] = None):
+    """ct_ingest_transform: the chain CastTo(float32), Normalize(max, min, range), ClampAlongDims evaluated in one pass
+    with the reference's float32 arithmetic (every operation rounded on its own, a correctly rounded division).
+    ``stack``: a contiguous uint8 / uint16 / float32 device stack, (B,C,H,W) for "nchw" or (B,H,W,3) for "nhwc" /
+    "nhwc_bgr"; the result is the planar float32 (B,C,H,W) stack (RGB planes for "nhwc_bgr").  ``stages``: up to 4 of
+    ("affine", sub, div, mul, add) -- ((x - sub) / div) * mul + add, the constants rounded to float32 -- and
+    ("clamp", pairs) with one (lo, hi) pair, or one per channel of the result (C <= 4).  ``out``: a contiguous float32
+    caller tensor of exactly the result's shape to write into.
+    ``consts``: the tensor ``ingest_extrema`` returned; then (ct_ingest_transform_data) one stage may be
+    ("affine_data", mul, add) -- a data-dependent Normalize, whose sub and div the kernel reads from ``consts[0:2]`` when
+    it runs.  No zero-range check happens here (see ``ingest_transform_data``)."""
+    _check_ingest_stack(stack, layout)
     shape = ingest_shape(tuple(stack.shape), layout)
-    arr, n_stages = _ingest_stages(stages, shape[1])
+    arr, n_stages = _ingest_stages(stages, shape[1], data=consts is not None)
+    if consts is not None:
+        _check_consts(consts, stack.device)
     if out is not None:
         _require_device(out, "out")
         if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != stack.device or not out.is_contiguous():
@@ -790,9 +816,80 @@ def ingest_transform(stack: torch.Tensor, stages, layout: str = "nchw", out: Opt
     if out.numel() == 0:
         return out
     with torch.cuda.device(stack.device):
-        rc = nv.load().ct_ingest_transform(_ptr(stack), _DTYPE[stack.dtype], _LAYOUT[layout], shape[0], shape[1],
-                                           shape[2] * shape[3], arr, n_stages, _ptr(out), _stream(stack.device))
-    nv.check(rc, "ct_ingest_transform")
+        if consts is None:
+            rc = nv.load().ct_ingest_transform(_ptr(stack), _DTYPE[stack.dtype], _LAYOUT[layout], shape[0], shape[1],
+                                               shape[2] * shape[3], arr, n_stages, _ptr(out), _stream(stack.device))
+        else:
+            rc = nv.load().ct_ingest_transform_data(_ptr(stack), _DTYPE[stack.dtype], _LAYOUT[layout], shape[0], shape[1],
+                                                    shape[2] * shape[3], arr, n_stages, _ptr(out), _ptr(consts),
+                                                    _stream(stack.device))
+    nv.check(rc, "ct_ingest_transform" if consts is None else "ct_ingest_transform_data")
+    return out
+
+
+# ---- a data-dependent Normalize (max_val / min_val None) in such a chain ------------------------------------------------
+ZERO_RANGE = "Normalization range is zero (min == max); cannot normalize."  # general_functions.py:378
+
+
+def ingest_extrema(stack: torch.Tensor, prefix_stages=(), layout: str = "nchw", min_val=None, max_val=None):
+    """ct_ingest_extrema: the constants of a data-dependent Normalize (reference general_functions.py:373-376), as a
+    4-element float32 device tensor ``consts`` = [sub, div, data min, data max].  The extrema are those of the whole
+    ``stack`` (as ``ingest_transform`` takes it) after the up to 3 constant ``prefix_stages`` that stand in front of the
+    Normalize; a NaN anywhere makes both NaN.  ``min_val`` / ``max_val``: None takes that bound from the data (at least
+    one must be None), a number fixes it: sub = min, div = fl32(max - min) in float32, as torch forms them.  One
+    streaming pass plus a fold, no synchronisation: ``div == 0``, where the reference raises, is for the caller to
+    check (``ingest_transform_data``).  An empty stack raises, as torch's ``x.min()`` does."""
+    _check_ingest_stack(stack, layout)
+    if min_val is not None and max_val is not None:
+        raise ValueError("min_val and max_val are both given: nothing depends on the data (use ingest_transform)")
+    shape = ingest_shape(tuple(stack.shape), layout)
+    arr, n_prefix = _ingest_stages(prefix_stages, shape[1], limit=nv.EXTREMA_MAX_PREFIX)
+    from_data = (nv.EXTREMA_MIN if min_val is None else 0) | (nv.EXTREMA_MAX if max_val is None else 0)
+    fixed_min = 0.0 if min_val is None else _number(min_val, "min_val")
+    fixed_max = 0.0 if max_val is None else _number(max_val, "max_val")
+    if stack.numel() == 0:
+        raise RuntimeError("ingest_extrema: the stack is empty (the extrema of an empty tensor are undefined)")
+    lib = nv.load()
+    ws_bytes = int(lib.ct_ingest_extrema_workspace())
+    ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=stack.device)
+    consts = torch.empty((4,), dtype=torch.float32, device=stack.device)
+    with torch.cuda.device(stack.device):
+        rc = lib.ct_ingest_extrema(_ptr(stack), _DTYPE[stack.dtype], _LAYOUT[layout], shape[0], shape[1], shape[2] * shape[3],
+                                   arr, n_prefix, from_data, fixed_min, fixed_max, _ptr(ws), ws_bytes, _ptr(consts),
+                                   _stream(stack.device))
+    nv.check(rc, "ct_ingest_extrema")
+    return consts
+
+
+def data_stage_prefix(stages):
+    """The constant stages in front of the ("affine_data", mul, add) entry of ``stages`` (which must hold one)."""
+    stages = list(stages)
+    at = [k for k, st in enumerate(stages) if isinstance(st, (tuple, list)) and st and st[0] == "affine_data"]
+    if len(at) != 1:
+        raise ValueError(f"stages must hold exactly one ('affine_data', mul, add) stage, got {len(at)}")
+    return stages[:at[0]]
+
+
+def check_ingest_consts(consts: torch.Tensor):
+    """Read the 16 bytes of ``ingest_extrema``'s constants back (ONE synchronisation) and raise the reference's
+    ValueError when the range is zero (general_functions.py:377-378); a NaN range passes, as it does there."""
+    if float(consts.cpu()[1]) == 0.0:
+        raise ValueError(ZERO_RANGE)
+
+
+def ingest_transform_data(stack: torch.Tensor, stages, layout: str = "nchw", min_val=None, max_val=None, check: bool = True,
+                          out: Optional[torch.Tensor] = None):
+    """A chain with one data-dependent Normalize: ``ingest_extrema`` over the constant stages in front of the
+    ("affine_data", mul, add) entry of ``stages``, then ``ingest_transform`` with those constants -- three launches on
+    the current stream.  ``check=True``: returns the planar float32 stack after reading the constants back (one
+    synchronisation per batch, which the reference's own ``if denominator == 0`` costs as well) and raising its
+    ValueError for a zero range.  ``check=False``: returns ``(out, consts)`` without synchronising -- the sequence can be
+    captured in a graph; ``consts[1] == 0`` then means every value of ``out`` is NaN or infinite."""
+    consts = ingest_extrema(stack, data_stage_prefix(stages), layout, min_val, max_val)
+    out = ingest_transform(stack, stages, layout, out=out, consts=consts)
+    if not check:
+        return out, consts
+    check_ingest_consts(consts)
     return out
 
 

@@ -20,6 +20,8 @@ and pair lists are passed as their component tensors / scalars.
     torch.ops.clair_hip.export_cv(x, to_f64) -> Tensor   (planar result -> the (H,W,C) BGR array save_image writes)
     torch.ops.clair_hip.ingest_transform(stack, stages, layout) -> Tensor   (CastTo / Normalize / ClampAlongDims chain in
                                   one pass; stages = 13 floats each: kind, sub, div, mul, add, lo[0..3], hi[0..3])
+    torch.ops.clair_hip.ingest_extrema(stack, prefix, layout, min_val?, max_val?) -> Tensor   (4 floats: sub, div, data
+                                  min, data max of a data-dependent Normalize behind the constant ``prefix`` stages)
 
 CPU tensors are refused by the kernels' front-end exactly as through ``ops`` (there is no CPU path).
 """
@@ -193,9 +195,7 @@ def flatten_ingest_stages(stages, channels: int):
     return flat
 
 
-@torch.library.custom_op(f"{_LIB}::ingest_transform", mutates_args=())
-def ingest_transform(stack: torch.Tensor, stages: Sequence[float], layout: str = "nchw") -> torch.Tensor:
-    """ct_ingest_transform: a CastTo(float32) / Normalize / ClampAlongDims chain in one pass, planar float32 result."""
+def _listed_ingest_stages(stack, stages, layout):
     if len(stages) % _STAGE_FLOATS != 0:
         raise ValueError(f"stages holds {_STAGE_FLOATS} floats per stage, got {len(stages)}")
     channels = ops.ingest_shape(tuple(stack.shape), layout)[1]
@@ -208,9 +208,28 @@ def ingest_transform(stack: torch.Tensor, stages: Sequence[float], layout: str =
         else:
             n = channels if channels <= 4 else 1
             listed.append(("clamp", [(lo[c], hi[c]) for c in range(n)]))
-    return ops.ingest_transform(stack, listed, layout)
+    return listed
+
+
+@torch.library.custom_op(f"{_LIB}::ingest_transform", mutates_args=())
+def ingest_transform(stack: torch.Tensor, stages: Sequence[float], layout: str = "nchw") -> torch.Tensor:
+    """ct_ingest_transform: a CastTo(float32) / Normalize / ClampAlongDims chain in one pass, planar float32 result."""
+    return ops.ingest_transform(stack, _listed_ingest_stages(stack, stages, layout), layout)
 
 
 @ingest_transform.register_fake
 def _(stack, stages, layout="nchw"):
     return stack.new_empty(ops.ingest_shape(tuple(stack.shape), layout), dtype=torch.float32)
+
+
+@torch.library.custom_op(f"{_LIB}::ingest_extrema", mutates_args=())
+def ingest_extrema(stack: torch.Tensor, prefix: Sequence[float], layout: str = "nchw", min_val: Optional[float] = None,
+                   max_val: Optional[float] = None) -> torch.Tensor:
+    """ct_ingest_extrema: [sub, div, data min, data max] of a data-dependent Normalize behind the constant ``prefix``
+    stages (flattened as for ``ingest_transform``); a bound that is None comes from the data."""
+    return ops.ingest_extrema(stack, _listed_ingest_stages(stack, prefix, layout), layout, min_val, max_val)
+
+
+@ingest_extrema.register_fake
+def _(stack, prefix, layout="nchw", min_val=None, max_val=None):
+    return stack.new_empty((4,), dtype=torch.float32)

@@ -363,6 +363,40 @@ int ct_ingest_transform(const void *src_dev, int32_t dtype, int32_t layout, int6
                         int64_t plane, const ct_ingest_stage *stages, int32_t n_stages, float *dst_dev, void *stream);
 
 /*
+ * ct_ingest_extrema / ct_ingest_transform_data -- a data-dependent Normalize (max_val and / or min_val None: the bound is
+ * the batch's own extremum; normalize_tensor, clair_torch/common/general_functions.py:373-376, the class at
+ * clair_torch/common/transforms.py:108-133) in such a chain, in two launches on one stream and without a readback.
+ *
+ * ct_ingest_extrema reads the raw stack once (src_dev, dtype, layout, n_images, channels, plane as ct_ingest_transform),
+ * evaluates the n_prefix <= CT_EXTREMA_MAX_PREFIX constant stages that stand in front of the data-dependent Normalize per
+ * element, reduces min, max and "any NaN" over ALL n_images*channels*plane values (torch's x.min() / x.max() of the whole
+ * batch) and writes four floats to consts_dev:
+ *   [0] sub = from_data & CT_EXTREMA_MIN ? min : fl32(fixed_min)      [2] the data minimum   (both NaN when any value is
+ *   [1] div = fl32(top - sub), top = from_data & CT_EXTREMA_MAX ? max : fl32(fixed_max)       [3] the data maximum    NaN)
+ * div == 0 is where the reference raises ValueError (general_functions.py:377-378): the caller reads consts_dev back if it
+ * wants that check.  Deterministic (no atomics): one partial per workgroup in workspace_dev -- at least
+ * ct_ingest_extrema_workspace() bytes, 16-byte aligned -- folded by a second one-workgroup kernel.  from_data = 0 and an
+ * empty stack (torch raises on the extrema of an empty tensor) are CT_ERR_INVALID_ARGUMENT; otherwise the arguments are
+ * validated as ct_ingest_transform's.  Reads nothing outside the stack, writes only the workspace and consts_dev.
+ *
+ * ct_ingest_transform_data is ct_ingest_transform with at most one stage of kind CT_INGEST_AFFINE_DATA: AFFINE whose sub
+ * and div are consts_dev[0..1] (mul = fl32(hi - lo) and add = fl32(lo) still come from the struct).  consts_dev: non-NULL,
+ * 4-byte aligned, read when the kernel runs.  ct_ingest_transform itself refuses that kind.
+ * Neither function allocates, synchronises or reads anything back.
+ */
+#define CT_INGEST_AFFINE_DATA 2
+#define CT_EXTREMA_MIN 1
+#define CT_EXTREMA_MAX 2
+#define CT_EXTREMA_MAX_PREFIX 3
+int64_t ct_ingest_extrema_workspace(void);
+int ct_ingest_extrema(const void *src_dev, int32_t dtype, int32_t layout, int64_t n_images, int32_t channels, int64_t plane,
+                      const ct_ingest_stage *prefix, int32_t n_prefix, int32_t from_data, float fixed_min, float fixed_max,
+                      void *workspace_dev, int64_t workspace_bytes, float *consts_dev, void *stream);
+int ct_ingest_transform_data(const void *src_dev, int32_t dtype, int32_t layout, int64_t n_images, int32_t channels,
+                             int64_t plane, const ct_ingest_stage *stages, int32_t n_stages, float *dst_dev,
+                             const float *consts_dev, void *stream);
+
+/*
  * ct_export_cv -- the array save_image hands to cv.imwrite (clair_torch/common/data_io.py:228-234: astype, transpose to
  * (H, W, C), channel reversal of a 3-channel image), made on the device from planar results:
  *   dst[f][p][c'] = (dst type) src[f][c][p],  p < plane = H*W,  c' = channels-1-c when reverse_channels, else c
