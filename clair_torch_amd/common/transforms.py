@@ -1,22 +1,29 @@
 """The reference's transform classes (clair_torch/common/transforms.py:68-216; ``to_config`` / ``from_config`` and the
 YAML registry are not part of this build).
 
-The entry points stage a batch through one of three routes (inference/_staging.py):
+The entry points stage a batch by ONE plan (``plan_staging``, executed by inference/_staging.py::stage_images); the first
+route of this table that applies is taken:
 
-- code route: ``[CastTo(float32), Normalize(max, 0)]`` applied to integer codes is folded into the kernels' load stage --
-  optionally behind a leading ``CvToTorch`` (raw OpenCV frames, folded into the kernels' addressing) and with one
-  ``StridedDownscale`` anywhere after that (the raw codes are compacted by ct_strided_downscale first);
-- fused ingest (``fusable_ingest``): any other chain of ``CastTo(float32)``, up to four ``Normalize(max, min, range)`` /
-  ``ClampAlongDims`` (one pair, or one per channel) stages, an optional leading ``CvToTorch`` and at most one
-  ``StridedDownscale`` is evaluated by ct_ingest_transform in one pass, bit for bit what these classes give on the CPU,
-  and the float32 kernel variant runs on its planar result;
-- fused ingest with device-side extrema (``fusable_ingest_data``): the same grammar with exactly one data-dependent
-  ``Normalize`` (``max_val`` and / or ``min_val`` None, e.g. ``[CastTo("float32"), Normalize()]``): ct_ingest_extrema
-  reduces the batch's own minimum / maximum behind the constant stages in front of it in one streaming pass, and
-  ct_ingest_transform_data evaluates the chain with those constants, again bit for bit the CPU classes;
-- torch route: everything else -- two data-dependent ``Normalize``s, casts to another dtype or device, clamps over a
-  non-channel dim, more than four stages, other transform classes, non-contiguous or non-4-D batches -- is executed
-  with these classes' ``__call__`` (plain PyTorch ops on the device) before the float32 kernel variant runs.
+= ============= ==================================================================== =====================================
+# route         the list, behind an optional leading ``CvToTorch`` on raw frames       what runs
+= ============= ==================================================================== =====================================
+1 "code"        route 2's pair with ONE ``StridedDownscale`` before, between or        ct_strided_downscale compacts the raw
+                behind it; 4-D batches only                                            codes, the kernels fold the pair
+2 "code"        ``CastTo(float32), Normalize(max, 0)`` on uint8 / uint16 codes         nothing: the kernels' load stage
+                (``isinstance``: subclasses count; any rank, any strides)              folds the pair
+3 "ingest"      ``CastTo(float32)``, one to four ``Normalize(max, min, range)`` /      ct_ingest_transform: one pass, bit for
+                ``ClampAlongDims`` (one pair, or one per channel) stages, at most      bit these classes on the CPU; the
+                one ``StridedDownscale`` (``type(t) is``; 4-D contiguous batches)      float32 kernel variant takes the result
+4 "ingest_data" route 3's grammar with exactly ONE data-dependent ``Normalize``        ct_ingest_extrema, then
+                (``max_val`` and / or ``min_val`` None); batch on a CUDA device        ct_ingest_transform_data
+5 "torch"       everything else: two data-dependent ``Normalize``s, other casts,       these classes' ``__call__`` (PyTorch
+                clamps over a non-channel dim, more than four stages, other            ops on the device), then the float32
+                classes, non-contiguous or non-4-D batches off the code pair           kernel variant
+= ============= ==================================================================== =====================================
+
+A leading ``CvToTorch`` on (B,H,W,3) uint8 / uint16 frames is never executed on routes 1-4: the code-route kernels read the
+interleaved frames as they are (layout "nhwc_bgr") and the fused ingest reads them itself.  A caller that needs a planar
+stack (``planar=True``: explicit std and dark-field images are planar) gets no "nhwc_bgr": such a list goes to route 3.
 """
 import ctypes
 from dataclasses import dataclass
@@ -133,28 +140,25 @@ def fusable_layout(images: torch.Tensor, transforms):
     return "nchw", ts
 
 
-def fusable_code_normalisation(images: torch.Tensor, transforms):
-    """If ``transforms`` applied to integer codes is exactly CastTo(float32)? + Normalize(max, 0, (0,1)),
-    return max_code so the kernels can ingest the raw codes; otherwise None."""
-    if images.dtype not in (torch.uint8, torch.uint16):
+_CODES = (torch.uint8, torch.uint16)
+
+
+def _code_pair(ts):
+    """max_code when ``ts`` is exactly CastTo(float32), Normalize(max, 0, (0, 1)) with an integer max in [1, 65535]."""
+    if len(ts) != 2 or not isinstance(ts[0], CastTo) or ts[0].data_type != torch.float32 or ts[0].device is not None:
         return None
-    ts = [t for t in transforms if t is not None]
-    if ts and isinstance(ts[0], CastTo) and ts[0].data_type in (None, torch.float32) and ts[0].device is None:
-        if ts[0].data_type is None:
-            return None
-        ts = ts[1:]
-    else:
-        return None
-    if len(ts) == 1 and isinstance(ts[0], Normalize):
-        n = ts[0]
-        if n.max_val is not None and (n.min_val in (0, 0.0)) and tuple(n.target_range) == (0.0, 1.0):
-            mc = float(n.max_val)
-            if 1.0 <= mc <= 65535.0 and mc == int(mc):
-                return mc
+    n = ts[1]
+    if isinstance(n, Normalize) and n.max_val is not None and (n.min_val in (0, 0.0)) and tuple(n.target_range) == (0.0, 1.0):
+        mc = float(n.max_val)
+        if 1.0 <= mc <= 65535.0 and mc == int(mc):
+            return mc
     return None
 
 
-_CODE_PROBE = torch.empty(0, dtype=torch.uint16)  # stands for "some integer code stack" when only the list is judged
+def fusable_code_normalisation(images: torch.Tensor, transforms):
+    """If ``transforms`` applied to integer codes is exactly CastTo(float32) + Normalize(max, 0, (0,1)),
+    return max_code so the kernels can ingest the raw codes; otherwise None."""
+    return _code_pair([t for t in transforms if t is not None]) if images.dtype in _CODES else None
 
 
 def fusable_downscale(transforms, images: Optional[torch.Tensor] = None):
@@ -168,17 +172,13 @@ def fusable_downscale(transforms, images: Optional[torch.Tensor] = None):
     found = [k for k, t in enumerate(ts) if isinstance(t, StridedDownscale)]
     if len(found) != 1 or ts[found[0]].step_size < 1:
         return None, ts
-    k = found[0]
-    rest = ts[:k] + ts[k + 1:]
-    if any(isinstance(t, CvToTorch) for t in ts[k + 1:]):
+    rest = ts[:found[0]] + ts[found[0] + 1:]
+    leading_cv = bool(rest) and isinstance(rest[0], CvToTorch)
+    if _code_pair(rest[1:] if leading_cv else rest) is None or (leading_cv and found[0] == 0):
         return None, ts
-    probe = _CODE_PROBE if images is None else images
-    tail = rest[1:] if rest and isinstance(rest[0], CvToTorch) else rest
-    if images is not None and tail is not rest and fusable_layout(images, rest)[0] == "nchw":
+    if images is not None and (images.dtype not in _CODES or (leading_cv and fusable_layout(images, rest)[0] == "nchw")):
         return None, ts
-    if fusable_code_normalisation(probe, tail) is None:
-        return None, ts
-    return ts[k].step_size, rest
+    return ts[found[0]].step_size, rest
 
 
 @dataclass(frozen=True)
@@ -215,19 +215,37 @@ def _clamp_stage(t: ClampAlongDims, channels: int):
     return "clamp", [(p[0], p[1]) for p in pairs]
 
 
-def _recognise_ingest(images: torch.Tensor, transforms, allow_data: bool):
-    """(layout, step, step_first, stages, index of the data-dependent stage or None), or None: the grammar that
-    ``fusable_ingest`` and ``fusable_ingest_data`` share.  Without ``allow_data`` a Normalize bound of None declines."""
+@dataclass(frozen=True)
+class StagingPlan:
+    """Everything ``stage_images`` needs to stage one batch.  ``route``: "code" | "ingest" | "ingest_data" | "torch" (the
+    table at the top of this module); ``layout``: of the staged result, "nhwc_bgr" only on the code route;
+    ``source_layout``: how the fused ingest reads the batch ("nhwc_bgr": raw frames behind a leading CvToTorch);
+    ``step``: the StridedDownscale to apply to the raw stack (1 = none); ``max_code``: of the code route; ``stages``,
+    ``step_first``, ``prefix``, ``min_val`` / ``max_val``: as in ``IngestPlan`` / ``DataIngestPlan``."""
+    route: str
+    layout: str = "nchw"
+    step: int = 1
+    step_first: bool = False
+    max_code: Optional[float] = None
+    stages: tuple = ()
+    prefix: tuple = ()
+    min_val: Optional[float] = None
+    max_val: Optional[float] = None
+    source_layout: str = "nchw"
+
+
+def _recognise_ingest(images: torch.Tensor, transforms) -> Optional[StagingPlan]:
+    """The "ingest" / "ingest_data" plan of the grammar that ``fusable_ingest`` and ``fusable_ingest_data`` share, or None."""
     if images.ndim != 4 or images.dtype not in (torch.uint8, torch.uint16, torch.float32) or not images.is_contiguous():
         return None
     layout, ts = fusable_layout(images, transforms)
     channels = images.shape[1] if layout == "nchw" else 3
-    is_float, step, stages, data_at, step_first = images.dtype == torch.float32, None, [], None, False
+    is_float, step, stages, data, data_at, step_first = images.dtype == torch.float32, None, [], None, None, False
     for t in ts:
         if type(t) is StridedDownscale:
             if step is not None or t.step_size < 1:
                 return None
-            step, step_first = t.step_size, data_at is None
+            step, step_first = t.step_size, data is None
         elif type(t) is CastTo:
             if t.data_type != torch.float32 or t.device is not None:
                 return None
@@ -238,11 +256,11 @@ def _recognise_ingest(images: torch.Tensor, transforms, allow_data: bool):
             lo, hi = t.target_range if len(t.target_range) == 2 else (None, None)
             if not _is_number(lo) or not _is_number(hi):
                 return None
-            if allow_data and (t.max_val is None or t.min_val is None):
+            if t.max_val is None or t.min_val is None:
                 given = t.min_val if t.max_val is None else t.max_val
-                if data_at is not None or not (given is None or _is_number(given)):
+                if data is not None or not (given is None or _is_number(given)):
                     return None
-                data_at = len(stages)
+                data, data_at = t, len(stages)
                 stages.append(("affine_data", hi - lo, lo))
                 continue
             if not _is_number(t.max_val) or not _is_number(t.min_val):
@@ -260,7 +278,10 @@ def _recognise_ingest(images: torch.Tensor, transforms, allow_data: bool):
             return None
     if not is_float or not 1 <= len(stages) <= INGEST_MAX_STAGES:
         return None
-    return layout, 1 if step is None else step, step is not None and step_first, tuple(stages), data_at
+    if data is None:
+        return StagingPlan("ingest", source_layout=layout, step=step or 1, stages=tuple(stages))
+    return StagingPlan("ingest_data", source_layout=layout, step=step or 1, step_first=step is not None and step_first,
+                       stages=tuple(stages), prefix=tuple(stages[:data_at]), min_val=data.min_val, max_val=data.max_val)
 
 
 def fusable_ingest(images: torch.Tensor, transforms) -> Optional[IngestPlan]:
@@ -273,10 +294,8 @@ def fusable_ingest(images: torch.Tensor, transforms) -> Optional[IngestPlan]:
     ClampAlongDims with a single (min, max) tuple or a list of C <= 4 pairs along the channel axis (``dim`` 1 or -3).
     The constants are formed as ``Normalize.__call__`` forms them (``max - min`` and ``hi - lo`` in Python's own
     arithmetic); the kernel rounds them to float32 as torch does a Python scalar."""
-    found = _recognise_ingest(images, transforms, allow_data=False)
-    if found is None:
-        return None
-    return IngestPlan(found[0], found[1], found[3])
+    p = _recognise_ingest(images, transforms)
+    return IngestPlan(p.source_layout, p.step, p.stages) if p is not None and p.route == "ingest" else None
 
 
 @dataclass(frozen=True)
@@ -302,9 +321,26 @@ def fusable_ingest_data(images: torch.Tensor, transforms) -> Optional[DataIngest
     arithmetic stages; else None.  Lists without such a Normalize belong to ``fusable_ingest``; two of them, subclasses
     and everything ``fusable_ingest`` declines stay on the torch route.  A zero range cannot be seen here: the staging
     checks the constants the device formed and raises as the reference does."""
-    found = _recognise_ingest(images, transforms, allow_data=True)
-    if found is None or found[4] is None:
+    p = _recognise_ingest(images, transforms)
+    if p is None or p.route != "ingest_data":
         return None
-    layout, step, step_first, stages, at = found
-    ts = [t for t in fusable_layout(images, transforms)[1] if type(t) is Normalize and (t.max_val is None or t.min_val is None)]
-    return DataIngestPlan(layout, step, step_first, stages, stages[:at], ts[0].min_val, ts[0].max_val)
+    return DataIngestPlan(p.source_layout, p.step, p.step_first, p.stages, p.prefix, p.min_val, p.max_val)
+
+
+def plan_staging(images: torch.Tensor, transforms, planar: bool = False) -> StagingPlan:
+    """The route ``transforms`` take on ``images``, read off the batch's shape, dtype, contiguity and device type alone
+    (no device call).  ``planar``: the caller cannot take an interleaved stack; the layout is then always "nchw"."""
+    ts = [t for t in transforms if t is not None]
+    # 1, 2: the code pair, behind one StridedDownscale (4-D batches) or alone; raw frames stay interleaved unless ``planar``
+    step, rest = fusable_downscale(ts)
+    if step is None or images.ndim != 4:
+        step, rest = 1, ts
+    layout, pair = ("nchw", rest) if planar else fusable_layout(images, rest)
+    max_code = fusable_code_normalisation(images, pair)
+    if max_code is not None:
+        return StagingPlan("code", layout, step, max_code=max_code, source_layout=layout)
+    # 3, 4: the fused ingest; with a data-dependent Normalize only on a CUDA device (on a CPU "device" the classes run)
+    fused = _recognise_ingest(images, ts)
+    if fused is not None and (fused.route == "ingest" or images.is_cuda):
+        return fused
+    return StagingPlan("torch")  # 5

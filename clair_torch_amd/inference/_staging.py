@@ -4,8 +4,7 @@ from typing import Iterable, Optional
 import torch
 
 from .. import ops
-from ..common.transforms import (StridedDownscale, fusable_code_normalisation, fusable_downscale, fusable_ingest,
-                                 fusable_ingest_data, fusable_layout)
+from ..common.transforms import StridedDownscale, plan_staging
 
 
 def resolve_device(device) -> torch.device:
@@ -26,69 +25,50 @@ def normalise_transform_list(gpu_transforms) -> list:
     return [gpu_transforms]
 
 
-def stage_images(val_batch: torch.Tensor, device: torch.device, transforms: list, want_layout: bool = False):
-    """Move the value batch to the device and run / fuse the device transforms.
+def stage_images(val_batch: torch.Tensor, device: torch.device, transforms: list, planar: bool = False):
+    """Move the value batch to the device and run / fuse the device transforms: (images, max_code, layout).
 
-    Returns (images, max_code): integer codes with their max_code when the transform list is the
-    CastTo(float32)+Normalize(max, 0) pair the kernels ingest directly, else float32 pixels and None.
-    With ``want_layout`` a third value is returned: "nhwc_bgr" when the list additionally starts with CvToTorch
-    on raw (B,H,W,3) frames (the kernel then reads the interleaved BGR frames as they are), else "nchw".
-    One StridedDownscale in such a list (``fusable_downscale``) keeps the code route: the raw codes are compacted on
-    the device in their own dtype and layout, and the smaller integer stack is returned.
-    Any other list that ``fusable_ingest`` recognises (a black level, a target range, clamps, ...) is evaluated by
-    ct_ingest_transform in one pass with the reference's CPU arithmetic.  A list of that grammar with one data-dependent
-    Normalize (``max_val`` / ``min_val`` None, ``fusable_ingest_data``) first has the batch's extrema reduced on the
-    device (ct_ingest_extrema) -- of the compacted stack when the StridedDownscale stands in front of that Normalize, of
-    the full-resolution one when it stands behind -- and costs one 16-byte readback per batch for the reference's
-    zero-range error.  The rest runs as torch ops.  All of these give float32 planar pixels."""
+    ``plan_staging`` picks the route (the table in common/transforms.py); what each of them does here and returns:
+
+    ============= ================================================================= ====================================
+    route         device work                                                       returns
+    ============= ================================================================= ====================================
+    "code"        ct_strided_downscale of the raw codes when the list holds one     integer codes, their max_code,
+                                                                                    "nchw" | "nhwc_bgr" (raw frames)
+    "ingest"      the downscale, then ct_ingest_transform: one pass, the            float32 planar pixels, None, "nchw"
+                  reference's CPU arithmetic
+    "ingest_data" ct_ingest_extrema -- of the compacted stack when the downscale    float32 planar pixels, None, "nchw"
+                  stands in front of the data-dependent Normalize, else of the full
+                  one --, the downscale where it stands, ct_ingest_transform_data,
+                  then ONE 16-byte readback for the reference's zero-range error
+    "torch"       the classes' ``__call__`` as torch ops                            float32 planar pixels, None, "nchw"
+    ============= ================================================================= ====================================
+
+    ``planar``: the caller holds explicit std or dark-field images, which are planar: the layout is then always "nchw"."""
     images = val_batch.to(device=device, non_blocking=True)  # the ONE host-to-device copy of the batch (a plain DMA when pinned)
-    step, rest = fusable_downscale(transforms)
-    if step is not None and images.ndim == 4:
-        layout, tail = fusable_layout(images, rest) if want_layout else ("nchw", rest)
-        max_code = fusable_code_normalisation(images, tail)
-        if max_code is not None:
-            images = ops.strided_downscale(images, step, layout=layout)
-            return (images, max_code, layout) if want_layout else (images, max_code)
-    if want_layout:
-        layout, rest = fusable_layout(images, transforms)
-        if layout != "nchw":
-            max_code = fusable_code_normalisation(images, rest)
-            if max_code is not None:
-                return images, max_code, layout
-        out = stage_images(images, device, transforms)  # already on the device: .to() is then the identity
-        return out[0], out[1], "nchw"
-    max_code = fusable_code_normalisation(images, transforms)
-    if max_code is not None:
-        return images, max_code
-    plan = fusable_ingest(images, transforms)
-    if plan is not None:
-        images = ops.strided_downscale(images, plan.step, layout=plan.layout)
-        return ops.ingest_transform(images, plan.stages, layout=plan.layout), None
-    plan = fusable_ingest_data(images, transforms) if images.is_cuda else None  # on a CPU "device" the classes run
-    if plan is not None:
+    plan = plan_staging(images, transforms, planar)
+    if plan.route == "code":
+        if plan.step > 1:
+            images = ops.strided_downscale(images, plan.step, layout=plan.layout)
+        return images, plan.max_code, plan.layout
+    if plan.route == "ingest":
+        images = ops.strided_downscale(images, plan.step, layout=plan.source_layout)
+        return ops.ingest_transform(images, plan.stages, layout=plan.source_layout), None, "nchw"
+    if plan.route == "ingest_data":
         if plan.step_first:
-            images = ops.strided_downscale(images, plan.step, layout=plan.layout)
-        consts = ops.ingest_extrema(images, plan.prefix, plan.layout, plan.min_val, plan.max_val)
+            images = ops.strided_downscale(images, plan.step, layout=plan.source_layout)
+        consts = ops.ingest_extrema(images, plan.prefix, plan.source_layout, plan.min_val, plan.max_val)
         if not plan.step_first:
-            images = ops.strided_downscale(images, plan.step, layout=plan.layout)
-        out = ops.ingest_transform(images, plan.stages, layout=plan.layout, consts=consts)
+            images = ops.strided_downscale(images, plan.step, layout=plan.source_layout)
+        out = ops.ingest_transform(images, plan.stages, layout=plan.source_layout, consts=consts)
         ops.check_ingest_consts(consts)
-        return out, None
+        return out, None, "nchw"
     for t in transforms:
         images = t(images)
     if images.dtype in (torch.uint8, torch.uint16):
         raise TypeError("integer images reached the kernel without a Normalize transform; pass "
                         "gpu_transforms=[CastTo('float32'), Normalize(max_val=<max code>, min_val=0)]")
-    return images.to(torch.float32).contiguous(), None
-
-
-def restage_planar(val_batch: torch.Tensor, images: torch.Tensor, device: torch.device, transforms: list):
-    """(images, max_code, "nchw") for a batch that ``stage_images`` handed over interleaved but that has to be planar
-    after all (explicit std / dark-field images are planar): the transforms run on the generic route.  ``images`` is
-    what ``stage_images`` returned -- the batch itself, already on the device, unless it was compacted by a
-    StridedDownscale, which must not be applied a second time: then staging starts over from ``val_batch``."""
-    source = val_batch if has_downscale(transforms) else images
-    return stage_images(source, device, transforms) + ("nchw",)
+    return images.to(torch.float32).contiguous(), None, "nchw"
 
 
 def has_downscale(transforms) -> bool:

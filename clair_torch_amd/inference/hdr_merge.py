@@ -13,8 +13,7 @@ from torch.utils.data import DataLoader
 from .. import ops
 from ..common.typecheck import expect
 from ..models.base import ICRFModelBase
-from ._staging import (normalise_transform_list, refuse_tile_with_downscale, resolve_device, restage_planar, stage_images,
-                       std_arguments)
+from ._staging import normalise_transform_list, refuse_tile_with_downscale, resolve_device, stage_images, std_arguments
 
 
 def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFModelBase] = None,
@@ -96,10 +95,9 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
         index_batch, val_batch, std_batch, meta_batch = pending
         pending = next(batches, None)
         last = pending is None
-        images, max_code, layout = stage_images(val_batch, dev, transforms, want_layout=True)
+        planar = std_batch is not None or dark is not None  # explicit std / dark images are planar
+        images, max_code, layout = stage_images(val_batch, dev, transforms, planar)
         std, std_mode, std_value = std_arguments(std_batch, dataloader.dataset, dev)
-        if (std is not None or dark is not None) and layout != "nchw":  # explicit std / dark images are planar
-            images, max_code, layout = restage_planar(val_batch, images, dev, transforms)
         if dark is not None:
             xb, sig = dark.apply(index_batch, images, max_code, std, std_mode, std_value, tile, group)
             if xb is not None:  # the blurred batch replaces the images; its uncertainty carries both variance terms

@@ -31,7 +31,7 @@ def compute_video_mean_and_std(dataloader: DataLoader, device, icrf_model: Optio
     mean = m2 = None
     n_frames = 0
     for _, val_batch, _std_batch, _meta in dataloader:
-        frames, max_code, layout = stage_images(val_batch, dev, transforms, want_layout=True)
+        frames, max_code, layout = stage_images(val_batch, dev, transforms)
         if mean is None:
             f = frames.shape  # interleaved frames as decoded (CvToTorch folded into the kernel): the state is planar
             chw = tuple(f[1:]) if layout == "nchw" else (f[3], f[1], f[2])

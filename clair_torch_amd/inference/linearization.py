@@ -28,8 +28,8 @@ from torch.utils.data import DataLoader
 from .. import ops
 from ..common.typecheck import expect
 from ..models.base import ICRFModelBase
-from ._staging import normalise_transform_list, resolve_device, restage_planar, stage_images, std_arguments
-from ..common.transforms import fusable_code_normalisation, fusable_layout
+from ._staging import normalise_transform_list, resolve_device, stage_images, std_arguments
+from ..common.transforms import plan_staging
 
 _GROUP_BYTES = 256 << 20  # device-to-host bytes per group (two float32 planes per frame): ~5 frames of 1080p RGB
 _SLOTS = 3                # ring slots = groups in flight (copy-in | compute | copy-out)
@@ -65,29 +65,24 @@ def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRF
     # layout) fold into the load, or float32 pixels with no device transform at all.  Anything else (arbitrary
     # gpu_transforms, a dark field: per-frame conditional blur) goes frame by frame through the generic staging.
     probe = first[1]
-    layout, rest = fusable_layout(probe, transforms)
-    max_code = fusable_code_normalisation(probe, rest)
-    if max_code is None:
-        layout = "nchw"
-    streamable = dark is None and probe.ndim == 4 and ((max_code is not None) or
+    plan = plan_staging(probe, transforms, planar=first[2] is not None)  # explicit uncertainty images are planar
+    streamable = dark is None and probe.ndim == 4 and ((plan.route == "code" and plan.step == 1) or
                                                        (not transforms and probe.dtype == torch.float32))
-    if first[2] is not None and layout != "nchw":  # explicit uncertainty images are planar: generic route
-        streamable = False
     if not streamable:
         yield from _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat, flat_std, dark,
                                    output_layout == "cv")
         return
-    yield from _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, max_code, layout, output_layout == "cv")
+    yield from _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan.max_code, plan.layout,
+                          output_layout == "cv")
 
 
 def _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat, flat_std, dark, cv):
     item = first
     while item is not None:
         index_batch, val_batch, std_batch, meta_batch = item
-        images, max_code, layout = stage_images(val_batch, dev, transforms, want_layout=True)
+        planar = std_batch is not None or dark is not None  # explicit std / dark images are planar
+        images, max_code, layout = stage_images(val_batch, dev, transforms, planar)
         std, std_mode, std_value = std_arguments(std_batch, dataloader.dataset, dev)
-        if (std is not None or dark is not None) and layout != "nchw":  # explicit std / dark images are planar
-            images, max_code, layout = restage_planar(val_batch, images, dev, transforms)
         if dark is not None:
             lin, lin_std = dark.linearize(index_batch, images, max_code, std, std_mode, std_value, lut, interp)
         else:

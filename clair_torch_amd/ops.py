@@ -77,6 +77,31 @@ def _check_stack(stack: torch.Tensor, name="stack"):
         raise ValueError(f"every image of {name} must be contiguous (C, H, W)")
 
 
+def _default_max_code(t: torch.Tensor, max_code):
+    """``max_code`` as given; for integer codes None means the dtype's full range (float32 pixels carry none)."""
+    if t.dtype != torch.float32 and max_code is None:
+        return 255.0 if t.dtype == torch.uint8 else 65535.0
+    return max_code
+
+
+def _explicit_std(std: torch.Tensor, stack: torch.Tensor, name: str = "stack"):
+    _require_device(std, "std")
+    if std.shape != stack.shape:
+        raise ValueError(f"std shape != {name} shape")
+    return std.to(torch.float32).contiguous()
+
+
+def _checked_out(out, shape, dtype, device, dtype_name=None):
+    """``out`` when it is the contiguous device tensor of exactly ``shape`` / ``dtype`` a caller may pass, a fresh one
+    for None."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _require_device(out, "out")
+    if tuple(out.shape) != shape or out.dtype != dtype or out.device != device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {dtype_name or dtype} tensor of shape {shape} on {device}")
+    return out
+
+
 def _icrf_struct(lut: Optional[torch.Tensor], interp, channels):
     if lut is None:
         return nv.Icrf(lut_dev=None, n_points=0, interp=nv.INTERP_NONE), None
@@ -97,6 +122,32 @@ class MergeState:
         self.sumw = torch.empty(shape, dtype=torch.float32, device=device)
         self.var = torch.empty(shape, dtype=torch.float32, device=device) if with_variance else None
         self.batches = 0
+
+
+def _merge_setup(stack, layout, out_layout, state, finalize, has_std, mean_dtype, reference_order, flags, what):
+    """What hdr_merge_batch and hdr_merge_batches share: (flag word, out_shape, mean_out, std_out) after the MergeState checks."""
+    if state is None or state.batches == 0:
+        flags |= nv.MERGE_FIRST_BATCH
+    if finalize:
+        flags |= nv.MERGE_FINALIZE
+    if reference_order is not None:
+        flags |= nv.MERGE_REFERENCE_ORDER if reference_order else nv.MERGE_CLOSED_FORM
+    if mean_dtype == torch.float32:
+        flags |= nv.MERGE_MEAN_OUT_F32
+    elif mean_dtype != torch.float64:
+        raise TypeError("mean_dtype must be float64 (reference) or float32")
+    out_shape = _out_shape(stack, layout, out_layout)
+    if out_layout == "input":
+        flags |= nv.MERGE_OUT_AS_INPUT
+    if state is None and not finalize:
+        raise ValueError(f"a non-final {what} needs a MergeState")
+    if state is not None and has_std and state.var is None:
+        raise ValueError("MergeState was created without a variance buffer")
+    if state is not None and tuple(state.mean.shape) != out_shape:
+        raise ValueError(f"MergeState has shape {tuple(state.mean.shape)}, this merge needs {out_shape}")
+    mean_out = torch.empty(out_shape, dtype=mean_dtype, device=stack.device) if finalize else None
+    std_out = torch.empty(out_shape, dtype=torch.float32, device=stack.device) if (finalize and has_std) else None
+    return flags, out_shape, mean_out, std_out
 
 
 def hdr_merge_batch(stack: torch.Tensor, exposures: torch.Tensor, *, lut: Optional[torch.Tensor] = None,
@@ -137,8 +188,7 @@ def hdr_merge_batch(stack: torch.Tensor, exposures: torch.Tensor, *, lut: Option
                 stack = stack.contiguous()
     if std_mode not in _STD:
         raise ValueError(f"unknown std_mode {std_mode}")
-    if stack.dtype != torch.float32 and max_code is None:
-        max_code = 255.0 if stack.dtype == torch.uint8 else 65535.0
+    max_code = _default_max_code(stack, max_code)
     if exposures.is_cuda or dev.type != "cuda":
         exposure_dev = exposures.to(device=dev, dtype=torch.float64).contiguous()
     else:
@@ -150,28 +200,8 @@ def hdr_merge_batch(stack: torch.Tensor, exposures: torch.Tensor, *, lut: Option
         raise ValueError(f"{exposure_dev.numel()} exposure times for a batch of {b}")
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _geometry(stack, tile, layout)
-    has_std = std_mode != "none"
-    first = state is None or state.batches == 0
-    flags = (nv.MERGE_FIRST_BATCH if first else 0) | (nv.MERGE_FINALIZE if finalize else 0)
-    if force_f64_moments:
-        flags |= nv.MERGE_F64_MOMENTS
-    if reference_order is not None:
-        flags |= nv.MERGE_REFERENCE_ORDER if reference_order else nv.MERGE_CLOSED_FORM
-    if mean_dtype == torch.float32:
-        flags |= nv.MERGE_MEAN_OUT_F32
-    elif mean_dtype != torch.float64:
-        raise TypeError("mean_dtype must be float64 (reference) or float32")
-    out_shape = _out_shape(stack, layout, out_layout)
-    if out_layout == "input":
-        flags |= nv.MERGE_OUT_AS_INPUT
-    if state is None and not finalize:
-        raise ValueError("a non-final batch needs a MergeState")
-    if state is not None and has_std and state.var is None:
-        raise ValueError("MergeState was created without a variance buffer")
-    if state is not None and tuple(state.mean.shape) != out_shape:
-        raise ValueError(f"MergeState has shape {tuple(state.mean.shape)}, this merge needs {out_shape}")
-    mean_out = torch.empty(out_shape, dtype=mean_dtype, device=dev) if finalize else None
-    std_out = torch.empty(out_shape, dtype=torch.float32, device=dev) if (finalize and has_std) else None
+    flags, _, mean_out, std_out = _merge_setup(stack, layout, out_layout, state, finalize, std_mode != "none", mean_dtype,
+                                               reference_order, nv.MERGE_F64_MOMENTS if force_f64_moments else 0, "batch")
     with torch.cuda.device(dev):
         rc = nv.load().ct_hdr_merge_batch(
             _ptr(stack), _DTYPE[stack.dtype], float(max_code or 1.0), b, ctypes.byref(geom), _ptr(std), _STD[std_mode],
@@ -227,8 +257,7 @@ def hdr_merge_batches(stacks, exposures, *, lut: Optional[torch.Tensor] = None, 
     if std_mode not in _STD:
         raise ValueError(f"unknown std_mode {std_mode}")
     stacks = [t.contiguous() for t in stacks]
-    if stacks[0].dtype != torch.float32 and max_code is None:
-        max_code = 255.0 if stacks[0].dtype == torch.uint8 else 65535.0
+    max_code = _default_max_code(stacks[0], max_code)
     sizes = [int(t.shape[0]) for t in stacks]
     for e, n in zip(exposures, sizes):
         if e.numel() != n:
@@ -238,30 +267,12 @@ def hdr_merge_batches(stacks, exposures, *, lut: Optional[torch.Tensor] = None, 
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _geometry(stacks[0], tile, layout)
     has_std = std_mode != "none"
-    first = state is None or state.batches == 0
-    flags = (nv.MERGE_FIRST_BATCH if first else 0) | (nv.MERGE_FINALIZE if finalize else 0)
-    if reference_order is not None:
-        flags |= nv.MERGE_REFERENCE_ORDER if reference_order else nv.MERGE_CLOSED_FORM
-    if require_one_launch:
-        flags |= nv.MERGE_REQUIRE_ONE_LAUNCH
-    out_shape = _out_shape(stacks[0], layout, out_layout)
-    if out_layout == "input":
-        flags |= nv.MERGE_OUT_AS_INPUT
-    if mean_dtype == torch.float32:
-        flags |= nv.MERGE_MEAN_OUT_F32
-    elif mean_dtype != torch.float64:
-        raise TypeError("mean_dtype must be float64 (reference) or float32")
-    if state is None and not finalize:
-        raise ValueError("a non-final call needs a MergeState")
+    flags, out_shape, mean_out, std_out = _merge_setup(stacks[0], layout, out_layout, state, finalize, has_std, mean_dtype,
+                                                       reference_order, nv.MERGE_REQUIRE_ONE_LAUNCH if require_one_launch else 0,
+                                                       "call")
     if state is None:
         # several batches: whatever cannot run as one launch walks them with the state in memory
         state = MergeState(out_shape, dev, has_std)
-    if has_std and state.var is None:
-        raise ValueError("MergeState was created without a variance buffer")
-    if tuple(state.mean.shape) != out_shape:
-        raise ValueError(f"MergeState has shape {tuple(state.mean.shape)}, this merge needs {out_shape}")
-    mean_out = torch.empty(out_shape, dtype=mean_dtype, device=dev) if finalize else None
-    std_out = torch.empty(out_shape, dtype=torch.float32, device=dev) if (finalize and has_std) else None
     ptr_arr = (ctypes.c_void_p * k)(*[t.data_ptr() for t in stacks])
     std_arr = (ctypes.c_void_p * k)(*[sd.data_ptr() for sd in stds]) if stds is not None else None
     size_arr = (ctypes.c_int32 * k)(*sizes)
@@ -290,14 +301,8 @@ def linearize_frames(frames: torch.Tensor, lut: torch.Tensor, interp: str = "lin
     c, h, w = _chw(frames, layout)
     dev = frames.device
     if std is not None:
-        std_mode = "explicit"
-        _require_device(std, "std")
-        if std.shape != frames.shape:
-            raise ValueError("std shape != frames shape")
-        std = std.to(torch.float32).contiguous()
-        frames = frames.contiguous()
-    if frames.dtype != torch.float32 and max_code is None:
-        max_code = 255.0 if frames.dtype == torch.uint8 else 65535.0
+        std_mode, std = "explicit", _explicit_std(std, frames, "frames")
+    max_code = _default_max_code(frames, max_code)
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     frames = frames.contiguous()
     geom = _geometry(frames, tile, layout)
@@ -420,14 +425,9 @@ def pair_residual_sums(stack: torch.Tensor, pairs: PairList, *, lut: Optional[to
     if n != pairs.n_images:
         raise ValueError(f"pair list was built for {pairs.n_images} images, stack has {n}")
     if std is not None:
-        std_mode = "explicit"
-        _require_device(std, "std")
-        if std.shape != stack.shape:
-            raise ValueError("std shape != stack shape")
-        std = std.to(torch.float32).contiguous()
+        std_mode, std = "explicit", _explicit_std(std, stack)
         stack = stack.contiguous()
-    if stack.dtype != torch.float32 and max_code is None:
-        max_code = 255.0 if stack.dtype == torch.uint8 else 65535.0
+    max_code = _default_max_code(stack, max_code)
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _geometry(stack, tile, layout)
     prm = _pair_params(lower, upper, use_relative, use_unc_weight, std_mode, std_value)
@@ -466,8 +466,7 @@ def pair_residual_lut_grad(stack: torch.Tensor, pairs: PairList, coef: torch.Ten
         stack = stack.contiguous()
     if not use_unc_weight:
         std, std_mode = None, "none"
-    if stack.dtype != torch.float32 and max_code is None:
-        max_code = 255.0 if stack.dtype == torch.uint8 else 65535.0
+    max_code = _default_max_code(stack, max_code)
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _geometry(stack, tile, layout)
     prm = _pair_params(lower, upper, use_relative, use_unc_weight, std_mode, std_value,
@@ -575,14 +574,9 @@ def dark_field_blur(stack: torch.Tensor, dark: torch.Tensor, dark_std: Optional[
     b, c, h, w = stack.shape
     dev = stack.device
     if std is not None:
-        std_mode = "explicit"
-        _require_device(std, "std")
-        if std.shape != stack.shape:
-            raise ValueError("std shape != stack shape")
-        std = std.to(torch.float32).contiguous()
+        std_mode, std = "explicit", _explicit_std(std, stack)
     stack = stack.contiguous()
-    if stack.dtype != torch.float32 and max_code is None:
-        max_code = 255.0 if stack.dtype == torch.uint8 else 65535.0
+    max_code = _default_max_code(stack, max_code)
     dark = dark.to(device=dev, dtype=torch.float32).contiguous()
     if dark.ndim != 4 or dark.shape[0] not in (1, b) or tuple(dark.shape[1:]) != (c, h, w):
         raise ValueError(f"mask_map batch dimension must be 1 or {b}, got shape {tuple(dark.shape)}")
@@ -626,29 +620,18 @@ def strided_downscale(stack: torch.Tensor, step: int, layout: str = "nchw", out:
     (B,ceil(H/step),ceil(W/step),C) for "nhwc" / "nhwc_bgr" (the channel order is untouched) -- bit-identical to
     ``x[..., ::step, ::step]`` on the planar view.  ``out``: a contiguous caller tensor of exactly that shape and dtype
     to write into.  ``step == 1`` returns the stack itself (copied into ``out`` when given)."""
-    _require_device(stack, "stack")
-    if stack.ndim != 4:
-        raise ValueError(f"stack must be 4-dimensional, got shape {tuple(stack.shape)}")
-    if stack.dtype not in _DTYPE:
-        raise TypeError(f"stack dtype {stack.dtype} unsupported (uint8, uint16 codes or float32 pixels)")
-    if layout not in _LAYOUT:
-        raise ValueError(f"unknown layout {layout!r} (nchw, nhwc, nhwc_bgr)")
+    _check_ingest_stack(stack, layout, for_ingest=False)
     if isinstance(step, bool) or not isinstance(step, int) or step < 1:
         raise ValueError(f"step must be an int >= 1, got {step!r}")
     shape = downscaled_shape(stack.shape, step, layout)
-    if out is not None:
-        _require_device(out, "out")
-        if tuple(out.shape) != shape or out.dtype != stack.dtype or out.device != stack.device or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous {stack.dtype} tensor of shape {shape} on {stack.device}")
+    if step == 1 and out is None:
+        return stack
+    out = _checked_out(out, shape, stack.dtype, stack.device)
     if step == 1:
-        if out is None:
-            return stack
         alias = torch.int16 if stack.dtype == torch.uint16 else stack.dtype  # torch has no uint16 copy kernel
         out.view(alias).copy_(stack.view(alias))
         return out
     stack = stack.contiguous()
-    if out is None:
-        out = torch.empty(shape, dtype=stack.dtype, device=stack.device)
     if out.numel() == 0:
         return out
     if layout == "nchw":
@@ -693,12 +676,7 @@ def export_cv(x: torch.Tensor, dtype: Optional[torch.dtype] = None, out: Optiona
     shape = export_shape(tuple(x.shape))
     if not x.is_contiguous():
         raise ValueError("x must be contiguous")
-    if out is not None:
-        _require_device(out, "out")
-        if tuple(out.shape) != shape or out.dtype != dtype or out.device != x.device or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous {dtype} tensor of shape {shape} on {x.device}")
-    else:
-        out = torch.empty(shape, dtype=dtype, device=x.device)
+    out = _checked_out(out, shape, dtype, x.device)
     if out.numel() == 0:
         return out
     if x.ndim == 2:
@@ -770,7 +748,7 @@ def _ingest_stages(stages, channels: int, data: bool = False, limit: int = nv.IN
     return arr, len(stages)
 
 
-def _check_ingest_stack(stack: torch.Tensor, layout: str):
+def _check_ingest_stack(stack: torch.Tensor, layout: str, for_ingest: bool = True):
     _require_device(stack, "stack")
     if stack.ndim != 4:
         raise ValueError(f"stack must be 4-dimensional, got shape {tuple(stack.shape)}")
@@ -778,6 +756,8 @@ def _check_ingest_stack(stack: torch.Tensor, layout: str):
         raise TypeError(f"stack dtype {stack.dtype} unsupported (uint8, uint16 codes or float32 pixels)")
     if layout not in _LAYOUT:
         raise ValueError(f"unknown layout {layout!r} (nchw, nhwc, nhwc_bgr)")
+    if not for_ingest:  # strided_downscale: pixels of any size, and it makes the stack contiguous itself
+        return
     if layout != "nchw" and stack.shape[3] != 3:
         raise ValueError(f"layout {layout!r} takes (B, H, W, 3) frames, got shape {tuple(stack.shape)}")
     if not stack.is_contiguous():
@@ -807,12 +787,7 @@ def ingest_transform(stack: torch.Tensor, stages, layout: str = "nchw", out: Opt
     arr, n_stages = _ingest_stages(stages, shape[1], data=consts is not None)
     if consts is not None:
         _check_consts(consts, stack.device)
-    if out is not None:
-        _require_device(out, "out")
-        if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != stack.device or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on {stack.device}")
-    else:
-        out = torch.empty(shape, dtype=torch.float32, device=stack.device)
+    out = _checked_out(out, shape, torch.float32, stack.device, "float32")
     if out.numel() == 0:
         return out
     with torch.cuda.device(stack.device):
@@ -904,8 +879,7 @@ def video_stats_batch(frames: torch.Tensor, mean_state: torch.Tensor, m2_state: 
     c, h, w = _chw(frames, layout)
     dev = frames.device
     frames = frames.contiguous()
-    if frames.dtype != torch.float32 and max_code is None:
-        max_code = 255.0 if frames.dtype == torch.uint8 else 65535.0
+    max_code = _default_max_code(frames, max_code)
     for name, t in (("mean_state", mean_state), ("m2_state", m2_state)):
         _require_device(t, name)
         if t.dtype != torch.float32 or tuple(t.shape) != (c, h, w) or not t.is_contiguous():

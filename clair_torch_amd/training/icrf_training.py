@@ -17,8 +17,8 @@ from torch.utils.data import DataLoader
 from .. import ops
 from ..common.general_functions import get_valid_exposure_pairs
 from ..common.typecheck import expect
-from ..inference._staging import (normalise_transform_list, refuse_tile_with_downscale, resolve_device, restage_planar,
-                                  stage_images, std_arguments)
+from ..inference._staging import (normalise_transform_list, refuse_tile_with_downscale, resolve_device, stage_images,
+                                  std_arguments)
 from ..models.base import ICRFModelBase
 from .linearity import linearity_loss
 from .losses import (compute_endpoint_penalty, compute_monotonicity_penalty, compute_range_penalty,
@@ -109,10 +109,9 @@ def train_icrf(dataloader: DataLoader, batch_size: int, device, icrf_model: ICRF
     for epoch in range(epochs):
         running_loss = torch.zeros(channels, device=dev, dtype=torch.float64)
         for _, val_batch, std_batch, meta_batch in dataloader:
-            images, max_code, layout = stage_images(val_batch, dev, transforms, want_layout=True)
+            # explicit uncertainty images are planar
+            images, max_code, layout = stage_images(val_batch, dev, transforms, planar=std_batch is not None)
             std, std_mode, std_value = std_arguments(std_batch, dataloader.dataset, dev)
-            if std is not None and layout != "nchw":  # explicit uncertainty images are planar
-                images, max_code, layout = restage_planar(val_batch, images, dev, transforms)
             if images.shape[0] < 2:
                 print("Skipped batch due to single image.")
                 continue

@@ -20,7 +20,7 @@ from .. import ops
 from ..common.general_functions import get_valid_exposure_pairs
 from ..common.typecheck import expect
 from ..inference._staging import (resolve_device, stage_images, std_arguments, normalise_transform_list,
-                                  refuse_tile_with_downscale, restage_planar)
+                                  refuse_tile_with_downscale)
 from ..models.base import ICRFModelBase
 
 
@@ -105,10 +105,9 @@ def measure_linearity(dataloader: DataLoader, device, use_uncertainty_weighting:
     transforms = normalise_transform_list(gpu_transforms)
     refuse_tile_with_downscale(tile, transforms)
     for _, val_batch, std_batch, meta_batch in dataloader:
-        images, max_code, layout = stage_images(val_batch, dev, transforms, want_layout=True)
+        # explicit uncertainty images are planar
+        images, max_code, layout = stage_images(val_batch, dev, transforms, planar=std_batch is not None)
         std, std_mode, std_value = std_arguments(std_batch, dataloader.dataset, dev)
-        if std is not None and layout != "nchw":  # explicit uncertainty images are planar
-            images, max_code, layout = restage_planar(val_batch, images, dev, transforms)
         exposures = meta_batch["exposure_time"].to(torch.float64)
         i_idx, j_idx, ratio = get_valid_exposure_pairs(exposures, 0.2)
         pairs = ops.PairList(i_idx, j_idx, ratio, images.shape[0], dev)

@@ -124,7 +124,7 @@ def _lists(dtype, s):
 @pytest.mark.parametrize("dtype", [torch.uint8, torch.uint16])
 def test_stage_images_keeps_the_code_route(dev, dtype, s):
     from clair_torch_amd.common.transforms import BaseTransform
-    from clair_torch_amd.inference._staging import restage_planar, stage_images
+    from clair_torch_amd.inference._staging import stage_images
     rng = np.random.default_rng(s)
     planar = _random(rng, (4, 3, 18, 34), dtype)
     raw = planar.flip(1).permute(0, 2, 3, 1).contiguous() if dtype == torch.uint8 else \
@@ -132,17 +132,17 @@ def test_stage_images_keeps_the_code_route(dev, dtype, s):
     planar_lists, raw_lists = _lists(dtype, s)
     max_code = 255.0 if dtype == torch.uint8 else 65535.0
     for ts in planar_lists:
-        for want_layout in (False, True):
-            out = stage_images(planar, dev, ts, want_layout=want_layout)
-            assert out[0].dtype == dtype and out[1] == max_code and (not want_layout or out[2] == "nchw")
+        for need_planar in (True, False):
+            out = stage_images(planar, dev, ts, planar=need_planar)
+            assert out[0].dtype == dtype and out[1] == max_code and out[2] == "nchw"
             assert torch.equal(_bits(out[0]).cpu(), _bits(_host_sliced(planar, s)))
     for ts in raw_lists:
-        images, mc, layout = stage_images(raw, dev, ts, want_layout=True)
+        images, mc, layout = stage_images(raw, dev, ts)
         assert images.dtype == dtype and mc == max_code and layout == "nhwc_bgr"
         assert torch.equal(_bits(images).cpu(), _bits(_host_sliced(raw, s, raw=True)))
-        # a batch that has to be planar after all is staged again from the batch itself: the downscale is applied once
-        again, mc2, layout2 = restage_planar(raw, images, dev, ts)
-        generic, _ = stage_images(raw, dev, ts)
+        # a batch that has to be planar is staged on the generic route from the batch itself: the downscale is applied once
+        again, mc2, layout2 = stage_images(raw, dev, ts, planar=True)
+        generic, _, _ = stage_images(raw.to(dev), dev, ts, planar=True)  # ... whether it comes from the host or is there already
         assert mc2 is None and layout2 == "nchw" and again.dtype == torch.float32
         assert tuple(again.shape) == (4, 3, -(-18 // s), -(-34 // s)) and torch.equal(again, generic)
 
@@ -151,7 +151,7 @@ def test_stage_images_keeps_the_code_route(dev, dtype, s):
             return x
 
     # any other list holding the transform runs its __call__ on the generic route
-    images, mc = stage_images(planar, dev, planar_lists[0] + [Identity()])
+    images, mc, _ = stage_images(planar, dev, planar_lists[0] + [Identity()])
     assert mc is None and images.dtype == torch.float32 and tuple(images.shape) == (4, 3, -(-18 // s), -(-34 // s))
 
 

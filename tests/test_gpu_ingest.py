@@ -196,11 +196,11 @@ def test_float32_special_values(dev):
 
 
 # ---- stage order and count, through the recogniser and stage_images ------------------------------------------------------
-def _staged(dev, host, transforms, want_layout=False):
+def _staged(dev, host, transforms, planar=False):
     from clair_torch_amd.inference._staging import stage_images
-    out = stage_images(host, dev, transforms, want_layout=want_layout)
+    out = stage_images(host, dev, transforms, planar=planar)
     assert out[1] is None and out[0].dtype == torch.float32 and out[0].is_contiguous() and out[0].is_cuda
-    assert not want_layout or out[2] == "nchw"
+    assert out[2] == "nchw"
     return out[0]
 
 
@@ -220,7 +220,7 @@ def test_stage_order_and_count(dev):
         _plan(planar, ts)
         want = _cpu_chain(planar, ts)
         assert _same_bits(_staged(dev, planar, ts), want), k
-        assert _same_bits(_staged(dev, planar, ts, want_layout=True), want), k
+        assert _same_bits(_staged(dev, planar, ts, planar=True), want), k
     # five stages: the torch route, as before.  No bit-exactness is promised there: each of its 12 float32 operations is
     # within 1 ulp (6e-8 of a magnitude below 8) of the CPU's, and the two trailing normalizes amplify by 2.5 each
     five = [cast, code_clamp, n1, T.ClampAlongDims(1, PAIRS[3]), n2, n2]
@@ -231,7 +231,7 @@ def test_stage_order_and_count(dev):
 @pytest.mark.parametrize("s", [2, 3])
 def test_with_strided_downscale(dev, s):
     T = _T()
-    from clair_torch_amd.inference._staging import restage_planar
+    from clair_torch_amd.inference._staging import stage_images
     rng = np.random.default_rng(17 + s)
     planar = _random(rng, (3, 3, 18, 34), torch.uint16, top=5000)
     raw = _bgr_frames(planar)
@@ -242,8 +242,8 @@ def test_with_strided_downscale(dev, s):
         assert _same_bits(_cpu_chain(planar, ts), want)
         assert _same_bits(_staged(dev, planar, ts), want), (k, "planar")
         assert _same_bits(_staged(dev, raw, [cv] + ts), want), (k, "raw")
-        assert _same_bits(_staged(dev, raw, [cv] + ts, want_layout=True), want), (k, "raw, want_layout")
-        again, max_code, layout = restage_planar(raw, raw.to(dev), dev, [cv] + ts)
+        assert _same_bits(_staged(dev, raw, [cv] + ts, planar=True), want), (k, "raw, planar")
+        again, max_code, layout = stage_images(raw, dev, [cv] + ts, planar=True)
         assert max_code is None and layout == "nchw" and _same_bits(again, want), (k, "restaged")
 
 
@@ -310,9 +310,9 @@ def test_entry_points_equal_the_cpu_staged_float_stack(dev):
 
     # stage_images itself: planar, and raw (B,H,W,3) frames behind CvToTorch
     assert _same_bits(_staged(dev, codes, ts), pixels)
-    assert _same_bits(_staged(dev, codes, ts, want_layout=True), pixels)
+    assert _same_bits(_staged(dev, codes, ts, planar=True), pixels)
     assert _same_bits(_staged(dev, _bgr_frames(codes), [T.CvToTorch()] + ts), pixels)
-    assert _same_bits(_staged(dev, _bgr_frames(codes), [T.CvToTorch()] + ts, want_layout=True), pixels)
+    assert _same_bits(_staged(dev, _bgr_frames(codes), [T.CvToTorch()] + ts, planar=True), pixels)
 
 
 # ---- front-end checks, the custom op, graph capture ------------------------------------------------------------------------

@@ -175,11 +175,11 @@ def test_extremum_at_every_kind_of_position(dev, mode):
 
 
 # ---- prefix, suffix, stage count ------------------------------------------------------------------------------------------
-def _staged(dev, host, transforms, want_layout=False):
+def _staged(dev, host, transforms, planar=False):
     from clair_torch_amd.inference._staging import stage_images
-    out = stage_images(host, dev, transforms, want_layout=want_layout)
+    out = stage_images(host, dev, transforms, planar=planar)
     assert out[1] is None and out[0].dtype == torch.float32 and out[0].is_contiguous() and out[0].is_cuda
-    assert not want_layout or out[2] == "nchw"
+    assert out[2] == "nchw"
     return out[0]
 
 
@@ -199,9 +199,9 @@ def test_prefix_suffix_and_stage_count(dev):
         assert T.fusable_ingest_data(planar, ts) is not None and T.fusable_ingest_data(raw, [cv] + ts).layout == "nhwc_bgr"
         want = _cpu_chain(planar, ts)
         assert _same(_staged(dev, planar, ts), want), (k, "planar")
-        assert _same(_staged(dev, planar, ts, want_layout=True), want), (k, "planar, want_layout")
+        assert _same(_staged(dev, planar, ts, planar=True), want), (k, "planar, planar=True")
         assert _same(_staged(dev, raw, [cv] + ts), want), (k, "raw")
-        assert _same(_staged(dev, raw, [cv] + ts, want_layout=True), want), (k, "raw, want_layout")
+        assert _same(_staged(dev, raw, [cv] + ts, planar=True), want), (k, "raw, planar=True")
         assert _same(_run(dev, _rgb_frames(planar), ts, "nhwc", planar), want), (k, "nhwc")
     # five stages: the torch route, as before.  No bit-exactness is promised there: the extrema are exact, each of the 12
     # elementwise float32 operations is within 1 ulp (6e-8 of a magnitude below 8) of the CPU's, and the one stage behind
@@ -220,7 +220,7 @@ def test_prefix_suffix_and_stage_count(dev):
 @pytest.mark.parametrize("s", [2, 3])
 def test_downscale_in_front_of_and_behind_the_normalize(dev, s):
     T = _T()
-    from clair_torch_amd.inference._staging import restage_planar
+    from clair_torch_amd.inference._staging import stage_images
     rng = np.random.default_rng(59 + s)
     planar = _random(rng, (3, 3, 18, 34), torch.uint16, top=5000)
     flat = planar.view(torch.int16)
@@ -239,8 +239,8 @@ def test_downscale_in_front_of_and_behind_the_normalize(dev, s):
         assert _same_bits(_cpu_chain(planar, ts), want)
         assert _same(_staged(dev, planar, ts), want), (k, "planar")
         assert _same(_staged(dev, raw, [cv] + ts), want), (k, "raw")
-        assert _same(_staged(dev, raw, [cv] + ts, want_layout=True), want), (k, "raw, want_layout")
-        again, max_code, layout = restage_planar(raw, raw.to(dev), dev, [cv] + ts)
+        assert _same(_staged(dev, raw, [cv] + ts, planar=True), want), (k, "raw, planar=True")
+        again, max_code, layout = stage_images(raw, dev, [cv] + ts, planar=True)
         assert max_code is None and layout == "nchw" and _same(again, want), (k, "restaged")
 
 
@@ -279,7 +279,7 @@ def test_nan_infinities_and_the_zero_range(dev):
         with pytest.raises(ValueError, match=ZERO):
             stage_images(const, dev, [cast, free])
         with pytest.raises(ValueError, match=ZERO):
-            stage_images(const, dev, [cast, T.Normalize(fill, None)], want_layout=True)
+            stage_images(const, dev, [cast, T.Normalize(fill, None)], planar=True)
         with pytest.raises(ValueError, match=ZERO):
             ops.ingest_transform_data(const.to(dev), [("affine_data", 1.0, 0.0)], check=True)
         out, consts = ops.ingest_transform_data(const.to(dev), [("affine_data", 1.0, 0.0)], check=False)

@@ -158,7 +158,7 @@ def test_stage_images_on_a_cpu_device_still_runs_the_classes():
         want = u16
         for t in ts:
             want = t(want)
-        got, max_code = stage_images(u16, cpu, ts)
+        got, max_code, _ = stage_images(u16, cpu, ts)
         assert max_code is None and got.dtype == torch.float32 and got.is_contiguous()
         assert np.array_equal(_bits(got.numpy()), _bits(want.contiguous().numpy()))
     with pytest.raises(ValueError, match="range is zero"):

@@ -159,9 +159,9 @@ def test_declined_lists_behave_as_before_on_the_torch_route():
         stage_images(u16, cpu, [cast, T.Normalize(64, 64)])
     with pytest.raises(ValueError, match="min/max pairs"):
         stage_images(u16, cpu, [cast, T.Normalize(4095, 64), T.ClampAlongDims(1, PAIRS3[:2])])
-    got, max_code = stage_images(u16, cpu, [cast, T.Normalize(None, 0)])
+    got, max_code, _ = stage_images(u16, cpu, [cast, T.Normalize(None, 0)])
     assert max_code is None and torch.equal(got, u16.to(torch.float32) / float(u16.to(torch.float32).max()))
-    got, max_code, layout = stage_images(u16, cpu, [cast, T.Normalize(4095, 64), T.ClampAlongDims(2, [(0.0, 1.0)] * 4)], want_layout=True)
+    got, max_code, layout = stage_images(u16, cpu, [cast, T.Normalize(4095, 64), T.ClampAlongDims(2, [(0.0, 1.0)] * 4)])
     assert max_code is None and layout == "nchw" and got.dtype == torch.float32
 
 
