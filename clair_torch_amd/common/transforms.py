@@ -21,6 +21,10 @@ route of this table that applies is taken:
                 classes, non-contiguous or non-4-D batches off the code pair           kernel variant
 = ============= ==================================================================== =====================================
 
+linearize_dataset_generator streams routes 2 and 3 (no ``StridedDownscale``, no dark field) through its copy / compute /
+copy pipeline -- route 3 by ct_linearize_ingest, which evaluates the chain and the ICRF in one pass over the raw frames --
+and float32 batches with an empty list; everything else goes frame by frame (inference/linearization.py::pipeline_route).
+
 A leading ``CvToTorch`` on (B,H,W,3) uint8 / uint16 frames is never executed on routes 1-4: the code-route kernels read the
 interleaved frames as they are (layout "nhwc_bgr") and the fused ingest reads them itself.  A caller that needs a planar
 stack (``planar=True``: explicit std and dark-field images are planar) gets no "nhwc_bgr": such a list goes to route 3.
@@ -221,7 +225,8 @@ class StagingPlan:
     table at the top of this module); ``layout``: of the staged result, "nhwc_bgr" only on the code route;
     ``source_layout``: how the fused ingest reads the batch ("nhwc_bgr": raw frames behind a leading CvToTorch);
     ``step``: the StridedDownscale to apply to the raw stack (1 = none); ``max_code``: of the code route; ``stages``,
-    ``step_first``, ``prefix``, ``min_val`` / ``max_val``: as in ``IngestPlan`` / ``DataIngestPlan``."""
+    ``step_first``, ``prefix``, ``min_val`` / ``max_val``: as in ``IngestPlan`` / ``DataIngestPlan``; ``no_transforms``: the
+    list is empty (route "torch" with nothing to run)."""
     route: str
     layout: str = "nchw"
     step: int = 1
@@ -232,6 +237,7 @@ class StagingPlan:
     min_val: Optional[float] = None
     max_val: Optional[float] = None
     source_layout: str = "nchw"
+    no_transforms: bool = False
 
 
 def _recognise_ingest(images: torch.Tensor, transforms) -> Optional[StagingPlan]:
@@ -343,4 +349,4 @@ def plan_staging(images: torch.Tensor, transforms, planar: bool = False) -> Stag
     fused = _recognise_ingest(images, ts)
     if fused is not None and (fused.route == "ingest" or images.is_cuda):
         return fused
-    return StagingPlan("torch")  # 5
+    return StagingPlan("torch", no_transforms=not ts)  # 5

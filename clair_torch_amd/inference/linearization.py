@@ -8,9 +8,18 @@ LINEAR / LOOKUP std bit for bit -- but the frames move through a three-stage pip
 
     DataLoader (one frame per item, as the reference requires)
       -> host-to-device copies of a GROUP of frames on a copy stream (plain DMA when the dataset hands out pinned memory)
-      -> ONE multi-frame ct_linearize_std launch (+ ct_flatfield_*) on the compute stream, into re-used ring slots
+      -> ONE multi-frame ct_linearize_std launch -- or, for a transform list the fused ingest evaluates, ONE
+         ct_linearize_ingest launch on the raw frames -- (+ ct_flatfield_*) on the compute stream, into re-used ring slots
       -> device-to-host copies of (lin, std) into pinned host tensors on a second copy stream
       -> each frame is yielded once its group's copy event has completed; the next groups are already in flight.
+
+Which inputs take the pipeline is ``pipeline_route``'s answer: the code pair ``[CastTo(float32), Normalize(max, 0)]`` on raw
+codes (folded into ct_linearize_std's load), float32 pixels with no transform list, and every list of ``plan_staging``'s
+route "ingest" without a StridedDownscale -- a black level, a target range, ``ClampAlongDims``, raw BGR frames behind
+``CvToTorch`` with explicit (planar) uncertainty images.  For the latter the ring slot keeps the RAW frames in their own
+dtype and memory order and ct_linearize_ingest evaluates chain and ICRF in one pass, bit for bit what ct_ingest_transform
+followed by ct_linearize_std gives on the frame-by-frame route.  A dark field, a downscale off the code pair, a
+data-dependent ``Normalize`` and lists that run as torch ops go frame by frame.
 
 ``output_layout="cv"`` (extension): every yielded pair is in the order the reference's ``save_image`` writes -- (H,W,C),
 a 3-channel frame reversed to BGR -- made by two ct_export_cv launches per group before the device-to-host copy, which
@@ -61,19 +70,30 @@ def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRF
     first = next(items, None)
     if first is None:
         return
-    # Which route?  The pipeline ingests what the kernel ingests: raw integer codes whose normalisation (and OpenCV
-    # layout) fold into the load, or float32 pixels with no device transform at all.  Anything else (arbitrary
-    # gpu_transforms, a dark field: per-frame conditional blur) goes frame by frame through the generic staging.
     probe = first[1]
     plan = plan_staging(probe, transforms, planar=first[2] is not None)  # explicit uncertainty images are planar
-    streamable = dark is None and probe.ndim == 4 and ((plan.route == "code" and plan.step == 1) or
-                                                       (not transforms and probe.dtype == torch.float32))
-    if not streamable:
+    if pipeline_route(probe, plan, dark is not None) != "pipelined":
         yield from _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat, flat_std, dark,
                                    output_layout == "cv")
         return
-    yield from _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan.max_code, plan.layout,
-                          output_layout == "cv")
+    yield from _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan, output_layout == "cv")
+
+
+def pipeline_route(probe: torch.Tensor, plan, has_dark: bool) -> str:
+    """"pipelined" | "frame_by_frame" for a run whose first value batch is ``probe`` (shape and dtype only: a CPU tensor
+    will do) and whose transform list ``plan_staging`` planned as ``plan``.  The pipeline ingests what one kernel
+    ingests from a ring slot: raw integer codes whose normalisation (and OpenCV layout) fold into ct_linearize_std's
+    load, float32 pixels with no device transform at all, or -- route "ingest" -- raw frames whose whole chain
+    ct_linearize_ingest evaluates.  Anything else goes frame by frame through the generic staging: a dark field
+    (per-frame conditional blur), a StridedDownscale off the code pair, a data-dependent Normalize (its extrema are per
+    frame here, per stack in ct_ingest_extrema), lists that run as torch ops."""
+    if has_dark or probe.ndim != 4:
+        return "frame_by_frame"
+    if plan.route in ("code", "ingest") and plan.step == 1:
+        return "pipelined"
+    if plan.route == "torch" and plan.no_transforms and probe.dtype == torch.float32:
+        return "pipelined"
+    return "frame_by_frame"
 
 
 def _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat, flat_std, dark, cv):
@@ -99,9 +119,10 @@ def _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat
 class _Slot:
     """One ring slot: device buffers for a group of frames and the events that order its three stages."""
 
-    def __init__(self, group, frame_shape, dtype, with_std, chw, dev, cv):
+    def __init__(self, group, frame_shape, dtype, std_shape, chw, dev, cv):
         self.frames = torch.empty((group,) + tuple(frame_shape), dtype=dtype, device=dev)
-        self.std = torch.empty((group,) + tuple(frame_shape), dtype=torch.float32, device=dev) if with_std else None
+        # explicit uncertainty images: frame-shaped beside ct_linearize_std, planar (C,H,W) beside ct_linearize_ingest
+        self.std = torch.empty((group,) + tuple(std_shape), dtype=torch.float32, device=dev) if std_shape is not None else None
         self.lin_out = torch.empty((group,) + tuple(chw), dtype=torch.float32, device=dev)
         self.std_out = torch.empty_like(self.lin_out)
         # output_layout="cv": the (group, H, W, C) exports the device-to-host copy reads instead
@@ -111,7 +132,7 @@ class _Slot:
         self.busy = False
 
 
-def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, max_code, layout, cv):
+def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan, cv):
     # Memory note for consumers: the yielded CPU tensors of one group (up to _GROUP_BYTES = 256 MB of output, 5 frames of
     # 1080p RGB) are views of two pinned host tensors, so keeping ONE frame alive keeps its group's pinned pages, and
     # list(generator) page-locks the whole output.  The reference hands out independent pageable .cpu() copies; copying
@@ -119,12 +140,16 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, max_c
     # frames should .clone() what it keeps.
     probe = first[1]
     frame_shape = tuple(probe.shape[1:])
+    # an ingest plan: the slot keeps the RAW frames, (H,W,3) behind a folded CvToTorch, and the kernel runs the chain
+    fused = plan.route == "ingest"
+    layout, max_code = (plan.source_layout if fused else plan.layout), plan.max_code
     chw = frame_shape if layout == "nchw" else (frame_shape[2], frame_shape[0], frame_shape[1])
     out_bytes = 2 * 4 * chw[0] * chw[1] * chw[2]
     group = max(1, min(16, _GROUP_BYTES // out_bytes))
     std_probe, std_mode, std_value = std_arguments(first[2], dataloader.dataset, torch.device("cpu"))
     with_std = std_probe is not None
-    slots = [_Slot(group, frame_shape, probe.dtype, with_std, chw, dev, cv) for _ in range(_SLOTS)]
+    std_shape = (chw if fused else frame_shape) if with_std else None
+    slots = [_Slot(group, frame_shape, probe.dtype, std_shape, chw, dev, cv) for _ in range(_SLOTS)]
     compute = torch.cuda.current_stream(dev)
     h2d, d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
     in_flight = deque()  # (slot, n frames, pinned lin, pinned std, metas)
@@ -163,9 +188,15 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, max_c
             slot.copied_in.record(h2d)
         compute.wait_event(slot.copied_in)
         compute.wait_event(slot.copied_out)  # the slot's output buffers were last read by its previous copy-out
-        lin, lin_std = ops.linearize_frames(slot.frames[:k], lut, interp, std=slot.std[:k] if with_std else None,
-                                            std_mode=std_mode, std_value=std_value, max_code=max_code, want_std=True,
-                                            layout=layout, out=(slot.lin_out[:k], slot.std_out[:k]))
+        if fused:
+            lin, lin_std = ops.linearize_ingest_frames(slot.frames[:k], plan.stages, lut, interp,
+                                                       std=slot.std[:k] if with_std else None, std_mode=std_mode,
+                                                       std_value=std_value, want_std=True, layout=layout,
+                                                       out=(slot.lin_out[:k], slot.std_out[:k]))
+        else:
+            lin, lin_std = ops.linearize_frames(slot.frames[:k], lut, interp, std=slot.std[:k] if with_std else None,
+                                                std_mode=std_mode, std_value=std_value, max_code=max_code, want_std=True,
+                                                layout=layout, out=(slot.lin_out[:k], slot.std_out[:k]))
         if flat is not None:  # linearization.py:118-130
             ops.flatfield_correct(lin, lin_std, flat, flat_std, input_is_variance=False, through_mean=False)
         if cv:

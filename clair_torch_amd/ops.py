@@ -802,6 +802,64 @@ def ingest_transform(stack: torch.Tensor, stages, layout: str = "nchw", out: Opt
     return out
 
 
+# ---- such a chain and the linearization in one pass ----------------------------------------------------------------------
+def linearize_ingest_frames(frames: torch.Tensor, stages, lut: Optional[torch.Tensor], interp: Optional[str] = "linear", *,
+                            std: Optional[torch.Tensor] = None, std_mode: str = "none", std_value: float = 0.0,
+                            want_std: bool = True, tile: Optional[TileGeometry] = None, layout: str = "nchw", out=None):
+    """ct_linearize_ingest: ``linearize_frames(ingest_transform(frames, stages, layout), lut, interp, ...)`` bit for bit,
+    in one launch and without the float32 stack in between -> (lin float32, std float32 | None), planar (F,C,H,W).
+    ``frames``: a contiguous uint8 / uint16 / float32 device stack, (F,C,H,W) for "nchw" or (F,H,W,3) for "nhwc" /
+    "nhwc_bgr" (the order of the source: a folded CvToTorch).  ``stages``: as ``ingest_transform`` takes them, without
+    ("affine_data", ...).  ``std``: explicit uncertainties, float32 and PLANAR (F,C,H,W) like the outputs whatever the
+    layout of the frames (gpu_transforms never touch the uncertainty images).  ``tile``: the frames are a row band of a
+    taller image, as in ``linearize_frames``.  ``out`` = (lin, std | None): caller-owned contiguous float32 (F,C,H,W)
+    device buffers to write into."""
+    _check_ingest_stack(frames, layout)
+    shape = ingest_shape(tuple(frames.shape), layout)
+    f, c, h, w = shape
+    dev = frames.device
+    arr, n_stages = _ingest_stages(stages, c)
+    if std is not None:
+        std_mode = "explicit"
+        _require_device(std, "std")
+        if std.dtype != torch.float32 or tuple(std.shape) != shape or std.device != dev:
+            raise ValueError(f"std must be a float32 tensor of shape {shape} (planar, like the outputs) on {dev}")
+        std = std.contiguous()
+    if std_mode not in _STD:
+        raise ValueError(f"unknown std_mode {std_mode}")
+    icrf, lut_keep = _icrf_struct(lut, interp, c)
+    hg, r0 = (h, 0) if tile is None else (tile.h_global, tile.row_offset)
+    if r0 < 0 or r0 + h > hg:
+        raise ValueError(f"tile rows [{r0}, {r0 + h}) do not fit a global height of {hg}")
+    geom = nv.Geometry(channels=c, h_tile=h, width=w, h_global=hg, row_offset=r0, image_stride=c * h * w, layout=_LAYOUT[layout])
+    if out is None:
+        lin = torch.empty(shape, dtype=torch.float32, device=dev)
+        std_out = torch.empty_like(lin) if want_std else None
+    else:
+        lin, std_out = out
+        for name, t in (("out[0]", lin), ("out[1]", std_out)):
+            if t is None:
+                continue
+            _require_device(t, name)
+            if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape}")
+        if lin is None:
+            raise ValueError("out[0] is required")
+        if want_std and std_out is None:
+            raise ValueError("want_std needs out[1]")
+        if not want_std:
+            std_out = None
+    if frames.numel() == 0:
+        return lin, std_out
+    with torch.cuda.device(dev):
+        rc = nv.load().ct_linearize_ingest(_ptr(frames), _DTYPE[frames.dtype], f, ctypes.byref(geom), arr, n_stages, _ptr(std),
+                                           _STD[std_mode], float(std_value), ctypes.byref(icrf), _ptr(lin), _ptr(std_out),
+                                           _stream(dev))
+    nv.check(rc, "ct_linearize_ingest")
+    del lut_keep
+    return lin, std_out
+
+
 # ---- a data-dependent Normalize (max_val / min_val None) in such a chain ------------------------------------------------
 ZERO_RANGE = "Normalization range is zero (min == max); cannot normalize."  # general_functions.py:378
 

@@ -20,6 +20,9 @@ and pair lists are passed as their component tensors / scalars.
     torch.ops.clair_hip.export_cv(x, to_f64) -> Tensor   (planar result -> the (H,W,C) BGR array save_image writes)
     torch.ops.clair_hip.ingest_transform(stack, stages, layout) -> Tensor   (CastTo / Normalize / ClampAlongDims chain in
                                   one pass; stages = 13 floats each: kind, sub, div, mul, add, lo[0..3], hi[0..3])
+    torch.ops.clair_hip.linearize_ingest(frames, stages, lut, interp, std?, std_mode, std_value, layout, h_global,
+                                  row_offset) -> (lin, std)   (such a chain and linearize_std in one pass; stages flattened
+                                  likewise; an explicit std is planar (F,C,H,W) like the outputs)
     torch.ops.clair_hip.ingest_extrema(stack, prefix, layout, min_val?, max_val?) -> Tensor   (4 floats: sub, div, data
                                   min, data max of a data-dependent Normalize behind the constant ``prefix`` stages)
 
@@ -220,6 +223,22 @@ def ingest_transform(stack: torch.Tensor, stages: Sequence[float], layout: str =
 @ingest_transform.register_fake
 def _(stack, stages, layout="nchw"):
     return stack.new_empty(ops.ingest_shape(tuple(stack.shape), layout), dtype=torch.float32)
+
+
+@torch.library.custom_op(f"{_LIB}::linearize_ingest", mutates_args=())
+def linearize_ingest(frames: torch.Tensor, stages: Sequence[float], lut: torch.Tensor, interp: str, std: Optional[torch.Tensor],
+                     std_mode: str, std_value: float, layout: str = "nchw", h_global: int = 0,
+                     row_offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ct_linearize_ingest: ingest_transform followed by linearize_std, bit for bit, in one pass over the raw frames."""
+    return ops.linearize_ingest_frames(frames, _listed_ingest_stages(frames, stages, layout), lut, interp, std=std,
+                                       std_mode=std_mode, std_value=std_value, want_std=True, tile=_tile(h_global, row_offset),
+                                       layout=layout)
+
+
+@linearize_ingest.register_fake
+def _(frames, stages, lut, interp, std, std_mode, std_value, layout="nchw", h_global=0, row_offset=0):
+    shape = ops.ingest_shape(tuple(frames.shape), layout)
+    return frames.new_empty(shape, dtype=torch.float32), frames.new_empty(shape, dtype=torch.float32)
 
 
 @torch.library.custom_op(f"{_LIB}::ingest_extrema", mutates_args=())

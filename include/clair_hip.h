@@ -397,6 +397,32 @@ int ct_ingest_transform_data(const void *src_dev, int32_t dtype, int32_t layout,
                              const float *consts_dev, void *stream);
 
 /*
+ * ct_linearize_ingest -- such a chain and the body of linearize_dataset_generator in ONE pass over F independent frames:
+ * the outputs are bit for bit those of ct_ingest_transform followed by ct_linearize_std on its float32 result,
+ *   x   = the stage list applied to (float)sample (CT_INGEST_AFFINE / CT_INGEST_CLAMP only, at most
+ *         CT_INGEST_MAX_STAGES; n_stages = 0 is the cast alone; a CT_INGEST_AFFINE_DATA stage is
+ *         CT_ERR_INVALID_ARGUMENT)
+ *   lin = f(x), std = sqrt((f'(x) * sigma)^2) as ct_linearize_std computes them for a CT_DTYPE_F32 frame holding x;
+ *         sigma = std_value (CONSTANT), std_value * x (MULTIPLIER, x behind the chain) or std_dev[...] (EXPLICIT)
+ * without the float32 stack in between (10 bytes of memory traffic per uint16 sample instead of 18).
+ *   frames_dev   CT_DTYPE_U8 / U16 / F32, aligned to its element; geom->layout CT_LAYOUT_NCHW (any C) or, with C == 3,
+ *                CT_LAYOUT_NHWC / NHWC_BGR: the order of the SOURCE (a folded CvToTorch); frames image_stride elements apart
+ *   geom         h_global / row_offset as for ct_linearize_std: a row band gives the same rows of the whole image (the
+ *                LINEAR / CATMULL LUT row is the global flat NCHW index modulo C, the LOOKUP row the channel)
+ *   lin_out_dev, std_out_dev   planar (F, C, H_tile, W) float32, dense, aligned to 4 bytes; std_out_dev may be NULL (value only)
+ *   std_dev      EXPLICIT: planar (F, C, H_tile, W) float32, dense, like the OUTPUTS -- not like the stack, as
+ *                ct_linearize_std's explicit std is: gpu_transforms never touch the uncertainty images, which are planar
+ *                even where the frames are interleaved
+ * CT_ERR_UNSUPPORTED: an interleaved layout with C != 3; clamp pairs that differ between channels with
+ * C > CT_INGEST_MAX_CHANNELS.  LUT size limits, CT_ERR_NO_GRADIENT_PATH and CT_ERR_TOO_LARGE as ct_linearize_std.  Every
+ * argument is validated before anything touches the device; n_frames == 0 is CT_OK without a launch.  Allocates nothing,
+ * synchronises nothing, never writes the frames, touches nothing outside F*C*H_tile*W elements of the outputs.
+ */
+int ct_linearize_ingest(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
+                        const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,
+                        float std_value, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev, void *stream);
+
+/*
  * ct_export_cv -- the array save_image hands to cv.imwrite (clair_torch/common/data_io.py:228-234: astype, transpose to
  * (H, W, C), channel reversal of a 3-channel image), made on the device from planar results:
  *   dst[f][p][c'] = (dst type) src[f][c][p],  p < plane = H*W,  c' = channels-1-c when reverse_channels, else c
