@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/clair_hip.h"
 
@@ -396,6 +397,17 @@ static inline int resident_workgroups(size_t lds_bytes, int block_threads)
     size_t slots = by_lds < by_waves ? by_lds : by_waves;
     if (slots < 1) slots = 1;
     return compute_units() * (int)slots;
+}
+
+// ---- host: dispatch ------------------------------------------------------------------------------------------------
+// Lifts a run-time value to a compile-time one: f(std::integral_constant<int, v>{}) for the v among VALUES that equals
+// `value`; CT_ERR_INVALID_ARGUMENT when none does.
+template <int... VALUES, typename F>
+static int with_enum(int value, F &&f)
+{
+    int rc = CT_ERR_INVALID_ARGUMENT;
+    (void)((value == VALUES ? (rc = f(std::integral_constant<int, VALUES>{}), true) : false) || ...);
+    return rc;
 }
 
 }  // namespace ct

@@ -719,16 +719,6 @@ static size_t pivot_lds_bytes(const MergeArgs &a, const PivotArgs &x, int interp
     return table + 2 * sizeof(float) * (size_t)a.batch;
 }
 
-// Lifts a run-time value to a compile-time one: f(std::integral_constant<int, v>{}) for the v among VALUES that equals
-// `value`; CT_ERR_INVALID_ARGUMENT when none does.
-template <int... VALUES, typename F>
-static int with_enum(int value, F &&f)
-{
-    int rc = CT_ERR_INVALID_ARGUMENT;
-    (void)((value == VALUES ? (rc = f(std::integral_constant<int, VALUES>{}), true) : false) || ...);
-    return rc;
-}
-
 // f(INTERP, WEIGHT, STD) with the three run-time modes of a merge as compile-time constants.
 template <typename F>
 static int with_merge_modes(int interp, int weight_mode, int std_mode, F &&f)

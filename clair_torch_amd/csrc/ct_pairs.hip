@@ -22,6 +22,10 @@
 //                   The uncertainty-weighted loss (weights depending on the LUT through err) uses the same kernel with the
 //                   linearized stds staged as a fourth per-column array.
 // Grids are sized to whole rounds of what the device holds at once (resident_workgroups, ct_device.hpp).
+// Shared by the kernels: phase 1 (stage_tile / VecStager), the LUT staging choice (stage_pair_lut) and, in the two backward
+// kernels, the column -> histogram-row table (fill_colrow) and the histogram flush (flush_hist).  Host: with_enum
+// compositions (ct_device.hpp) lift dtype, interpolation, std mode, level and the relative flag to template arguments;
+// set_tile fixes a launch's tile geometry; with_pixel_type is the dtype step of both entry points.
 //
 // Arithmetic: the reference computes the residual in float64 because the ratio is float64.  Here
 // diff = I_i - I_j * r is formed with two float32 FMAs against r = r_hi + r_lo, which is exact to ~1 ulp of the
@@ -32,11 +36,10 @@
 #include <cstdlib>
 #include "ct_device.hpp"
 
-namespace ct {
+extern "C" int ct_norm_constants(float max_code, float *hi, float *lo);
+extern "C" int ct_pivot_floor_constants(float max_code, int n_points, float *rcp_step);
 
-#ifndef CT_ABLATE_PAIR_PHASE
-#define CT_ABLATE_PAIR_PHASE 0  // 1 (tools/pairs_bench only): skip the pair loops, time staging + scatter + barriers alone
-#endif
+namespace ct {
 
 struct PairArgs {
     const void *stack;
@@ -78,12 +81,6 @@ struct PairArgs {
     float code_lo, code_hi;          // smallest / largest code whose normalised value lies in [lower, upper]
     float code_dk_mul, code_dk_add;  // Gaussian weight = exp2(-dk^2), dk = code * mul + add
 };
-
-template <typename T>
-__device__ __forceinline__ float load_pixel(const void *base, int64_t idx, NormConst nc)
-{
-    return to_pixel<T>(static_cast<const T *>(base)[idx], nc);
-}
 
 // Where channel plane c of pixel `pixel` (index inside the tile's plane) lives in one image, and the distance to the next
 // pixel of the same plane: planar stacks c * plane + pixel / 1, interleaved (H, W, C) stacks pixel * C + c' / C with
@@ -134,7 +131,7 @@ __device__ __forceinline__ float2 code_domain_sample(const PairArgs &a, const ch
     return make_float2(lin, valid ? gw : -INFINITY);
 }
 
-// Phase 1 shared by both kernels: linearize every sample of the tile into LDS.
+// Phase 1 shared by all kernels: linearize every sample of the tile into LDS.
 //   val[n*pitch + px] = (f(x), gauss(x))   gauss = -inf when x is outside [lo, hi]: the pair weight g_i + g_j is then
 //                                          -inf as well and max(., 0) applies the pair mask in one instruction
 //   aux[n*pitch + px] = LUT coordinate s (backward) or linearized std |f'(x) sigma| (forward, STD != none)
@@ -413,6 +410,16 @@ struct VecStager {
     }
 };
 
+// The LUT in LDS as the staging of this launch reads it: {g[i], slope} for the code domain, interpolation entries otherwise.
+template <int INTERP>
+__device__ __forceinline__ void stage_pair_lut(const PairArgs &a, char *lds)
+{
+    if (INTERP == CT_INTERP_LINEAR && a.code_domain)
+        stage_lut_slope(lds, a.lut, a.channels, a.n_points, a.code_step);
+    else
+        stage_lut<INTERP>(lds, a.lut, a.channels, a.n_points);
+}
+
 // sign(d) in {-1, 0, +1} without compares: d * 2^127 is >= 2 in magnitude for every normal d, the median clamps it.
 __device__ __forceinline__ float sign_of(float d)
 {
@@ -421,11 +428,8 @@ __device__ __forceinline__ float sign_of(float d)
 
 // ---- forward -------------------------------------------------------------------------------------
 // LEVEL 0: sums 0,1 (training loss).  LEVEL 1: all five sums (measure_linearity: std, error, count).
-#ifndef CT_FWD_KERNEL_ATTR
-#define CT_FWD_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
-#endif
 template <typename T, int INTERP, int STD, int PPT, int LEVEL, bool REL>
-__global__ __launch_bounds__(kBlock) CT_FWD_KERNEL_ATTR void pair_fwd_kernel(const PairArgs a)
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void pair_fwd_kernel(const PairArgs a)
 {
     extern __shared__ __align__(16) char lds[];
     constexpr int kEntry = lut_entry_bytes(INTERP);
@@ -434,10 +438,7 @@ __global__ __launch_bounds__(kBlock) CT_FWD_KERNEL_ATTR void pair_fwd_kernel(con
     const int lut_bytes = INTERP == CT_INTERP_NONE ? 0 : ((C * L * kEntry + 15) & ~15);
     float2 *val = reinterpret_cast<float2 *>(lds + lut_bytes);
     float *aux = reinterpret_cast<float *>(val + (size_t)N * a.row_pitch);
-    if (INTERP == CT_INTERP_LINEAR && a.code_domain)
-        stage_lut_slope(lds, a.lut, C, L, a.code_step);
-    else
-        stage_lut<INTERP>(lds, a.lut, C, L);
+    stage_pair_lut<INTERP>(a, lds);
 
     // my pairs
     int bi[PPT], bj[PPT];
@@ -495,18 +496,11 @@ __global__ __launch_bounds__(kBlock) CT_FWD_KERNEL_ATTR void pair_fwd_kernel(con
             float f[NS];
 #pragma unroll
             for (int k = 0; k < NS; ++k) f[k] = 0.0f;
-#ifdef CT_ABLATE_FWD_ONE_READ  // tools/pairs_bench only: both operands from one LDS read (wrong sums, timing only)
-            const float2 *vi = val + bi[s], *vj = vi;
-#else
             const float2 *vi = val + bi[s], *vj = val + bj[s];
-#endif
             const float *xi = aux + bi[s], *xj = aux + bj[s];
             // partial tiles: padding columns carry weight -inf and contribute nothing (their order is permuted when a.vec)
-#ifndef CT_FWD_UNROLL
-#define CT_FWD_UNROLL 8
-#endif
-#pragma unroll CT_FWD_UNROLL
-            for (int px = 0; px < (CT_ABLATE_PAIR_PHASE ? 0 : ncol); ++px) {
+#pragma unroll 8
+            for (int px = 0; px < ncol; ++px) {
                 const float2 A = vi[px], Bv = vj[px];
                 // expected = I_j * r, diff = I_i - expected (losses.py:41-43), compensated in float32
                 const float d1 = __builtin_fmaf(-Bv.x, rhi[s], A.x);
@@ -781,6 +775,25 @@ __device__ __forceinline__ void scatter_lut_grad(double *hrow, float s, float Gk
     }
 }
 
+// colrow[column] = offset of the column's row in the histogram: the LUT row depends on the pixel only (models/base.py:173-176)
+template <int INTERP>
+__device__ __forceinline__ void fill_colrow(const PairArgs &a, int *colrow, int c, uint32_t pix0)
+{
+    if ((int)threadIdx.x < a.tp) {
+        const uint32_t px = (uint32_t)pixel_of_column(a, (int)threadIdx.x);
+        const uint32_t qg = (uint32_t)c * (a.plane_local + a.tile.chan_skip) + a.tile.base + pix0 + px;
+        colrow[threadIdx.x] = lut_row<INTERP>(qg, c, a.channels) * a.n_points;
+    }
+}
+
+// The (C, L) float64 histogram of a backward workgroup is added to the global gradient after the walk.
+__device__ __forceinline__ void flush_hist(const double *hist64, double *lut_grad, int n)
+{
+    __syncthreads();
+    for (int k = threadIdx.x; k < n; k += blockDim.x)
+        if (hist64[k] != 0.0) atomicAdd(&lut_grad[k], hist64[k]);
+}
+
 template <typename T, int INTERP, bool REL, int STD>
 __global__ __launch_bounds__(kBwdBlock) void pair_bwd_once_kernel(const PairArgs a)
 {
@@ -803,10 +816,7 @@ __global__ __launch_bounds__(kBwdBlock) void pair_bwd_once_kernel(const PairArgs
     ConstWords ent = (ConstWords)(uintptr_t)(static_cast<const OnceEntry *>(a.table_g) + (size_t)c * a.n_pairs);
     if (first[N + 1 + c] == 0) return;  // no upstream gradient for this channel (uniform: the whole workgroup leaves)
     if (first[N + 1 + C + c] != 0) return;  // the lane <-> sample kernel of this launch sequence handles the channel
-    if (INTERP == CT_INTERP_LINEAR && a.code_domain)
-        stage_lut_slope(lds, a.lut, C, L, a.code_step);
-    else
-        stage_lut<INTERP>(lds, a.lut, C, L);
+    stage_pair_lut<INTERP>(a, lds);
     for (int k = threadIdx.x; k < C * L; k += blockDim.x) hist64[k] = 0.0;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr int nwaves = kBwdBlock >> 6;
@@ -829,11 +839,7 @@ __global__ __launch_bounds__(kBwdBlock) void pair_bwd_once_kernel(const PairArgs
             stage_tile<T, INTERP, STD, true>(a, lds, val, aux, c, pix0, npix, kBwdBlock, lsdv);
         }
         for (int k = threadIdx.x; k < N * a.row_pitch; k += blockDim.x) gacc[k] = 0.0;
-        if ((int)threadIdx.x < a.tp) {  // the LUT row of a column depends on the pixel only (models/base.py:173-176)
-            const uint32_t px = (uint32_t)pixel_of_column(a, (int)threadIdx.x);
-            const uint32_t qg = (uint32_t)c * (a.plane_local + a.tile.chan_skip) + a.tile.base + pix0 + px;
-            colrow[threadIdx.x] = lut_row<INTERP>(qg, c, C) * L;
-        }
+        fill_colrow<INTERP>(a, colrow, c, pix0);
         lds_barrier();
         {   // uniform control flow throughout: with 32-column tiles the upper half-wave works on a masked copy
             const char *valb = reinterpret_cast<const char *>(val + col);
@@ -892,9 +898,7 @@ __global__ __launch_bounds__(kBwdBlock) void pair_bwd_once_kernel(const PairArgs
             if (Gk != 0.0f) scatter_lut_grad<INTERP>(hist64 + colrow[colk], aux[n * a.row_pitch + colk], Gk, L);
         }
     }
-    __syncthreads();
-    for (int k = threadIdx.x; k < C * L; k += blockDim.x)
-        if (hist64[k] != 0.0) atomicAdd(&a.lut_grad[k], hist64[k]);
+    flush_hist(hist64, a.lut_grad, C * L);
 }
 
 // ---- backward, lane <-> sample variant -------------------------------------------------------------------
@@ -911,10 +915,7 @@ __global__ __launch_bounds__(kBwdBlock) void pair_bwd_once_kernel(const PairArgs
 // 512-thread workgroups share a CU and one stages while the other computes.  Measured on C3: 5.40 ms against 7.71 ms.
 // Rotation (not shift) keeps the bookkeeping consistent modulo 64; wrapped or absent pairs have all-zero constants.
 constexpr int kLaneBlock = 512;
-#ifndef CT_LANE_COLS
-#define CT_LANE_COLS 4  // measured on C3: 4 columns 5.40 ms, 2: 5.78, 8: 5.80 (128 VGPRs, spills)
-#endif
-constexpr int kLaneCols = CT_LANE_COLS;
+constexpr int kLaneCols = 4;  // measured on C3: 4 columns 5.40 ms, 2: 5.78, 8: 5.80 (128 VGPRs, spills)
 
 __device__ __forceinline__ float lane_rotate_up(float v)  // lane i receives the value of lane (i - 1) mod 64
 {
@@ -943,10 +944,7 @@ __global__ __launch_bounds__(kLaneBlock) __attribute__((amdgpu_waves_per_eu(4, 4
     typedef const int32_t __attribute__((address_space(4))) *ConstInts;
     ConstInts first = (ConstInts)(uintptr_t)a.first_g;
     if (first[N + 1 + c] == 0 || first[N + 1 + C + c] == 0) return;  // no gradient / the generic kernel has the channel
-    if (INTERP == CT_INTERP_LINEAR && a.code_domain)
-        stage_lut_slope(lds, a.lut, C, L, a.code_step);
-    else
-        stage_lut<INTERP>(lds, a.lut, C, L);
+    stage_pair_lut<INTERP>(a, lds);
     for (int k = threadIdx.x; k < C * L; k += blockDim.x) hist64[k] = 0.0;
     {
         const float4 *src = static_cast<const float4 *>(a.lane_table_g) + (size_t)c * band * 64;
@@ -978,11 +976,7 @@ __global__ __launch_bounds__(kLaneBlock) __attribute__((amdgpu_waves_per_eu(4, 4
         } else {
             stage_tile<T, INTERP, CT_STD_NONE, true>(a, lds, val, aux, c, pix0, npix, kLaneBlock);
         }
-        if ((int)threadIdx.x < a.tp) {
-            const uint32_t px = (uint32_t)pixel_of_column(a, (int)threadIdx.x);
-            const uint32_t qg = (uint32_t)c * (a.plane_local + a.tile.chan_skip) + a.tile.base + pix0 + px;
-            colrow[threadIdx.x] = lut_row<INTERP>(qg, c, C) * L;
-        }
+        fill_colrow<INTERP>(a, colrow, c, pix0);
         lds_barrier();
         for (int col0 = wave * kLaneCols; col0 < a.tp; col0 += nwaves * kLaneCols) {
             float2 own[kLaneCols], oth[kLaneCols];
@@ -1018,7 +1012,7 @@ __global__ __launch_bounds__(kLaneBlock) __attribute__((amdgpu_waves_per_eu(4, 4
                 }
             };
             float2 alt[kLaneCols];
-            for (int d = CT_ABLATE_PAIR_PHASE ? 0 : band; d >= 2; d -= 2) {
+            for (int d = band; d >= 2; d -= 2) {
                 step(d, oth, alt);
                 step(d - 1, alt, oth);
             }
@@ -1030,9 +1024,7 @@ __global__ __launch_bounds__(kLaneBlock) __attribute__((amdgpu_waves_per_eu(4, 4
             }
         }
     }
-    __syncthreads();
-    for (int k = threadIdx.x; k < C * L; k += blockDim.x)
-        if (hist64[k] != 0.0) atomicAdd(&a.lut_grad[k], hist64[k]);
+    flush_hist(hist64, a.lut_grad, C * L);
 }
 
 // ---- host side -------------------------------------------------------------------------------------
@@ -1061,6 +1053,32 @@ static int vec_ok(const PairArgs &a, int block, int max_passes)
     return aligned && (a.n_images + nstep - 1) / nstep <= max_passes ? 1 : 0;
 }
 
+// Tile geometry of a launch: tp pixels per tile (32 or 64, pick_tile), odd LDS row pitch, and whether the vectorised
+// staging applies for a workgroup of `block` threads with room for `max_passes` samples per thread.
+template <typename T>
+static void set_tile(PairArgs &a, int tp, int block, int max_passes)
+{
+    a.tp = tp;
+    a.tp_shift = tp == 64 ? 6 : 5;
+    a.row_pitch = tp + 1;
+    a.vec = vec_ok<T>(a, block, max_passes);
+}
+
+// The modes of a launch as compile-time constants: f(INTERP, STD) with INTERP among INTERPS, CT_ERR_INVALID_ARGUMENT
+// for a value outside either list; a 0 / 1 flag the same way.
+template <int... INTERPS, typename F>
+static int with_pair_modes(int interp, int std_mode, F &&f)
+{
+    return with_enum<INTERPS...>(interp, [&](auto I) {
+        return with_enum<CT_STD_NONE, CT_STD_CONSTANT, CT_STD_MULTIPLIER, CT_STD_EXPLICIT>(std_mode, [&](auto S) { return f(I, S); });
+    });
+}
+template <typename F>
+static int with_flag(int flag, F &&f)
+{
+    return with_enum<0, 1>(flag ? 1 : 0, [&](auto B) { return f(std::integral_constant<bool, decltype(B)::value != 0>{}); });
+}
+
 template <typename T, int INTERP, int STD, int PPT, int LEVEL, bool REL>
 static int fwd_launch_one(const PairArgs &a, size_t lds, hipStream_t s)
 {
@@ -1071,14 +1089,6 @@ static int fwd_launch_one(const PairArgs &a, size_t lds, hipStream_t s)
     return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
 }
 
-template <typename T, int INTERP, int STD, int PPT>
-static int fwd_launch_level(const PairArgs &a, size_t lds, int level, hipStream_t s)
-{
-    if (level == 0)
-        return a.use_relative ? fwd_launch_one<T, INTERP, STD, PPT, 0, true>(a, lds, s) : fwd_launch_one<T, INTERP, STD, PPT, 0, false>(a, lds, s);
-    return a.use_relative ? fwd_launch_one<T, INTERP, STD, PPT, 1, true>(a, lds, s) : fwd_launch_one<T, INTERP, STD, PPT, 1, false>(a, lds, s);
-}
-
 template <typename T, int INTERP, int STD>
 static int fwd_launch(PairArgs a, int level, hipStream_t s)
 {
@@ -1087,51 +1097,26 @@ static int fwd_launch(PairArgs a, int level, hipStream_t s)
     // 64-pixel tiles: ~40 KB of LDS at N = 64 -> four workgroups (16 waves) per CU hide the LDS latency of phase 2
     const int tp = pick_tile(a.n_images, lut_bytes, entry, 64);
     if (tp == 0) return CT_ERR_TOO_LARGE;
-    a.tp = tp;
-    a.tp_shift = tp == 64 ? 6 : 5;
-    a.row_pitch = tp + 1;
-    a.vec = vec_ok<T>(a, kBlock, 8);
+    set_tile<T>(a, tp, kBlock, 8);
     const size_t lds = lut_bytes + (size_t)a.n_images * a.row_pitch * entry;
     // pairs are walked in chunks of 4 * 256 per launch
     for (int begin = 0; begin < a.n_pairs; begin += 4 * kBlock) {
         a.pair_begin = begin;
         // always four pair slots per thread (slots past the end of the list are skipped): one instantiation instead of
         // three keeps the build time of this file in check
-        const int rc = fwd_launch_level<T, INTERP, STD, 4>(a, lds, level, s);
+        const int rc = with_enum<0, 1>(level, [&](auto LEVEL) {
+            return with_flag(a.use_relative, [&](auto REL) { return fwd_launch_one<T, INTERP, STD, 4, LEVEL, REL>(a, lds, s); });
+        });
         if (rc != CT_OK) return rc;
     }
     return CT_OK;
 }
 
-// CT_PAIRS_MINIMAL (tools/pairs_bench.hip only): instantiate just uint16 / LINEAR / no std so the harness builds fast.
-template <typename T, int INTERP>
-static int fwd_dispatch_std(const PairArgs &a, int std_mode, int level, hipStream_t s)
-{
-#ifdef CT_PAIRS_MINIMAL
-    return std_mode == CT_STD_NONE ? fwd_launch<T, INTERP, CT_STD_NONE>(a, level, s) : CT_ERR_UNSUPPORTED;
-#endif
-    switch (std_mode) {
-        case CT_STD_NONE: return fwd_launch<T, INTERP, CT_STD_NONE>(a, level, s);
-        case CT_STD_CONSTANT: return fwd_launch<T, INTERP, CT_STD_CONSTANT>(a, level, s);
-        case CT_STD_MULTIPLIER: return fwd_launch<T, INTERP, CT_STD_MULTIPLIER>(a, level, s);
-        case CT_STD_EXPLICIT: return fwd_launch<T, INTERP, CT_STD_EXPLICIT>(a, level, s);
-    }
-    return CT_ERR_INVALID_ARGUMENT;
-}
-
 template <typename T>
 static int fwd_dispatch(const PairArgs &a, int interp, int std_mode, int level, hipStream_t s)
 {
-#ifdef CT_PAIRS_MINIMAL
-    return interp == CT_INTERP_LINEAR ? fwd_dispatch_std<T, CT_INTERP_LINEAR>(a, std_mode, level, s) : CT_ERR_UNSUPPORTED;
-#endif
-    switch (interp) {
-        case CT_INTERP_LOOKUP: return fwd_dispatch_std<T, CT_INTERP_LOOKUP>(a, std_mode, level, s);
-        case CT_INTERP_LINEAR: return fwd_dispatch_std<T, CT_INTERP_LINEAR>(a, std_mode, level, s);
-        case CT_INTERP_CATMULL: return fwd_dispatch_std<T, CT_INTERP_CATMULL>(a, std_mode, level, s);
-        case CT_INTERP_NONE: return fwd_dispatch_std<T, CT_INTERP_NONE>(a, std_mode, level, s);
-    }
-    return CT_ERR_INVALID_ARGUMENT;
+    return with_pair_modes<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(
+        interp, std_mode, [&](auto I, auto S) { return fwd_launch<T, I, S>(a, level, s); });
 }
 
 // Workspace of the backward: [first: N + 1 offsets | C "channel has gradient" flags | C "lane kernel has the channel"
@@ -1184,11 +1169,8 @@ static int bwd_launch_once(PairArgs a, void *workspace, size_t workspace_bytes, 
                 lane_lds = fixed + (size_t)band * 64 * sizeof(float4) + tile_bytes;
                 la.lane_lds_bytes = (int32_t)lane_lds;
                 if (lane_lds > 80 * 1024) continue;
-                la.tp = tp;
-                la.tp_shift = tp == 64 ? 6 : 5;
+                set_tile<T>(la, tp, kLaneBlock, 2);
                 la.val_offset = (int32_t)fixed;
-                la.row_pitch = tp + 1;
-                la.vec = vec_ok<T>(la, kLaneBlock, 2);
                 la.lane_table_g = lane_table;
                 lane = true;
             }
@@ -1201,64 +1183,40 @@ static int bwd_launch_once(PairArgs a, void *workspace, size_t workspace_bytes, 
     const int per_sample = 8 + 12 + (STD == CT_STD_NONE ? 0 : 4);
     const int tp = pick_tile(a.n_images, fixed, per_sample, 64);
     if (tp == 0) return CT_ERR_TOO_LARGE;
-    a.tp = tp;
-    a.tp_shift = tp == 64 ? 6 : 5;
+    set_tile<T>(a, tp, kBwdBlock, 4);
     a.val_offset = (int32_t)(fixed - 256);
-    a.row_pitch = tp + 1;
-    a.vec = vec_ok<T>(a, kBwdBlock, 4);
     a.lane_band = lane ? la.lane_band : 0;
     hipLaunchKernelGGL(pair_entries_kernel, dim3(a.channels), dim3(256), 0, s, a, first, table, lane ? lane_table : nullptr);
     if constexpr (STD == CT_STD_NONE) {
         if (lane) {
             const uint32_t tiles = (plane + la.tp - 1) / la.tp;
             const int grid = workgroups_per_channel(lane_lds, kLaneBlock, tiles) * la.channels;
-            if (la.use_relative)
-                hipLaunchKernelGGL((pair_bwd_lane_kernel<T, INTERP, true>), dim3(grid), dim3(kLaneBlock), lane_lds, s, la);
-            else
-                hipLaunchKernelGGL((pair_bwd_lane_kernel<T, INTERP, false>), dim3(grid), dim3(kLaneBlock), lane_lds, s, la);
+            with_flag(la.use_relative, [&](auto REL) {
+                hipLaunchKernelGGL((pair_bwd_lane_kernel<T, INTERP, REL>), dim3(grid), dim3(kLaneBlock), lane_lds, s, la);
+                return (int)CT_OK;
+            });
         }
     }
     const size_t lds = fixed + (size_t)a.n_images * a.row_pitch * per_sample;
     const uint32_t tiles = (a.plane_local + tp - 1) / tp;
     const int per_chan = workgroups_per_channel(lds, kBwdBlock, tiles);
     const int grid = per_chan * a.channels;
-    if (a.use_relative)
-        hipLaunchKernelGGL((pair_bwd_once_kernel<T, INTERP, true, STD>), dim3(grid), dim3(kBwdBlock), lds, s, a);
-    else
-        hipLaunchKernelGGL((pair_bwd_once_kernel<T, INTERP, false, STD>), dim3(grid), dim3(kBwdBlock), lds, s, a);
-    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
+    return with_flag(a.use_relative, [&](auto REL) {
+        hipLaunchKernelGGL((pair_bwd_once_kernel<T, INTERP, REL, STD>), dim3(grid), dim3(kBwdBlock), lds, s, a);
+        return (int)(hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH);
+    });
 }
 
-template <typename T, int INTERP>
-static int bwd_dispatch_std(const PairArgs &a, int std_mode, void *ws, size_t ws_bytes, hipStream_t s)
-{
-#ifdef CT_PAIRS_MINIMAL
-    return std_mode == CT_STD_NONE ? bwd_launch_once<T, INTERP, CT_STD_NONE>(a, ws, ws_bytes, s) : CT_ERR_UNSUPPORTED;
-#endif
-    if constexpr (INTERP == CT_INTERP_LOOKUP) {  // with uncertainties LOOKUP has no gradient path (rejected by the caller)
-        return std_mode == CT_STD_NONE ? bwd_launch_once<T, INTERP, CT_STD_NONE>(a, ws, ws_bytes, s) : CT_ERR_NO_GRADIENT_PATH;
-    }
-    switch (std_mode) {
-        case CT_STD_NONE: return bwd_launch_once<T, INTERP, CT_STD_NONE>(a, ws, ws_bytes, s);
-        case CT_STD_CONSTANT: return bwd_launch_once<T, INTERP, CT_STD_CONSTANT>(a, ws, ws_bytes, s);
-        case CT_STD_MULTIPLIER: return bwd_launch_once<T, INTERP, CT_STD_MULTIPLIER>(a, ws, ws_bytes, s);
-        case CT_STD_EXPLICIT: return bwd_launch_once<T, INTERP, CT_STD_EXPLICIT>(a, ws, ws_bytes, s);
-    }
-    return CT_ERR_INVALID_ARGUMENT;
-}
-
+// The backward never instantiates CT_INTERP_NONE (no LUT, nothing to differentiate: refused by the entry point).
 template <typename T>
 static int bwd_dispatch(const PairArgs &a, int interp, int std_mode, void *ws, size_t ws_bytes, hipStream_t s)
 {
-#ifdef CT_PAIRS_MINIMAL
-    return interp == CT_INTERP_LINEAR ? bwd_dispatch_std<T, CT_INTERP_LINEAR>(a, std_mode, ws, ws_bytes, s) : CT_ERR_UNSUPPORTED;
-#endif
-    switch (interp) {
-        case CT_INTERP_LOOKUP: return bwd_dispatch_std<T, CT_INTERP_LOOKUP>(a, std_mode, ws, ws_bytes, s);
-        case CT_INTERP_LINEAR: return bwd_dispatch_std<T, CT_INTERP_LINEAR>(a, std_mode, ws, ws_bytes, s);
-        case CT_INTERP_CATMULL: return bwd_dispatch_std<T, CT_INTERP_CATMULL>(a, std_mode, ws, ws_bytes, s);
-    }
-    return CT_ERR_INVALID_ARGUMENT;
+    return with_pair_modes<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL>(interp, std_mode, [&](auto I, auto S) -> int {
+        // with uncertainties LOOKUP has no gradient path (rejected by the entry point before it gets here).  A plain `if`:
+        // the LOOKUP kernels with a std mode have always been part of the code object, and they stay in it.
+        if (I == CT_INTERP_LOOKUP && S != CT_STD_NONE) return CT_ERR_NO_GRADIENT_PATH;
+        return bwd_launch_once<T, I, S>(a, ws, ws_bytes, s);
+    });
 }
 
 static int fill_common(PairArgs &a, const void *stack_dev, int32_t n_images, const ct_geometry *g, const float *std_dev,
@@ -1300,12 +1258,6 @@ static int fill_common(PairArgs &a, const void *stack_dev, int32_t n_images, con
     return CT_OK;
 }
 
-}  // namespace ct
-
-extern "C" int ct_norm_constants(float max_code, float *hi, float *lo);
-extern "C" int ct_pivot_floor_constants(float max_code, int n_points, float *rcp_step);
-
-namespace ct {
 // Code-domain staging is taken for integer stacks at the type's full range with a LINEAR curve whose step is a whole
 // number of codes (host-verified for every code: ct_pivot_floor_constants) and no uncertainties.  The reference's validity
 // mask lower <= fl(u / max) <= upper (general_functions.py:302) becomes a code interval by bisection with the same float32
@@ -1343,6 +1295,18 @@ static void fill_code_domain(PairArgs &a, int32_t dtype, float max_code, int int
     a.code_dk_add = (float)(-0.5 * kk);
     a.code_domain = 1;
 }
+
+// The dtype step of both entry points: integer stacks get their normalisation constants and the code-domain decision,
+// then f(T{}) runs with the element type (f dispatches on the remaining modes).
+template <typename F>
+static int with_pixel_type(PairArgs &a, int32_t dtype, float max_code, int interp, const ct_pair_params &prm, F &&f)
+{
+    if (dtype == CT_DTYPE_F32) return f(float{});
+    if (dtype != CT_DTYPE_U8 && dtype != CT_DTYPE_U16) return CT_ERR_UNSUPPORTED;
+    if (ct_norm_constants(max_code, &a.norm.hi, &a.norm.lo) != CT_OK) return CT_ERR_UNSUPPORTED;
+    fill_code_domain(a, dtype, max_code, interp, prm.std_mode, prm.weight_scale);
+    return dtype == CT_DTYPE_U8 ? f(uint8_t{}) : f(uint16_t{});
+}
 }  // namespace ct
 
 extern "C" int ct_pair_residual_fwd(const void *stack_dev, int32_t dtype, float max_code, int32_t n_images,
@@ -1365,20 +1329,9 @@ extern "C" int ct_pair_residual_fwd(const void *stack_dev, int32_t dtype, float 
     a.sums = sums_dev;
     a.center = center_dev;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-#ifndef CT_PAIRS_MINIMAL
-        case CT_DTYPE_U8:
-            if (ct_norm_constants(max_code, &a.norm.hi, &a.norm.lo) != CT_OK) return CT_ERR_UNSUPPORTED;
-            fill_code_domain(a, dtype, max_code, icrf->interp, params->std_mode, params->weight_scale);
-            return fwd_dispatch<uint8_t>(a, icrf->interp, params->std_mode, level, s);
-        case CT_DTYPE_F32: return fwd_dispatch<float>(a, icrf->interp, params->std_mode, level, s);
-#endif
-        case CT_DTYPE_U16:
-            if (ct_norm_constants(max_code, &a.norm.hi, &a.norm.lo) != CT_OK) return CT_ERR_UNSUPPORTED;
-            fill_code_domain(a, dtype, max_code, icrf->interp, params->std_mode, params->weight_scale);
-            return fwd_dispatch<uint16_t>(a, icrf->interp, params->std_mode, level, s);
-    }
-    return CT_ERR_UNSUPPORTED;
+    return with_pixel_type(a, dtype, max_code, icrf->interp, *params, [&](auto t) {
+        return fwd_dispatch<decltype(t)>(a, icrf->interp, params->std_mode, level, s);
+    });
 }
 
 extern "C" int ct_pair_residual_bwd(const void *stack_dev, int32_t dtype, float max_code, int32_t n_images,
@@ -1413,20 +1366,9 @@ extern "C" int ct_pair_residual_bwd(const void *stack_dev, int32_t dtype, float 
     a.smean = smean_dev;
     a.lut_grad = lut_grad_dev;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-#ifndef CT_PAIRS_MINIMAL
-        case CT_DTYPE_U8:
-            if (ct_norm_constants(max_code, &a.norm.hi, &a.norm.lo) != CT_OK) return CT_ERR_UNSUPPORTED;
-            fill_code_domain(a, dtype, max_code, icrf->interp, prm.std_mode, prm.weight_scale);
-            return bwd_dispatch<uint8_t>(a, icrf->interp, prm.std_mode, workspace_dev, (size_t)workspace_bytes, s);
-        case CT_DTYPE_F32: return bwd_dispatch<float>(a, icrf->interp, prm.std_mode, workspace_dev, (size_t)workspace_bytes, s);
-#endif
-        case CT_DTYPE_U16:
-            if (ct_norm_constants(max_code, &a.norm.hi, &a.norm.lo) != CT_OK) return CT_ERR_UNSUPPORTED;
-            fill_code_domain(a, dtype, max_code, icrf->interp, prm.std_mode, prm.weight_scale);
-            return bwd_dispatch<uint16_t>(a, icrf->interp, prm.std_mode, workspace_dev, (size_t)workspace_bytes, s);
-    }
-    return CT_ERR_UNSUPPORTED;
+    return with_pixel_type(a, dtype, max_code, icrf->interp, prm, [&](auto t) {
+        return bwd_dispatch<decltype(t)>(a, icrf->interp, prm.std_mode, workspace_dev, (size_t)workspace_bytes, s);
+    });
 }
 
 extern "C" int64_t ct_pair_residual_bwd_workspace(int32_t n_images, int32_t n_pairs, int32_t channels)

@@ -644,6 +644,139 @@ def test_pair_backward_workspace_contract(lib):
     assert call(ctypes.c_void_p(0x2000), -5) == -1
 
 
+
+# ---- ct_pair_residual_fwd / ct_pair_residual_bwd: malformed and boundary calls keep their status --------------------
+# Every row returns before any HIP call (fake pointers, never dereferenced); the well-formed base call is never made.
+def _valid_pair_call():
+    return dict(stack=_FAKE, dtype=2, max_code=1.0, n_images=4, geom=True, std=None, icrf_given=True, prm_given=True,
+                g=dict(channels=3, h_tile=8, width=8, h_global=8, row_offset=0, image_stride=192, layout=0),
+                icrf=dict(lut_dev=_LUT, n_points=256, interp=1), n_pairs=3, level=0,
+                prm=dict(lower=0.0, upper=1.0, weight_scale=10.0, use_relative=1, use_uncertainty_weighting=0, std_mode=0,
+                         std_value=0.1, pair_band=0),
+                i_idx=0x5000, j_idx=0x6000, ratio=0x7000, sums=0x8000, part_off=0x9000, part_sample=0xA000, part_pair=0xB000,
+                coef=0xC000, smean=0xD000, lut_grad=0xE000)
+
+
+def _prm(**kw):
+    return lambda c: c["prm"].update(kw)
+
+
+def _both(*fs):
+    return lambda c: [f(c) for f in fs]
+
+
+# row -> (mutation, entry points it applies to)
+_PAIR_MALFORMED = {
+    "null_stack": (_set(stack=None), "both"),
+    "null_geometry": (_set(geom=False), "both"),
+    "null_icrf": (_set(icrf_given=False), "both"),
+    "null_params": (_set(prm_given=False), "both"),
+    "one_image": (_set(n_images=1), "both"),
+    "negative_n_pairs": (_set(n_pairs=-1), "both"),
+    "no_pairs_and_null_pair_pointers": (_set(n_pairs=0, i_idx=None, j_idx=None, ratio=None, sums=None, part_off=None, part_sample=None,
+                                             part_pair=None, coef=None, lut_grad=None), "both"),
+    "no_channels": (_g(channels=0), "both"),
+    "rows_past_h_global": (_g(row_offset=4, h_tile=8, h_global=8), "both"),
+    "image_stride_one_short": (_g(image_stride=191), "both"),
+    "layout_out_of_range": (_g(layout=3), "both"),
+    "two_to_the_31_elements": (_g(h_global=1 << 20, width=1 << 10, image_stride=3 * 8 * 1024), "both"),
+    "interp_out_of_range": (_icrf(interp=4), "both"),
+    "lut_missing": (_icrf(lut_dev=None), "both"),
+    "n_points_below_2": (_icrf(n_points=1), "both"),
+    "std_mode_out_of_range": (_prm(std_mode=4, use_uncertainty_weighting=1), "both"),
+    "explicit_without_std_pointer": (_prm(std_mode=3, use_uncertainty_weighting=1), "both"),
+    "lower_above_upper": (_prm(lower=0.6, upper=0.4), "both"),
+    "null_i_idx": (_set(i_idx=None), "fwd"),
+    "null_j_idx": (_set(j_idx=None), "fwd"),
+    "null_ratio": (_set(ratio=None), "both"),
+    "null_sums": (_set(sums=None), "fwd"),
+    "null_partner_offsets": (_set(part_off=None), "bwd"),
+    "null_partner_sample": (_set(part_sample=None), "bwd"),
+    "null_partner_pair": (_set(part_pair=None), "bwd"),
+    "null_coef": (_set(coef=None), "bwd"),
+    "null_lut_grad": (_set(lut_grad=None), "bwd"),
+    "level_out_of_range": (_set(level=2), "fwd"),
+    "lookup_with_std_mode": (_both(_icrf(interp=0), _prm(std_mode=1)), "fwd"),
+    "lookup_with_uncertainty_weighting": (_both(_icrf(interp=0), _prm(std_mode=1, use_uncertainty_weighting=1)), "bwd"),
+    "uncertainty_weighting_without_smean": (_both(_set(smean=None), _prm(std_mode=1, use_uncertainty_weighting=1)), "bwd"),
+    "no_model_has_no_backward": (_icrf(interp=3, lut_dev=None, n_points=0), "bwd"),
+    "unknown_dtype": (_set(dtype=7), "both"),
+    "max_code_refused_by_norm_constants": (_set(dtype=1, max_code=0.5), "both"),
+    "more_than_1024_images": (_set(n_images=1025), "bwd"),
+    # float32, no LUT: 2000 images x 33 columns x 8 bytes exceed the 144 KiB staging budget at the narrowest tile
+    "staging_exceeds_lds": (_both(_set(n_images=2000), _icrf(interp=3, lut_dev=None, n_points=0)), "fwd"),
+}
+
+# status per row and entry point, recorded from the library before the pair dispatch was rewritten
+_PAIR_MALFORMED_STATUS = {
+    'null_stack': {'fwd': -1, 'bwd': -1},
+    'null_geometry': {'fwd': -1, 'bwd': -1},
+    'null_icrf': {'fwd': -1, 'bwd': -1},
+    'null_params': {'fwd': -1, 'bwd': -1},
+    'one_image': {'fwd': -1, 'bwd': -1},
+    'negative_n_pairs': {'fwd': -1, 'bwd': -1},
+    'no_pairs_and_null_pair_pointers': {'fwd': 0, 'bwd': 0},
+    'no_channels': {'fwd': -1, 'bwd': -1},
+    'rows_past_h_global': {'fwd': -1, 'bwd': -1},
+    'image_stride_one_short': {'fwd': -1, 'bwd': -1},
+    'layout_out_of_range': {'fwd': -1, 'bwd': -1},
+    'two_to_the_31_elements': {'fwd': -5, 'bwd': -5},
+    'interp_out_of_range': {'fwd': -1, 'bwd': -1},
+    'lut_missing': {'fwd': -1, 'bwd': -1},
+    'n_points_below_2': {'fwd': -1, 'bwd': -1},
+    'std_mode_out_of_range': {'fwd': -1, 'bwd': -1},
+    'explicit_without_std_pointer': {'fwd': -1, 'bwd': -1},
+    'lower_above_upper': {'fwd': -1, 'bwd': -1},
+    'null_i_idx': {'fwd': -1},
+    'null_j_idx': {'fwd': -1},
+    'null_ratio': {'fwd': -1, 'bwd': -1},
+    'null_sums': {'fwd': -1},
+    'null_partner_offsets': {'bwd': -1},
+    'null_partner_sample': {'bwd': -1},
+    'null_partner_pair': {'bwd': -1},
+    'null_coef': {'bwd': -1},
+    'null_lut_grad': {'bwd': -1},
+    'level_out_of_range': {'fwd': -1},
+    'lookup_with_std_mode': {'fwd': -4},
+    'lookup_with_uncertainty_weighting': {'bwd': -4},
+    'uncertainty_weighting_without_smean': {'bwd': -1},
+    'no_model_has_no_backward': {'bwd': -1},
+    'unknown_dtype': {'fwd': -2, 'bwd': -2},
+    'max_code_refused_by_norm_constants': {'fwd': -2, 'bwd': -2},
+    'more_than_1024_images': {'bwd': -5},
+    'staging_exceeds_lds': {'fwd': -5},
+}
+
+
+def _pair_status(lib, nv, fn, row):
+    c = _valid_pair_call()
+    _PAIR_MALFORMED[row][0](c)
+    g, icrf, prm = nv.Geometry(**c["g"]), nv.Icrf(**c["icrf"]), nv.PairParams(**c["prm"])
+    gp = ctypes.byref(g) if c["geom"] else None
+    ip = ctypes.byref(icrf) if c["icrf_given"] else None
+    pp = ctypes.byref(prm) if c["prm_given"] else None
+    if fn == "fwd":
+        return lib.ct_pair_residual_fwd(c["stack"], c["dtype"], c["max_code"], c["n_images"], gp, c["std"], ip, c["i_idx"], c["j_idx"],
+                                        c["ratio"], c["n_pairs"], pp, c["level"], None, c["sums"], None)
+    ws_bytes = lib.ct_pair_residual_bwd_workspace(c["n_images"], max(c["n_pairs"], 0), c["g"]["channels"])
+    return lib.ct_pair_residual_bwd(c["stack"], c["dtype"], c["max_code"], c["n_images"], gp, c["std"], ip, c["ratio"], c["n_pairs"],
+                                    c["part_off"], c["part_sample"], c["part_pair"], pp, c["coef"], c["smean"], c["lut_grad"],
+                                    0x10000, ws_bytes, None)
+
+
+def _malformed_pair_cases():
+    for row, (_, where) in _PAIR_MALFORMED.items():
+        for fn in ("fwd", "bwd"):
+            if where in ("both", fn):
+                yield fn, row
+
+
+@pytest.mark.parametrize("fn,row", list(_malformed_pair_cases()))
+def test_malformed_pair_calls_keep_their_status(lib, fn, row):
+    from clair_torch_amd import _native as nv
+    assert _pair_status(lib, nv, fn, row) == _PAIR_MALFORMED_STATUS[row][fn]
+
+
 def test_public_tensor_helpers_match_reference_vectors():
     """The reference's public helper names that the fused kernels replace on the hot path, kept as plain torch fronts:
     weighted_mean_and_std / flat_field_mean / flatfield_correction against vectors recorded from the reference

@@ -1,8 +1,11 @@
 // pairs_bench.hip -- standalone timing harness for ct_pair_residual_fwd / ct_pair_residual_bwd on the C3 shape
-// (64 x 2048 x 2048 x 3 uint16, 888 pairs).  Compiles the product source directly so -D switches can select
-// experimental variants:  hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize
-//                         tools/pairs_bench.hip clair_torch_amd/csrc/ct_api.cpp -o tools/pairs_bench
-#include "../clair_torch_amd/csrc/ct_pairs.hip"
+// (64 x 2048 x 2048 x 3 uint16, 888 pairs): the shipped forward, generic backward and lane backward through the C ABI
+// of the built library (python clair_torch_amd/build.py first):
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/pairs_bench.hip -Lclair_torch_amd/lib -lclair_hip
+//         -Wl,-rpath,'$ORIGIN/../clair_torch_amd/lib' -o tools/pairs_bench
+#include <hip/hip_runtime.h>
+
+#include "../include/clair_hip.h"
 
 #include <algorithm>
 #include <cmath>
