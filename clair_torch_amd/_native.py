@@ -19,7 +19,7 @@ MERGE_FIRST_BATCH, MERGE_FINALIZE, MERGE_MEAN_OUT_F32, MERGE_F64_MOMENTS = 1, 2,
 MERGE_REFERENCE_ORDER, MERGE_CLOSED_FORM, MERGE_STD_HINT, MERGE_REQUIRE_ONE_LAUNCH, MERGE_OUT_AS_INPUT = 16, 32, 64, 128, 256
 INGEST_AFFINE, INGEST_CLAMP, INGEST_MAX_STAGES, INGEST_MAX_CHANNELS = 0, 1, 4, 4
 INGEST_AFFINE_DATA, EXTREMA_MIN, EXTREMA_MAX, EXTREMA_MAX_PREFIX = 2, 1, 2, 3
-ERR_NO_GRADIENT_PATH = -4
+ERR_INVALID_ARGUMENT, ERR_UNSUPPORTED, ERR_LAUNCH, ERR_NO_GRADIENT_PATH, ERR_TOO_LARGE = -1, -2, -3, -4, -5
 
 ABI_VERSION = 3
 EXPORTS = ("ct_abi_version", "ct_error_string", "ct_hdr_merge_batch", "ct_hdr_merge_batches", "ct_linearize_std", "ct_linearize_fwd",
@@ -142,6 +142,6 @@ def check(rc, what):
     if rc == ERR_NO_GRADIENT_PATH:
         # torch.autograd.grad's error text in the reference (hdr_merge.py:108, linearization.py:100)
         raise RuntimeError("element 0 of tensors does not require grad and does not have a grad_fn")
-    if rc in (-1, -5):
+    if rc in (ERR_INVALID_ARGUMENT, ERR_TOO_LARGE):
         raise ValueError(f"{what}: {msg}")
     raise NativeLibraryError(f"{what}: {msg} (code {rc})")

@@ -87,6 +87,7 @@ __global__ __launch_bounds__(kBlock) void flatfield_apply_kernel(VT *value, floa
             } else {
                 value[q] = (v / den) * M;
                 grad = -(M * v) / (den * den);
+                if (through) grad += (float)thr;  // float32 frames with the mean in the graph (through == NULL: unchanged)
             }
             if (var_or_std) {
                 float var = var_or_std[q];

@@ -538,6 +538,10 @@ def flatfield_correct(value: torch.Tensor, var_or_std: Optional[torch.Tensor], f
     if not value.is_contiguous():
         raise ValueError("value must be contiguous")
     frames = 1 if value.ndim == 3 else value.shape[0]
+    if through_mean and frames != 1:
+        # sum value / (flat + eps) is one number per channel of ONE image; several frames have no common term
+        raise ValueError("through_mean=True needs a single (C,H,W) image: the term through the flat field's mean is "
+                         f"per image, got {frames} frames")
     is_f64 = value.dtype == torch.float64
     if value.dtype not in (torch.float64, torch.float32):
         raise TypeError("value must be float32 or float64")
@@ -548,7 +552,7 @@ def flatfield_correct(value: torch.Tensor, var_or_std: Optional[torch.Tensor], f
     dev = value.device
     sums = torch.zeros((c, 2), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        rc = nv.load().ct_flatfield_sums(_ptr(value) if (through_mean and frames == 1) else None, int(is_f64), _ptr(flat),
+        rc = nv.load().ct_flatfield_sums(_ptr(value) if through_mean else None, int(is_f64), _ptr(flat),
                                          c, plane, _ptr(sums), _stream(dev))
     nv.check(rc, "ct_flatfield_sums")
     if reduce is not None:

@@ -270,7 +270,9 @@ int ct_pair_residual_bwd(const void *stack_dev, int32_t dtype, float max_code, i
  * ct_flatfield_apply: value (F, C, plane) float64 or float32, in place: value / (flat + 1e-6) * M_c;
  *   var_or_std_dev (F, C, plane) float32 in place (or NULL): on entry the variance (input_is_variance != 0, merge)
  *   or the std (linearize) of the image term, on exit sqrt(var + (grad * flat_std)^2) with
- *   grad = -value * M_c / (flat + 1e-6)^2 + through_mean_dev[c]  (through_mean_dev NULL = 0, flat_std_dev NULL = no term).
+ *   grad = -value * M_c / (flat + 1e-6)^2 + through_mean_dev[c]  (through_mean_dev NULL = 0, flat_std_dev NULL = no term),
+ *   for both value types.  through_mean_dev[c] is one number per channel of ONE image, so with n_frames > 1 it is the
+ *   caller's business what it means; ops.flatfield_correct refuses through_mean with several frames.
  */
 int ct_flatfield_sums(const void *value_dev, int32_t value_is_f64, const float *flat_dev, int32_t channels,
                       int64_t plane, double *sums_dev, void *stream);
@@ -286,6 +288,11 @@ int ct_flatfield_apply(void *value_dev, int32_t value_is_f64, int64_t n_frames, 
  *   out_dev (6, C) float64 rows = min mean, max mean, sum mean, min std, max std, sum std   (std rows 0 when std_dev NULL)
  * mean_dev (C, plane) float64 and std_dev (C, plane) float32 are ct_hdr_merge_batch's outputs.  Deterministic (no
  * atomics); min / max / sum combine over bands.  workspace_dev: ct_band_stats_workspace(channels) bytes, 8-byte aligned.
+ * Non-finite data: min / max are IEEE minNum / maxNum (fmin / fmax) -- a NaN is SKIPPED, +-inf is a number like any
+ * other, and a channel that holds no number at all reports the identities (+inf, -inf).  The sums are plain additions
+ * and carry NaN and inf, so a NaN anywhere in a channel always shows in that channel's sum row: a gather that must
+ * notice NaN tests the sums.  (torch's amin / amax propagate NaN instead; the sign of a zero minimum or maximum is
+ * unspecified when both zeros occur.)
  */
 int64_t ct_band_stats_workspace(int32_t channels);
 int ct_band_stats(const double *mean_dev, const float *std_dev, int32_t channels, int64_t plane, void *workspace_dev,
