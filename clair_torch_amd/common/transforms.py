@@ -21,6 +21,11 @@ route of this table that applies is taken:
                 classes, non-contiguous or non-4-D batches off the code pair           kernel variant
 = ============= ==================================================================== =====================================
 
+compute_hdr_image does not execute routes 3 and 4 on uint8 / uint16 frames (``stage_images(defer_ingest=True)``): the chain
+is evaluated inside the merge kernel, one ct_hdr_merge_ingest_batch launch per batch and no float32 copy of the batch --
+unless there is a dark-field dataset, the mode is one of the reference-order kernel's (LOOKUP / CATMULL with uncertainties
+by default) or ``fused_ingest=False``; route 4 still runs ct_ingest_extrema first and checks its constants.
+
 linearize_dataset_generator streams routes 2 and 3 (no ``StridedDownscale``, no dark field) through its copy / compute /
 copy pipeline -- route 3 by ct_linearize_ingest, which evaluates the chain and the ICRF in one pass over the raw frames --
 and float32 batches with an empty list; everything else goes frame by frame (inference/linearization.py::pipeline_route).

@@ -1,4 +1,5 @@
 """Shared staging of a collated batch onto the device for the inference / training entry points."""
+from dataclasses import dataclass
 from typing import Iterable, Optional
 
 import torch
@@ -25,7 +26,20 @@ def normalise_transform_list(gpu_transforms) -> list:
     return [gpu_transforms]
 
 
-def stage_images(val_batch: torch.Tensor, device: torch.device, transforms: list, planar: bool = False):
+@dataclass
+class DeferredIngest:
+    """A batch on routes "ingest" / "ingest_data" whose chain has NOT been executed (``stage_images(defer_ingest=True)``): the
+    raw device ``frames`` (behind the StridedDownscale compaction where the plan has one), the ``stages`` as
+    ``ops.ingest_transform`` takes them, the ``layout`` of the frames, and for "ingest_data" the ``consts`` of
+    ``ops.ingest_extrema`` (already checked for a zero range), else None.  ``ops.hdr_merge_ingest_batch`` takes all four."""
+    frames: torch.Tensor
+    stages: tuple
+    layout: str
+    consts: Optional[torch.Tensor] = None
+
+
+def stage_images(val_batch: torch.Tensor, device: torch.device, transforms: list, planar: bool = False,
+                 defer_ingest: bool = False):
     """Move the value batch to the device and run / fuse the device transforms: (images, max_code, layout).
 
     ``plan_staging`` picks the route (the table in common/transforms.py); what each of them does here and returns:
@@ -44,7 +58,10 @@ def stage_images(val_batch: torch.Tensor, device: torch.device, transforms: list
     "torch"       the classes' ``__call__`` as torch ops                            float32 planar pixels, None, "nchw"
     ============= ================================================================= ====================================
 
-    ``planar``: the caller holds explicit std or dark-field images, which are planar: the layout is then always "nchw"."""
+    ``planar``: the caller holds explicit std or dark-field images, which are planar: the layout is then always "nchw".
+    ``defer_ingest`` (opt-in): routes "ingest" and "ingest_data" do everything but ct_ingest_transform(_data) and return a
+    ``DeferredIngest`` in place of the float32 pixels, for a kernel that evaluates the chain itself; the other routes
+    return what they always do."""
     images = val_batch.to(device=device, non_blocking=True)  # the ONE host-to-device copy of the batch (a plain DMA when pinned)
     plan = plan_staging(images, transforms, planar)
     if plan.route == "code":
@@ -53,6 +70,8 @@ def stage_images(val_batch: torch.Tensor, device: torch.device, transforms: list
         return images, plan.max_code, plan.layout
     if plan.route == "ingest":
         images = ops.strided_downscale(images, plan.step, layout=plan.source_layout)
+        if defer_ingest:
+            return DeferredIngest(images, plan.stages, plan.source_layout), None, "nchw"
         return ops.ingest_transform(images, plan.stages, layout=plan.source_layout), None, "nchw"
     if plan.route == "ingest_data":
         if plan.step_first:
@@ -60,6 +79,9 @@ def stage_images(val_batch: torch.Tensor, device: torch.device, transforms: list
         consts = ops.ingest_extrema(images, plan.prefix, plan.source_layout, plan.min_val, plan.max_val)
         if not plan.step_first:
             images = ops.strided_downscale(images, plan.step, layout=plan.source_layout)
+        if defer_ingest:
+            ops.check_ingest_consts(consts)
+            return DeferredIngest(images, plan.stages, plan.source_layout, consts), None, "nchw"
         out = ops.ingest_transform(images, plan.stages, layout=plan.source_layout, consts=consts)
         ops.check_ingest_consts(consts)
         return out, None, "nchw"

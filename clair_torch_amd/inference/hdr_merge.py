@@ -13,13 +13,13 @@ from torch.utils.data import DataLoader
 from .. import ops
 from ..common.typecheck import expect
 from ..models.base import ICRFModelBase
-from ._staging import normalise_transform_list, refuse_tile_with_downscale, resolve_device, stage_images, std_arguments
+from ._staging import DeferredIngest, normalise_transform_list, refuse_tile_with_downscale, resolve_device, stage_images, std_arguments
 
 
 def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFModelBase] = None,
                       weight_fn: Optional[Callable] = None, flat_field_dataset=None, gpu_transforms=None,
                       dark_field_dataset=None, tile: Optional[ops.TileGeometry] = None, group=None,
-                      output_layout: str = "planar", reference_order: Optional[bool] = None):
+                      output_layout: str = "planar", reference_order: Optional[bool] = None, fused_ingest: bool = True):
     """Merge the exposure stack served by ``dataloader`` into an HDR image and its standard uncertainty.
 
     Returns ``(mean float64 (C,H,W), std float32 (C,H,W) | None)`` on ``device`` (squeezed like the reference).
@@ -41,6 +41,10 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
     with uncertainties follow the reference's own float32 autograd order (within 1e-5 of what the reference computes, 4-5x
     the time), LINEAR / no model the closed form; False = the closed-form kernels in every mode (better conditioned than the
     reference, up to 4e-5 away from it on single pixels in those two modes); True = reference order in every mode.
+    ``fused_ingest`` (extension): a ``gpu_transforms`` list on route "ingest" / "ingest_data" (common/transforms.py: a black
+    level, a clamp, a target range, a data-dependent Normalize on raw codes) is evaluated inside the merge kernel
+    (ct_hdr_merge_ingest_batch: one launch per batch, no float32 copy of the batch) when there is no dark-field dataset and
+    the mode is a closed-form one; False = ct_ingest_transform, then the float32 merge.  The results are the same bit for bit.
     """
     if output_layout not in ("planar", "input", "cv"):
         raise ValueError(f"unknown output_layout {output_layout!r} (planar, input, cv)")
@@ -78,6 +82,16 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
         if not queue:
             return
         k0 = queue[0]
+        if isinstance(k0["images"], DeferredIngest):  # (always alone in the queue) the chain and the merge in one launch
+            d = k0["images"]
+            if state is None and (not final or flat_field_dataset is not None):
+                state = ops.MergeState(ops.ingest_shape(tuple(d.frames.shape), d.layout)[1:], dev, with_variance=k0["std_mode"] != "none")
+            result = ops.hdr_merge_ingest_batch(d.frames, d.stages, k0["exposure"], lut=lut, interp=interp,
+                                                gaussian_weight=weight_fn is not None, std=k0["std"], std_mode=k0["std_mode"],
+                                                std_value=k0["std_value"], state=state, finalize=final and flat_field_dataset is None,
+                                                tile=tile, layout=d.layout, reference_order=reference_order, consts=d.consts)
+            queue = []
+            return
         out_layout = "input" if (output_layout == "input" and k0["layout"] != "nchw") else "planar"
         if state is None and (not final or flat_field_dataset is not None):
             chw = tuple(k0["images"].shape[1:]) if (k0["layout"] == "nchw" or out_layout == "input") else \
@@ -96,20 +110,26 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
         pending = next(batches, None)
         last = pending is None
         planar = std_batch is not None or dark is not None  # explicit std / dark images are planar
-        images, max_code, layout = stage_images(val_batch, dev, transforms, planar)
+        images, max_code, layout = stage_images(val_batch, dev, transforms, planar, defer_ingest=fused_ingest and dark is None)
         std, std_mode, std_value = std_arguments(std_batch, dataloader.dataset, dev)
+        fused = isinstance(images, DeferredIngest)
+        if fused and (images.frames.dtype == torch.float32 or reference_order is True or
+                      (interp in ("lookup", "catmull") and std_mode != "none" and reference_order is None)):
+            # float32 frames have no copy to save, and the reference-order kernel is not fused: they get the float32 stack
+            images = ops.ingest_transform(images.frames, images.stages, layout=images.layout, consts=images.consts)
+            fused = False
         if dark is not None:
             xb, sig = dark.apply(index_batch, images, max_code, std, std_mode, std_value, tile, group)
             if xb is not None:  # the blurred batch replaces the images; its uncertainty carries both variance terms
                 images, max_code, std, std_mode, std_value = xb, None, sig, "explicit", 0.0
-        key = (images.dtype, tuple(images.shape[1:]), max_code, layout, std_mode, std_value, std is None)
-        if queue and (key != queue_key or len(queue) == ops.MAX_MERGE_BATCHES):
+        key = None if fused else (images.dtype, tuple(images.shape[1:]), max_code, layout, std_mode, std_value, std is None)
+        if queue and (fused or key != queue_key or len(queue) == ops.MAX_MERGE_BATCHES):
             flush(False)
         queue_key = key
         queue.append(dict(images=images, exposure=meta_batch["exposure_time"], std=std, std_mode=std_mode, std_value=std_value,
                           max_code=max_code, layout=layout))
-        if last:
-            flush(True)
+        if last or fused:  # a fused batch is one launch of its own, as a float32 batch is
+            flush(last)
     if flat_field_dataset is not None:
         mean, std = _flat_field_epilogue(state, flat_field_dataset, dataloader.dataset, dev, tile, group)
     else:

@@ -126,6 +126,12 @@ class MergeState:
 
 def _merge_setup(stack, layout, out_layout, state, finalize, has_std, mean_dtype, reference_order, flags, what):
     """What hdr_merge_batch and hdr_merge_batches share: (flag word, out_shape, mean_out, std_out) after the MergeState checks."""
+    return _merge_setup_for(_out_shape(stack, layout, out_layout), stack.device, out_layout, state, finalize, has_std, mean_dtype,
+                            reference_order, flags, what)
+
+
+def _merge_setup_for(out_shape, device, out_layout, state, finalize, has_std, mean_dtype, reference_order, flags, what):
+    """``_merge_setup`` for a state / output shape and device given as such."""
     if state is None or state.batches == 0:
         flags |= nv.MERGE_FIRST_BATCH
     if finalize:
@@ -136,7 +142,8 @@ def _merge_setup(stack, layout, out_layout, state, finalize, has_std, mean_dtype
         flags |= nv.MERGE_MEAN_OUT_F32
     elif mean_dtype != torch.float64:
         raise TypeError("mean_dtype must be float64 (reference) or float32")
-    out_shape = _out_shape(stack, layout, out_layout)
+    if out_layout not in ("planar", "input"):
+        raise ValueError(f"unknown out_layout {out_layout!r} (planar, input)")
     if out_layout == "input":
         flags |= nv.MERGE_OUT_AS_INPUT
     if state is None and not finalize:
@@ -145,8 +152,8 @@ def _merge_setup(stack, layout, out_layout, state, finalize, has_std, mean_dtype
         raise ValueError("MergeState was created without a variance buffer")
     if state is not None and tuple(state.mean.shape) != out_shape:
         raise ValueError(f"MergeState has shape {tuple(state.mean.shape)}, this merge needs {out_shape}")
-    mean_out = torch.empty(out_shape, dtype=mean_dtype, device=stack.device) if finalize else None
-    std_out = torch.empty(out_shape, dtype=torch.float32, device=stack.device) if (finalize and has_std) else None
+    mean_out = torch.empty(out_shape, dtype=mean_dtype, device=device) if finalize else None
+    std_out = torch.empty(out_shape, dtype=torch.float32, device=device) if (finalize and has_std) else None
     return flags, out_shape, mean_out, std_out
 
 
@@ -862,6 +869,70 @@ def linearize_ingest_frames(frames: torch.Tensor, stages, lut: Optional[torch.Te
     nv.check(rc, "ct_linearize_ingest")
     del lut_keep
     return lin, std_out
+
+
+# ---- such a chain and one batch of the HDR merge in one pass ---------------------------------------------------------------
+def hdr_merge_ingest_batch(frames: torch.Tensor, stages, exposures: torch.Tensor, *, lut: Optional[torch.Tensor] = None,
+                           interp: Optional[str] = "linear", gaussian_weight: bool = True, std: Optional[torch.Tensor] = None,
+                           std_mode: str = "none", std_value: float = 0.0, state: Optional[MergeState] = None,
+                           finalize: bool = True, tile: Optional[TileGeometry] = None, mean_dtype: torch.dtype = torch.float64,
+                           layout: str = "nchw", reference_order: Optional[bool] = None, consts: Optional[torch.Tensor] = None):
+    """ct_hdr_merge_ingest_batch: ``hdr_merge_batch(ingest_transform(frames, stages, layout, consts=consts), exposures, ...)``
+    bit for bit, in one launch and without the float32 stack in between.  Returns (mean, std|None), planar (C,H,W), when
+    ``finalize`` else None.
+
+    ``frames``: a contiguous uint8 / uint16 device stack, (B,C,H,W) for "nchw" or (B,H,W,3) for "nhwc" / "nhwc_bgr" (the
+    order of the source: a folded CvToTorch).  ``stages``: as ``ingest_transform`` takes them; with ``consts`` (the tensor
+    ``ingest_extrema`` returned) one of them may be ("affine_data", mul, add).  ``std``: explicit uncertainties, float32 and
+    PLANAR (B,C,H,W) like the state whatever the layout of the frames.  ``exposures``, ``lut``, ``interp``,
+    ``gaussian_weight``, ``std_mode``, ``std_value``, ``state``, ``finalize``, ``tile``, ``mean_dtype``: as in
+    ``hdr_merge_batch``.  ``reference_order``: False = the closed-form kernels for LOOKUP / CATMULL with uncertainties as
+    well (CT_MERGE_CLOSED_FORM); None leaves those two modes, and True every mode, to the reference-order kernel, which
+    this entry point does not have (NativeLibraryError: use ``ingest_transform`` + ``hdr_merge_batch``)."""
+    _check_ingest_stack(frames, layout)
+    if frames.dtype == torch.float32:
+        raise TypeError("hdr_merge_ingest_batch takes uint8 / uint16 codes (float32 pixels: ingest_transform + hdr_merge_batch)")
+    shape = ingest_shape(tuple(frames.shape), layout)
+    b, c, h, w = shape
+    dev = frames.device
+    if b < 1:
+        raise ValueError("empty batch")
+    arr, n_stages = _ingest_stages(stages, c, data=consts is not None)
+    if consts is not None:
+        _check_consts(consts, dev)
+    if std is not None:
+        std_mode = "explicit"
+        _require_device(std, "std")
+        if std.dtype != torch.float32 or tuple(std.shape) != shape or std.device != dev:
+            raise ValueError(f"std must be a float32 tensor of shape {shape} (planar, like the state) on {dev}")
+        std = std.contiguous()
+    if std_mode not in _STD:
+        raise ValueError(f"unknown std_mode {std_mode}")
+    if exposures.is_cuda:
+        exposure_dev = exposures.to(device=dev, dtype=torch.float64).contiguous()
+    else:  # staged through pinned memory the copy does not wait for the stream (see hdr_merge_batch)
+        exposure_dev = exposures.to(torch.float64).contiguous().pin_memory().to(dev, non_blocking=True)
+    if exposure_dev.numel() != b:
+        raise ValueError(f"{exposure_dev.numel()} exposure times for a batch of {b}")
+    icrf, lut_keep = _icrf_struct(lut, interp, c)
+    hg, r0 = (h, 0) if tile is None else (tile.h_global, tile.row_offset)
+    if r0 < 0 or r0 + h > hg:
+        raise ValueError(f"tile rows [{r0}, {r0 + h}) do not fit a global height of {hg}")
+    geom = nv.Geometry(channels=c, h_tile=h, width=w, h_global=hg, row_offset=r0, image_stride=c * h * w, layout=_LAYOUT[layout])
+    # (state and outputs are planar whatever the order of the source)
+    flags, _, mean_out, std_out = _merge_setup_for((c, h, w), dev, "planar", state, finalize, std_mode != "none", mean_dtype,
+                                                   reference_order, 0, "batch")
+    with torch.cuda.device(dev):
+        rc = nv.load().ct_hdr_merge_ingest_batch(
+            _ptr(frames), _DTYPE[frames.dtype], b, ctypes.byref(geom), arr, n_stages, _ptr(consts), _ptr(std), _STD[std_mode],
+            float(std_value), _ptr(exposure_dev), ctypes.byref(icrf), nv.WEIGHT_GAUSS if gaussian_weight else nv.WEIGHT_NONE,
+            _ptr(state.mean) if state else None, _ptr(state.sumw) if state else None,
+            _ptr(state.var) if (state and state.var is not None) else None, _ptr(mean_out), _ptr(std_out), flags, _stream(dev))
+    nv.check(rc, "ct_hdr_merge_ingest_batch")
+    del lut_keep
+    if state is not None:
+        state.batches += 1
+    return (mean_out, std_out) if finalize else None
 
 
 # ---- a data-dependent Normalize (max_val / min_val None) in such a chain ------------------------------------------------

@@ -25,6 +25,10 @@ and pair lists are passed as their component tensors / scalars.
                                   likewise; an explicit std is planar (F,C,H,W) like the outputs)
     torch.ops.clair_hip.ingest_extrema(stack, prefix, layout, min_val?, max_val?) -> Tensor   (4 floats: sub, div, data
                                   min, data max of a data-dependent Normalize behind the constant ``prefix`` stages)
+    torch.ops.clair_hip.hdr_merge_ingest_batch(frames, stages, exposures, lut?, interp, gaussian, std?, std_mode, std_value,
+                                  layout, h_global, row_offset, closed_form, consts?) -> (mean float64, std float32)   (such
+                                  a chain and hdr_merge in one pass over the raw frames; with ``consts`` a stage of kind 2 is
+                                  the data-dependent Normalize: kind, 0, 0, mul, add)
 
 CPU tensors are refused by the kernels' front-end exactly as through ``ops`` (there is no CPU path).
 """
@@ -182,7 +186,7 @@ def _(x, to_f64):
     return x.new_empty(ops.export_shape(tuple(x.shape)), dtype=torch.float64 if to_f64 else torch.float32)
 
 
-_STAGE_FLOATS = 13  # kind (0 affine, 1 clamp), sub, div, mul, add, lo[0..3], hi[0..3]: ct_ingest_stage, flattened
+_STAGE_FLOATS = 13  # kind (0 affine, 1 clamp, 2 affine_data: mul and add only), sub, div, mul, add, lo[0..3], hi[0..3]: ct_ingest_stage, flattened
 
 
 def flatten_ingest_stages(stages, channels: int):
@@ -191,6 +195,8 @@ def flatten_ingest_stages(stages, channels: int):
     for st in stages:
         if st[0] == "affine":
             flat += [0.0] + [float(v) for v in st[1:5]] + [0.0] * 8
+        elif st[0] == "affine_data":
+            flat += [2.0, 0.0, 0.0, float(st[1]), float(st[2])] + [0.0] * 8
         else:
             pairs = list(st[1]) * (4 if len(st[1]) == 1 else 1)
             pairs += [pairs[-1]] * (4 - len(pairs))
@@ -208,6 +214,8 @@ def _listed_ingest_stages(stack, stages, layout):
         lo, hi = stages[k + 5:k + 9], stages[k + 9:k + 13]
         if kind == 0:
             listed.append(("affine", sub, div, mul, add))
+        elif kind == 2:
+            listed.append(("affine_data", mul, add))
         else:
             n = channels if channels <= 4 else 1
             listed.append(("clamp", [(lo[c], hi[c]) for c in range(n)]))
@@ -252,3 +260,25 @@ def ingest_extrema(stack: torch.Tensor, prefix: Sequence[float], layout: str = "
 @ingest_extrema.register_fake
 def _(stack, prefix, layout="nchw", min_val=None, max_val=None):
     return stack.new_empty((4,), dtype=torch.float32)
+
+
+@torch.library.custom_op(f"{_LIB}::hdr_merge_ingest_batch", mutates_args=())
+def hdr_merge_ingest_batch(frames: torch.Tensor, stages: Sequence[float], exposures: torch.Tensor, lut: Optional[torch.Tensor],
+                           interp: str, gaussian: bool, std: Optional[torch.Tensor], std_mode: str, std_value: float,
+                           layout: str = "nchw", h_global: int = 0, row_offset: int = 0, closed_form: bool = False,
+                           consts: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ct_hdr_merge_ingest_batch: ingest_transform followed by hdr_merge, bit for bit, in one pass over the raw frames
+    (a single-batch merge; an explicit std is planar (B,C,H,W))."""
+    mean, sd = ops.hdr_merge_ingest_batch(frames, _listed_ingest_stages(frames, stages, layout), exposures, lut=lut,
+                                          interp=interp if lut is not None else None, gaussian_weight=gaussian, std=std,
+                                          std_mode=std_mode, std_value=std_value, tile=_tile(h_global, row_offset), layout=layout,
+                                          reference_order=False if closed_form else None, consts=consts)
+    return mean, (sd if sd is not None else mean.new_zeros(0, dtype=torch.float32))
+
+
+@hdr_merge_ingest_batch.register_fake
+def _(frames, stages, exposures, lut, interp, gaussian, std, std_mode, std_value, layout="nchw", h_global=0, row_offset=0,
+      closed_form=False, consts=None):
+    chw = ops.ingest_shape(tuple(frames.shape), layout)[1:]
+    has_std = std is not None or std_mode != "none"
+    return frames.new_empty(chw, dtype=torch.float64), frames.new_empty(chw if has_std else (0,), dtype=torch.float32)

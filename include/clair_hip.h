@@ -430,6 +430,42 @@ int ct_linearize_ingest(const void *frames_dev, int32_t dtype, int64_t n_frames,
                         float std_value, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev, void *stream);
 
 /*
+ * ct_hdr_merge_ingest_batch -- such a chain and one batch of compute_hdr_image's loop body in ONE pass over B raw frames:
+ * state and outputs are bit for bit those of ct_ingest_transform (with consts_dev: ct_ingest_transform_data) into a dense
+ * planar float32 (B, C, H_tile, W) stack followed by ct_hdr_merge_batch on that stack with CT_DTYPE_F32, the same geometry
+ * with layout CT_LAYOUT_NCHW and the same flags,
+ *   x = the stage list applied to (float)code (CT_INGEST_AFFINE / CT_INGEST_CLAMP, at most CT_INGEST_MAX_STAGES; n_stages = 0
+ *       is the cast alone; with consts_dev non-NULL at most one CT_INGEST_AFFINE_DATA stage, whose sub and div are
+ *       consts_dev[0..1] as ct_ingest_extrema left them, read when the kernel runs; without it that kind is
+ *       CT_ERR_INVALID_ARGUMENT)
+ *   then the closed-form merge of a float32 pixel x: LUT coordinate clamped with its gradient mask (x may lie below 0 or
+ *       above 1 behind a chain), float32 moments about a per-pixel pivot, sigma = std_value (CONSTANT), std_value * x
+ *       (MULTIPLIER, x behind the chain) or std_dev[...] (EXPLICIT)
+ * without the float32 stack in between: B * sizeof(code) bytes read and 12 written per output element, where the two
+ * launches move 8 B per sample more (4 written, 4 read again), and no (B, C, H_tile, W) float32 buffer exists.
+ *   frames_dev   CT_DTYPE_U8 / U16 codes, aligned to their element (CT_DTYPE_F32 is CT_ERR_UNSUPPORTED: such a stack has no
+ *                copy to save); geom->layout CT_LAYOUT_NCHW (any C) or, with C == 3, CT_LAYOUT_NHWC / NHWC_BGR: the order of
+ *                the SOURCE (a folded CvToTorch); frames image_stride elements apart, exposures sorted as for ct_hdr_merge_batch
+ *   geom         h_global / row_offset as for ct_hdr_merge_batch: a row band gives the same rows of the whole image
+ *   std_dev      EXPLICIT: planar (B, C, H_tile, W) float32, dense, like the state -- not like the frames: gpu_transforms
+ *                never touch the uncertainty images (as ct_linearize_ingest takes it)
+ *   exposure_dev, icrf, weight_mode, state, outputs   as ct_hdr_merge_batch; state and outputs are planar (C, H_tile, W)
+ *   flags        CT_MERGE_FIRST_BATCH, CT_MERGE_FINALIZE, CT_MERGE_MEAN_OUT_F32, CT_MERGE_CLOSED_FORM
+ * CT_ERR_UNSUPPORTED: CT_MERGE_F64_MOMENTS, CT_MERGE_REFERENCE_ORDER, CT_MERGE_OUT_AS_INPUT, and every call that
+ * ct_hdr_merge_batch would send to the reference-order kernel (LOOKUP / CATMULL with uncertainties and no
+ * CT_MERGE_CLOSED_FORM: that kernel waits for its float64 arithmetic, not for its bytes); an interleaved layout with C != 3;
+ * clamp pairs that differ between channels with C > CT_INGEST_MAX_CHANNELS.  CT_ERR_NO_GRADIENT_PATH and CT_ERR_TOO_LARGE as
+ * ct_hdr_merge_batch.  Every argument is validated before anything touches the device; batch == 0 or an empty image is
+ * CT_OK without a launch.  Allocates nothing, synchronises nothing, reads nothing back, never writes the frames, touches
+ * nothing outside C*H_tile*W elements of the state and the outputs.
+ */
+int ct_hdr_merge_ingest_batch(const void *frames_dev, int32_t dtype, int32_t batch, const ct_geometry *geom,
+                              const ct_ingest_stage *stages, int32_t n_stages, const float *consts_dev, const float *std_dev,
+                              int32_t std_mode, float std_value, const double *exposure_dev, const ct_icrf *icrf,
+                              int32_t weight_mode, double *mean_state_dev, float *sumw_state_dev, float *var_state_dev,
+                              void *mean_out_dev, float *std_out_dev, uint32_t flags, void *stream);
+
+/*
  * ct_export_cv -- the array save_image hands to cv.imwrite (clair_torch/common/data_io.py:228-234: astype, transpose to
  * (H, W, C), channel reversal of a 3-channel image), made on the device from planar results:
  *   dst[f][p][c'] = (dst type) src[f][c][p],  p < plane = H*W,  c' = channels-1-c when reverse_channels, else c
