@@ -1,0 +1,315 @@
+// ct_stats_ingest.hip -- a recognised gpu_transforms chain and one batch of compute_video_mean_and_std's loop body in ONE
+// pass (gfx950): B raw uint8 / uint16 frames in, the float32 planar (C, H, W) WBOMeanVar state (mean, m2) updated in place.
+// The state is bit for bit that of ct_ingest_transform (or _data, ct_ingest.hip) into a dense planar float32 stack followed
+// by ct_video_stats_batch (ct_stats.hip) on that stack -- the same device functions run here on a value that never leaves
+// the registers: (float)code, ct::ingest_stages (ct_ingest_stages.hpp), icrf_sample<INTERP, true, false> (ct_device.hpp;
+// RANGED = false: the second launch of the pair sees float32 pixels), then the sums in ct_stats.hip's order -- float32
+// sum / B, sum (x - mean_b)^2 over the frames in order -- and ct::merge_state (ct_stats_merge.hpp, the one copy).
+//
+// Roofline: HBM.  sizeof(T) bytes read per sample, every byte once while B <= 32, plus 16 B of state per element and batch:
+// 2 B per uint16 sample where the two launches move 10 (2 read + 4 written, then 4 read), 1 B against 9 for uint8.
+//
+// Both walks of ct_stats.hip are kept.  B <= 16 and B <= 32 are register-cached (BMAX = 16 / 32): all B loads of a thread
+// are in flight together, every frame is loaded and the chain evaluated exactly once, the B values per element stay in
+// registers between the mean and the m2 pass.  B > 32 (BMAX = 0) walks the frames twice and evaluates the chain in both
+// passes: the same values again, so the result does not depend on the walk.
+//
+// Ownership.  The LUT is staged in LDS by stage_lut<INTERP> as in ct_stats.hip; the stage list travels by value in the
+// kernel arguments and its loop is wave-uniform, as is the channel that selects a clamp pair and the LOOKUP row:
+// PLANAR (any C): a workgroup row (blockIdx.y) is one channel plane.  G = 4: a thread owns 4 consecutive elements of the
+//   plane whose state accesses are one 16-byte aligned packet each in mean and m2 (the host launches this only where the two
+//   arrays are equally aligned), and fetches their codes with one 4- or 8-byte load of any alignment per frame.  What
+//   precedes a plane's first aligned packet and what follows its last whole one -- at most 3 elements each -- goes to a
+//   second launch of the G = 1 instantiation: the vector body plus scalar tail of ct_stats.hip, per plane.  The LINEAR /
+//   CATMULL row is the reference's flat NCHW index modulo C (base.py:173-176) taken from the global position
+//   c * H_global * W + row_offset * W + p: one modulo for the first element, an add and a conditional subtract for the rest.
+// PACKED3 (interleaved (F, H, W, 3), RGB or BGR): a thread owns whole pixels, ONE of them (G = 1): consecutive memory
+//   elements belong to different channels and ingest_stages takes one channel per call, so the three elements of a pixel
+//   make three calls with a compile-time memory channel; BGR is a wave-uniform plane index (2 - memory channel), not a
+//   variant.  Its 3 codes are one 3- / 6-byte load per frame, its state accesses one element per plane, dense across the
+//   wavefront.  One pixel and not the four of linearize_ingest_packed3_kernel: the cached walk holds BMAX values per
+//   element, and 12 elements x 32 frames do not fit the register file (the listing: DESIGN.md).  Calling ingest_stages
+//   per element of a 4-element memory packet instead would make the clamp pair a per-lane choice inside the frame loop.
+// Every load is that of a code of the thread's own elements (pixels) in one of the B frames, every store lies in the
+// thread's own elements of mean_state and m2_state.  The consts of a CT_INGEST_AFFINE_DATA stage are read once per thread,
+// before anything is stored.  No atomics, no LDS traffic besides the LUT, the frames are read only.
+#include "ct_ingest_stages.hpp"
+#include "ct_stats_merge.hpp"
+
+namespace ct {
+
+struct StatsIngestArgs {
+    const void *frames;
+    const float *consts;    // sub, div of a CT_INGEST_AFFINE_DATA stage (ct_ingest_extrema), or NULL
+    const float *lut;
+    float *mean_state, *m2_state;
+    int64_t image_stride;   // source elements between consecutive frames
+    uint32_t plane;         // H_tile * W
+    uint32_t plane_global;  // H_global * W: global flat index of (c, local p) = c * plane_global + base + p
+    uint32_t base;          // row_offset * W
+    int32_t batch, channels, n_points;
+    uint32_t reversed;      // PACKED3: memory channel cm feeds plane 2 - cm (BGR)
+    uint32_t by_channel;    // some clamp holds different pairs for different channels (then C <= CT_INGEST_MAX_CHANNELS)
+    uint32_t state_lead;    // PLANAR: (mean_state address / 4) % 4, or kSiNoPackets: every element goes through G = 1
+    float count_before;     // W_A (number of frames merged so far)
+    uint32_t n_stages;
+    ct_ingest_stage stage[CT_INGEST_MAX_STAGES];
+};
+
+constexpr int kSiGroup = 4;  // PLANAR: elements per thread of the vector body, one 16-byte state packet
+constexpr uint32_t kSiNoPackets = 4;
+
+template <typename T, int N>
+struct SiRaw {
+    T v[N];
+};
+
+// elements in front of a plane's first aligned state packet, and the end of its last whole one
+__device__ __forceinline__ void si_body(const StatsIngestArgs &a, uint32_t c, uint32_t &head, uint32_t &body_end)
+{
+    head = a.state_lead == kSiNoPackets ? a.plane : (0u - (a.state_lead + c * a.plane)) & (uint32_t)(kSiGroup - 1);
+    head = head < a.plane ? head : a.plane;
+    body_end = head + ((a.plane - head) & ~(uint32_t)(kSiGroup - 1));
+}
+
+// One thread: G consecutive elements of every plane it owns, the whole batch and the state.  (The walk stands in the kernel
+// itself and not in a device function of its own: a callee is unrolled before it is inlined, and the kernel would then meet
+// its by-value argument block with more users than the optimizer follows and keep a copy of it in scratch.)
+template <typename T, bool PACKED, int G, int INTERP, int BMAX, bool DATA>
+__global__ __launch_bounds__(kBlock) void video_stats_ingest_kernel(const StatsIngestArgs a)
+{
+    extern __shared__ __align__(16) char lds[];
+    static_assert(PACKED ? G == 1 : (G == 1 || G == kSiGroup), "one pixel, or one element / one packet of a plane");
+    stage_lut<INTERP>(lds, a.lut, a.channels, a.n_points);
+    // the constants of a data-dependent Normalize: one wave-uniform load, before anything is stored
+    const float dsub = DATA ? a.consts[0] : 0.0f, ddiv = DATA ? a.consts[1] : 1.0f;
+    __syncthreads();
+    const uint32_t t = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+    uint32_t c0 = 0u, p0;  // plane (PLANAR) and first local pixel
+    if constexpr (PACKED) {
+        if (t >= a.plane) return;
+        p0 = t;
+    } else {
+        c0 = blockIdx.y;
+        uint32_t head, body_end;
+        si_body(a, c0, head, body_end);
+        if constexpr (G == kSiGroup) {
+            const uint64_t at = (uint64_t)head + (uint64_t)t * kSiGroup;
+            if (at >= body_end) return;
+            p0 = (uint32_t)at;
+        } else {  // the edges: [0, head) and [body_end, plane)
+            const uint64_t at = t < head ? (uint64_t)t : (uint64_t)body_end + (t - head);
+            if (at >= a.plane) return;
+            p0 = (uint32_t)at;
+        }
+    }
+
+    constexpr int NP = PACKED ? 3 : 1;  // planes per thread
+    constexpr int NE = NP * G;
+    constexpr int kEntry = lut_entry_bytes(INTERP);
+    const int C = a.channels, L = a.n_points, B = a.batch;
+    const float top = INTERP == CT_INTERP_NONE ? 1.0f : (float)(L - 1);
+
+    uint32_t cj[NP];  // plane of the state (wave-uniform)
+    uint32_t q[NP];   // index of the first element in the planar (C, plane) state
+    int row_off[NE];  // byte offset of each element's LUT row inside the LDS table
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        cj[j] = PACKED ? (a.reversed ? (uint32_t)(NP - 1 - j) : (uint32_t)j) : c0;
+        q[j] = cj[j] * a.plane + p0;
+        // TileMap::locate's q_global for a channel that is known: the global flat NCHW index (< 2^31)
+        const uint32_t qg = cj[j] * a.plane_global + a.base + p0;
+        int r = lut_row<INTERP>(qg, (int)cj[j], PACKED ? 3 : C);  // (a constant divisor where the frames are interleaved)
+#pragma unroll
+        for (int e = 0; e < G; ++e) {
+            row_off[j * G + e] = r * L * kEntry;
+            if constexpr (INTERP != CT_INTERP_LOOKUP) {  // the next element's flat index is one further
+                ++r;
+                r = r >= C ? r - C : r;
+            }
+        }
+    }
+    const T *src = static_cast<const T *>(a.frames) + (PACKED ? (int64_t)p0 * NP : (int64_t)c0 * a.plane + p0);
+
+    auto load_raw = [&](int n) __attribute__((always_inline)) {
+        SiRaw<T, NE> r;
+        __builtin_memcpy(&r, src + (int64_t)n * a.image_stride, sizeof(r));  // any alignment: frames are only element-aligned
+        return r;
+    };
+    // the thread's NE samples of one frame: the chain, then the model
+    auto sample = [&](const SiRaw<T, NE> &raw, float (&out)[NE]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            float x[G];
+#pragma unroll
+            for (int e = 0; e < G; ++e) x[e] = (float)raw.v[e * NP + j];
+            ingest_stages<DATA>(x, a, a.by_channel ? cj[j] : 0u, dsub, ddiv);
+#pragma unroll
+            for (int e = 0; e < G; ++e) {
+                float d;
+                out[j * G + e] = icrf_sample<INTERP, true, false>(x[e], lds + row_off[j * G + e], top, d);
+            }
+        }
+    };
+
+    float sum[NE], m2[NE], mean_b[NE];
+#pragma unroll
+    for (int k = 0; k < NE; ++k) sum[k] = m2[k] = 0.0f;
+    if constexpr (BMAX > 0) {  // the values stay in registers between the mean and the m2 pass
+        SiRaw<T, NE> raw[BMAX];
+#pragma unroll
+        for (int n = 0; n < BMAX; ++n)
+            if (n < B) raw[n] = load_raw(n);
+        float xs[BMAX][NE];
+#pragma unroll
+        for (int n = 0; n < BMAX; ++n) {
+            if (n < B) {
+                sample(raw[n], xs[n]);
+#pragma unroll
+                for (int k = 0; k < NE; ++k) sum[k] += xs[n][k];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NE; ++k) mean_b[k] = sum[k] / (float)B;  // torch.mean: float32 sum / count
+#pragma unroll
+        for (int n = 0; n < BMAX; ++n) {
+            if (n < B) {
+#pragma unroll
+                for (int k = 0; k < NE; ++k) {
+                    const float dv = xs[n][k] - mean_b[k];
+                    m2[k] += dv * dv;
+                }
+            }
+        }
+    } else {
+#pragma unroll 4
+        for (int n = 0; n < B; ++n) {
+            float x[NE];
+            sample(load_raw(n), x);
+#pragma unroll
+            for (int k = 0; k < NE; ++k) sum[k] += x[k];
+        }
+#pragma unroll
+        for (int k = 0; k < NE; ++k) mean_b[k] = sum[k] / (float)B;  // torch.mean: float32 sum / count
+#pragma unroll 4
+        for (int n = 0; n < B; ++n) {
+            float x[NE];
+            sample(load_raw(n), x);
+#pragma unroll
+            for (int k = 0; k < NE; ++k) {
+                const float dv = x[k] - mean_b[k];
+                m2[k] += dv * dv;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        float mb[G], mm[G];
+        uint32_t unused[G] = {};  // (the interleaved form of merge_state is not used: the state is addressed per plane)
+#pragma unroll
+        for (int e = 0; e < G; ++e) {
+            mb[e] = mean_b[j * G + e];
+            mm[e] = m2[j * G + e];
+        }
+        merge_state<G, false>(a, q[j], unused, mb, mm);
+    }
+}
+
+template <typename T, bool PACKED, int G, int INTERP, bool DATA>
+static int si_launch(const StatsIngestArgs &a, uint32_t threads_x, hipStream_t s)
+{
+    const size_t lds = INTERP == CT_INTERP_NONE ? 0 : (size_t)a.channels * a.n_points * lut_entry_bytes(INTERP);
+    const dim3 grid((threads_x + kBlock - 1) / kBlock, PACKED ? 1u : (uint32_t)a.channels), block(kBlock);
+    if (a.batch <= 16)
+        hipLaunchKernelGGL((video_stats_ingest_kernel<T, PACKED, G, INTERP, 16, DATA>), grid, block, lds, s, a);
+    else if (a.batch <= 32)
+        hipLaunchKernelGGL((video_stats_ingest_kernel<T, PACKED, G, INTERP, 32, DATA>), grid, block, lds, s, a);
+    else
+        hipLaunchKernelGGL((video_stats_ingest_kernel<T, PACKED, G, INTERP, 0, DATA>), grid, block, lds, s, a);
+    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
+}
+
+template <typename T, int INTERP, bool DATA>
+static int si_layout(StatsIngestArgs a, bool packed, hipStream_t s)
+{
+    if (packed) return si_launch<T, true, 1, INTERP, DATA>(a, a.plane, s);
+    auto lead = [](const void *p) { return (uint32_t)((reinterpret_cast<uintptr_t>(p) / sizeof(float)) % kSiGroup); };
+    // packets only where mean and m2 are equally aligned (always, for two allocations); else element by element
+    const bool packets = lead(a.mean_state) == lead(a.m2_state) && a.plane >= (uint32_t)kSiGroup;
+    a.state_lead = packets ? lead(a.mean_state) : kSiNoPackets;
+    if (packets) {
+        const int rc = si_launch<T, false, kSiGroup, INTERP, DATA>(a, a.plane / kSiGroup, s);  // (a thread per possible packet)
+        if (rc != CT_OK) return rc;
+        if (a.state_lead == 0 && a.plane % kSiGroup == 0) return CT_OK;  // every plane is whole packets
+        return si_launch<T, false, 1, INTERP, DATA>(a, 2 * (kSiGroup - 1), s);
+    }
+    return si_launch<T, false, 1, INTERP, DATA>(a, a.plane, s);
+}
+
+template <typename T>
+static int si_dispatch(const StatsIngestArgs &a, bool packed, int interp, hipStream_t s)
+{
+    return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
+        return a.consts ? si_layout<T, I, true>(a, packed, s) : si_layout<T, I, false>(a, packed, s);
+    });
+}
+
+}  // namespace ct
+
+extern "C" int ct_video_stats_ingest_batch(const void *frames_dev, int32_t dtype, int32_t batch, const ct_geometry *geom,
+                                           const ct_ingest_stage *stages, int32_t n_stages, const float *consts_dev,
+                                           const ct_icrf *icrf, float frames_before, float *mean_state_dev, float *m2_state_dev,
+                                           void *stream)
+{
+    using namespace ct;
+    // everything that needs no pointer into device memory first: geometry (as ct_video_stats_batch, an empty plane allowed),
+    // the stack and the stage list (as ct_ingest_transform / _data), the model
+    if (!geom || !icrf) return CT_ERR_INVALID_ARGUMENT;
+    if (geom->channels <= 0 || geom->h_tile < 0 || geom->width < 0 || geom->h_global < geom->h_tile || geom->row_offset < 0 ||
+        geom->row_offset + geom->h_tile > geom->h_global)
+        return CT_ERR_INVALID_ARGUMENT;
+    if (geom->layout < CT_LAYOUT_NCHW || geom->layout > CT_LAYOUT_NHWC_BGR) return CT_ERR_INVALID_ARGUMENT;
+    if (geom->h_global * geom->width * geom->channels >= (int64_t)1 << 31) return CT_ERR_TOO_LARGE;
+    const int64_t plane = geom->h_tile * geom->width;
+    bool by_channel = false;
+    const int rc = ingest_validate(dtype, geom->layout, batch, geom->channels, plane, stages, n_stages, CT_INGEST_MAX_STAGES,
+                                   consts_dev ? 1 : 0, by_channel);
+    if (rc != CT_OK) return rc;
+    if (dtype == CT_DTYPE_F32) return CT_ERR_UNSUPPORTED;  // float32 pixels have no copy to save: ct_video_stats_batch takes them
+    if (reinterpret_cast<uintptr_t>(consts_dev) % sizeof(float) != 0) return CT_ERR_INVALID_ARGUMENT;
+    const int interp = icrf->interp;
+    if (interp < CT_INTERP_LOOKUP || interp > CT_INTERP_NONE) return CT_ERR_INVALID_ARGUMENT;
+    if (interp != CT_INTERP_NONE && (!icrf->lut_dev || icrf->n_points < 2)) return CT_ERR_INVALID_ARGUMENT;
+    if (!(frames_before >= 0.0f)) return CT_ERR_INVALID_ARGUMENT;
+    if (geom->image_stride < plane * geom->channels) return CT_ERR_INVALID_ARGUMENT;
+    const int n_points = interp == CT_INTERP_NONE ? 2 : icrf->n_points;
+    if (interp != CT_INTERP_NONE && (size_t)geom->channels * (size_t)n_points * lut_entry_bytes(interp) > 160 * 1024)
+        return CT_ERR_TOO_LARGE;
+    const bool packed = geom->layout != CT_LAYOUT_NCHW;
+    if (!packed && geom->channels > 65535) return CT_ERR_TOO_LARGE;  // a plane is a row of the grid
+    if (batch == 0 || plane == 0) return CT_OK;
+    auto aligned = [](const void *p, uintptr_t b) { return reinterpret_cast<uintptr_t>(p) % b == 0; };
+    if (!frames_dev || !mean_state_dev || !m2_state_dev) return CT_ERR_INVALID_ARGUMENT;
+    if (!aligned(frames_dev, dtype == CT_DTYPE_U16 ? 2 : 1) || !aligned(mean_state_dev, sizeof(float)) || !aligned(m2_state_dev, sizeof(float)))
+        return CT_ERR_INVALID_ARGUMENT;
+    StatsIngestArgs a = {};
+    a.frames = frames_dev;
+    a.consts = consts_dev;
+    a.lut = icrf->lut_dev;
+    a.mean_state = mean_state_dev;
+    a.m2_state = m2_state_dev;
+    a.image_stride = geom->image_stride;
+    a.plane = (uint32_t)plane;
+    a.plane_global = (uint32_t)(geom->h_global * geom->width);
+    a.base = (uint32_t)(geom->row_offset * geom->width);
+    a.batch = batch;
+    a.channels = geom->channels;
+    a.n_points = n_points;
+    a.reversed = geom->layout == CT_LAYOUT_NHWC_BGR ? 1u : 0u;
+    a.by_channel = by_channel ? 1u : 0u;
+    a.count_before = frames_before;
+    a.n_stages = (uint32_t)n_stages;
+    for (int32_t k = 0; k < n_stages; ++k) a.stage[k] = stages[k];
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dtype == CT_DTYPE_U8 ? si_dispatch<uint8_t>(a, packed, interp, s) : si_dispatch<uint16_t>(a, packed, interp, s);
+}

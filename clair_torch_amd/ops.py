@@ -1025,3 +1025,40 @@ def video_stats_batch(frames: torch.Tensor, mean_state: torch.Tensor, m2_state: 
                                             _ptr(mean_state), _ptr(m2_state), _stream(dev))
     nv.check(rc, "ct_video_stats_batch")
     del lut_keep
+
+
+# ---- a gpu_transforms chain and the streaming video statistics in one pass ------------------------------------------------
+def video_stats_ingest_batch(frames: torch.Tensor, stages, mean_state: torch.Tensor, m2_state: torch.Tensor, frames_before: int, *,
+                             lut: Optional[torch.Tensor] = None, interp: Optional[str] = None,
+                             tile: Optional[TileGeometry] = None, layout: str = "nchw", consts: Optional[torch.Tensor] = None):
+    """ct_video_stats_ingest_batch: ``video_stats_batch(ingest_transform(frames, stages, layout, consts=consts), ...)`` bit for
+    bit, in one launch and without the float32 stack in between; the running (mean, m2) float32 state is updated in place.
+
+    ``frames``: a contiguous uint8 / uint16 device stack, (B,C,H,W) for "nchw" or (B,H,W,3) for "nhwc" / "nhwc_bgr" (the
+    order of the source: a folded CvToTorch).  ``stages``: as ``ingest_transform`` takes them; with ``consts`` (the tensor
+    ``ingest_extrema`` returned) one of them may be ("affine_data", mul, add).  ``mean_state``, ``m2_state``: contiguous
+    float32 (C,H,W), planar whatever the layout of the frames (``ingest_shape(frames.shape, layout)[1:]``).
+    ``frames_before``, ``lut``, ``interp``, ``tile``: as in ``video_stats_batch``."""
+    _check_ingest_stack(frames, layout)
+    if frames.dtype == torch.float32:
+        raise TypeError("video_stats_ingest_batch takes uint8 / uint16 codes (float32 pixels: ingest_transform + video_stats_batch)")
+    b, c, h, w = ingest_shape(tuple(frames.shape), layout)
+    dev = frames.device
+    arr, n_stages = _ingest_stages(stages, c, data=consts is not None)
+    if consts is not None:
+        _check_consts(consts, dev)
+    for name, t in (("mean_state", mean_state), ("m2_state", m2_state)):
+        _require_device(t, name)
+        if t.dtype != torch.float32 or tuple(t.shape) != (c, h, w) or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float32 (C,H,W) = {(c, h, w)} tensor on {dev}")
+    icrf, lut_keep = _icrf_struct(lut, interp, c)
+    hg, r0 = (h, 0) if tile is None else (tile.h_global, tile.row_offset)
+    if r0 < 0 or r0 + h > hg:
+        raise ValueError(f"tile rows [{r0}, {r0 + h}) do not fit a global height of {hg}")
+    geom = nv.Geometry(channels=c, h_tile=h, width=w, h_global=hg, row_offset=r0, image_stride=c * h * w, layout=_LAYOUT[layout])
+    with torch.cuda.device(dev):
+        rc = nv.load().ct_video_stats_ingest_batch(_ptr(frames), _DTYPE[frames.dtype], b, ctypes.byref(geom), arr, n_stages,
+                                                   _ptr(consts), ctypes.byref(icrf), float(frames_before), _ptr(mean_state),
+                                                   _ptr(m2_state), _stream(dev))
+    nv.check(rc, "ct_video_stats_ingest_batch")
+    del lut_keep

@@ -466,6 +466,38 @@ int ct_hdr_merge_ingest_batch(const void *frames_dev, int32_t dtype, int32_t bat
                               void *mean_out_dev, float *std_out_dev, uint32_t flags, void *stream);
 
 /*
+ * ct_video_stats_ingest_batch -- such a chain and one batch of compute_video_mean_and_std's loop body in ONE pass over B raw
+ * frames: the state is bit for bit that of ct_ingest_transform (with consts_dev: ct_ingest_transform_data) into a dense
+ * planar float32 (B, C, H_tile, W) stack followed by ct_video_stats_batch on that stack with CT_DTYPE_F32 and the same
+ * geometry with layout CT_LAYOUT_NCHW,
+ *   x = the stage list applied to (float)code (CT_INGEST_AFFINE / CT_INGEST_CLAMP, at most CT_INGEST_MAX_STAGES; n_stages = 0
+ *       is the cast alone; with consts_dev non-NULL at most one CT_INGEST_AFFINE_DATA stage, whose sub and div are
+ *       consts_dev[0..1] as ct_ingest_extrema left them, read when the kernel runs; without it that kind is
+ *       CT_ERR_INVALID_ARGUMENT)
+ *   then the optional ICRF of a float32 pixel x (LUT coordinate clamped on both sides: x may lie below 0 or above 1 behind a
+ *       chain) and the unweighted WBOMeanVar update in ct_video_stats_batch's order of operations
+ * without the float32 stack in between: sizeof(code) bytes read per sample, where the two launches move 8 B per sample more
+ * (4 written, 4 read again), and no (B, C, H_tile, W) float32 buffer exists.  The state traffic, 16 B per element and
+ * batch, is the same.
+ *   frames_dev   CT_DTYPE_U8 / U16 codes, aligned to their element and no further (CT_DTYPE_F32 is CT_ERR_UNSUPPORTED: such a
+ *                stack has no copy to save); geom->layout CT_LAYOUT_NCHW (any C) or, with C == 3, CT_LAYOUT_NHWC / NHWC_BGR:
+ *                the order of the SOURCE (a folded CvToTorch); frames image_stride elements apart
+ *   geom         h_global / row_offset as for ct_video_stats_batch: a row band gives the same rows of the whole image (the
+ *                LINEAR / CATMULL LUT row is the global flat NCHW index modulo C, the LOOKUP row the channel)
+ *   frames_before, mean_state_dev, m2_state_dev   as ct_video_stats_batch: planar (C, H_tile, W) float32, updated in place,
+ *                aligned to 4 bytes (an interior slice of a larger buffer is fine)
+ * CT_ERR_UNSUPPORTED: an interleaved layout with C != 3; clamp pairs that differ between channels with
+ * C > CT_INGEST_MAX_CHANNELS.  CT_ERR_TOO_LARGE: C * H_global * W >= 2^31, a LUT beyond the 160 KB of LDS, more than 65535
+ * planar channels.  Every argument is validated before anything touches the device; batch == 0 or an empty image is CT_OK
+ * without a launch.  Allocates nothing, synchronises nothing, reads nothing back, never writes the frames, touches nothing
+ * outside C*H_tile*W elements of the state.
+ */
+int ct_video_stats_ingest_batch(const void *frames_dev, int32_t dtype, int32_t batch, const ct_geometry *geom,
+                                const ct_ingest_stage *stages, int32_t n_stages, const float *consts_dev,
+                                const ct_icrf *icrf, float frames_before, float *mean_state_dev, float *m2_state_dev,
+                                void *stream);
+
+/*
  * ct_export_cv -- the array save_image hands to cv.imwrite (clair_torch/common/data_io.py:228-234: astype, transpose to
  * (H, W, C), channel reversal of a 3-channel image), made on the device from planar results:
  *   dst[f][p][c'] = (dst type) src[f][c][p],  p < plane = H*W,  c' = channels-1-c when reverse_channels, else c
