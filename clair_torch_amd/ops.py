@@ -468,8 +468,7 @@ def pair_residual_lut_grad(stack: torch.Tensor, pairs: PairList, coef: torch.Ten
     c, _, _ = _chw(stack, layout)
     dev = stack.device
     if std is not None:
-        std_mode = "explicit"
-        std = std.to(device=dev, dtype=torch.float32).contiguous()
+        std_mode, std = "explicit", _explicit_std(std, stack)  # the kernel reads it at the stack's indices: same shape
         stack = stack.contiguous()
     if not use_unc_weight:
         std, std_mode = None, "none"
