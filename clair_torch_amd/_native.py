@@ -28,7 +28,8 @@ EXPORTS = ("ct_abi_version", "ct_error_string", "ct_hdr_merge_batch", "ct_hdr_me
            "ct_merge_set_retry_counter", "ct_norm_constants", "ct_index_constants", "ct_pivot_index_constants",
            "ct_pivot_floor_constants", "ct_pivot_interval_constants", "ct_band_stats", "ct_band_stats_workspace",
            "ct_strided_downscale", "ct_export_cv", "ct_ingest_transform", "ct_ingest_extrema_workspace", "ct_ingest_extrema",
-           "ct_ingest_transform_data", "ct_linearize_ingest", "ct_hdr_merge_ingest_batch", "ct_video_stats_ingest_batch")
+           "ct_ingest_transform_data", "ct_linearize_ingest", "ct_hdr_merge_ingest_batch", "ct_video_stats_ingest_batch",
+           "ct_hdr_merge_ingest_batches")
 
 
 class Geometry(ctypes.Structure):
@@ -129,6 +130,9 @@ def load():
     lib.ct_hdr_merge_ingest_batch.restype = i32
     lib.ct_hdr_merge_ingest_batch.argtypes = [vp, i32, i32, gp, ctypes.POINTER(IngestStage), i32, vp, vp, i32, f32, vp, ip, i32, vp, vp,
                                               vp, vp, vp, u32, vp]
+    lib.ct_hdr_merge_ingest_batches.restype = i32
+    lib.ct_hdr_merge_ingest_batches.argtypes = [vp, vp, i32, i32, gp, ctypes.POINTER(IngestStage), i32, vp, vp, i32, f32, vp, ip, i32, vp,
+                                                vp, vp, vp, vp, u32, vp]
     lib.ct_video_stats_ingest_batch.restype = i32
     lib.ct_video_stats_ingest_batch.argtypes = [vp, i32, i32, gp, ctypes.POINTER(IngestStage), i32, vp, ip, f32, vp, vp, vp]
     lib.ct_video_stats_batch.restype = i32

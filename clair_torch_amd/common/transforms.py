@@ -22,7 +22,7 @@ route of this table that applies is taken:
 = ============= ==================================================================== =====================================
 
 compute_hdr_image does not execute routes 3 and 4 on uint8 / uint16 frames (``stage_images(defer_ingest=True)``): the chain
-is evaluated inside the merge kernel, one ct_hdr_merge_ingest_batch launch per batch and no float32 copy of the batch --
+is evaluated inside the merge kernel, up to 16 batches per ct_hdr_merge_ingest_batches launch and no float32 copy of a batch --
 unless there is a dark-field dataset, the mode is one of the reference-order kernel's (LOOKUP / CATMULL with uncertainties
 by default) or ``fused_ingest=False``; route 4 still runs ct_ingest_extrema first and checks its constants.
 

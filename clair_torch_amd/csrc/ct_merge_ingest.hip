@@ -23,284 +23,9 @@
 // inside a larger buffer -- is accessed element by element.  What precedes the first packet of a plane
 // and what follows the last whole one goes through the same code with ONE element (pixel) per step.  PF samples are in
 // flight ahead of the one being reduced, as in merge_kernel's ring.  No atomics, no LDS regroup, the frames are read only.
-#include "ct_ingest_stages.hpp"
-#include "ct_merge_ingest.hpp"
+#include "ct_merge_ingest_kernel.hpp"
 
 namespace ct {
-
-struct MergeIngestArgs {
-    const void *frames;
-    const float *std_stack;  // EXPLICIT: planar (B, C, plane) float32, dense
-    const float *consts;     // sub, div of a CT_INGEST_AFFINE_DATA stage (ct_ingest_extrema), or NULL
-    const double *exposure;
-    const float *lut;
-    double *mean_state;
-    float *sumw_state;
-    float *var_state;
-    void *mean_out;
-    float *std_out;
-    int64_t image_stride;   // source elements between consecutive frames
-    uint32_t plane;         // H_tile * W
-    uint32_t plane_global;  // H_global * W: global flat index of (c, local p) = c * plane_global + base + p
-    uint32_t base;          // row_offset * W
-    int32_t batch, channels, n_points;
-    uint32_t reversed;      // PACKED3: memory channel cm feeds plane 2 - cm (BGR)
-    uint32_t by_channel;    // some clamp holds different pairs for different channels (then C <= CT_INGEST_MAX_CHANNELS)
-    float std_value;
-    float weight_scale;     // Gaussian scale (30)
-    uint32_t flags;
-    uint32_t n_stages;
-    ct_ingest_stage stage[CT_INGEST_MAX_STAGES];
-};
-
-constexpr int kMiGroup = 4;        // PLANAR: output elements per thread, one 16-byte packet
-constexpr int kMiPackedGroup = 2;  // PACKED3: pixels per thread (see the head of this file)
-constexpr int kMiPF = 2;     // samples in flight ahead of the one being reduced
-
-template <typename T, int N>
-struct MiRaw {
-    T v[N];
-};
-
-// alignment at which G values of X move as whole packets: their size, 16 bytes at the most
-template <typename X, int G>
-constexpr uintptr_t mi_packet_align() { return sizeof(X) * G < 16 ? sizeof(X) * G : 16; }
-
-// G values at p[0..G): one or two packet accesses where the packet is aligned in memory, else element by element
-template <typename X, int G>
-__device__ __forceinline__ void mi_load(const X *p, X (&v)[G])
-{
-    if constexpr (G > 1) {
-        constexpr uintptr_t kAlign = mi_packet_align<X, G>();
-        if ((reinterpret_cast<uintptr_t>(p) & (kAlign - 1)) == 0) {
-            __builtin_memcpy(v, __builtin_assume_aligned(p, kAlign), sizeof(v));
-            return;
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < G; ++e) v[e] = p[e];
-}
-
-template <bool STREAM, typename X, int G>
-__device__ __forceinline__ void mi_store(X *p, const X (&v)[G])
-{
-    if constexpr (G > 1) {
-        if ((reinterpret_cast<uintptr_t>(p) & (mi_packet_align<X, G>() - 1)) == 0) {
-            Packet<X, G> o;
-#pragma unroll
-            for (int e = 0; e < G; ++e) o.v[e] = v[e];
-            if constexpr (STREAM)
-                store_stream(reinterpret_cast<Packet<X, G> *>(p), o);  // outputs: written once, never re-read here
-            else
-                *reinterpret_cast<Packet<X, G> *>(p) = o;
-            return;
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < G; ++e) p[e] = v[e];
-}
-
-// G consecutive elements of every plane the thread owns, from local pixel p0: the whole batch, state and outputs
-template <typename T, bool PACKED, int G, int INTERP, int WEIGHT, int STD>
-__device__ __forceinline__ void mi_run(const MergeIngestArgs &a, const char *lds, const float *inv_t, const float *cq, uint32_t c0,
-                                       uint32_t p0, float dsub, float ddiv)
-{
-    constexpr int NP = PACKED ? 3 : 1;  // planes per thread
-    constexpr int NE = NP * G;
-    constexpr bool kHasStd = STD != CT_STD_NONE;
-    constexpr bool kGauss = WEIGHT == CT_WEIGHT_GAUSS;
-    constexpr int kEntry = lut_entry_bytes(INTERP);
-    const int C = a.channels, L = a.n_points, B = a.batch;
-    const float top = INTERP == CT_INTERP_NONE ? 1.0f : (float)(L - 1);
-    const float kk = sqrtf(a.weight_scale * 1.4426950408889634f);
-    const float K = -2.0f * a.weight_scale;
-    const float dk_mul = kk, dk_add = -0.5f * kk;
-    const bool first = a.flags & CT_MERGE_FIRST_BATCH;
-    const bool finalize = a.flags & CT_MERGE_FINALIZE;
-    const bool keep_state = a.mean_state != nullptr;
-
-    uint32_t cj[NP];   // plane of the state / outputs (wave-uniform)
-    uint32_t q[NP];    // index of the first element in the planar (C, plane) arrays
-    int row_off[NE];   // byte offset of each element's LUT row inside the LDS table
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        cj[j] = PACKED ? (a.reversed ? (uint32_t)(NP - 1 - j) : (uint32_t)j) : c0;
-        q[j] = cj[j] * a.plane + p0;
-        const uint32_t qg = cj[j] * a.plane_global + a.base + p0;  // global flat NCHW index (< 2^31)
-        int r = PACKED ? (int)(qg % 3u) : (int)(qg % (uint32_t)C);
-#pragma unroll
-        for (int e = 0; e < G; ++e) {
-            row_off[j * G + e] = (INTERP == CT_INTERP_LOOKUP ? (int)cj[j] : r) * L * kEntry;
-            ++r;
-            r = r >= C ? r - C : r;
-        }
-    }
-    const T *src = static_cast<const T *>(a.frames) + (PACKED ? (int64_t)p0 * NP : (int64_t)c0 * a.plane + p0);
-    const int64_t std_stride = (int64_t)C * a.plane;  // the explicit uncertainties are planar and dense
-
-    auto load_raw = [&](int64_t frame_offset) {
-        MiRaw<T, NE> r;
-        __builtin_memcpy(&r, src + frame_offset, sizeof(r));  // any alignment: planes are only element-aligned in general
-        return r;
-    };
-    // the G pixels of plane j behind the chain
-    auto pixels = [&](const MiRaw<T, NE> &raw, int j, float (&x)[G]) {
-#pragma unroll
-        for (int e = 0; e < G; ++e) x[e] = (float)raw.v[e * NP + j];
-        ingest_stages<true>(x, a, a.by_channel ? cj[j] : 0u, dsub, ddiv);
-    };
-
-    // ---- pivot: the middle exposure's sample on a first batch, else the running mean ----
-    float p[NE];
-    if (first) {
-        const int probe = B / 2;
-        const MiRaw<T, NE> raw = load_raw((int64_t)probe * a.image_stride);
-        const float itp = inv_t[probe];
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            float x[G];
-            pixels(raw, j, x);
-#pragma unroll
-            for (int e = 0; e < G; ++e) {
-                float lin, dfds;
-                mi_sample<INTERP>(x[e], lds + row_off[j * G + e], top, lin, dfds);
-                p[j * G + e] = lin * itp;
-            }
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            double m[G];
-            mi_load(a.mean_state + q[j], m);
-#pragma unroll
-            for (int e = 0; e < G; ++e) p[j * G + e] = (float)m[e];
-        }
-    }
-
-    // scale of the folded second moments back to true units
-    double fs = 1.0;
-    if constexpr (kGauss) fs = (double)K / (double)kk;
-    if constexpr (STD == CT_STD_CONSTANT || STD == CT_STD_MULTIPLIER) fs *= (double)a.std_value;
-    const double sv2 = fs * fs;
-
-    MiResult res[NE];
-    for (int pass_no = 0;; ++pass_no) {
-        MiSums sum[NE];
-#pragma unroll
-        for (int k = 0; k < NE; ++k) sum[k] = MiSums{0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-
-        // software pipeline, as merge_kernel's: kMiPF loads in flight per thread ahead of the sample being reduced
-        MiRaw<T, NE> ring[kMiPF];
-        float sring[STD == CT_STD_EXPLICIT ? kMiPF : 1][NE];
-        auto load_std = [&](int64_t nn, float (&sg)[NE]) {
-#pragma unroll
-            for (int j = 0; j < NP; ++j) __builtin_memcpy(&sg[j * G], a.std_stack + nn * std_stride + q[j], G * sizeof(float));
-        };
-#pragma unroll
-        for (int k = 0; k < kMiPF; ++k) {
-            const int nn = k < B ? k : B - 1;
-            ring[k] = load_raw((int64_t)nn * a.image_stride);
-            if constexpr (STD == CT_STD_EXPLICIT) load_std(nn, sring[k]);
-        }
-#pragma unroll kMiPF
-        for (int n = 0; n < B; ++n) {
-            const int nn = n + kMiPF < B ? n + kMiPF : B - 1;  // the tail re-loads the last exposure (cache hit, unused)
-            // (the exposure index is laundered through an empty asm, as in merge_kernel: otherwise the compiler re-loads the
-            //  sample at its point of use and the prefetch is gone)
-            int64_t opaque_zero = 0;
-            asm volatile("" : "+s"(opaque_zero));
-            const int64_t nl = (int64_t)nn + opaque_zero;
-            const MiRaw<T, NE> incoming = load_raw(nl * a.image_stride);
-            float sincoming[NE];
-            if constexpr (STD == CT_STD_EXPLICIT) load_std(nl, sincoming);
-            const MiRaw<T, NE> raw = ring[0];
-            float sg[NE];
-#pragma unroll
-            for (int k = 0; k < NE; ++k) sg[k] = STD == CT_STD_EXPLICIT ? sring[0][k] : 1.0f;
-#pragma unroll
-            for (int k = 0; k + 1 < kMiPF; ++k) {
-                ring[k] = ring[k + 1];
-                if constexpr (STD == CT_STD_EXPLICIT) {
-#pragma unroll
-                    for (int i = 0; i < NE; ++i) sring[k][i] = sring[k + 1][i];
-                }
-            }
-            ring[kMiPF - 1] = incoming;
-            if constexpr (STD == CT_STD_EXPLICIT) {
-#pragma unroll
-                for (int i = 0; i < NE; ++i) sring[kMiPF - 1][i] = sincoming[i];
-            }
-            const float it = inv_t[n];
-            const float cqn = cq[n];
-#pragma unroll
-            for (int j = 0; j < NP; ++j) {
-                float x[G], lin[G], dfds[G];
-                pixels(raw, j, x);
-#pragma unroll
-                for (int e = 0; e < G; ++e) mi_sample<INTERP>(x[e], lds + row_off[j * G + e], top, lin[e], dfds[e]);  // the G gathers issue together
-#pragma unroll
-                for (int e = 0; e < G; ++e)
-                    mi_accumulate<INTERP, WEIGHT, STD>(x[e], lin[e], dfds[e], sg[j * G + e], it, cqn, p[j * G + e], dk_mul, dk_add,
-                                                       sum[j * G + e]);
-            }
-        }
-
-        bool any_bad = false;
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            float WA[G] = {}, varA[G] = {};
-            double meanA[G] = {};
-            if (!first) {
-                mi_load(a.sumw_state + q[j], WA);
-                mi_load(a.mean_state + q[j], meanA);
-                if constexpr (kHasStd) mi_load(a.var_state + q[j], varA);
-            }
-#pragma unroll
-            for (int e = 0; e < G; ++e) {
-                const int k = j * G + e;
-                res[k] = mi_epilogue<WEIGHT, STD>(sum[k], p[k], B, first, WA[e], meanA[e], varA[e], sv2);
-                any_bad |= res[k].bad;
-            }
-        }
-        // an ill-conditioned pivot anywhere in the wavefront: repeat the batch once with those elements' pivot at the now
-        // known mean; the others recompute bit-identically, so an element's result does not depend on its neighbours
-        if (pass_no == 0 && __any(any_bad)) {
-#pragma unroll
-            for (int k = 0; k < NE; ++k) p[k] = res[k].bad ? res[k].mb : p[k];
-            continue;
-        }
-        break;
-    }
-
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        double mean[G];
-        float var[G], wt[G], sd[G];
-#pragma unroll
-        for (int e = 0; e < G; ++e) {
-            mean[e] = res[j * G + e].mean;
-            var[e] = res[j * G + e].var;
-            wt[e] = res[j * G + e].Wt;
-            sd[e] = __builtin_amdgcn_sqrtf(var[e]);
-        }
-        if (keep_state) {
-            mi_store<false>(a.mean_state + q[j], mean);
-            mi_store<false>(a.sumw_state + q[j], wt);
-            if constexpr (kHasStd) mi_store<false>(a.var_state + q[j], var);
-        }
-        if (finalize) {
-            if (a.flags & CT_MERGE_MEAN_OUT_F32) {
-                float m32[G];
-#pragma unroll
-                for (int e = 0; e < G; ++e) m32[e] = (float)mean[e];
-                mi_store<true>(static_cast<float *>(a.mean_out) + q[j], m32);
-            } else {
-                mi_store<true>(static_cast<double *>(a.mean_out) + q[j], mean);
-            }
-            if constexpr (kHasStd) mi_store<true>(a.std_out + q[j], sd);
-        }
-    }
-}
 
 template <typename T, bool PACKED, int INTERP, int WEIGHT, int STD>
 __global__ __launch_bounds__(kBlock) void merge_ingest_kernel(const MergeIngestArgs a)
@@ -336,13 +61,13 @@ __global__ __launch_bounds__(kBlock) void merge_ingest_kernel(const MergeIngestA
         n = a.plane - p0 < kG ? a.plane - p0 : kG;
     }
     if (n == kG) {
-        mi_run<T, PACKED, (int)kG, INTERP, WEIGHT, STD>(a, lds, inv_t, cq, c0, p0, dsub, ddiv);
+        mi_run<T, PACKED, (int)kG, INTERP, WEIGHT, STD, false>(a, nullptr, lds, inv_t, cq, c0, p0, dsub, ddiv);
         return;
     }
     // a plane's head and tail (at most kG - 1 elements each): one lane, one element (pixel) after the other, each with its
     // own walk over the batch -- a few serial batches of latency in two lanes per plane, nothing next to a plane's packets
 #pragma unroll 1
-    for (uint32_t k = 0; k < n; ++k) mi_run<T, PACKED, 1, INTERP, WEIGHT, STD>(a, lds, inv_t, cq, c0, p0 + k, dsub, ddiv);
+    for (uint32_t k = 0; k < n; ++k) mi_run<T, PACKED, 1, INTERP, WEIGHT, STD, false>(a, nullptr, lds, inv_t, cq, c0, p0 + k, dsub, ddiv);
 }
 
 template <typename T, bool PACKED, int INTERP, int WEIGHT, int STD>
@@ -372,29 +97,48 @@ static int mi_dispatch(const MergeIngestArgs &a, int interp, int weight_mode, in
     });
 }
 
-}  // namespace ct
+// What ct_hdr_merge_ingest_batch and ct_hdr_merge_ingest_batches have in common besides the frames: one geometry, one stage
+// list, one dtype, one set of modes, the state and the outputs.
+struct MergeIngestCall {
+    int32_t dtype;
+    const ct_geometry *geom;
+    const ct_ingest_stage *stages;
+    int32_t n_stages;
+    int32_t std_mode;
+    float std_value;
+    const double *exposure;
+    const ct_icrf *icrf;
+    int32_t weight_mode;
+    double *mean_state;
+    float *sumw_state, *var_state;
+    void *mean_out;
+    float *std_out;
+    uint32_t flags;
+    bool has_state() const { return mean_state && sumw_state && (std_mode == CT_STD_NONE || var_state); }
+    int64_t plane() const { return geom->h_tile * geom->width; }
+    int n_points() const { return icrf->interp == CT_INTERP_NONE ? 2 : icrf->n_points; }
+};
 
-extern "C" int ct_hdr_merge_ingest_batch(const void *frames_dev, int32_t dtype, int32_t batch, const ct_geometry *geom,
-                                         const ct_ingest_stage *stages, int32_t n_stages, const float *consts_dev,
-                                         const float *std_dev, int32_t std_mode, float std_value, const double *exposure_dev,
-                                         const ct_icrf *icrf, int32_t weight_mode, double *mean_state_dev, float *sumw_state_dev,
-                                         float *var_state_dev, void *mean_out_dev, float *std_out_dev, uint32_t flags, void *stream)
+// Everything that needs no pointer into device memory, in the order the status codes are documented: geometry and modes (as
+// ct_hdr_merge_batch), a stack of `batch` frames and the stage list (as ct_ingest_transform / _data), the flags these entry
+// points do not take.  FIRST_BATCH / FINALIZE in c.flags are those of the whole call.
+static int mi_validate(const MergeIngestCall &c, int32_t batch, const float *consts_dev, bool &by_channel)
 {
-    using namespace ct;
-    // everything that needs no pointer into device memory first: geometry and modes (as ct_hdr_merge_batch), the stack and
-    // the stage list (as ct_ingest_transform / _data), the flags this entry point does not take
+    const ct_geometry *geom = c.geom;
+    const ct_icrf *icrf = c.icrf;
+    const int32_t std_mode = c.std_mode, weight_mode = c.weight_mode;
+    const uint32_t flags = c.flags;
     if (!geom || !icrf) return CT_ERR_INVALID_ARGUMENT;
     if (geom->channels <= 0 || geom->h_tile < 0 || geom->width < 0 || geom->h_global < geom->h_tile || geom->row_offset < 0 ||
         geom->row_offset + geom->h_tile > geom->h_global)
         return CT_ERR_INVALID_ARGUMENT;
     if (geom->layout < CT_LAYOUT_NCHW || geom->layout > CT_LAYOUT_NHWC_BGR) return CT_ERR_INVALID_ARGUMENT;
     if (geom->h_global * geom->width * geom->channels >= (int64_t)1 << 31) return CT_ERR_TOO_LARGE;
-    const int64_t plane = geom->h_tile * geom->width;
-    bool by_channel = false;
-    int rc = ingest_validate(dtype, geom->layout, batch, geom->channels, plane, stages, n_stages, CT_INGEST_MAX_STAGES,
+    const int64_t plane = c.plane();
+    int rc = ingest_validate(c.dtype, geom->layout, batch, geom->channels, plane, c.stages, c.n_stages, CT_INGEST_MAX_STAGES,
                              consts_dev ? 1 : 0, by_channel);
     if (rc != CT_OK) return rc;
-    if (dtype == CT_DTYPE_F32) return CT_ERR_UNSUPPORTED;  // float32 pixels have no copy to save: ct_hdr_merge_batch takes them
+    if (c.dtype == CT_DTYPE_F32) return CT_ERR_UNSUPPORTED;  // float32 pixels have no copy to save: ct_hdr_merge_batch takes them
     if (reinterpret_cast<uintptr_t>(consts_dev) % sizeof(float) != 0) return CT_ERR_INVALID_ARGUMENT;
     const int interp = icrf->interp;
     if (interp < CT_INTERP_LOOKUP || interp > CT_INTERP_NONE) return CT_ERR_INVALID_ARGUMENT;
@@ -407,49 +151,143 @@ extern "C" int ct_hdr_merge_ingest_batch(const void *frames_dev, int32_t dtype, 
     // what ct_hdr_merge_batch sends to the reference-order kernel (float64-VALU bound: its bytes are not what it waits for)
     if ((interp == CT_INTERP_CATMULL || interp == CT_INTERP_LOOKUP) && std_mode != CT_STD_NONE && !(flags & CT_MERGE_CLOSED_FORM))
         return CT_ERR_UNSUPPORTED;
-    const bool has_state = mean_state_dev && sumw_state_dev && (std_mode == CT_STD_NONE || var_state_dev);
-    if (!has_state && !((flags & CT_MERGE_FIRST_BATCH) && (flags & CT_MERGE_FINALIZE))) return CT_ERR_INVALID_ARGUMENT;
-    if ((flags & CT_MERGE_FINALIZE) && (!mean_out_dev || (std_mode != CT_STD_NONE && !std_out_dev))) return CT_ERR_INVALID_ARGUMENT;
+    if (!c.has_state() && !((flags & CT_MERGE_FIRST_BATCH) && (flags & CT_MERGE_FINALIZE))) return CT_ERR_INVALID_ARGUMENT;
+    if ((flags & CT_MERGE_FINALIZE) && (!c.mean_out || (std_mode != CT_STD_NONE && !c.std_out))) return CT_ERR_INVALID_ARGUMENT;
     if (geom->image_stride < plane * geom->channels) return CT_ERR_INVALID_ARGUMENT;
-    const int n_points = interp == CT_INTERP_NONE ? 2 : icrf->n_points;
-    if ((interp == CT_INTERP_NONE ? 0 : (size_t)geom->channels * (size_t)n_points * lut_entry_bytes(interp)) +
-            2 * sizeof(float) * (size_t)batch > 160 * 1024)
-        return CT_ERR_TOO_LARGE;
-    if (batch == 0 || plane == 0) return CT_OK;
+    if (mi_lds_bytes(interp, geom->channels, c.n_points(), batch) > 160 * 1024) return CT_ERR_TOO_LARGE;
+    return CT_OK;
+}
+
+// the pointers of a call that has something to do: present and aligned to their element
+static bool mi_pointers_ok(const MergeIngestCall &c, const void *frames_dev, const float *std_dev)
+{
     auto aligned = [](const void *p, uintptr_t b) { return reinterpret_cast<uintptr_t>(p) % b == 0; };
-    if (!frames_dev || !exposure_dev || (std_mode == CT_STD_EXPLICIT && !std_dev)) return CT_ERR_INVALID_ARGUMENT;
-    if (!aligned(frames_dev, dtype == CT_DTYPE_U16 ? 2 : 1) || !aligned(exposure_dev, sizeof(double)) || !aligned(std_dev, sizeof(float)) ||
-        !aligned(mean_state_dev, sizeof(double)) || !aligned(sumw_state_dev, sizeof(float)) || !aligned(var_state_dev, sizeof(float)) ||
-        !aligned(mean_out_dev, (flags & CT_MERGE_MEAN_OUT_F32) ? sizeof(float) : sizeof(double)) || !aligned(std_out_dev, sizeof(float)))
-        return CT_ERR_INVALID_ARGUMENT;
+    if (!frames_dev || !c.exposure || (c.std_mode == CT_STD_EXPLICIT && !std_dev)) return false;
+    return aligned(frames_dev, c.dtype == CT_DTYPE_U16 ? 2 : 1) && aligned(c.exposure, sizeof(double)) && aligned(std_dev, sizeof(float)) &&
+           aligned(c.mean_state, sizeof(double)) && aligned(c.sumw_state, sizeof(float)) && aligned(c.var_state, sizeof(float)) &&
+           aligned(c.mean_out, (c.flags & CT_MERGE_MEAN_OUT_F32) ? sizeof(float) : sizeof(double)) && aligned(c.std_out, sizeof(float));
+}
+
+// the kernels' argument block for `batch` exposures (MULTI: of all batches) whose times are at `exposure`
+static MergeIngestArgs mi_fill_args(const MergeIngestCall &c, const void *frames_dev, const float *std_dev, const float *consts_dev,
+                                    const double *exposure, int32_t batch, uint32_t flags, bool by_channel)
+{
+    const ct_geometry *geom = c.geom;
+    const bool has_state = c.has_state();
     MergeIngestArgs a = {};
     a.frames = frames_dev;
-    a.std_stack = std_mode == CT_STD_EXPLICIT ? std_dev : nullptr;
+    a.std_stack = c.std_mode == CT_STD_EXPLICIT ? std_dev : nullptr;
     a.consts = consts_dev;
-    a.exposure = exposure_dev;
-    a.lut = icrf->lut_dev;
-    a.mean_state = has_state ? mean_state_dev : nullptr;
-    a.sumw_state = has_state ? sumw_state_dev : nullptr;
-    a.var_state = has_state ? var_state_dev : nullptr;
-    a.mean_out = mean_out_dev;
-    a.std_out = std_out_dev;
+    a.exposure = exposure;
+    a.lut = c.icrf->lut_dev;
+    a.mean_state = has_state ? c.mean_state : nullptr;
+    a.sumw_state = has_state ? c.sumw_state : nullptr;
+    a.var_state = has_state ? c.var_state : nullptr;
+    a.mean_out = c.mean_out;
+    a.std_out = c.std_out;
     a.image_stride = geom->image_stride;
-    a.plane = (uint32_t)plane;
+    a.plane = (uint32_t)c.plane();
     a.plane_global = (uint32_t)(geom->h_global * geom->width);
     a.base = (uint32_t)(geom->row_offset * geom->width);
     a.batch = batch;
     a.channels = geom->channels;
-    a.n_points = n_points;
+    a.n_points = c.n_points();
     a.reversed = geom->layout == CT_LAYOUT_NHWC_BGR ? 1u : 0u;
     a.by_channel = by_channel ? 1u : 0u;
-    a.std_value = std_value;
+    a.std_value = c.std_value;
     a.weight_scale = 30.0f;  // gaussian_value_weights default scale, hdr_merge.py:95
     a.flags = flags;
-    a.n_stages = (uint32_t)n_stages;
-    for (int32_t k = 0; k < n_stages; ++k) a.stage[k] = stages[k];
+    a.n_stages = (uint32_t)c.n_stages;
+    for (int32_t k = 0; k < c.n_stages; ++k) a.stage[k] = c.stages[k];
+    return a;
+}
+
+}  // namespace ct
+
+extern "C" int ct_hdr_merge_ingest_batch(const void *frames_dev, int32_t dtype, int32_t batch, const ct_geometry *geom,
+                                         const ct_ingest_stage *stages, int32_t n_stages, const float *consts_dev,
+                                         const float *std_dev, int32_t std_mode, float std_value, const double *exposure_dev,
+                                         const ct_icrf *icrf, int32_t weight_mode, double *mean_state_dev, float *sumw_state_dev,
+                                         float *var_state_dev, void *mean_out_dev, float *std_out_dev, uint32_t flags, void *stream)
+{
+    using namespace ct;
+    const MergeIngestCall c{dtype, geom, stages, n_stages, std_mode, std_value, exposure_dev, icrf, weight_mode, mean_state_dev,
+                            sumw_state_dev, var_state_dev, mean_out_dev, std_out_dev, flags};
+    bool by_channel = false;
+    if (const int rc = mi_validate(c, batch, consts_dev, by_channel); rc != CT_OK) return rc;
+    if (batch == 0 || c.plane() == 0) return CT_OK;
+    if (!mi_pointers_ok(c, frames_dev, std_dev)) return CT_ERR_INVALID_ARGUMENT;
+    const MergeIngestArgs a = mi_fill_args(c, frames_dev, std_dev, consts_dev, exposure_dev, batch, flags, by_channel);
+    const int interp = icrf->interp;
     const bool packed = geom->layout != CT_LAYOUT_NCHW;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (dtype == CT_DTYPE_U8)
         return packed ? mi_dispatch<uint8_t, true>(a, interp, weight_mode, std_mode, s) : mi_dispatch<uint8_t, false>(a, interp, weight_mode, std_mode, s);
     return packed ? mi_dispatch<uint16_t, true>(a, interp, weight_mode, std_mode, s) : mi_dispatch<uint16_t, false>(a, interp, weight_mode, std_mode, s);
+}
+
+// Several consecutive batches of one merge behind one chain: ONE launch of the MULTI kernels (ct_merge_ingest_multi.hip) where
+// the batches agree on having constants and their exposures fit the LDS together; otherwise one launch per batch with the
+// state in memory, exactly what the caller would have done.
+extern "C" int ct_hdr_merge_ingest_batches(const void *const *frames_devs, const int32_t *batch_sizes, int32_t n_batches, int32_t dtype,
+                                           const ct_geometry *geom, const ct_ingest_stage *stages, int32_t n_stages,
+                                           const float *const *consts_devs, const float *const *std_devs, int32_t std_mode,
+                                           float std_value, const double *exposure_dev, const ct_icrf *icrf, int32_t weight_mode,
+                                           double *mean_state_dev, float *sumw_state_dev, float *var_state_dev, void *mean_out_dev,
+                                           float *std_out_dev, uint32_t flags, void *stream)
+{
+    using namespace ct;
+    if (n_batches < 1 || n_batches > kMaxIngestBatches || !frames_devs || !batch_sizes) return CT_ERR_INVALID_ARGUMENT;
+    const uint32_t single_flags = flags & ~CT_MERGE_REQUIRE_ONE_LAUNCH;
+    if (n_batches == 1)
+        return ct_hdr_merge_ingest_batch(frames_devs[0], dtype, batch_sizes[0], geom, stages, n_stages, consts_devs ? consts_devs[0] : nullptr,
+                                         std_devs ? std_devs[0] : nullptr, std_mode, std_value, exposure_dev, icrf, weight_mode,
+                                         mean_state_dev, sumw_state_dev, var_state_dev, mean_out_dev, std_out_dev, single_flags, stream);
+    const MergeIngestCall c{dtype, geom, stages, n_stages, std_mode, std_value, exposure_dev, icrf, weight_mode, mean_state_dev,
+                            sumw_state_dev, var_state_dev, mean_out_dev, std_out_dev, single_flags};
+    // every batch as the single-batch entry point would judge it (FIRST_BATCH / FINALIZE: of the whole call, so that a state
+    // is needed unless the call is a whole merge); nothing has touched the device when one of them is refused
+    bool by_channel = false;
+    for (int b = 0; b < n_batches; ++b)
+        if (const int rc = mi_validate(c, batch_sizes[b], consts_devs ? consts_devs[b] : nullptr, by_channel); rc != CT_OK) return rc;
+    // the batches that have something to do (an empty one is skipped: FIRST_BATCH is the first and FINALIZE the last of these)
+    MergeIngestBatches mb = {};
+    int64_t offset[kMaxIngestBatches] = {}, total = 0;
+    int n = 0, n_consts = 0;
+    for (int b = 0; b < n_batches; ++b) {
+        if (batch_sizes[b] > 0) {
+            mb.frames[n] = frames_devs[b];
+            mb.std_stack[n] = (std_mode == CT_STD_EXPLICIT && std_devs) ? std_devs[b] : nullptr;
+            mb.consts[n] = consts_devs ? consts_devs[b] : nullptr;
+            mb.batch[n] = batch_sizes[b];
+            offset[n] = total;
+            n_consts += mb.consts[n] ? 1 : 0;
+            ++n;
+        }
+        total += batch_sizes[b];
+    }
+    mb.n_batches = n;
+    if (n == 0 || c.plane() == 0) return CT_OK;
+    for (int b = 0; b < n; ++b)
+        if (!mi_pointers_ok(c, mb.frames[b], mb.std_stack[b])) return CT_ERR_INVALID_ARGUMENT;
+    const int interp = icrf->interp;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool one_launch = n >= 2 && (n_consts == 0 || n_consts == n) &&
+                            mi_lds_bytes(interp, geom->channels, c.n_points(), total) <= 160 * 1024;
+    if (one_launch) {
+        const MergeIngestArgs a = mi_fill_args(c, nullptr, nullptr, nullptr, exposure_dev, (int32_t)total, single_flags, by_channel);
+        return merge_ingest_multi(a, mb, dtype, geom->layout != CT_LAYOUT_NCHW, interp, weight_mode, std_mode, s);
+    }
+    if (n > 1 && (flags & CT_MERGE_REQUIRE_ONE_LAUNCH)) return CT_ERR_UNSUPPORTED;  // (tests: make the route explicit)
+    if (n > 1 && !c.has_state()) return CT_ERR_INVALID_ARGUMENT;
+    const bool first = flags & CT_MERGE_FIRST_BATCH, finalize = flags & CT_MERGE_FINALIZE;
+    for (int b = 0; b < n; ++b) {
+        const uint32_t f = (single_flags & ~(CT_MERGE_FIRST_BATCH | CT_MERGE_FINALIZE)) | ((first && b == 0) ? CT_MERGE_FIRST_BATCH : 0u) |
+                           ((finalize && b == n - 1) ? CT_MERGE_FINALIZE : 0u);
+        const int rc = ct_hdr_merge_ingest_batch(mb.frames[b], dtype, mb.batch[b], geom, stages, n_stages, mb.consts[b], mb.std_stack[b],
+                                                 std_mode, std_value, exposure_dev + offset[b], icrf, weight_mode, mean_state_dev,
+                                                 sumw_state_dev, var_state_dev, mean_out_dev, std_out_dev, f, stream);
+        if (rc != CT_OK) return rc;
+    }
+    return CT_OK;
 }

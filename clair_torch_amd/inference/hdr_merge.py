@@ -43,7 +43,7 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
     reference, up to 4e-5 away from it on single pixels in those two modes); True = reference order in every mode.
     ``fused_ingest`` (extension): a ``gpu_transforms`` list on route "ingest" / "ingest_data" (common/transforms.py: a black
     level, a clamp, a target range, a data-dependent Normalize on raw codes) is evaluated inside the merge kernel
-    (ct_hdr_merge_ingest_batch: one launch per batch, no float32 copy of the batch) when there is no dark-field dataset and
+    (ct_hdr_merge_ingest_batches: up to 16 batches per launch, no float32 copy of a batch) when there is no dark-field dataset and
     the mode is a closed-form one; False = ct_ingest_transform, then the float32 merge.  The results are the same bit for bit.
     """
     if output_layout not in ("planar", "input", "cv"):
@@ -82,14 +82,19 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
         if not queue:
             return
         k0 = queue[0]
-        if isinstance(k0["images"], DeferredIngest):  # (always alone in the queue) the chain and the merge in one launch
+        if isinstance(k0["images"], DeferredIngest):
+            # the chain and the merge of every queued batch in one launch (ct_hdr_merge_ingest_batches): the raw frames are
+            # read once and the streaming state stays in registers between the batches, as on the code route
             d = k0["images"]
             if state is None and (not final or flat_field_dataset is not None):
                 state = ops.MergeState(ops.ingest_shape(tuple(d.frames.shape), d.layout)[1:], dev, with_variance=k0["std_mode"] != "none")
-            result = ops.hdr_merge_ingest_batch(d.frames, d.stages, k0["exposure"], lut=lut, interp=interp,
-                                                gaussian_weight=weight_fn is not None, std=k0["std"], std_mode=k0["std_mode"],
-                                                std_value=k0["std_value"], state=state, finalize=final and flat_field_dataset is None,
-                                                tile=tile, layout=d.layout, reference_order=reference_order, consts=d.consts)
+            stds = None if k0["std"] is None else [q["std"] for q in queue]
+            consts = None if d.consts is None else [q["images"].consts for q in queue]
+            result = ops.hdr_merge_ingest_batches([q["images"].frames for q in queue], d.stages, [q["exposure"] for q in queue],
+                                                  lut=lut, interp=interp, gaussian_weight=weight_fn is not None, stds=stds,
+                                                  std_mode=k0["std_mode"], std_value=k0["std_value"], state=state,
+                                                  finalize=final and flat_field_dataset is None, tile=tile, layout=d.layout,
+                                                  reference_order=reference_order, consts=consts)
             queue = []
             return
         out_layout = "input" if (output_layout == "input" and k0["layout"] != "nchw") else "planar"
@@ -122,13 +127,17 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
             xb, sig = dark.apply(index_batch, images, max_code, std, std_mode, std_value, tile, group)
             if xb is not None:  # the blurred batch replaces the images; its uncertainty carries both variance terms
                 images, max_code, std, std_mode, std_value = xb, None, sig, "explicit", 0.0
-        key = None if fused else (images.dtype, tuple(images.shape[1:]), max_code, layout, std_mode, std_value, std is None)
-        if queue and (fused or key != queue_key or len(queue) == ops.MAX_MERGE_BATCHES):
+        if fused:  # one dtype, shape, layout and chain per call; every batch with constants of its own, or none
+            key = ("ingest", images.frames.dtype, tuple(images.frames.shape[1:]), images.layout, images.stages, std_mode, std_value,
+                   std is None, images.consts is None)
+        else:
+            key = (images.dtype, tuple(images.shape[1:]), max_code, layout, std_mode, std_value, std is None)
+        if queue and (key != queue_key or len(queue) == ops.MAX_MERGE_BATCHES):
             flush(False)
         queue_key = key
         queue.append(dict(images=images, exposure=meta_batch["exposure_time"], std=std, std_mode=std_mode, std_value=std_value,
                           max_code=max_code, layout=layout))
-        if last or fused:  # a fused batch is one launch of its own, as a float32 batch is
+        if last:
             flush(last)
     if flat_field_dataset is not None:
         mean, std = _flat_field_epilogue(state, flat_field_dataset, dataloader.dataset, dev, tile, group)

@@ -934,6 +934,100 @@ def hdr_merge_ingest_batch(frames: torch.Tensor, stages, exposures: torch.Tensor
     return (mean_out, std_out) if finalize else None
 
 
+def hdr_merge_ingest_batches(frames_list, stages, exposures_list, *, lut: Optional[torch.Tensor] = None,
+                             interp: Optional[str] = "linear", gaussian_weight: bool = True, stds=None, std_mode: str = "none",
+                             std_value: float = 0.0, state: Optional[MergeState] = None, finalize: bool = True,
+                             tile: Optional[TileGeometry] = None, mean_dtype: torch.dtype = torch.float64, layout: str = "nchw",
+                             reference_order: Optional[bool] = None, consts=None, require_one_launch: bool = False):
+    """Several CONSECUTIVE batches of one merge behind one chain in one call (ct_hdr_merge_ingest_batches): the same result,
+    bit for bit, as ``hdr_merge_ingest_batch`` on each of them in turn with ``state`` carried along -- but one launch walks
+    them all with the streaming state in registers in between (no state traffic between the batches).
+
+    ``frames_list``: list of (B_k,C,H,W) / (B_k,H,W,3) uint8 / uint16 device stacks of one dtype, image shape and device,
+    each as ``hdr_merge_ingest_batch`` takes it; ``exposures_list``: list of (B_k) tensors; ``stds``: list of explicit
+    planar std tensors or None; ``consts``: list of the tensors ``ingest_extrema`` returned for each batch (then one stage may
+    be ("affine_data", mul, add)), or None; a list may hold None for a batch without constants.  At most MAX_MERGE_BATCHES.
+    ``require_one_launch`` (tests): raise instead of falling back to one launch per batch (batches with and without
+    constants mixed; more exposure times than the LDS holds).  Everything else as in ``hdr_merge_ingest_batch``.
+    Returns (mean, std|None), planar (C,H,W), when ``finalize`` else None."""
+    k = len(frames_list)
+    if k == 0 or k != len(exposures_list) or (stds is not None and len(stds) != k) or (consts is not None and len(consts) != k):
+        raise ValueError("frames / exposures / stds / consts must be non-empty lists of equal length")
+    if k > MAX_MERGE_BATCHES:
+        raise ValueError(f"at most {MAX_MERGE_BATCHES} batches per call")
+    if k == 1:
+        return hdr_merge_ingest_batch(frames_list[0], stages, exposures_list[0], lut=lut, interp=interp,
+                                      gaussian_weight=gaussian_weight, std=None if stds is None else stds[0], std_mode=std_mode,
+                                      std_value=std_value, state=state, finalize=finalize, tile=tile, mean_dtype=mean_dtype,
+                                      layout=layout, reference_order=reference_order, consts=None if consts is None else consts[0])
+    f0 = frames_list[0]
+    for t in frames_list:
+        _check_ingest_stack(t, layout)
+        if t.dtype == torch.float32:
+            raise TypeError("hdr_merge_ingest_batches takes uint8 / uint16 codes (float32 pixels: ingest_transform + hdr_merge_batches)")
+        if t.dtype != f0.dtype or t.shape[1:] != f0.shape[1:] or t.device != f0.device:
+            raise ValueError("all batches of one call must share dtype, image shape and device")
+        if t.shape[0] < 1:
+            raise ValueError("empty batch")
+    dev = f0.device
+    _, c, h, w = ingest_shape(tuple(f0.shape), layout)
+    has_consts = consts is not None and any(t is not None for t in consts)
+    arr, n_stages = _ingest_stages(stages, c, data=has_consts)
+    if consts is not None:
+        for t in consts:
+            if t is not None:
+                _check_consts(t, dev)
+    if stds is not None:
+        std_mode = "explicit"
+        for sd, t in zip(stds, frames_list):
+            _require_device(sd, "std")
+            shape = ingest_shape(tuple(t.shape), layout)
+            if sd.dtype != torch.float32 or tuple(sd.shape) != shape or sd.device != dev:
+                raise ValueError(f"std must be a float32 tensor of shape {shape} (planar, like the state) on {dev}")
+        stds = [sd.contiguous() for sd in stds]
+    if std_mode not in _STD:
+        raise ValueError(f"unknown std_mode {std_mode}")
+    sizes = [int(t.shape[0]) for t in frames_list]
+    for e, n in zip(exposures_list, sizes):
+        if e.numel() != n:
+            raise ValueError(f"{e.numel()} exposure times for a batch of {n}")
+    # staged through pinned memory the copy does not wait for the stream (see hdr_merge_batch)
+    host_exp = torch.cat([e.detach().to("cpu", torch.float64).reshape(-1) for e in exposures_list])
+    exposure_dev = host_exp.pin_memory().to(dev, non_blocking=True)
+    icrf, lut_keep = _icrf_struct(lut, interp, c)
+    hg, r0 = (h, 0) if tile is None else (tile.h_global, tile.row_offset)
+    if r0 < 0 or r0 + h > hg:
+        raise ValueError(f"tile rows [{r0}, {r0 + h}) do not fit a global height of {hg}")
+    geom = nv.Geometry(channels=c, h_tile=h, width=w, h_global=hg, row_offset=r0, image_stride=c * h * w, layout=_LAYOUT[layout])
+    has_std = std_mode != "none"
+    flags, out_shape, mean_out, std_out = _merge_setup_for((c, h, w), dev, "planar", state, finalize, has_std, mean_dtype, reference_order,
+                                                           nv.MERGE_REQUIRE_ONE_LAUNCH if require_one_launch else 0, "call")
+    ptr_arr = (ctypes.c_void_p * k)(*[t.data_ptr() for t in frames_list])
+    size_arr = (ctypes.c_int32 * k)(*sizes)
+    std_arr = (ctypes.c_void_p * k)(*[sd.data_ptr() for sd in stds]) if stds is not None else None
+    consts_arr = (ctypes.c_void_p * k)(*[None if t is None else t.data_ptr() for t in consts]) if consts is not None else None
+
+    def call(st, fl):
+        with torch.cuda.device(dev):
+            return nv.load().ct_hdr_merge_ingest_batches(
+                ptr_arr, size_arr, k, _DTYPE[f0.dtype], ctypes.byref(geom), arr, n_stages, consts_arr, std_arr, _STD[std_mode],
+                float(std_value), _ptr(exposure_dev), ctypes.byref(icrf), nv.WEIGHT_GAUSS if gaussian_weight else nv.WEIGHT_NONE,
+                _ptr(st.mean) if st else None, _ptr(st.sumw) if st else None,
+                _ptr(st.var) if (st and st.var is not None) else None, _ptr(mean_out), _ptr(std_out), fl, _stream(dev))
+
+    # a whole merge in one launch needs no state arrays at all; only what cannot run as one launch walks the batches with
+    # the state in memory (nothing has been launched when the library says so)
+    rc = call(state, flags | (nv.MERGE_REQUIRE_ONE_LAUNCH if state is None else 0))
+    if rc == nv.ERR_UNSUPPORTED and state is None and not require_one_launch:
+        state = MergeState(out_shape, dev, has_std)
+        rc = call(state, flags)
+    nv.check(rc, "ct_hdr_merge_ingest_batches")
+    del lut_keep
+    if state is not None:
+        state.batches += k
+    return (mean_out, std_out) if finalize else None
+
+
 # ---- a data-dependent Normalize (max_val / min_val None) in such a chain ------------------------------------------------
 ZERO_RANGE = "Normalization range is zero (min == max); cannot normalize."  # general_functions.py:378
 

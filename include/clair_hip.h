@@ -68,7 +68,7 @@ extern "C" {
                                         float64 exp / divisions; ct_merge_exact.hip).  Default for LOOKUP and CATMULL with
                                         uncertainties, whose reference results are dominated by float32 cancellation */
 #define CT_MERGE_CLOSED_FORM 32u     /* keep the fast closed-form kernels for LOOKUP / CATMULL with uncertainties as well */
-#define CT_MERGE_REQUIRE_ONE_LAUNCH 128u /* ct_hdr_merge_batches: CT_ERR_UNSUPPORTED instead of one launch per batch */
+#define CT_MERGE_REQUIRE_ONE_LAUNCH 128u /* ct_hdr_merge_batches, ct_hdr_merge_ingest_batches: CT_ERR_UNSUPPORTED instead of one launch per batch */
 #define CT_MERGE_STD_HINT 64u        /* ct_hdr_merge_kernel_name only: uncertainties are propagated */
 #define CT_MERGE_OUT_AS_INPUT 256u   /* extension: state and outputs in the MEMORY ORDER OF THE INPUT stack instead of planar
                                         (C, H, W): an interleaved (H, W, C) RGB / BGR stack then gives (H, W, C) outputs in the
@@ -464,6 +464,37 @@ int ct_hdr_merge_ingest_batch(const void *frames_dev, int32_t dtype, int32_t bat
                               int32_t std_mode, float std_value, const double *exposure_dev, const ct_icrf *icrf,
                               int32_t weight_mode, double *mean_state_dev, float *sumw_state_dev, float *var_state_dev,
                               void *mean_out_dev, float *std_out_dev, uint32_t flags, void *stream);
+
+/*
+ * ct_hdr_merge_ingest_batches -- n_batches consecutive batches of one merge behind one chain in one call: exactly
+ * ct_hdr_merge_ingest_batch applied to batch 0 .. n_batches - 1 in turn with the state carried along, bit for bit -- but where
+ * it can, ONE launch walks all of them with (mean, sum of weights, variance) in registers in between: the state arrays are
+ * read at most once (not at all with CT_MERGE_FIRST_BATCH) and written at most once, where a launch per batch reads 16 B and
+ * writes 16 B per element and batch beside B * sizeof(code) bytes of samples.
+ *   frames_devs, batch_sizes   HOST arrays of n_batches (1 .. 16) device pointers / batch sizes: batch b is batch_sizes[b]
+ *                frames at frames_devs[b], each as ct_hdr_merge_ingest_batch takes it; one dtype, one geometry (image_stride
+ *                included), one stage list for all of them.  A batch of size 0 is skipped.
+ *   consts_devs  HOST array of n_batches device pointers, each the 4 floats ct_ingest_extrema left for that batch (read when
+ *                the kernel runs), or NULL as a whole without a CT_INGEST_AFFINE_DATA stage
+ *   std_devs     CT_STD_EXPLICIT: HOST array of n_batches device pointers, each planar (B_b, C, H_tile, W) float32; else
+ *                NULL as a whole
+ *   exposure_dev the exposure times of all batches, concatenated (sum of batch_sizes doubles)
+ *   flags        as ct_hdr_merge_ingest_batch; CT_MERGE_FIRST_BATCH applies to the first and CT_MERGE_FINALIZE to the last
+ *                batch that is not empty.  With more than one batch a state is required unless both are set.
+ *                CT_MERGE_REQUIRE_ONE_LAUNCH: CT_ERR_UNSUPPORTED instead of one launch per batch.
+ * n_batches outside 1 .. 16 is CT_ERR_INVALID_ARGUMENT; n_batches == 1 is ct_hdr_merge_ingest_batch.  Every batch is judged
+ * as ct_hdr_merge_ingest_batch judges it (the same status codes, the first refusal wins) before anything touches the device.
+ * One launch needs every batch, or none, to have constants, and the LUT with 8 B per exposure of ALL batches to fit 160 KiB
+ * of LDS; otherwise the batches are launched one by one with the state in memory, which then must be given
+ * (CT_ERR_INVALID_ARGUMENT without).  Allocates nothing, synchronises nothing, reads nothing back, never writes the frames,
+ * touches nothing outside C*H_tile*W elements of the state and the outputs.
+ */
+int ct_hdr_merge_ingest_batches(const void *const *frames_devs, const int32_t *batch_sizes, int32_t n_batches, int32_t dtype,
+                                const ct_geometry *geom, const ct_ingest_stage *stages, int32_t n_stages,
+                                const float *const *consts_devs, const float *const *std_devs, int32_t std_mode, float std_value,
+                                const double *exposure_dev, const ct_icrf *icrf, int32_t weight_mode, double *mean_state_dev,
+                                float *sumw_state_dev, float *var_state_dev, void *mean_out_dev, float *std_out_dev,
+                                uint32_t flags, void *stream);
 
 /*
  * ct_video_stats_ingest_batch -- such a chain and one batch of compute_video_mean_and_std's loop body in ONE pass over B raw
