@@ -74,6 +74,10 @@ def load():
         raise NativeLibraryError(
             f"{path} is missing: build it with `python -m clair_torch_amd.build` (hipcc, gfx950). "
             "clair_torch_amd has no CPU fallback for its kernels.")
+    # torch first: its wheel carries a HIP runtime of its own under a file name that is not the soname this library asks
+    # for.  Loaded after torch, the library binds to that runtime; loaded before it, the system's runtime comes in as a
+    # second one beside torch's, and the first launch on one of torch's streams fails (CT_ERR_LAUNCH).
+    import torch  # noqa: F401
     lib = ctypes.CDLL(path)
     vp, i32, i64, f32, u32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_uint32
     gp, ip = ctypes.POINTER(Geometry), ctypes.POINTER(Icrf)

@@ -19,6 +19,12 @@ extern "C" const char *ct_error_string(int code)
     return "unknown error";
 }
 
+// max_code is a whole number an 8- / 16-bit container can hold (NaN fails), and a LUT of n_points has an interval
+static bool code_range_ok(float max_code, int n_points = 2)
+{
+    return max_code >= 1.0f && max_code <= 65535.0f && floorf(max_code) == max_code && n_points >= 2;
+}
+
 // The reference normalises integer codes with one float32 division u / max_code
 // (clair_torch/common/general_functions.py:377).  The kernels use fma(u, hi, u * lo) with hi + lo ~ 1/max_code;
 // this routine derives the pair and proves on the host, over every code 0..max_code, that the two agree bit
@@ -28,7 +34,7 @@ extern "C" int ct_norm_constants(float max_code, float *hi, float *lo)
     static std::mutex mu;
     static float cached_max = 0.0f, cached_hi = 0.0f, cached_lo = 0.0f;
     static int cached_rc = CT_ERR_UNSUPPORTED;
-    if (!(max_code >= 1.0f) || max_code > 65535.0f || floorf(max_code) != max_code) return CT_ERR_UNSUPPORTED;
+    if (!code_range_ok(max_code)) return CT_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lock(mu);
     if (cached_max != max_code) {
         const double rd = 1.0 / (double)max_code;
@@ -65,8 +71,7 @@ extern "C" int ct_index_constants(float max_code, int n_points, float *hi, float
     static std::mutex mu;
     static float cached_max = 0.0f, cached_hi = 0.0f, cached_lo = 0.0f;
     static int cached_L = 0, cached_rc = CT_ERR_UNSUPPORTED;
-    if (!(max_code >= 1.0f) || max_code > 65535.0f || floorf(max_code) != max_code || n_points < 2)
-        return CT_ERR_UNSUPPORTED;
+    if (!code_range_ok(max_code, n_points)) return CT_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lock(mu);
     if (cached_max != max_code || cached_L != n_points) {
         const float top = (float)(n_points - 1);
@@ -106,8 +111,7 @@ extern "C" int ct_pivot_index_constants(float max_code, int n_points, uint32_t *
     static float cached_max = 0.0f, cached_step = 0.0f;
     static uint32_t cached_mul = 0;
     static int cached_L = 0, cached_rc = CT_ERR_UNSUPPORTED;
-    if (!(max_code >= 1.0f) || max_code > 65535.0f || floorf(max_code) != max_code || n_points < 2)
-        return CT_ERR_UNSUPPORTED;
+    if (!code_range_ok(max_code, n_points)) return CT_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lock(mu);
     if (cached_max != max_code || cached_L != n_points) {
         const int maxc = (int)max_code, top = n_points - 1;
@@ -153,8 +157,7 @@ extern "C" int ct_pivot_floor_constants(float max_code, int n_points, float *rcp
     static std::mutex mu;
     static float cached_max = 0.0f, cached_rcp = 0.0f;
     static int cached_L = 0, cached_rc = CT_ERR_UNSUPPORTED;
-    if (!(max_code >= 1.0f) || max_code > 65535.0f || floorf(max_code) != max_code || n_points < 2)
-        return CT_ERR_UNSUPPORTED;
+    if (!code_range_ok(max_code, n_points)) return CT_ERR_UNSUPPORTED;
     if (n_points - 1 > (int)max_code || (int)max_code % (n_points - 1) != 0) return CT_ERR_UNSUPPORTED;  // whole steps only
     const float step = (float)((int)max_code / (n_points - 1));
     std::lock_guard<std::mutex> lock(mu);
@@ -196,9 +199,7 @@ extern "C" int ct_pivot_interval_constants(float max_code, int n_points, int loo
     static std::mutex mu;
     static Entry cache[8];
     static int used = 0, next = 0;
-    if (!(max_code >= 1.0f) || max_code > 65535.0f || floorf(max_code) != max_code || n_points < 2 || dtype_max < (int)max_code ||
-        dtype_max > 65535)
-        return CT_ERR_UNSUPPORTED;
+    if (!code_range_ok(max_code, n_points) || dtype_max < (int)max_code || dtype_max > 65535) return CT_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lock(mu);
     for (int k = 0; k < used; ++k)
         if (cache[k].max_code == max_code && cache[k].n_points == n_points && cache[k].lookup == lookup && cache[k].dtype_max == dtype_max) {

@@ -27,7 +27,7 @@
 // reflect padding applies instead and that halo row is ignored.  Roofline: HBM (a few planes per frame, each read once
 // from HBM and re-read from L2 by the neighbouring rows' threads); written for clarity, one element per thread.
 #include <algorithm>
-#include "ct_device.hpp"
+#include "ct_args.hpp"
 
 namespace ct {
 
@@ -113,24 +113,22 @@ extern "C" int ct_dark_field_blur(const void *stack_dev, int32_t dtype, float ma
 {
     using namespace ct;
     if (!stack_dev || !geom || !dark_dev || !xb_out_dev || batch <= 0) return CT_ERR_INVALID_ARGUMENT;
-    if (geom->channels <= 0 || geom->h_tile <= 0 || geom->width < 2 || geom->h_global < 2 || geom->h_global < geom->h_tile ||
-        geom->row_offset < 0 || geom->row_offset + geom->h_tile > geom->h_global)
-        return CT_ERR_INVALID_ARGUMENT;
+    // (the 3 x 3 blur reflects at the borders: two columns and two global rows at least)
+    if (!shape_positive(geom) || geom->width < 2 || geom->h_global < 2 || !band_fits(geom)) return CT_ERR_INVALID_ARGUMENT;
     if (geom->layout != CT_LAYOUT_NCHW) return CT_ERR_UNSUPPORTED;
     if (dark_batch != 1 && dark_batch != batch) return CT_ERR_INVALID_ARGUMENT;
     // One SHARED dark field for several frames with its uncertainty propagated: the reference's autograd on a (1, C, H, W)
     // mask_map sums the gradient over the frames BEFORE squaring, (sum_n g_n)^2 sigma_D^2, which a per-frame effective
     // sigma cannot express (it would give sum_n (g_n sigma_D)^2).  Not built; refuse rather than return the other quantity.
     if (dark_batch == 1 && batch > 1 && dark_std_dev && std_out_dev) return CT_ERR_UNSUPPORTED;
-    if (std_mode < CT_STD_NONE || std_mode > CT_STD_EXPLICIT) return CT_ERR_INVALID_ARGUMENT;
-    if (std_mode == CT_STD_EXPLICIT && !std_dev) return CT_ERR_INVALID_ARGUMENT;
+    if (!std_mode_ok(std_mode, std_dev)) return CT_ERR_INVALID_ARGUMENT;
     if (std_out_dev && !dark_std_dev) return CT_ERR_INVALID_ARGUMENT;
     // a band that does not touch the global top / bottom needs its neighbours' rows; so does a one-row band's reflection
     const bool top = geom->row_offset == 0, bottom = geom->row_offset + geom->h_tile == geom->h_global;
     if ((!top || !bottom) && !halo_dev) return CT_ERR_INVALID_ARGUMENT;
     if ((top || bottom) && geom->h_tile < 2 && !(top && bottom)) return CT_ERR_UNSUPPORTED;
     const int64_t plane = geom->h_tile * geom->width;
-    if (geom->image_stride < plane * geom->channels) return CT_ERR_INVALID_ARGUMENT;
+    if (!stride_holds_image(geom)) return CT_ERR_INVALID_ARGUMENT;
     DarkArgs a{};
     a.stack = stack_dev;
     a.halo = halo_dev;

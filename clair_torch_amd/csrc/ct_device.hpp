@@ -387,17 +387,7 @@ static inline int compute_units()
     return n_cu;
 }
 
-// Workgroups that can be resident on the whole device at once, for kernels that walk their work in a grid-stride
-// loop: a grid that is a multiple of this runs as full rounds of equal work.  (1026 long-running workgroups on 256
-// one-slot units run 4 full rounds plus 2 stragglers that cost a whole fifth round.)
-static inline int resident_workgroups(size_t lds_bytes, int block_threads)
-{
-    const size_t by_lds = lds_bytes ? (size_t)(160 * 1024) / lds_bytes : 64;
-    const size_t by_waves = (size_t)2048 / (size_t)block_threads;  // 32 wavefronts per unit
-    size_t slots = by_lds < by_waves ? by_lds : by_waves;
-    if (slots < 1) slots = 1;
-    return compute_units() * (int)slots;
-}
+// (resident_workgroups, which needs the LDS budget, is in ct_args.hpp)
 
 // ---- host: dispatch ------------------------------------------------------------------------------------------------
 // Lifts a run-time value to a compile-time one: f(std::integral_constant<int, v>{}) for the v among VALUES that equals

@@ -11,7 +11,7 @@
 // ranks all-reduce them), then an elementwise apply.  Both are HBM-bound on a few image planes -- negligible beside
 // the stack pass -- so they are written for clarity, with 16-byte accesses where alignment allows.
 #include <algorithm>
-#include "ct_device.hpp"
+#include "ct_args.hpp"
 
 namespace ct {
 

@@ -4,7 +4,7 @@
 #pragma once
 #include <string.h>
 
-#include "ct_device.hpp"
+#include "ct_args.hpp"
 
 namespace ct {
 
@@ -64,6 +64,22 @@ static inline int ingest_validate(int32_t dtype, int32_t layout, int64_t n_image
     if (layout != CT_LAYOUT_NCHW && channels != 3) return CT_ERR_UNSUPPORTED;
     if (by_channel && channels > CT_INGEST_MAX_CHANNELS) return CT_ERR_UNSUPPORTED;
     return CT_OK;
+}
+
+// What ct_video_stats_ingest_batch and ct_hdr_merge_ingest_batch check first, in this order: the geometry (an empty plane is
+// a call with nothing to do), a stack of `n_images` frames and the stage list, 8-bit / 16-bit codes (float32 pixels have no
+// copy to save: ct_video_stats_batch / ct_hdr_merge_batch take them), the constants' alignment, the model.
+static inline int check_code_ingest(int32_t dtype, int64_t n_images, const ct_geometry *geom, const ct_ingest_stage *stages,
+                                    int32_t n_stages, const float *consts_dev, const ct_icrf *icrf, bool &by_channel)
+{
+    if (!geom || !icrf) return CT_ERR_INVALID_ARGUMENT;
+    int rc = check_ingest_geometry(geom, true);
+    if (rc != CT_OK) return rc;
+    rc = ingest_validate(dtype, geom->layout, n_images, geom->channels, geom->h_tile * geom->width, stages, n_stages,
+                         CT_INGEST_MAX_STAGES, consts_dev ? 1 : 0, by_channel);
+    if (rc != CT_OK) return rc;
+    if (dtype == CT_DTYPE_F32) return CT_ERR_UNSUPPORTED;
+    return aligned(consts_dev, sizeof(float)) && icrf_ok(icrf) ? CT_OK : CT_ERR_INVALID_ARGUMENT;
 }
 
 }  // namespace ct

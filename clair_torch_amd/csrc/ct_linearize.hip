@@ -13,7 +13,7 @@
 //
 // Roofline: HBM (sizeof(T) read + 4 or 8 B written per sample).  No reuse between workgroups, so no XCD remap.
 #include <algorithm>
-#include "ct_device.hpp"
+#include "ct_args.hpp"
 
 namespace ct {
 
@@ -265,8 +265,8 @@ static int lin_launch_planar(const LinArgs &a, hipStream_t s)
     uint32_t gy = (a.n_frames + 1) / 2;
     if (gy < 1) gy = 1;
     if (gy > 65535) gy = 65535;
-    const size_t lds = INTERP == CT_INTERP_NONE ? 0 : (size_t)a.channels * a.n_points * lut_entry_bytes(INTERP);
-    if (lds > 160 * 1024) return CT_ERR_TOO_LARGE;
+    const size_t lds = lut_lds_bytes(INTERP, a.channels, a.n_points);
+    if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;
     hipLaunchKernelGGL((linearize_planar_kernel<T, kLinPackets, INTERP, STD, WRITE_STD>), dim3(gx, gy), dim3(kBlock), lds, s, a);
     return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
 }
@@ -411,9 +411,9 @@ static int lin_launch_rgb(const LinArgs &a, hipStream_t s)
     uint32_t gy = (a.n_frames + 1) / 2;
     if (gy < 1) gy = 1;
     if (gy > 65535) gy = 65535;
-    const size_t lds = ((INTERP == CT_INTERP_NONE ? 0 : (size_t)3 * a.n_points * lut_entry_bytes(INTERP)) + 15 & ~(size_t)15) +
+    const size_t lds = (lut_lds_bytes(INTERP, 3, a.n_points) + 15 & ~(size_t)15) +
                        (size_t)(kBlock / 64) * 768 * sizeof(float);  // LUT | 3 KB of exchange space per wavefront
-    if (lds > 160 * 1024) return CT_ERR_TOO_LARGE;
+    if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;
     hipLaunchKernelGGL((linearize_rgb_kernel<T, INTERP, STD, WRITE_STD>), dim3(gx, gy), dim3(kBlock), lds, s, a);
     return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
 }
@@ -454,8 +454,8 @@ static int lin_launch(const LinArgs &a, hipStream_t s)
     uint32_t gy = (a.n_frames + 1) / 2;
     if (gy < 1) gy = 1;
     if (gy > 65535) gy = 65535;
-    const size_t lds = INTERP == CT_INTERP_NONE ? 0 : (size_t)a.channels * a.n_points * lut_entry_bytes(INTERP);
-    if (lds > 160 * 1024) return CT_ERR_TOO_LARGE;
+    const size_t lds = lut_lds_bytes(INTERP, a.channels, a.n_points);
+    if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;
     hipLaunchKernelGGL((linearize_kernel<T, V, INTERP, STD, WRITE_STD>), dim3(gx, gy), dim3(kBlock), lds, s, a);
     return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
 }
@@ -495,7 +495,6 @@ static int lin_typed(LinArgs a, uint32_t Q, int interp, int std_mode, bool write
 #define CT_LINEARIZE_V_INT 8
 #endif
     constexpr int V = sizeof(T) == 4 ? 8 : CT_LINEARIZE_V_INT;
-    auto aligned = [](const void *p, size_t b) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % b) == 0; };
     const bool vec_ok = aligned(a.frames, sizeof(T) * V) && (a.image_stride % V) == 0 && aligned(a.std_stack, 4 * V) &&
                         aligned(a.lin_out, 4 * V) && aligned(a.std_out, 4 * V);
     uint32_t q_vec = vec_ok ? (Q / V) * V : 0;
@@ -619,7 +618,7 @@ static int bwd_launch(const BwdArgs &a, hipStream_t s)
     if (gy < 1) gy = 1;
     const size_t lut_bytes = (size_t)a.channels * a.n_points * lut_entry_bytes(INTERP);
     const size_t lds = ((lut_bytes + 15) & ~(size_t)15) + sizeof(double) * (size_t)a.channels * a.n_points;
-    if (lds > 160 * 1024) return CT_ERR_TOO_LARGE;
+    if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;
     // the whole grid is what the device holds at once: one round of equal grid-stride work, and as few histogram
     // flushes (global atomics on C*L addresses) as possible
     uint32_t gx = (a.q_count + kBlock - 1) / kBlock;
@@ -627,28 +626,6 @@ static int bwd_launch(const BwdArgs &a, hipStream_t s)
     if (gx > cap) gx = cap;
     hipLaunchKernelGGL((linearize_bwd_kernel<INTERP>), dim3(gx, gy), dim3(kBlock), lds, s, a);
     return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
-}
-
-static int check_geom(const ct_geometry *g)
-{
-    if (!g || g->channels <= 0 || g->h_tile <= 0 || g->width <= 0 || g->h_global < g->h_tile || g->row_offset < 0 ||
-        g->row_offset + g->h_tile > g->h_global)
-        return CT_ERR_INVALID_ARGUMENT;
-    if (g->h_global * g->width * g->channels >= (int64_t)1 << 31) return CT_ERR_TOO_LARGE;
-    if (g->image_stride < g->h_tile * g->width * g->channels) return CT_ERR_INVALID_ARGUMENT;
-    if (g->layout < CT_LAYOUT_NCHW || g->layout > CT_LAYOUT_NHWC_BGR) return CT_ERR_INVALID_ARGUMENT;
-    return CT_OK;
-}
-
-static TileMap make_tile(const ct_geometry *g)
-{
-    TileMap t;
-    t.plane_local = (uint32_t)(g->h_tile * g->width);
-    t.chan_skip = (uint32_t)((g->h_global - g->h_tile) * g->width);
-    t.base = (uint32_t)(g->row_offset * g->width);
-    t.layout = (uint32_t)g->layout;
-    t.channels = (uint32_t)g->channels;
-    return t;
 }
 
 }  // namespace ct
@@ -661,13 +638,10 @@ extern "C" int ct_linearize_std(const void *frames_dev, int32_t dtype, float max
 {
     using namespace ct;
     if (!frames_dev || !icrf || !lin_out_dev || n_frames <= 0 || n_frames > 0x7fffffff) return CT_ERR_INVALID_ARGUMENT;
-    int rc = check_geom(geom);
+    int rc = geom ? check_stack_geometry(geom) : CT_ERR_INVALID_ARGUMENT;
     if (rc != CT_OK) return rc;
     const int interp = icrf->interp;
-    if (interp < CT_INTERP_LOOKUP || interp > CT_INTERP_NONE) return CT_ERR_INVALID_ARGUMENT;
-    if (interp != CT_INTERP_NONE && (!icrf->lut_dev || icrf->n_points < 2)) return CT_ERR_INVALID_ARGUMENT;
-    if (std_mode < CT_STD_NONE || std_mode > CT_STD_EXPLICIT) return CT_ERR_INVALID_ARGUMENT;
-    if (std_mode == CT_STD_EXPLICIT && !std_dev) return CT_ERR_INVALID_ARGUMENT;
+    if (!icrf_ok(icrf) || !std_mode_ok(std_mode, std_dev)) return CT_ERR_INVALID_ARGUMENT;
     // linearization.py:100-105: autograd.grad raises for LOOKUP (no gradient path) when stds are present
     if (std_mode != CT_STD_NONE && interp == CT_INTERP_LOOKUP) return CT_ERR_NO_GRADIENT_PATH;
     LinArgs a{};
@@ -677,13 +651,13 @@ extern "C" int ct_linearize_std(const void *frames_dev, int32_t dtype, float max
     a.lin_out = lin_out_dev;
     a.std_out = std_out_dev;
     a.image_stride = geom->image_stride;
-    a.out_stride = geom->h_tile * geom->width * geom->channels;
+    a.out_stride = local_elements(geom);
     a.n_frames = (uint32_t)n_frames;
     a.tile = make_tile(geom);
     a.channels = geom->channels;
-    a.n_points = interp == CT_INTERP_NONE ? 2 : icrf->n_points;
+    a.n_points = icrf_points(icrf);
     a.std_value = std_value;
-    const uint32_t Q = (uint32_t)(geom->h_tile * geom->width * geom->channels);
+    const uint32_t Q = (uint32_t)local_elements(geom);
     const bool write_std = std_out_dev != nullptr;
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (dtype) {
@@ -712,12 +686,11 @@ extern "C" int ct_linearize_bwd(const float *x_dev, const float *grad_out_dev, i
     using namespace ct;
     if (!x_dev || !grad_out_dev || !icrf || n_images <= 0 || n_images > 0x7fffffff) return CT_ERR_INVALID_ARGUMENT;
     if (!grad_x_dev && !lut_grad_dev) return CT_OK;
-    int rc = check_geom(geom);
+    int rc = geom ? check_stack_geometry(geom) : CT_ERR_INVALID_ARGUMENT;
     if (rc != CT_OK) return rc;
     if (geom->layout != CT_LAYOUT_NCHW) return CT_ERR_UNSUPPORTED;
     const int interp = icrf->interp;
-    if (interp < CT_INTERP_LOOKUP || interp > CT_INTERP_CATMULL || !icrf->lut_dev || icrf->n_points < 2)
-        return CT_ERR_INVALID_ARGUMENT;
+    if (!icrf_ok(icrf, false)) return CT_ERR_INVALID_ARGUMENT;
     BwdArgs a{};
     a.x = x_dev;
     a.grad_out = grad_out_dev;
@@ -725,7 +698,7 @@ extern "C" int ct_linearize_bwd(const float *x_dev, const float *grad_out_dev, i
     a.grad_x = grad_x_dev;
     a.lut_grad = lut_grad_dev;
     a.image_stride = geom->image_stride;
-    a.q_count = (uint32_t)(geom->h_tile * geom->width * geom->channels);
+    a.q_count = (uint32_t)local_elements(geom);
     a.n_images = (uint32_t)n_images;
     a.tile = make_tile(geom);
     a.channels = geom->channels;

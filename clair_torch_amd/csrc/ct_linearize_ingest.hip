@@ -22,6 +22,7 @@
 // What precedes the first aligned packet of a plane (slot 0) and what follows the last whole one goes element by element.
 // Every load is that of an element of the thread's own pixels, every store lies in the thread's own [p0, p0 + n).  The
 // stage list travels by value in the kernel arguments; the stage loop is wave-uniform.  No atomics.
+#include "ct_args.hpp"
 #include "ct_ingest_stages.hpp"
 
 namespace ct {
@@ -219,7 +220,7 @@ static int li_launch(LinIngestArgs a, bool packed, int64_t rows, hipStream_t s)
 {
     const int64_t slots = 1 + (a.plane + kLiGroup - 1) / kLiGroup;
     const int64_t per_block = (int64_t)kBlock * kLiSlots;
-    const size_t lds = INTERP == CT_INTERP_NONE ? 0 : (size_t)a.channels * a.n_points * lut_entry_bytes(INTERP);
+    const size_t lds = lut_lds_bytes(INTERP, a.channels, a.n_points);
     const dim3 block(kBlock);
     for (int64_t first = 0; first < rows; first += kLiMaxRows) {
         a.first = (uint32_t)first;
@@ -267,34 +268,26 @@ extern "C" int ct_linearize_ingest(const void *frames_dev, int32_t dtype, int64_
                                    float std_value, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev, void *stream)
 {
     using namespace ct;
-    // everything that needs no pointer into device memory first: geometry (as ct_linearize_std), the stack and the stage
-    // list (as ct_ingest_transform, without AFFINE_DATA), the model and the uncertainty mode (as ct_linearize_std)
+    // everything that needs no pointer into device memory first: geometry (check_ingest_geometry, no empty plane), the stack
+    // and the stage list (ingest_validate, without AFFINE_DATA), the model and the uncertainty mode (icrf_ok, std_mode_ok)
     if (!geom || !icrf) return CT_ERR_INVALID_ARGUMENT;
-    if (geom->channels <= 0 || geom->h_tile <= 0 || geom->width <= 0 || geom->h_global < geom->h_tile || geom->row_offset < 0 ||
-        geom->row_offset + geom->h_tile > geom->h_global)
-        return CT_ERR_INVALID_ARGUMENT;
-    if (geom->layout < CT_LAYOUT_NCHW || geom->layout > CT_LAYOUT_NHWC_BGR) return CT_ERR_INVALID_ARGUMENT;
-    if (geom->h_global * geom->width * geom->channels >= (int64_t)1 << 31) return CT_ERR_TOO_LARGE;
+    int rc = check_ingest_geometry(geom, false);
+    if (rc != CT_OK) return rc;
     const int64_t plane = geom->h_tile * geom->width;
-    if (geom->image_stride < plane * geom->channels) return CT_ERR_INVALID_ARGUMENT;
+    if (!stride_holds_image(geom)) return CT_ERR_INVALID_ARGUMENT;
     bool by_channel = false;
-    int rc = ingest_validate(dtype, geom->layout, n_frames, geom->channels, plane, stages, n_stages, CT_INGEST_MAX_STAGES, 0, by_channel);
+    rc = ingest_validate(dtype, geom->layout, n_frames, geom->channels, plane, stages, n_stages, CT_INGEST_MAX_STAGES, 0, by_channel);
     if (rc != CT_OK) return rc;
     const int interp = icrf->interp;
-    if (interp < CT_INTERP_LOOKUP || interp > CT_INTERP_NONE) return CT_ERR_INVALID_ARGUMENT;
-    if (interp != CT_INTERP_NONE && (!icrf->lut_dev || icrf->n_points < 2)) return CT_ERR_INVALID_ARGUMENT;
-    if (std_mode < CT_STD_NONE || std_mode > CT_STD_EXPLICIT) return CT_ERR_INVALID_ARGUMENT;
-    if (std_mode == CT_STD_EXPLICIT && !std_dev) return CT_ERR_INVALID_ARGUMENT;
+    if (!icrf_ok(icrf) || !std_mode_ok(std_mode, std_dev)) return CT_ERR_INVALID_ARGUMENT;
     // linearization.py:100-105: autograd.grad raises for LOOKUP (no gradient path) when stds are present
     if (std_mode != CT_STD_NONE && interp == CT_INTERP_LOOKUP) return CT_ERR_NO_GRADIENT_PATH;
-    if (interp != CT_INTERP_NONE && (size_t)geom->channels * (size_t)icrf->n_points * lut_entry_bytes(interp) > 160 * 1024)
-        return CT_ERR_TOO_LARGE;
+    if (lut_lds_bytes(interp, geom->channels, icrf->n_points) > kLdsBudget) return CT_ERR_TOO_LARGE;
     const bool packed = geom->layout != CT_LAYOUT_NCHW;
     int64_t rows = n_frames;
     if ((!packed && __builtin_mul_overflow(n_frames, (int64_t)geom->channels, &rows)) || rows > 0x7fffffff) return CT_ERR_TOO_LARGE;
     if (n_frames == 0) return CT_OK;
     const uintptr_t src_align = dtype == CT_DTYPE_U8 ? 1 : (dtype == CT_DTYPE_U16 ? 2 : 4);
-    auto aligned = [](const void *p, uintptr_t b) { return reinterpret_cast<uintptr_t>(p) % b == 0; };
     if (!frames_dev || !lin_out_dev || !aligned(frames_dev, src_align) || !aligned(lin_out_dev, sizeof(float)) ||
         !aligned(std_out_dev, sizeof(float)) || !aligned(std_dev, sizeof(float)))
         return CT_ERR_INVALID_ARGUMENT;
@@ -304,17 +297,8 @@ extern "C" int ct_linearize_ingest(const void *frames_dev, int32_t dtype, int64_
     a.lut = icrf->lut_dev;
     a.lin_out = lin_out_dev;
     a.std_out = std_out_dev;
-    a.image_stride = geom->image_stride;
-    a.plane = plane;
-    a.channels = (uint32_t)geom->channels;
-    a.n_points = interp == CT_INTERP_NONE ? 2u : (uint32_t)icrf->n_points;
-    a.plane_global = (uint32_t)(geom->h_global * geom->width);
-    a.base = (uint32_t)(geom->row_offset * geom->width);
-    a.reversed = geom->layout == CT_LAYOUT_NHWC_BGR ? 1u : 0u;
-    a.by_channel = by_channel ? 1u : 0u;
+    fill_ingest_args(a, geom, icrf_points(icrf), by_channel, stages, n_stages);
     a.std_value = std_value;
-    a.n_stages = (uint32_t)n_stages;
-    for (int32_t k = 0; k < n_stages; ++k) a.stage[k] = stages[k];
     const bool write_std = std_out_dev != nullptr;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (dtype == CT_DTYPE_U8) return li_dispatch<uint8_t>(a, packed, rows, interp, std_mode, write_std, s);

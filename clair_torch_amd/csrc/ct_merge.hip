@@ -407,17 +407,16 @@ static int launch_pivot(const MergeArgs &a, PivotArgs x, hipStream_t stream)
         x.rgb252 = 0;
         if constexpr (V == 4) {
             // interleaved RGB / BGR, the whole image in this launch, outputs only (no streaming state): packet stores
-            auto aligned16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) % 16) == 0; };
             if (a.tile.layout != CT_LAYOUT_NCHW && !(a.flags & CT_MERGE_OUT_AS_INPUT) && a.channels == 3 && a.tile.plane_local % 4 == 0 && !a.mean_state &&
                 (a.flags & CT_MERGE_FINALIZE) && !(a.flags & CT_MERGE_MEAN_OUT_F32) && a.q_begin == 0 &&
-                a.q_count == 3u * a.tile.plane_local && aligned16(a.mean_out) && aligned16(a.std_out)) {
+                a.q_count == 3u * a.tile.plane_local && aligned(a.mean_out, 16) && aligned(a.std_out, 16)) {
                 x.rgb252 = 1;
                 lds = (lds + 15) & ~(size_t)15;
                 x.stage_off = (uint32_t)lds;
                 lds += 4 * 3072;
             }
         }
-        if (lds > 160 * 1024) return CT_ERR_TOO_LARGE;
+        if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;
         if constexpr (V == 4) {
             if (x.rgb252)
                 return (a.flags & CT_MERGE_FIRST_BATCH)
@@ -456,9 +455,9 @@ static int launch_one(const MergeArgs &a, hipStream_t stream, bool fold)
     if (a.q_count == 0) return CT_OK;
     const uint32_t vecs = a.q_count / V;
     const uint32_t grid = (vecs + kBlock - 1) / kBlock;
-    const size_t lds = (INTERP == CT_INTERP_NONE ? 0 : (size_t)a.channels * a.n_points * lut_entry_bytes(INTERP)) +
+    const size_t lds = lut_lds_bytes(INTERP, a.channels, a.n_points) +
                        2 * sizeof(float) * (size_t)a.batch;
-    if (lds > 160 * 1024) return CT_ERR_TOO_LARGE;
+    if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;
     const bool f64 = a.flags & CT_MERGE_F64_MOMENTS;  // diagnostic: the round-1 float64 moments
     if constexpr (sizeof(T) != 4) {
         if (fold && f64)
@@ -502,7 +501,7 @@ struct VecWidth {
 // too (the generic kernel; the pivoted one addresses its state element by element).
 static bool packets_aligned(const MergeArgs &a, size_t elem_bytes, int V, bool with_state)
 {
-    auto ok = [V](const void *p, size_t bytes) { return reinterpret_cast<uintptr_t>(p) % (bytes * V) == 0; };
+    auto ok = [V](const void *p, size_t bytes) { return aligned(p, bytes * V); };
     return ok(a.stack, elem_bytes) && a.image_stride % V == 0 && ok(a.std_stack, 4) && ok(a.mean_out, 8) && ok(a.std_out, 4) &&
            (!with_state || (ok(a.mean_state, 8) && ok(a.sumw_state, 4) && ok(a.var_state, 4)));
 }
@@ -635,41 +634,33 @@ struct MergeCall {
     uint32_t flags;
     bool has_state() const { return mean_state && sumw_state && (std_mode == CT_STD_NONE || var_state); }
     bool state_ok() const { return has_state() || ((flags & CT_MERGE_FIRST_BATCH) && (flags & CT_MERGE_FINALIZE)); }
-    bool positive_shape() const { return geom->channels > 0 && geom->h_tile > 0 && geom->width > 0; }
     // hdr_merge.py:107-113: autograd.grad raises when nothing connects the mean to the image
     bool no_gradient_path() const { return std_mode != CT_STD_NONE && icrf->interp == CT_INTERP_LOOKUP && weight_mode == CT_WEIGHT_NONE; }
-    int64_t local_elements() const { return geom->h_tile * geom->width * geom->channels; }
 };
 
 // The argument checks of a merge, in the order their status codes are documented; nothing is launched before they pass.
 static int validate_merge(const MergeCall &c)
 {
+    using namespace ct;
     const ct_geometry *geom = c.geom;
     if (!geom || !c.icrf || !c.exposure) return CT_ERR_INVALID_ARGUMENT;
-    if (!c.positive_shape() || geom->h_global < geom->h_tile || geom->row_offset < 0 || geom->row_offset + geom->h_tile > geom->h_global)
-        return CT_ERR_INVALID_ARGUMENT;
-    if (geom->layout < CT_LAYOUT_NCHW || geom->layout > CT_LAYOUT_NHWC_BGR) return CT_ERR_INVALID_ARGUMENT;
-    const int interp = c.icrf->interp;
-    if (interp < CT_INTERP_LOOKUP || interp > CT_INTERP_NONE) return CT_ERR_INVALID_ARGUMENT;
-    if (interp != CT_INTERP_NONE && (!c.icrf->lut_dev || c.icrf->n_points < 2)) return CT_ERR_INVALID_ARGUMENT;
-    if (c.std_mode < CT_STD_NONE || c.std_mode > CT_STD_EXPLICIT) return CT_ERR_INVALID_ARGUMENT;
-    if (c.weight_mode != CT_WEIGHT_NONE && c.weight_mode != CT_WEIGHT_GAUSS) return CT_ERR_INVALID_ARGUMENT;
+    if (!shape_positive(geom) || !band_fits(geom) || !layout_ok(geom) || !icrf_ok(c.icrf)) return CT_ERR_INVALID_ARGUMENT;
+    if (!std_mode_in_range(c.std_mode) || (c.weight_mode != CT_WEIGHT_NONE && c.weight_mode != CT_WEIGHT_GAUSS)) return CT_ERR_INVALID_ARGUMENT;
     if (c.no_gradient_path()) return CT_ERR_NO_GRADIENT_PATH;
     if (!c.state_ok()) return CT_ERR_INVALID_ARGUMENT;
     if ((c.flags & CT_MERGE_FINALIZE) && (!c.mean_out || (c.std_mode != CT_STD_NONE && !c.std_out))) return CT_ERR_INVALID_ARGUMENT;
-    if (geom->h_global * geom->width * geom->channels >= (int64_t)1 << 31) return CT_ERR_TOO_LARGE;
-    if (geom->image_stride < c.local_elements()) return CT_ERR_INVALID_ARGUMENT;
-    return CT_OK;
+    if (!global_below_2_31(geom)) return CT_ERR_TOO_LARGE;
+    return stride_holds_image(geom) ? CT_OK : CT_ERR_INVALID_ARGUMENT;
 }
 
 // The kernels' argument block for `batch` exposures at `stack` (explicit uncertainties at `std_stack`).  q_begin / q_count
 // are the launcher's; norm, index and inv_max_code are set by the integer-code routes.
 static ct::MergeArgs fill_merge_args(const MergeCall &c, const void *stack, const float *std_stack, int32_t batch)
 {
+    using namespace ct;
     const ct_geometry *geom = c.geom;
-    const int64_t plane_g = geom->h_global * geom->width, plane_l = geom->h_tile * geom->width;
     const bool has_state = c.has_state();
-    ct::MergeArgs a{};
+    MergeArgs a{};
     a.stack = stack;
     a.std_stack = c.std_mode == CT_STD_EXPLICIT ? std_stack : nullptr;
     a.exposure = c.exposure;
@@ -680,14 +671,10 @@ static ct::MergeArgs fill_merge_args(const MergeCall &c, const void *stack, cons
     a.mean_out = c.mean_out;
     a.std_out = c.std_out;
     a.image_stride = geom->image_stride;
-    a.tile.plane_local = (uint32_t)plane_l;
-    a.tile.chan_skip = (uint32_t)(plane_g - plane_l);
-    a.tile.base = (uint32_t)(geom->row_offset * geom->width);
-    a.tile.layout = (uint32_t)geom->layout;
-    a.tile.channels = (uint32_t)geom->channels;
+    a.tile = make_tile(geom);
     a.batch = batch;
     a.channels = geom->channels;
-    a.n_points = c.icrf->interp == CT_INTERP_NONE ? 2 : c.icrf->n_points;
+    a.n_points = icrf_points(c.icrf);
     a.std_value = c.std_value;
     a.weight_scale = 30.0f;  // gaussian_value_weights default scale, hdr_merge.py:95
     a.inv_max_code = 1.0f;
@@ -707,7 +694,7 @@ extern "C" int ct_hdr_merge_batch(const void *stack_dev, int32_t dtype, float ma
     if (!stack_dev || batch <= 0 || (std_mode == CT_STD_EXPLICIT && !std_dev)) return CT_ERR_INVALID_ARGUMENT;
     if (const int rc = validate_merge(c); rc != CT_OK) return rc;
     MergeArgs a = fill_merge_args(c, stack_dev, std_dev, batch);
-    const uint32_t Ql = (uint32_t)c.local_elements();
+    const uint32_t Ql = (uint32_t)local_elements(geom);
     const int interp = icrf->interp;
     hipStream_t s = static_cast<hipStream_t>(stream);
     PivotArgs px{};
@@ -748,7 +735,7 @@ extern "C" int ct_hdr_merge_batches(const void *const *stack_devs, const float *
                       mean_out_dev, std_out_dev, flags};
     const int valid = validate_merge(c);  // of the whole sequence (FIRST: before its first batch, FINALIZE: after its last)
     const int interp = icrf->interp;
-    const int64_t Ql = c.local_elements();
+    const int64_t Ql = local_elements(geom);
     hipStream_t s = static_cast<hipStream_t>(stream);
     MergeArgs a = fill_merge_args(c, stack_devs[0], std_mode == CT_STD_EXPLICIT ? std_devs[0] : nullptr, (int32_t)total);
     PivotArgs px{};
@@ -770,7 +757,7 @@ extern "C" int ct_hdr_merge_batches(const void *const *stack_devs, const float *
     // the pivoted kernel in one launch: a well-formed problem in whole packets; what else may be wrong with the call is
     // reported from here, before anything is launched
     bool fast = route == MergeRoute::Pivot && n_batches >= 2 && n_batches <= kMaxMultiBatches && total <= 0x7fffffff && c.state_ok() &&
-                c.positive_shape() && !c.no_gradient_path() && Ql % kPivotV == 0;
+                shape_positive(geom) && !c.no_gradient_path() && Ql % kPivotV == 0;
     for (int b = 0; fast && b < n_batches; ++b) {
         a.stack = stack_devs[b];
         a.std_stack = std_mode == CT_STD_EXPLICIT ? std_devs[b] : nullptr;

@@ -1,6 +1,6 @@
 // ct_merge.hpp -- argument block and packet type shared by the merge kernels (ct_merge.hip, ct_merge_exact.hip).
 #pragma once
-#include "ct_device.hpp"
+#include "ct_args.hpp"
 
 namespace ct {
 

@@ -298,7 +298,7 @@ __global__ __launch_bounds__(kBlock) void merge_reference_order_kernel(const Mer
 
 static size_t exact_fixed_lds(const MergeArgs &a, int interp)
 {
-    return ((interp == CT_INTERP_NONE ? 0 : (size_t)a.channels * a.n_points * lut_entry_bytes(interp)) + 7 & ~(size_t)7) +
+    return (lut_lds_bytes(interp, a.channels, a.n_points) + 7 & ~(size_t)7) +
            sizeof(double) * (size_t)a.batch;
 }
 
@@ -330,7 +330,7 @@ static int exact_launch(const MergeArgs &a, const ExactRoute &r, hipStream_t s)
     if (a.q_count == 0) return CT_OK;
     const uint32_t vecs = (a.q_count + V - 1) / V, grid = (vecs + kBlock - 1) / kBlock;
     const size_t lds = exact_fixed_lds(a, INTERP) + (size_t)CACHE * r.b_max * V * kBlock * sizeof(float);
-    if (lds > 160 * 1024) return CT_ERR_TOO_LARGE;
+    if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;
     hipLaunchKernelGGL((merge_reference_order_kernel<T, V, INTERP, WEIGHT, STD, CACHE>), dim3(grid), dim3(kBlock), lds, s, a, r.mb);
     return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
 }
@@ -389,7 +389,6 @@ static int exact_typed(MergeArgs a, const ExactRoute &r, uint32_t Q, int interp,
 {
     // packets of 4 where every exposure's packet is naturally aligned; the rest (and everything, on odd strides) one by one
     constexpr int V = 4;
-    auto aligned = [](const void *p, size_t bytes) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % bytes) == 0; };
     bool vec_ok = aligned(a.stack, sizeof(T) * V) && (a.image_stride % V) == 0 && aligned(a.std_stack, 4 * V);
     for (int b = 0; b < r.mb.n_batches; ++b) vec_ok = vec_ok && aligned(r.mb.batch_ptr[b], sizeof(T) * V) && aligned(r.mb.std_ptr[b], 4 * V);
     const uint32_t q_vec = vec_ok ? (Q / V) * V : 0;

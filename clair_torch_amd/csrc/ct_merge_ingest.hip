@@ -116,35 +116,21 @@ struct MergeIngestCall {
     uint32_t flags;
     bool has_state() const { return mean_state && sumw_state && (std_mode == CT_STD_NONE || var_state); }
     int64_t plane() const { return geom->h_tile * geom->width; }
-    int n_points() const { return icrf->interp == CT_INTERP_NONE ? 2 : icrf->n_points; }
+    int n_points() const { return icrf_points(icrf); }
 };
 
-// Everything that needs no pointer into device memory, in the order the status codes are documented: geometry and modes (as
-// ct_hdr_merge_batch), a stack of `batch` frames and the stage list (as ct_ingest_transform / _data), the flags these entry
-// points do not take.  FIRST_BATCH / FINALIZE in c.flags are those of the whole call.
+// Everything that needs no pointer into device memory, in the order the status codes are documented: geometry, a stack of
+// `batch` frames of codes, the stage list and the model (check_code_ingest), the modes (as validate_merge of ct_merge.hip),
+// the flags these entry points do not take.  FIRST_BATCH / FINALIZE in c.flags are those of the whole call.
 static int mi_validate(const MergeIngestCall &c, int32_t batch, const float *consts_dev, bool &by_channel)
 {
     const ct_geometry *geom = c.geom;
     const ct_icrf *icrf = c.icrf;
     const int32_t std_mode = c.std_mode, weight_mode = c.weight_mode;
     const uint32_t flags = c.flags;
-    if (!geom || !icrf) return CT_ERR_INVALID_ARGUMENT;
-    if (geom->channels <= 0 || geom->h_tile < 0 || geom->width < 0 || geom->h_global < geom->h_tile || geom->row_offset < 0 ||
-        geom->row_offset + geom->h_tile > geom->h_global)
-        return CT_ERR_INVALID_ARGUMENT;
-    if (geom->layout < CT_LAYOUT_NCHW || geom->layout > CT_LAYOUT_NHWC_BGR) return CT_ERR_INVALID_ARGUMENT;
-    if (geom->h_global * geom->width * geom->channels >= (int64_t)1 << 31) return CT_ERR_TOO_LARGE;
-    const int64_t plane = c.plane();
-    int rc = ingest_validate(c.dtype, geom->layout, batch, geom->channels, plane, c.stages, c.n_stages, CT_INGEST_MAX_STAGES,
-                             consts_dev ? 1 : 0, by_channel);
-    if (rc != CT_OK) return rc;
-    if (c.dtype == CT_DTYPE_F32) return CT_ERR_UNSUPPORTED;  // float32 pixels have no copy to save: ct_hdr_merge_batch takes them
-    if (reinterpret_cast<uintptr_t>(consts_dev) % sizeof(float) != 0) return CT_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_code_ingest(c.dtype, batch, geom, c.stages, c.n_stages, consts_dev, icrf, by_channel); rc != CT_OK) return rc;
     const int interp = icrf->interp;
-    if (interp < CT_INTERP_LOOKUP || interp > CT_INTERP_NONE) return CT_ERR_INVALID_ARGUMENT;
-    if (interp != CT_INTERP_NONE && (!icrf->lut_dev || icrf->n_points < 2)) return CT_ERR_INVALID_ARGUMENT;
-    if (std_mode < CT_STD_NONE || std_mode > CT_STD_EXPLICIT) return CT_ERR_INVALID_ARGUMENT;
-    if (weight_mode != CT_WEIGHT_NONE && weight_mode != CT_WEIGHT_GAUSS) return CT_ERR_INVALID_ARGUMENT;
+    if (!std_mode_in_range(std_mode) || (weight_mode != CT_WEIGHT_NONE && weight_mode != CT_WEIGHT_GAUSS)) return CT_ERR_INVALID_ARGUMENT;
     // hdr_merge.py:107-113: autograd.grad raises when nothing connects the mean to the image
     if (std_mode != CT_STD_NONE && interp == CT_INTERP_LOOKUP && weight_mode == CT_WEIGHT_NONE) return CT_ERR_NO_GRADIENT_PATH;
     if (flags & (CT_MERGE_F64_MOMENTS | CT_MERGE_REFERENCE_ORDER | CT_MERGE_OUT_AS_INPUT)) return CT_ERR_UNSUPPORTED;
@@ -153,15 +139,14 @@ static int mi_validate(const MergeIngestCall &c, int32_t batch, const float *con
         return CT_ERR_UNSUPPORTED;
     if (!c.has_state() && !((flags & CT_MERGE_FIRST_BATCH) && (flags & CT_MERGE_FINALIZE))) return CT_ERR_INVALID_ARGUMENT;
     if ((flags & CT_MERGE_FINALIZE) && (!c.mean_out || (std_mode != CT_STD_NONE && !c.std_out))) return CT_ERR_INVALID_ARGUMENT;
-    if (geom->image_stride < plane * geom->channels) return CT_ERR_INVALID_ARGUMENT;
-    if (mi_lds_bytes(interp, geom->channels, c.n_points(), batch) > 160 * 1024) return CT_ERR_TOO_LARGE;
+    if (!stride_holds_image(geom)) return CT_ERR_INVALID_ARGUMENT;
+    if (mi_lds_bytes(interp, geom->channels, c.n_points(), batch) > kLdsBudget) return CT_ERR_TOO_LARGE;
     return CT_OK;
 }
 
 // the pointers of a call that has something to do: present and aligned to their element
 static bool mi_pointers_ok(const MergeIngestCall &c, const void *frames_dev, const float *std_dev)
 {
-    auto aligned = [](const void *p, uintptr_t b) { return reinterpret_cast<uintptr_t>(p) % b == 0; };
     if (!frames_dev || !c.exposure || (c.std_mode == CT_STD_EXPLICIT && !std_dev)) return false;
     return aligned(frames_dev, c.dtype == CT_DTYPE_U16 ? 2 : 1) && aligned(c.exposure, sizeof(double)) && aligned(std_dev, sizeof(float)) &&
            aligned(c.mean_state, sizeof(double)) && aligned(c.sumw_state, sizeof(float)) && aligned(c.var_state, sizeof(float)) &&
@@ -185,20 +170,11 @@ static MergeIngestArgs mi_fill_args(const MergeIngestCall &c, const void *frames
     a.var_state = has_state ? c.var_state : nullptr;
     a.mean_out = c.mean_out;
     a.std_out = c.std_out;
-    a.image_stride = geom->image_stride;
-    a.plane = (uint32_t)c.plane();
-    a.plane_global = (uint32_t)(geom->h_global * geom->width);
-    a.base = (uint32_t)(geom->row_offset * geom->width);
+    fill_ingest_args(a, geom, c.n_points(), by_channel, c.stages, c.n_stages);
     a.batch = batch;
-    a.channels = geom->channels;
-    a.n_points = c.n_points();
-    a.reversed = geom->layout == CT_LAYOUT_NHWC_BGR ? 1u : 0u;
-    a.by_channel = by_channel ? 1u : 0u;
     a.std_value = c.std_value;
     a.weight_scale = 30.0f;  // gaussian_value_weights default scale, hdr_merge.py:95
     a.flags = flags;
-    a.n_stages = (uint32_t)c.n_stages;
-    for (int32_t k = 0; k < c.n_stages; ++k) a.stage[k] = c.stages[k];
     return a;
 }
 
@@ -273,7 +249,7 @@ extern "C" int ct_hdr_merge_ingest_batches(const void *const *frames_devs, const
     const int interp = icrf->interp;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool one_launch = n >= 2 && (n_consts == 0 || n_consts == n) &&
-                            mi_lds_bytes(interp, geom->channels, c.n_points(), total) <= 160 * 1024;
+                            mi_lds_bytes(interp, geom->channels, c.n_points(), total) <= kLdsBudget;
     if (one_launch) {
         const MergeIngestArgs a = mi_fill_args(c, nullptr, nullptr, nullptr, exposure_dev, (int32_t)total, single_flags, by_channel);
         return merge_ingest_multi(a, mb, dtype, geom->layout != CT_LAYOUT_NCHW, interp, weight_mode, std_mode, s);

@@ -4,6 +4,7 @@
 // the element-by-element walk.  MULTI is a template flag of that one body; everything it adds is behind `if constexpr`, and
 // the order of the text is kept so that the single-batch kernels compile to the instructions they had without it.
 #pragma once
+#include "ct_args.hpp"
 #include "ct_ingest_stages.hpp"
 #include "ct_merge_ingest.hpp"
 
@@ -55,8 +56,7 @@ int merge_ingest_multi(const MergeIngestArgs &a, const MergeIngestBatches &mb, i
 // LDS of a launch over `batch` exposures: the LUT, 1 / t_n and the derivative scales
 inline size_t mi_lds_bytes(int interp, int channels, int n_points, int64_t batch)
 {
-    return (interp == CT_INTERP_NONE ? 0 : (size_t)channels * (size_t)n_points * lut_entry_bytes(interp)) +
-           2 * sizeof(float) * (size_t)batch;
+    return lut_lds_bytes(interp, channels, n_points) + 2 * sizeof(float) * (size_t)batch;
 }
 
 constexpr int kMiGroup = 4;        // PLANAR: output elements per thread, one 16-byte packet

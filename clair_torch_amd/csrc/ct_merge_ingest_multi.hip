@@ -58,7 +58,7 @@ static int mi_launch_multi(const MergeIngestArgs &a, const MergeIngestBatches &m
         return CT_ERR_NO_GRADIENT_PATH;  // (refused by the entry point before it gets here)
     } else {
         const size_t lds = mi_lds_bytes(INTERP, a.channels, a.n_points, a.batch);
-        if (lds > 160 * 1024) return CT_ERR_TOO_LARGE;  // (the entry point walks such a call batch by batch instead)
+        if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;  // (the entry point walks such a call batch by batch instead)
         hipLaunchKernelGGL((merge_ingest_multi_kernel<T, PACKED, INTERP, WEIGHT, STD>), mi_grid<PACKED>(a), dim3(kBlock), lds, s, a, mb);
         return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
     }

@@ -16,7 +16,7 @@ static int launch_pivot_multi(const MergeArgs &a, PivotArgs x, hipStream_t strea
         x.n_tiles = (a.q_count + (uint32_t)(kBlock * V) - 1) / (uint32_t)(kBlock * V);
         const size_t lds = pivot_lds_bytes(a, x, INTERP);
         // TODO: fall back to one launch per batch instead (the summed exposures of all batches need more LDS than one batch)
-        if (lds > 160 * 1024) return CT_ERR_TOO_LARGE;
+        if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;
         return launch_pivot_grid<merge_pivot_kernel<T, V, INTERP, WEIGHT, STD, false, CLAMP, true>>(a, x, lds, stream);
     }
 }

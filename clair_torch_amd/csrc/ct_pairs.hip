@@ -21,7 +21,7 @@
 //                   float64 global atomics at the end.  Pair constants come from a global table through scalar loads.
 //                   The uncertainty-weighted loss (weights depending on the LUT through err) uses the same kernel with the
 //                   linearized stds staged as a fourth per-column array.
-// Grids are sized to whole rounds of what the device holds at once (resident_workgroups, ct_device.hpp).
+// Grids are sized to whole rounds of what the device holds at once (resident_workgroups, ct_args.hpp).
 // Shared by the kernels: phase 1 (stage_tile / VecStager), the LUT staging choice (stage_pair_lut) and, in the two backward
 // kernels, the column -> histogram-row table (fill_colrow) and the histogram flush (flush_hist).  Host: with_enum
 // compositions (ct_device.hpp) lift dtype, interpolation, std mode, level and the relative flag to template arguments;
@@ -34,7 +34,7 @@
 // Roofline: float32 VALU (P pair evaluations per N loaded samples per pixel; P >> N), not HBM.
 #include <algorithm>
 #include <cstdlib>
-#include "ct_device.hpp"
+#include "ct_args.hpp"
 
 extern "C" int ct_norm_constants(float max_code, float *hi, float *lo);
 extern "C" int ct_pivot_floor_constants(float max_code, int n_points, float *rcp_step);
@@ -1223,31 +1223,19 @@ static int fill_common(PairArgs &a, const void *stack_dev, int32_t n_images, con
                        const ct_icrf *icrf, const ct_pair_params *prm, int32_t n_pairs)
 {
     if (!stack_dev || !g || !icrf || !prm || n_images < 2 || n_pairs < 0) return CT_ERR_INVALID_ARGUMENT;
-    if (g->channels <= 0 || g->h_tile <= 0 || g->width <= 0 || g->h_global < g->h_tile || g->row_offset < 0 ||
-        g->row_offset + g->h_tile > g->h_global)
-        return CT_ERR_INVALID_ARGUMENT;
-    if (g->h_global * g->width * g->channels >= (int64_t)1 << 31) return CT_ERR_TOO_LARGE;
-    if (g->image_stride < g->h_tile * g->width * g->channels) return CT_ERR_INVALID_ARGUMENT;
-    if (g->layout < CT_LAYOUT_NCHW || g->layout > CT_LAYOUT_NHWC_BGR) return CT_ERR_INVALID_ARGUMENT;
-    if (icrf->interp < CT_INTERP_LOOKUP || icrf->interp > CT_INTERP_NONE) return CT_ERR_INVALID_ARGUMENT;
-    if (icrf->interp != CT_INTERP_NONE && (!icrf->lut_dev || icrf->n_points < 2)) return CT_ERR_INVALID_ARGUMENT;
-    if (prm->std_mode < CT_STD_NONE || prm->std_mode > CT_STD_EXPLICIT) return CT_ERR_INVALID_ARGUMENT;
-    if (prm->std_mode == CT_STD_EXPLICIT && !std_dev) return CT_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_stack_geometry(g); rc != CT_OK) return rc;
+    if (!icrf_ok(icrf) || !std_mode_ok(prm->std_mode, std_dev)) return CT_ERR_INVALID_ARGUMENT;
     if (prm->lower > prm->upper) return CT_ERR_INVALID_ARGUMENT;
     a.stack = stack_dev;
     a.std_stack = prm->std_mode == CT_STD_EXPLICIT ? std_dev : nullptr;
     a.lut = icrf->lut_dev;
     a.image_stride = g->image_stride;
-    a.tile.plane_local = (uint32_t)(g->h_tile * g->width);
-    a.tile.chan_skip = (uint32_t)((g->h_global - g->h_tile) * g->width);
-    a.tile.base = (uint32_t)(g->row_offset * g->width);
-    a.tile.layout = (uint32_t)g->layout;  // planar, or interleaved RGB / BGR (the stack AND an explicit std stack)
-    a.tile.channels = (uint32_t)g->channels;
+    a.tile = make_tile(g);  // planar, or interleaved RGB / BGR (the stack AND an explicit std stack)
     a.plane_local = a.tile.plane_local;
     a.n_images = n_images;
     a.n_pairs = n_pairs;
     a.channels = g->channels;
-    a.n_points = icrf->interp == CT_INTERP_NONE ? 2 : icrf->n_points;
+    a.n_points = icrf_points(icrf);
     a.lower = prm->lower;
     a.upper = prm->upper;
     a.neg_scale_log2e = -prm->weight_scale * 1.4426950408889634f;

@@ -14,6 +14,7 @@
 // Interleaved (F, H, W, C) frames as OpenCV decodes them (IL instantiations): a thread still owns V consecutive MEMORY
 // elements -- the frame loads stay packets -- and only the LUT row and the position in the planar (C, H, W) state follow
 // from TileMap::planar_index; the state is touched element by element, once per batch of frames.
+#include "ct_args.hpp"
 #include "ct_stats_merge.hpp"
 
 namespace ct {
@@ -144,8 +145,8 @@ static int stats_launch_layout(const StatsArgs &a, hipStream_t s)
 {
     if (a.q_count == 0) return CT_OK;
     const uint32_t vecs = a.q_count / V, grid = (vecs + kBlock - 1) / kBlock;
-    const size_t lds = INTERP == CT_INTERP_NONE ? 0 : (size_t)a.channels * a.n_points * lut_entry_bytes(INTERP);
-    if (lds > 160 * 1024) return CT_ERR_TOO_LARGE;
+    const size_t lds = lut_lds_bytes(INTERP, a.channels, a.n_points);
+    if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;
     if (a.batch <= 16)
         hipLaunchKernelGGL((video_stats_cached_kernel<T, V, INTERP, 16, IL>), dim3(grid), dim3(kBlock), lds, s, a);
     else if (a.batch <= 32)
@@ -177,7 +178,6 @@ template <typename T>
 static int stats_typed(StatsArgs a, uint32_t Q, int interp, hipStream_t s)
 {
     constexpr int V = 4;  // 4 elements per thread: 32 frames x 4 values fit the register file
-    auto aligned = [](const void *p, size_t b) { return (reinterpret_cast<uintptr_t>(p) % b) == 0; };
     const bool vec_ok = aligned(a.frames, sizeof(T) * V) && (a.image_stride % V) == 0 && aligned(a.mean_state, 4 * V) &&
                         aligned(a.m2_state, 4 * V);
     const uint32_t q_vec = vec_ok ? (Q / V) * V : 0;
@@ -207,30 +207,21 @@ extern "C" int ct_video_stats_batch(const void *frames_dev, int32_t dtype, float
     using namespace ct;
     if (!frames_dev || !geom || !icrf || !mean_state_dev || !m2_state_dev || batch <= 0 || frames_before < 0.0f)
         return CT_ERR_INVALID_ARGUMENT;
-    if (geom->channels <= 0 || geom->h_tile <= 0 || geom->width <= 0 || geom->h_global < geom->h_tile ||
-        geom->row_offset < 0 || geom->row_offset + geom->h_tile > geom->h_global)
-        return CT_ERR_INVALID_ARGUMENT;
+    if (!shape_positive(geom) || !band_fits(geom) || !icrf_ok(icrf)) return CT_ERR_INVALID_ARGUMENT;
+    if (!global_below_2_31(geom)) return CT_ERR_TOO_LARGE;
+    if (!stride_holds_image(geom) || !layout_ok(geom)) return CT_ERR_INVALID_ARGUMENT;
     const int interp = icrf->interp;
-    if (interp < CT_INTERP_LOOKUP || interp > CT_INTERP_NONE) return CT_ERR_INVALID_ARGUMENT;
-    if (interp != CT_INTERP_NONE && (!icrf->lut_dev || icrf->n_points < 2)) return CT_ERR_INVALID_ARGUMENT;
-    const int64_t Qg = geom->h_global * geom->width * geom->channels, Ql = geom->h_tile * geom->width * geom->channels;
-    if (Qg >= (int64_t)1 << 31) return CT_ERR_TOO_LARGE;
-    if (geom->image_stride < Ql) return CT_ERR_INVALID_ARGUMENT;
-    if (geom->layout < CT_LAYOUT_NCHW || geom->layout > CT_LAYOUT_NHWC_BGR) return CT_ERR_INVALID_ARGUMENT;
+    const int64_t Ql = local_elements(geom);
     StatsArgs a{};
     a.frames = frames_dev;
     a.lut = icrf->lut_dev;
     a.mean_state = mean_state_dev;
     a.m2_state = m2_state_dev;
     a.image_stride = geom->image_stride;
-    a.tile.plane_local = (uint32_t)(geom->h_tile * geom->width);
-    a.tile.chan_skip = (uint32_t)((geom->h_global - geom->h_tile) * geom->width);
-    a.tile.base = (uint32_t)(geom->row_offset * geom->width);
-    a.tile.layout = (uint32_t)geom->layout;  // frames planar or interleaved; the state is always planar (C, H, W)
-    a.tile.channels = (uint32_t)geom->channels;
+    a.tile = make_tile(geom);  // frames planar or interleaved; the state is always planar (C, H, W)
     a.batch = batch;
     a.channels = geom->channels;
-    a.n_points = interp == CT_INTERP_NONE ? 2 : icrf->n_points;
+    a.n_points = icrf_points(icrf);
     a.count_before = frames_before;
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (dtype) {

@@ -33,6 +33,7 @@
 // Every load is that of a code of the thread's own elements (pixels) in one of the B frames, every store lies in the
 // thread's own elements of mean_state and m2_state.  The consts of a CT_INGEST_AFFINE_DATA stage are read once per thread,
 // before anything is stored.  No atomics, no LDS traffic besides the LUT, the frames are read only.
+#include "ct_args.hpp"
 #include "ct_ingest_stages.hpp"
 #include "ct_stats_merge.hpp"
 
@@ -218,7 +219,7 @@ __global__ __launch_bounds__(kBlock) void video_stats_ingest_kernel(const StatsI
 template <typename T, bool PACKED, int G, int INTERP, bool DATA>
 static int si_launch(const StatsIngestArgs &a, uint32_t threads_x, hipStream_t s)
 {
-    const size_t lds = INTERP == CT_INTERP_NONE ? 0 : (size_t)a.channels * a.n_points * lut_entry_bytes(INTERP);
+    const size_t lds = lut_lds_bytes(INTERP, a.channels, a.n_points);
     const dim3 grid((threads_x + kBlock - 1) / kBlock, PACKED ? 1u : (uint32_t)a.channels), block(kBlock);
     if (a.batch <= 16)
         hipLaunchKernelGGL((video_stats_ingest_kernel<T, PACKED, G, INTERP, 16, DATA>), grid, block, lds, s, a);
@@ -262,33 +263,17 @@ extern "C" int ct_video_stats_ingest_batch(const void *frames_dev, int32_t dtype
                                            void *stream)
 {
     using namespace ct;
-    // everything that needs no pointer into device memory first: geometry (as ct_video_stats_batch, an empty plane allowed),
-    // the stack and the stage list (as ct_ingest_transform / _data), the model
-    if (!geom || !icrf) return CT_ERR_INVALID_ARGUMENT;
-    if (geom->channels <= 0 || geom->h_tile < 0 || geom->width < 0 || geom->h_global < geom->h_tile || geom->row_offset < 0 ||
-        geom->row_offset + geom->h_tile > geom->h_global)
-        return CT_ERR_INVALID_ARGUMENT;
-    if (geom->layout < CT_LAYOUT_NCHW || geom->layout > CT_LAYOUT_NHWC_BGR) return CT_ERR_INVALID_ARGUMENT;
-    if (geom->h_global * geom->width * geom->channels >= (int64_t)1 << 31) return CT_ERR_TOO_LARGE;
-    const int64_t plane = geom->h_tile * geom->width;
+    // everything that needs no pointer into device memory first: geometry (an empty plane allowed), the stack and the stage
+    // list of 8-bit / 16-bit codes, the model (check_code_ingest, which ct_hdr_merge_ingest_batch shares)
     bool by_channel = false;
-    const int rc = ingest_validate(dtype, geom->layout, batch, geom->channels, plane, stages, n_stages, CT_INGEST_MAX_STAGES,
-                                   consts_dev ? 1 : 0, by_channel);
-    if (rc != CT_OK) return rc;
-    if (dtype == CT_DTYPE_F32) return CT_ERR_UNSUPPORTED;  // float32 pixels have no copy to save: ct_video_stats_batch takes them
-    if (reinterpret_cast<uintptr_t>(consts_dev) % sizeof(float) != 0) return CT_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_code_ingest(dtype, batch, geom, stages, n_stages, consts_dev, icrf, by_channel); rc != CT_OK) return rc;
+    const int64_t plane = geom->h_tile * geom->width;
     const int interp = icrf->interp;
-    if (interp < CT_INTERP_LOOKUP || interp > CT_INTERP_NONE) return CT_ERR_INVALID_ARGUMENT;
-    if (interp != CT_INTERP_NONE && (!icrf->lut_dev || icrf->n_points < 2)) return CT_ERR_INVALID_ARGUMENT;
-    if (!(frames_before >= 0.0f)) return CT_ERR_INVALID_ARGUMENT;
-    if (geom->image_stride < plane * geom->channels) return CT_ERR_INVALID_ARGUMENT;
-    const int n_points = interp == CT_INTERP_NONE ? 2 : icrf->n_points;
-    if (interp != CT_INTERP_NONE && (size_t)geom->channels * (size_t)n_points * lut_entry_bytes(interp) > 160 * 1024)
-        return CT_ERR_TOO_LARGE;
+    if (!(frames_before >= 0.0f) || !stride_holds_image(geom)) return CT_ERR_INVALID_ARGUMENT;
+    if (lut_lds_bytes(interp, geom->channels, icrf->n_points) > kLdsBudget) return CT_ERR_TOO_LARGE;
     const bool packed = geom->layout != CT_LAYOUT_NCHW;
     if (!packed && geom->channels > 65535) return CT_ERR_TOO_LARGE;  // a plane is a row of the grid
     if (batch == 0 || plane == 0) return CT_OK;
-    auto aligned = [](const void *p, uintptr_t b) { return reinterpret_cast<uintptr_t>(p) % b == 0; };
     if (!frames_dev || !mean_state_dev || !m2_state_dev) return CT_ERR_INVALID_ARGUMENT;
     if (!aligned(frames_dev, dtype == CT_DTYPE_U16 ? 2 : 1) || !aligned(mean_state_dev, sizeof(float)) || !aligned(m2_state_dev, sizeof(float)))
         return CT_ERR_INVALID_ARGUMENT;
@@ -298,18 +283,9 @@ extern "C" int ct_video_stats_ingest_batch(const void *frames_dev, int32_t dtype
     a.lut = icrf->lut_dev;
     a.mean_state = mean_state_dev;
     a.m2_state = m2_state_dev;
-    a.image_stride = geom->image_stride;
-    a.plane = (uint32_t)plane;
-    a.plane_global = (uint32_t)(geom->h_global * geom->width);
-    a.base = (uint32_t)(geom->row_offset * geom->width);
+    fill_ingest_args(a, geom, icrf_points(icrf), by_channel, stages, n_stages);
     a.batch = batch;
-    a.channels = geom->channels;
-    a.n_points = n_points;
-    a.reversed = geom->layout == CT_LAYOUT_NHWC_BGR ? 1u : 0u;
-    a.by_channel = by_channel ? 1u : 0u;
     a.count_before = frames_before;
-    a.n_stages = (uint32_t)n_stages;
-    for (int32_t k = 0; k < n_stages; ++k) a.stage[k] = stages[k];
     hipStream_t s = static_cast<hipStream_t>(stream);
     return dtype == CT_DTYPE_U8 ? si_dispatch<uint8_t>(a, packed, interp, s) : si_dispatch<uint16_t>(a, packed, interp, s);
 }

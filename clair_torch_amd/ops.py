@@ -58,21 +58,39 @@ def _out_shape(stack: torch.Tensor, layout: str, out_layout: str):
     return tuple(stack.shape[1:]) if out_layout == "input" else tuple(_chw(stack, layout))
 
 
-def _geometry(stack: torch.Tensor, tile: Optional[TileGeometry], layout: str = "nchw") -> nv.Geometry:
-    c, h, w = _chw(stack, layout)
+def _tile_rows(h: int, tile: Optional[TileGeometry]):
+    """(h_global, row_offset) of a band of ``h`` rows: the band itself without ``tile``."""
     hg, r0 = (h, 0) if tile is None else (tile.h_global, tile.row_offset)
     if r0 < 0 or r0 + h > hg:
         raise ValueError(f"tile rows [{r0}, {r0 + h}) do not fit a global height of {hg}")
+    return hg, r0
+
+
+def _geometry(stack: torch.Tensor, tile: Optional[TileGeometry], layout: str = "nchw") -> nv.Geometry:
+    c, h, w = _chw(stack, layout)
+    hg, r0 = _tile_rows(h, tile)
     return nv.Geometry(channels=c, h_tile=h, width=w, h_global=hg, row_offset=r0, image_stride=stack.stride(0),
                        layout=_LAYOUT[layout])
 
 
-def _check_stack(stack: torch.Tensor, name="stack"):
+def _ingest_geometry(shape, tile: Optional[TileGeometry], layout: str) -> nv.Geometry:
+    """Geometry of a contiguous stack the ingest fronts take, from its planar shape (B, C, H, W) (``ingest_shape``)."""
+    _, c, h, w = shape
+    hg, r0 = _tile_rows(h, tile)
+    return nv.Geometry(channels=c, h_tile=h, width=w, h_global=hg, row_offset=r0, image_stride=c * h * w, layout=_LAYOUT[layout])
+
+
+def _check_4d(stack: torch.Tensor, name: str, dims: str):
+    """A 4-dimensional device tensor of a dtype the kernels read; ``dims``: how the caller words the four dimensions."""
     _require_device(stack, name)
     if stack.ndim != 4:
-        raise ValueError(f"{name} must be (N, C, H, W), got shape {tuple(stack.shape)}")
+        raise ValueError(f"{name} must be {dims}, got shape {tuple(stack.shape)}")
     if stack.dtype not in _DTYPE:
         raise TypeError(f"{name} dtype {stack.dtype} unsupported (uint8, uint16 codes or float32 pixels)")
+
+
+def _check_stack(stack: torch.Tensor, name="stack"):
+    _check_4d(stack, name, "(N, C, H, W)")
     if stack.shape[0] > 0 and not stack[0].is_contiguous():
         raise ValueError(f"every image of {name} must be contiguous (C, H, W)")
 
@@ -84,11 +102,75 @@ def _default_max_code(t: torch.Tensor, max_code):
     return max_code
 
 
-def _explicit_std(std: torch.Tensor, stack: torch.Tensor, name: str = "stack"):
+def _explicit_std(std: torch.Tensor, stack: torch.Tensor, name: str = "stack", shapes: bool = False):
+    """Explicit uncertainties in the stack's own layout as the kernels read them: float32, contiguous.  ``shapes``: the
+    merge fronts' message, which names the two shapes."""
     _require_device(std, "std")
     if std.shape != stack.shape:
-        raise ValueError(f"std shape != {name} shape")
+        raise ValueError(f"std shape {tuple(std.shape)} != stack shape {tuple(stack.shape)}" if shapes else f"std shape != {name} shape")
     return std.to(torch.float32).contiguous()
+
+
+def _planar_std(std: torch.Tensor, shape, device, like: str):
+    """Explicit uncertainties of an ingest front: float32 and planar ``shape`` like the ``like`` (outputs / state)."""
+    _require_device(std, "std")
+    if std.dtype != torch.float32 or tuple(std.shape) != shape or std.device != device:
+        raise ValueError(f"std must be a float32 tensor of shape {shape} (planar, like the {like}) on {device}")
+    return std.contiguous()
+
+
+def _exposures_to_device(exposures: torch.Tensor, batch: int, device):
+    """The ``batch`` exposure times as float64 on ``device``."""
+    if exposures.is_cuda or device.type != "cuda":
+        exposure_dev = exposures.to(device=device, dtype=torch.float64).contiguous()
+    else:
+        # A copy from pageable host memory blocks the host until the stream reaches it -- i.e. until the previous merge
+        # kernel has finished -- which serialises this call's host work with the device (measured: 1.18 ms per
+        # compute_hdr_image call against a 0.95 ms kernel).  Staged through pinned memory the copy is asynchronous.
+        exposure_dev = exposures.to(torch.float64).contiguous().pin_memory().to(device, non_blocking=True)
+    if exposure_dev.numel() != batch:
+        raise ValueError(f"{exposure_dev.numel()} exposure times for a batch of {batch}")
+    return exposure_dev
+
+
+def _exposure_list_to_device(exposures, sizes, device):
+    """The exposure times of several batches of ``sizes`` frames, one after the other, as float64 on ``device`` (staged
+    through pinned memory: see ``_exposures_to_device``)."""
+    for e, n in zip(exposures, sizes):
+        if e.numel() != n:
+            raise ValueError(f"{e.numel()} exposure times for a batch of {n}")
+    host_exp = torch.cat([e.detach().to("cpu", torch.float64).reshape(-1) for e in exposures])
+    return host_exp.pin_memory().to(device, non_blocking=True) if device.type == "cuda" else host_exp
+
+
+def _lin_std_out(out, shape, device, want_std: bool, lin_required: bool):
+    """The (lin, std | None) float32 outputs of a linearization: fresh ones, or the caller's ``out`` pair checked.
+    ``lin_required``: refuse a pair without out[0] here (else the library does)."""
+    if out is None:
+        lin = torch.empty(shape, dtype=torch.float32, device=device)
+        return lin, (torch.empty_like(lin) if want_std else None)
+    lin, std_out = out
+    for name, t in (("out[0]", lin), ("out[1]", std_out)):
+        if t is None:
+            continue
+        _require_device(t, name)
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape}")
+    if lin_required and lin is None:
+        raise ValueError("out[0] is required")
+    if want_std and std_out is None:
+        raise ValueError("want_std needs out[1]")
+    return lin, (std_out if want_std else None)
+
+
+def _check_stats_state(mean_state, m2_state, shape, device=None):
+    """The running (mean, m2) state: contiguous float32 ``shape``; on ``device`` where the caller names one."""
+    what = "(C,H,W) tensor" if device is None else f"(C,H,W) = {shape} tensor on {device}"
+    for name, t in (("mean_state", mean_state), ("m2_state", m2_state)):
+        _require_device(t, name)
+        if (t.dtype != torch.float32 or tuple(t.shape) != shape or (device is not None and t.device != device)
+                or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous float32 {what}")
 
 
 def _checked_out(out, shape, dtype, device, dtype_name=None):
@@ -112,6 +194,13 @@ def _icrf_struct(lut: Optional[torch.Tensor], interp, channels):
         raise ValueError(f"Unknown interpolation mode {interp}")
     lut_c = lut.detach().to(torch.float32).contiguous()
     return nv.Icrf(lut_dev=lut_c.data_ptr(), n_points=lut_c.shape[1], interp=_INTERP[interp]), lut_c
+
+
+def _state_ptrs(state):
+    """(mean, sumw, var) pointers of a MergeState; NULL for no state / no variance buffer."""
+    if not state:
+        return None, None, None
+    return _ptr(state.mean), _ptr(state.sumw), _ptr(state.var)
 
 
 class MergeState:
@@ -188,23 +277,13 @@ def hdr_merge_batch(stack: torch.Tensor, exposures: torch.Tensor, *, lut: Option
         std_mode = "explicit"
         _require_device(std, "std")
         if std.shape != stack.shape or std.dtype != torch.float32 or std.stride() != stack.stride():
-            if std.shape != stack.shape:
-                raise ValueError(f"std shape {tuple(std.shape)} != stack shape {tuple(stack.shape)}")
-            std = std.to(torch.float32).contiguous()
+            std = _explicit_std(std, stack, shapes=True)
             if std.stride() != stack.stride():
                 stack = stack.contiguous()
     if std_mode not in _STD:
         raise ValueError(f"unknown std_mode {std_mode}")
     max_code = _default_max_code(stack, max_code)
-    if exposures.is_cuda or dev.type != "cuda":
-        exposure_dev = exposures.to(device=dev, dtype=torch.float64).contiguous()
-    else:
-        # A copy from pageable host memory blocks the host until the stream reaches it -- i.e. until the previous merge
-        # kernel has finished -- which serialises this call's host work with the device (measured: 1.18 ms per
-        # compute_hdr_image call against a 0.95 ms kernel).  Staged through pinned memory the copy is asynchronous.
-        exposure_dev = exposures.to(torch.float64).contiguous().pin_memory().to(dev, non_blocking=True)
-    if exposure_dev.numel() != b:
-        raise ValueError(f"{exposure_dev.numel()} exposure times for a batch of {b}")
+    exposure_dev = _exposures_to_device(exposures, b, dev)
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _geometry(stack, tile, layout)
     flags, _, mean_out, std_out = _merge_setup(stack, layout, out_layout, state, finalize, std_mode != "none", mean_dtype,
@@ -213,9 +292,7 @@ def hdr_merge_batch(stack: torch.Tensor, exposures: torch.Tensor, *, lut: Option
         rc = nv.load().ct_hdr_merge_batch(
             _ptr(stack), _DTYPE[stack.dtype], float(max_code or 1.0), b, ctypes.byref(geom), _ptr(std), _STD[std_mode],
             float(std_value), _ptr(exposure_dev), ctypes.byref(icrf), nv.WEIGHT_GAUSS if gaussian_weight else nv.WEIGHT_NONE,
-            _ptr(state.mean) if state else None, _ptr(state.sumw) if state else None,
-            _ptr(state.var) if (state and state.var is not None) else None, _ptr(mean_out), _ptr(std_out), flags,
-            _stream(dev))
+            *_state_ptrs(state), _ptr(mean_out), _ptr(std_out), flags, _stream(dev))
     nv.check(rc, "ct_hdr_merge_batch")
     del lut_keep
     if state is not None:
@@ -257,20 +334,13 @@ def hdr_merge_batches(stacks, exposures, *, lut: Optional[torch.Tensor] = None, 
     c, h, w = _chw(stacks[0], layout)
     if stds is not None:
         std_mode = "explicit"
-        stds = [sd.to(device=dev, dtype=torch.float32).contiguous() for sd in stds]
-        for sd, t in zip(stds, stacks):
-            if sd.shape != t.shape:
-                raise ValueError(f"std shape {tuple(sd.shape)} != stack shape {tuple(t.shape)}")
+        stds = [_explicit_std(sd.to(dev), t, shapes=True) for sd, t in zip(stds, stacks)]
     if std_mode not in _STD:
         raise ValueError(f"unknown std_mode {std_mode}")
     stacks = [t.contiguous() for t in stacks]
     max_code = _default_max_code(stacks[0], max_code)
     sizes = [int(t.shape[0]) for t in stacks]
-    for e, n in zip(exposures, sizes):
-        if e.numel() != n:
-            raise ValueError(f"{e.numel()} exposure times for a batch of {n}")
-    host_exp = torch.cat([e.detach().to("cpu", torch.float64).reshape(-1) for e in exposures])
-    exposure_dev = host_exp.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else host_exp
+    exposure_dev = _exposure_list_to_device(exposures, sizes, dev)
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _geometry(stacks[0], tile, layout)
     has_std = std_mode != "none"
@@ -287,8 +357,7 @@ def hdr_merge_batches(stacks, exposures, *, lut: Optional[torch.Tensor] = None, 
         rc = nv.load().ct_hdr_merge_batches(
             ptr_arr, std_arr, size_arr, k, _DTYPE[stacks[0].dtype], float(max_code or 1.0), ctypes.byref(geom), _STD[std_mode],
             float(std_value), _ptr(exposure_dev), ctypes.byref(icrf), nv.WEIGHT_GAUSS if gaussian_weight else nv.WEIGHT_NONE,
-            _ptr(state.mean), _ptr(state.sumw), _ptr(state.var) if state.var is not None else None, _ptr(mean_out),
-            _ptr(std_out), flags, _stream(dev))
+            *_state_ptrs(state), _ptr(mean_out), _ptr(std_out), flags, _stream(dev))
     nv.check(rc, "ct_hdr_merge_batches")
     del lut_keep
     state.batches += k
@@ -313,21 +382,7 @@ def linearize_frames(frames: torch.Tensor, lut: torch.Tensor, interp: str = "lin
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     frames = frames.contiguous()
     geom = _geometry(frames, tile, layout)
-    if out is None:
-        lin = torch.empty((f, c, h, w), dtype=torch.float32, device=dev)
-        std_out = torch.empty_like(lin) if want_std else None
-    else:
-        lin, std_out = out
-        for name, t in (("out[0]", lin), ("out[1]", std_out)):
-            if t is None:
-                continue
-            _require_device(t, name)
-            if t.dtype != torch.float32 or tuple(t.shape) != (f, c, h, w) or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous float32 tensor of shape {(f, c, h, w)}")
-        if want_std and std_out is None:
-            raise ValueError("want_std needs out[1]")
-        if not want_std:
-            std_out = None
+    lin, std_out = _lin_std_out(out, (f, c, h, w), dev, want_std, lin_required=False)
     with torch.cuda.device(dev):
         rc = nv.load().ct_linearize_std(_ptr(frames), _DTYPE[frames.dtype], float(max_code or 1.0), f, ctypes.byref(geom),
                                         _ptr(std), _STD[std_mode], float(std_value), ctypes.byref(icrf), _ptr(lin),
@@ -758,12 +813,9 @@ def _ingest_stages(stages, channels: int, data: bool = False, limit: int = nv.IN
     return arr, len(stages)
 
 
-def _check_ingest_stack(stack: torch.Tensor, layout: str, for_ingest: bool = True):
-    _require_device(stack, "stack")
-    if stack.ndim != 4:
-        raise ValueError(f"stack must be 4-dimensional, got shape {tuple(stack.shape)}")
-    if stack.dtype not in _DTYPE:
-        raise TypeError(f"stack dtype {stack.dtype} unsupported (uint8, uint16 codes or float32 pixels)")
+def _check_ingest_stack(stack: torch.Tensor, layout: str, for_ingest: bool = True, codes_only: Optional[str] = None):
+    """A stack the ingest fronts take.  ``codes_only``: the TypeError text of a front that takes no float32 pixels."""
+    _check_4d(stack, "stack", "4-dimensional")
     if layout not in _LAYOUT:
         raise ValueError(f"unknown layout {layout!r} (nchw, nhwc, nhwc_bgr)")
     if not for_ingest:  # strided_downscale: pixels of any size, and it makes the stack contiguous itself
@@ -772,6 +824,8 @@ def _check_ingest_stack(stack: torch.Tensor, layout: str, for_ingest: bool = Tru
         raise ValueError(f"layout {layout!r} takes (B, H, W, 3) frames, got shape {tuple(stack.shape)}")
     if not stack.is_contiguous():
         raise ValueError("stack must be contiguous")
+    if codes_only is not None and stack.dtype == torch.float32:
+        raise TypeError(codes_only)
 
 
 def _check_consts(consts, device):
@@ -830,35 +884,12 @@ def linearize_ingest_frames(frames: torch.Tensor, stages, lut: Optional[torch.Te
     dev = frames.device
     arr, n_stages = _ingest_stages(stages, c)
     if std is not None:
-        std_mode = "explicit"
-        _require_device(std, "std")
-        if std.dtype != torch.float32 or tuple(std.shape) != shape or std.device != dev:
-            raise ValueError(f"std must be a float32 tensor of shape {shape} (planar, like the outputs) on {dev}")
-        std = std.contiguous()
+        std_mode, std = "explicit", _planar_std(std, shape, dev, "outputs")
     if std_mode not in _STD:
         raise ValueError(f"unknown std_mode {std_mode}")
     icrf, lut_keep = _icrf_struct(lut, interp, c)
-    hg, r0 = (h, 0) if tile is None else (tile.h_global, tile.row_offset)
-    if r0 < 0 or r0 + h > hg:
-        raise ValueError(f"tile rows [{r0}, {r0 + h}) do not fit a global height of {hg}")
-    geom = nv.Geometry(channels=c, h_tile=h, width=w, h_global=hg, row_offset=r0, image_stride=c * h * w, layout=_LAYOUT[layout])
-    if out is None:
-        lin = torch.empty(shape, dtype=torch.float32, device=dev)
-        std_out = torch.empty_like(lin) if want_std else None
-    else:
-        lin, std_out = out
-        for name, t in (("out[0]", lin), ("out[1]", std_out)):
-            if t is None:
-                continue
-            _require_device(t, name)
-            if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape}")
-        if lin is None:
-            raise ValueError("out[0] is required")
-        if want_std and std_out is None:
-            raise ValueError("want_std needs out[1]")
-        if not want_std:
-            std_out = None
+    geom = _ingest_geometry(shape, tile, layout)
+    lin, std_out = _lin_std_out(out, shape, dev, want_std, lin_required=True)
     if frames.numel() == 0:
         return lin, std_out
     with torch.cuda.device(dev):
@@ -888,9 +919,8 @@ def hdr_merge_ingest_batch(frames: torch.Tensor, stages, exposures: torch.Tensor
     ``hdr_merge_batch``.  ``reference_order``: False = the closed-form kernels for LOOKUP / CATMULL with uncertainties as
     well (CT_MERGE_CLOSED_FORM); None leaves those two modes, and True every mode, to the reference-order kernel, which
     this entry point does not have (NativeLibraryError: use ``ingest_transform`` + ``hdr_merge_batch``)."""
-    _check_ingest_stack(frames, layout)
-    if frames.dtype == torch.float32:
-        raise TypeError("hdr_merge_ingest_batch takes uint8 / uint16 codes (float32 pixels: ingest_transform + hdr_merge_batch)")
+    _check_ingest_stack(frames, layout, codes_only="hdr_merge_ingest_batch takes uint8 / uint16 codes (float32 pixels: "
+                                                   "ingest_transform + hdr_merge_batch)")
     shape = ingest_shape(tuple(frames.shape), layout)
     b, c, h, w = shape
     dev = frames.device
@@ -900,24 +930,12 @@ def hdr_merge_ingest_batch(frames: torch.Tensor, stages, exposures: torch.Tensor
     if consts is not None:
         _check_consts(consts, dev)
     if std is not None:
-        std_mode = "explicit"
-        _require_device(std, "std")
-        if std.dtype != torch.float32 or tuple(std.shape) != shape or std.device != dev:
-            raise ValueError(f"std must be a float32 tensor of shape {shape} (planar, like the state) on {dev}")
-        std = std.contiguous()
+        std_mode, std = "explicit", _planar_std(std, shape, dev, "state")
     if std_mode not in _STD:
         raise ValueError(f"unknown std_mode {std_mode}")
-    if exposures.is_cuda:
-        exposure_dev = exposures.to(device=dev, dtype=torch.float64).contiguous()
-    else:  # staged through pinned memory the copy does not wait for the stream (see hdr_merge_batch)
-        exposure_dev = exposures.to(torch.float64).contiguous().pin_memory().to(dev, non_blocking=True)
-    if exposure_dev.numel() != b:
-        raise ValueError(f"{exposure_dev.numel()} exposure times for a batch of {b}")
+    exposure_dev = _exposures_to_device(exposures, b, dev)
     icrf, lut_keep = _icrf_struct(lut, interp, c)
-    hg, r0 = (h, 0) if tile is None else (tile.h_global, tile.row_offset)
-    if r0 < 0 or r0 + h > hg:
-        raise ValueError(f"tile rows [{r0}, {r0 + h}) do not fit a global height of {hg}")
-    geom = nv.Geometry(channels=c, h_tile=h, width=w, h_global=hg, row_offset=r0, image_stride=c * h * w, layout=_LAYOUT[layout])
+    geom = _ingest_geometry(shape, tile, layout)
     # (state and outputs are planar whatever the order of the source)
     flags, _, mean_out, std_out = _merge_setup_for((c, h, w), dev, "planar", state, finalize, std_mode != "none", mean_dtype,
                                                    reference_order, 0, "batch")
@@ -925,8 +943,7 @@ def hdr_merge_ingest_batch(frames: torch.Tensor, stages, exposures: torch.Tensor
         rc = nv.load().ct_hdr_merge_ingest_batch(
             _ptr(frames), _DTYPE[frames.dtype], b, ctypes.byref(geom), arr, n_stages, _ptr(consts), _ptr(std), _STD[std_mode],
             float(std_value), _ptr(exposure_dev), ctypes.byref(icrf), nv.WEIGHT_GAUSS if gaussian_weight else nv.WEIGHT_NONE,
-            _ptr(state.mean) if state else None, _ptr(state.sumw) if state else None,
-            _ptr(state.var) if (state and state.var is not None) else None, _ptr(mean_out), _ptr(std_out), flags, _stream(dev))
+            *_state_ptrs(state), _ptr(mean_out), _ptr(std_out), flags, _stream(dev))
     nv.check(rc, "ct_hdr_merge_ingest_batch")
     del lut_keep
     if state is not None:
@@ -962,15 +979,15 @@ def hdr_merge_ingest_batches(frames_list, stages, exposures_list, *, lut: Option
                                       layout=layout, reference_order=reference_order, consts=None if consts is None else consts[0])
     f0 = frames_list[0]
     for t in frames_list:
-        _check_ingest_stack(t, layout)
-        if t.dtype == torch.float32:
-            raise TypeError("hdr_merge_ingest_batches takes uint8 / uint16 codes (float32 pixels: ingest_transform + hdr_merge_batches)")
+        _check_ingest_stack(t, layout, codes_only="hdr_merge_ingest_batches takes uint8 / uint16 codes (float32 pixels: "
+                                                  "ingest_transform + hdr_merge_batches)")
         if t.dtype != f0.dtype or t.shape[1:] != f0.shape[1:] or t.device != f0.device:
             raise ValueError("all batches of one call must share dtype, image shape and device")
         if t.shape[0] < 1:
             raise ValueError("empty batch")
     dev = f0.device
-    _, c, h, w = ingest_shape(tuple(f0.shape), layout)
+    shape0 = ingest_shape(tuple(f0.shape), layout)
+    _, c, h, w = shape0
     has_consts = consts is not None and any(t is not None for t in consts)
     arr, n_stages = _ingest_stages(stages, c, data=has_consts)
     if consts is not None:
@@ -979,26 +996,13 @@ def hdr_merge_ingest_batches(frames_list, stages, exposures_list, *, lut: Option
                 _check_consts(t, dev)
     if stds is not None:
         std_mode = "explicit"
-        for sd, t in zip(stds, frames_list):
-            _require_device(sd, "std")
-            shape = ingest_shape(tuple(t.shape), layout)
-            if sd.dtype != torch.float32 or tuple(sd.shape) != shape or sd.device != dev:
-                raise ValueError(f"std must be a float32 tensor of shape {shape} (planar, like the state) on {dev}")
-        stds = [sd.contiguous() for sd in stds]
+        stds = [_planar_std(sd, ingest_shape(tuple(t.shape), layout), dev, "state") for sd, t in zip(stds, frames_list)]
     if std_mode not in _STD:
         raise ValueError(f"unknown std_mode {std_mode}")
     sizes = [int(t.shape[0]) for t in frames_list]
-    for e, n in zip(exposures_list, sizes):
-        if e.numel() != n:
-            raise ValueError(f"{e.numel()} exposure times for a batch of {n}")
-    # staged through pinned memory the copy does not wait for the stream (see hdr_merge_batch)
-    host_exp = torch.cat([e.detach().to("cpu", torch.float64).reshape(-1) for e in exposures_list])
-    exposure_dev = host_exp.pin_memory().to(dev, non_blocking=True)
+    exposure_dev = _exposure_list_to_device(exposures_list, sizes, dev)
     icrf, lut_keep = _icrf_struct(lut, interp, c)
-    hg, r0 = (h, 0) if tile is None else (tile.h_global, tile.row_offset)
-    if r0 < 0 or r0 + h > hg:
-        raise ValueError(f"tile rows [{r0}, {r0 + h}) do not fit a global height of {hg}")
-    geom = nv.Geometry(channels=c, h_tile=h, width=w, h_global=hg, row_offset=r0, image_stride=c * h * w, layout=_LAYOUT[layout])
+    geom = _ingest_geometry(shape0, tile, layout)
     has_std = std_mode != "none"
     flags, out_shape, mean_out, std_out = _merge_setup_for((c, h, w), dev, "planar", state, finalize, has_std, mean_dtype, reference_order,
                                                            nv.MERGE_REQUIRE_ONE_LAUNCH if require_one_launch else 0, "call")
@@ -1012,8 +1016,7 @@ def hdr_merge_ingest_batches(frames_list, stages, exposures_list, *, lut: Option
             return nv.load().ct_hdr_merge_ingest_batches(
                 ptr_arr, size_arr, k, _DTYPE[f0.dtype], ctypes.byref(geom), arr, n_stages, consts_arr, std_arr, _STD[std_mode],
                 float(std_value), _ptr(exposure_dev), ctypes.byref(icrf), nv.WEIGHT_GAUSS if gaussian_weight else nv.WEIGHT_NONE,
-                _ptr(st.mean) if st else None, _ptr(st.sumw) if st else None,
-                _ptr(st.var) if (st and st.var is not None) else None, _ptr(mean_out), _ptr(std_out), fl, _stream(dev))
+                *_state_ptrs(st), _ptr(mean_out), _ptr(std_out), fl, _stream(dev))
 
     # a whole merge in one launch needs no state arrays at all; only what cannot run as one launch walks the batches with
     # the state in memory (nothing has been launched when the library says so)
@@ -1106,10 +1109,7 @@ def video_stats_batch(frames: torch.Tensor, mean_state: torch.Tensor, m2_state: 
     dev = frames.device
     frames = frames.contiguous()
     max_code = _default_max_code(frames, max_code)
-    for name, t in (("mean_state", mean_state), ("m2_state", m2_state)):
-        _require_device(t, name)
-        if t.dtype != torch.float32 or tuple(t.shape) != (c, h, w) or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous float32 (C,H,W) tensor")
+    _check_stats_state(mean_state, m2_state, (c, h, w))
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _geometry(frames, tile, layout)
     with torch.cuda.device(dev):
@@ -1132,23 +1132,17 @@ def video_stats_ingest_batch(frames: torch.Tensor, stages, mean_state: torch.Ten
     ``ingest_extrema`` returned) one of them may be ("affine_data", mul, add).  ``mean_state``, ``m2_state``: contiguous
     float32 (C,H,W), planar whatever the layout of the frames (``ingest_shape(frames.shape, layout)[1:]``).
     ``frames_before``, ``lut``, ``interp``, ``tile``: as in ``video_stats_batch``."""
-    _check_ingest_stack(frames, layout)
-    if frames.dtype == torch.float32:
-        raise TypeError("video_stats_ingest_batch takes uint8 / uint16 codes (float32 pixels: ingest_transform + video_stats_batch)")
-    b, c, h, w = ingest_shape(tuple(frames.shape), layout)
+    _check_ingest_stack(frames, layout, codes_only="video_stats_ingest_batch takes uint8 / uint16 codes (float32 pixels: "
+                                                   "ingest_transform + video_stats_batch)")
+    shape = ingest_shape(tuple(frames.shape), layout)
+    b, c, h, w = shape
     dev = frames.device
     arr, n_stages = _ingest_stages(stages, c, data=consts is not None)
     if consts is not None:
         _check_consts(consts, dev)
-    for name, t in (("mean_state", mean_state), ("m2_state", m2_state)):
-        _require_device(t, name)
-        if t.dtype != torch.float32 or tuple(t.shape) != (c, h, w) or t.device != dev or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous float32 (C,H,W) = {(c, h, w)} tensor on {dev}")
+    _check_stats_state(mean_state, m2_state, (c, h, w), dev)
     icrf, lut_keep = _icrf_struct(lut, interp, c)
-    hg, r0 = (h, 0) if tile is None else (tile.h_global, tile.row_offset)
-    if r0 < 0 or r0 + h > hg:
-        raise ValueError(f"tile rows [{r0}, {r0 + h}) do not fit a global height of {hg}")
-    geom = nv.Geometry(channels=c, h_tile=h, width=w, h_global=hg, row_offset=r0, image_stride=c * h * w, layout=_LAYOUT[layout])
+    geom = _ingest_geometry(shape, tile, layout)
     with torch.cuda.device(dev):
         rc = nv.load().ct_video_stats_ingest_batch(_ptr(frames), _DTYPE[frames.dtype], b, ctypes.byref(geom), arr, n_stages,
                                                    _ptr(consts), ctypes.byref(icrf), float(frames_before), _ptr(mean_state),

@@ -903,3 +903,14 @@ def test_torch_library_ops_are_registered_with_schemas_and_fake_kernels():
         assert tuple(st.shape) == (6, 3) and st.dtype == torch.float64
     with pytest.raises(RuntimeError, match="MI355X"):
         torch.ops.clair_hip.icrf_forward(torch.zeros((1, 3, 4, 4)), torch.zeros((3, 16)), "linear")
+
+
+def test_one_hip_runtime_whichever_of_torch_and_the_library_loads_first(lib):
+    """torch's wheel carries a HIP runtime whose file name is not the soname the library links against: loaded before torch,
+    the library used to bring the system's runtime in as a second one, and its first launch on a torch stream failed
+    (CT_ERR_LAUNCH from build() followed by smoke() in one process).  _native.load() imports torch first."""
+    import subprocess
+    code = ("from clair_torch_amd import _native; _native.load(); import torch; "
+            "print(len({l.split()[-1] for l in open('/proc/self/maps') if 'libamdhip64' in l}))")
+    out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, check=True)
+    assert out.stdout.strip() == "1", out.stdout + out.stderr
