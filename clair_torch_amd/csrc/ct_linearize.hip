@@ -53,28 +53,15 @@ __global__ __launch_bounds__(kBlock) void linearize_kernel(const LinArgs a)
     const uint32_t q0 = a.q_begin + vec * (uint32_t)V;
     const float top = (float)(L - 1);
     int row_off[V];
-    if (a.tile.layout == CT_LAYOUT_NCHW) {
-        // planar frames: the channel by comparisons, the row of the first element by ONE modulo (a constant divisor for
-        // C == 3), the following elements by an add and a conditional subtract -- runtime 32-bit divisions cost ~30
-        // instructions each, and two of them per element were a third of this kernel's arithmetic
+    if (V == 1 && a.tile.layout == CT_LAYOUT_NCHW) {
+        // planar frames come here one element per thread only (lin_typed: their packets go to linearize_planar_kernel):
+        // the channel by comparisons and the row by ONE modulo (a constant divisor for C == 3) -- runtime 32-bit
+        // divisions cost ~30 instructions each
         int ch = 0;
         for (int c = 1; c < C; ++c) ch += q0 >= (uint32_t)c * a.tile.plane_local ? 1 : 0;
         const uint32_t qg = q0 + (uint32_t)ch * a.tile.chan_skip + a.tile.base;
-        uint32_t off = q0 - (uint32_t)ch * a.tile.plane_local;
-        int r = C == 3 ? (int)(qg % 3u) : (int)(qg % (uint32_t)C);
-        const int skip_mod = (int)(a.tile.chan_skip % (uint32_t)C);
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            row_off[e] = (INTERP == CT_INTERP_LOOKUP ? ch : r) * L * kEntry;
-            int inc = 1;
-            if (++off == a.tile.plane_local) {
-                off = 0;
-                ++ch;
-                inc += skip_mod;
-            }
-            r += inc;
-            r = r >= C ? r - C : r;
-        }
+        const int r = C == 3 ? (int)(qg % 3u) : (int)(qg % (uint32_t)C);
+        row_off[0] = (INTERP == CT_INTERP_LOOKUP ? ch : r) * L * kEntry;
     } else {
 #pragma unroll
         for (int e = 0; e < V; ++e) {
@@ -141,7 +128,9 @@ __global__ __launch_bounds__(kBlock) void linearize_kernel(const LinArgs a)
                 }
             }
         }
-        if (a.tile.layout != CT_LAYOUT_NCHW) {  // interleaved input -> planar outputs, element-wise stores
+        // interleaved input -> planar outputs, element-wise stores (packets are interleaved input: no alignment asked of
+        // out_stride)
+        if (V > 1 || a.tile.layout != CT_LAYOUT_NCHW) {
 #pragma unroll
             for (int e = 0; e < V; ++e) {
                 const int64_t oq = (int64_t)f * a.out_stride + a.tile.planar_index(q0 + e);
@@ -495,8 +484,11 @@ static int lin_typed(LinArgs a, uint32_t Q, int interp, int std_mode, bool write
 #define CT_LINEARIZE_V_INT 8
 #endif
     constexpr int V = sizeof(T) == 4 ? 8 : CT_LINEARIZE_V_INT;
-    const bool vec_ok = aligned(a.frames, sizeof(T) * V) && (a.image_stride % V) == 0 && aligned(a.std_stack, 4 * V) &&
-                        aligned(a.lin_out, 4 * V) && aligned(a.std_out, 4 * V);
+    // Packets of V are for interleaved frames, whose outputs are stored element by element.  Planar frames with whole packets
+    // go to linearize_planar_kernel below; what it refuses (Q % 4 != 0: output frames out_stride = Q apart are 4-byte aligned
+    // only, whatever image_stride is) goes element by element.
+    const bool vec_ok = a.tile.layout != CT_LAYOUT_NCHW && aligned(a.frames, sizeof(T) * V) && (a.image_stride % V) == 0 &&
+                        aligned(a.std_stack, 4 * V) && aligned(a.lin_out, 4 * V) && aligned(a.std_out, 4 * V);
     uint32_t q_vec = vec_ok ? (Q / V) * V : 0;
     int rc = CT_OK;
     // interleaved RGB / BGR with whole packets of four pixels per plane: the pixel-owning kernel (packet stores)
