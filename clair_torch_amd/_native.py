@@ -29,7 +29,8 @@ EXPORTS = ("ct_abi_version", "ct_error_string", "ct_hdr_merge_batch", "ct_hdr_me
            "ct_pivot_floor_constants", "ct_pivot_interval_constants", "ct_band_stats", "ct_band_stats_workspace",
            "ct_strided_downscale", "ct_export_cv", "ct_ingest_transform", "ct_ingest_extrema_workspace", "ct_ingest_extrema",
            "ct_ingest_transform_data", "ct_linearize_ingest", "ct_hdr_merge_ingest_batch", "ct_video_stats_ingest_batch",
-           "ct_hdr_merge_ingest_batches")
+           "ct_hdr_merge_ingest_batches", "ct_ingest_extrema_frames_workspace", "ct_ingest_extrema_frames",
+           "ct_linearize_ingest_data")
 
 
 class Geometry(ctypes.Structure):
@@ -131,6 +132,13 @@ def load():
     lib.ct_ingest_transform_data.argtypes = [vp, i32, i32, i64, i32, i64, ctypes.POINTER(IngestStage), i32, vp, vp, vp]
     lib.ct_linearize_ingest.restype = i32
     lib.ct_linearize_ingest.argtypes = [vp, i32, i64, gp, ctypes.POINTER(IngestStage), i32, vp, i32, f32, ip, vp, vp, vp]
+    lib.ct_ingest_extrema_frames_workspace.restype = i64
+    lib.ct_ingest_extrema_frames_workspace.argtypes = [i64]
+    lib.ct_ingest_extrema_frames.restype = i32
+    lib.ct_ingest_extrema_frames.argtypes = [vp, i32, i32, i64, i32, i64, ctypes.POINTER(IngestStage), i32, i32, f32, f32, vp, i64, vp,
+                                             vp]
+    lib.ct_linearize_ingest_data.restype = i32
+    lib.ct_linearize_ingest_data.argtypes = [vp, i32, i64, gp, ctypes.POINTER(IngestStage), i32, vp, i32, f32, ip, vp, vp, vp, vp]
     lib.ct_hdr_merge_ingest_batch.restype = i32
     lib.ct_hdr_merge_ingest_batch.argtypes = [vp, i32, i32, gp, ctypes.POINTER(IngestStage), i32, vp, vp, i32, f32, vp, ip, i32, vp, vp,
                                               vp, vp, vp, u32, vp]

@@ -28,7 +28,10 @@ by default) or ``fused_ingest=False``; route 4 still runs ct_ingest_extrema firs
 
 linearize_dataset_generator streams routes 2 and 3 (no ``StridedDownscale``, no dark field) through its copy / compute /
 copy pipeline -- route 3 by ct_linearize_ingest, which evaluates the chain and the ICRF in one pass over the raw frames --
-and float32 batches with an empty list; everything else goes frame by frame (inference/linearization.py::pipeline_route).
+and float32 batches with an empty list (inference/linearization.py::pipeline_route) -- and route 4 (likewise without a
+downscale or a dark field; ``pipeline_data_route``): every frame is a batch of its own there, so ct_ingest_extrema_frames
+takes the extrema of each frame of a group in one launch pair and ct_linearize_ingest_data reads the constants per frame.
+Everything else goes frame by frame.
 
 A leading ``CvToTorch`` on (B,H,W,3) uint8 / uint16 frames is never executed on routes 1-4: the code-route kernels read the
 interleaved frames as they are (layout "nhwc_bgr") and the fused ingest reads them itself.  A caller that needs a planar
@@ -338,9 +341,10 @@ def fusable_ingest_data(images: torch.Tensor, transforms) -> Optional[DataIngest
     return DataIngestPlan(p.source_layout, p.step, p.step_first, p.stages, p.prefix, p.min_val, p.max_val)
 
 
-def plan_staging(images: torch.Tensor, transforms, planar: bool = False) -> StagingPlan:
+def plan_staging(images: torch.Tensor, transforms, planar: bool = False, on_device: bool = False) -> StagingPlan:
     """The route ``transforms`` take on ``images``, read off the batch's shape, dtype, contiguity and device type alone
-    (no device call).  ``planar``: the caller cannot take an interleaved stack; the layout is then always "nchw"."""
+    (no device call).  ``planar``: the caller cannot take an interleaved stack; the layout is then always "nchw".
+    ``on_device``: ``images`` is a host probe of batches that are staged on a CUDA device: plan as for a batch there."""
     ts = [t for t in transforms if t is not None]
     # 1, 2: the code pair, behind one StridedDownscale (4-D batches) or alone; raw frames stay interleaved unless ``planar``
     step, rest = fusable_downscale(ts)
@@ -352,6 +356,6 @@ def plan_staging(images: torch.Tensor, transforms, planar: bool = False) -> Stag
         return StagingPlan("code", layout, step, max_code=max_code, source_layout=layout)
     # 3, 4: the fused ingest; with a data-dependent Normalize only on a CUDA device (on a CPU "device" the classes run)
     fused = _recognise_ingest(images, ts)
-    if fused is not None and (fused.route == "ingest" or images.is_cuda):
+    if fused is not None and (fused.route == "ingest" or images.is_cuda or on_device):
         return fused
     return StagingPlan("torch", no_transforms=not ts)  # 5

@@ -23,6 +23,14 @@
 // Integer codes with an empty prefix are reduced as integers (packed 16-bit min / max: the cast to float32 is exact and
 // monotone) and converted once per workgroup.
 // Every load is that of an element of [src, src + n); nothing is written except partial[blockIdx.x].
+//
+// ct_ingest_extrema_frames is the same reduction with one set of constants PER FRAME of a dense stack, for a consumer whose
+// frames are batches of their own (linearize_dataset_generator).  The frame is the grid's y index, so it is
+// workgroup-uniform; a frame's workgroups walk that frame alone with the span walk above, which starts at the frame's own
+// base address -- the head length and, for PACKED3, the channel phase of the registers follow from that address, so they
+// are per frame (a frame's byte size need not be a multiple of 16).  Partials go to workspace[frame][group], the fold
+// kernel runs one workgroup per frame: two launches for the whole stack, and since min, max and the NaN flag are exact and
+// order-independent the four floats of frame f are those ct_ingest_extrema gives for that frame alone.
 #include <algorithm>
 
 #include "ct_ingest_stages.hpp"
@@ -264,9 +272,8 @@ __global__ __launch_bounds__(kBlock) void ingest_extrema_kernel(const ExtremaArg
 }
 
 // one workgroup: consts = {sub, div, data min, data max}
-__global__ __launch_bounds__(kBlock) void ingest_extrema_fold_kernel(const ExtremaPartial *__restrict__ partial, int n_partials,
-                                                                     int from_data, float fixed_min, float fixed_max,
-                                                                     float *__restrict__ consts)
+__device__ __forceinline__ void extrema_fold_partials(const ExtremaPartial *__restrict__ partial, int n_partials, int from_data,
+                                                      float fixed_min, float fixed_max, float *__restrict__ consts)
 {
     FloatAcc acc;
     for (int k = threadIdx.x; k < n_partials; k += kBlock) {
@@ -286,6 +293,47 @@ __global__ __launch_bounds__(kBlock) void ingest_extrema_fold_kernel(const Extre
     consts[3] = hi;
 }
 
+__global__ __launch_bounds__(kBlock) void ingest_extrema_fold_kernel(const ExtremaPartial *__restrict__ partial, int n_partials,
+                                                                     int from_data, float fixed_min, float fixed_max,
+                                                                     float *__restrict__ consts)
+{
+    extrema_fold_partials(partial, n_partials, from_data, fixed_min, fixed_max, consts);
+}
+
+// ---- one set of constants per frame ------------------------------------------------------------------------------------
+// Frame blockIdx.y of a dense stack: a.span * a.n_spans elements per frame (PLANES: n_spans = channels planes of a.span
+// elements; else one span).  Workgroup blockIdx.x of gridDim.x walks that frame and leaves partial[frame][blockIdx.x].
+template <typename T, int MODE>
+__global__ __launch_bounds__(kBlock) void ingest_extrema_frames_kernel(const ExtremaArgs a)
+{
+    const T *src = static_cast<const T *>(a.src) + (int64_t)blockIdx.y * ((int64_t)a.n_spans * a.span);
+    FloatAcc acc;
+    if constexpr (MODE == kRawCodes) {
+        CodeAcc codes;
+        extrema_span<T, false, false>(a, src, a.span, 0u, codes);
+        acc = codes.as_float();
+    } else if constexpr (MODE == kUniform) {
+        extrema_span<T, false, false>(a, src, a.span, 0u, acc);
+    } else if constexpr (MODE == kPlanes) {
+        for (uint32_t q = 0; q < a.n_spans; ++q) extrema_span<T, false, false>(a, src + (int64_t)q * a.span, a.span, q, acc);
+    } else {
+        extrema_span<T, true, MODE == kPacked3Rev>(a, src, a.span, 0u, acc);
+    }
+    if (extrema_block_fold(acc)) {
+        u32x4_t out = {__float_as_uint(acc.lo), __float_as_uint(acc.hi), acc.nan, 0u};
+        *reinterpret_cast<u32x4_t *>(&a.partial[(int64_t)blockIdx.y * gridDim.x + blockIdx.x]) = out;
+    }
+}
+
+// workgroup f: the n_partials partials of frame f -> consts[4 f .. 4 f + 3]
+__global__ __launch_bounds__(kBlock) void ingest_extrema_frames_fold_kernel(const ExtremaPartial *__restrict__ partial,
+                                                                            int n_partials, int from_data, float fixed_min,
+                                                                            float fixed_max, float *__restrict__ consts)
+{
+    extrema_fold_partials(partial + (int64_t)blockIdx.x * n_partials, n_partials, from_data, fixed_min, fixed_max,
+                          consts + 4 * (int64_t)blockIdx.x);
+}
+
 template <typename T>
 static void launch_extrema(const ExtremaArgs &a, int mode, int groups, hipStream_t s)
 {
@@ -299,6 +347,29 @@ static void launch_extrema(const ExtremaArgs &a, int mode, int groups, hipStream
     else
         hipLaunchKernelGGL((ingest_extrema_kernel<T, kPacked3Rev>), grid, block, 0, s, a);
 }
+
+template <typename T>
+static void launch_extrema_frames(const ExtremaArgs &a, int mode, dim3 grid, hipStream_t s)
+{
+    const dim3 block(kBlock);
+    if (mode == kUniform)
+        hipLaunchKernelGGL((ingest_extrema_frames_kernel<T, kUniform>), grid, block, 0, s, a);
+    else if (mode == kPlanes)
+        hipLaunchKernelGGL((ingest_extrema_frames_kernel<T, kPlanes>), grid, block, 0, s, a);
+    else if (mode == kPacked3)
+        hipLaunchKernelGGL((ingest_extrema_frames_kernel<T, kPacked3>), grid, block, 0, s, a);
+    else
+        hipLaunchKernelGGL((ingest_extrema_frames_kernel<T, kPacked3Rev>), grid, block, 0, s, a);
+}
+
+// Partials (= most workgroups) per frame of an n_frames launch: together about kExtremaGroups, which is what fills the
+// device (8 workgroups per CU) -- one 1080p uint8 frame alone has 380 trips and cannot
+static inline int64_t extrema_groups_per_frame(int64_t n_frames)
+{
+    return n_frames >= kExtremaGroups ? 1 : (kExtremaGroups + n_frames - 1) / n_frames;
+}
+
+constexpr int64_t kExtremaMaxFrames = 65535;  // a grid's y extent
 
 }  // namespace ct
 
@@ -361,5 +432,74 @@ extern "C" int ct_ingest_extrema(const void *src_dev, int32_t dtype, int32_t lay
     if (hipGetLastError() != hipSuccess) return CT_ERR_LAUNCH;
     hipLaunchKernelGGL(ingest_extrema_fold_kernel, dim3(1), dim3(kBlock), 0, s, a.partial, groups, from_data, fixed_min, fixed_max,
                        consts_dev);
+    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
+}
+
+extern "C" int64_t ct_ingest_extrema_frames_workspace(int64_t n_frames)
+{
+    if (n_frames < 1 || n_frames > ct::kExtremaMaxFrames) return 0;
+    return n_frames * ct::extrema_groups_per_frame(n_frames) * (int64_t)sizeof(ct::ExtremaPartial);
+}
+
+extern "C" int ct_ingest_extrema_frames(const void *src_dev, int32_t dtype, int32_t layout, int64_t n_frames, int32_t channels,
+                                        int64_t plane, const ct_ingest_stage *prefix, int32_t n_prefix, int32_t from_data,
+                                        float fixed_min, float fixed_max, void *workspace_dev, int64_t workspace_bytes,
+                                        float *consts_dev, void *stream)
+{
+    using namespace ct;
+    bool by_channel = false;
+    const int rc = ingest_validate(dtype, layout, n_frames, channels, plane, prefix, n_prefix, CT_EXTREMA_MAX_PREFIX, 0, by_channel);
+    if (rc != CT_OK) return rc;
+    if (from_data < CT_EXTREMA_MIN || from_data > (CT_EXTREMA_MIN | CT_EXTREMA_MAX)) return CT_ERR_INVALID_ARGUMENT;
+    if (n_frames == 0 || plane == 0) return CT_ERR_INVALID_ARGUMENT;  // torch raises on the extrema of an empty tensor
+    const uintptr_t src_align = dtype == CT_DTYPE_U8 ? 1 : (dtype == CT_DTYPE_U16 ? 2 : 4);
+    if (!src_dev || reinterpret_cast<uintptr_t>(src_dev) % src_align != 0) return CT_ERR_INVALID_ARGUMENT;
+    if (!consts_dev || reinterpret_cast<uintptr_t>(consts_dev) % sizeof(float) != 0) return CT_ERR_INVALID_ARGUMENT;
+    int64_t rows, total;
+    if (__builtin_mul_overflow(n_frames, (int64_t)channels, &rows) || __builtin_mul_overflow(rows, plane, &total) ||
+        total > (INT64_MAX >> 4) || rows > 0x7fffffff || n_frames > kExtremaMaxFrames)
+        return CT_ERR_TOO_LARGE;
+    if (!workspace_dev || workspace_bytes < ct_ingest_extrema_frames_workspace(n_frames) ||
+        reinterpret_cast<uintptr_t>(workspace_dev) % 16 != 0)
+        return CT_ERR_INVALID_ARGUMENT;
+    ExtremaArgs a = {};
+    a.src = src_dev;
+    a.partial = static_cast<ExtremaPartial *>(workspace_dev);
+    a.n_stages = (uint32_t)n_prefix;
+    for (int32_t k = 0; k < n_prefix; ++k) a.stage[k] = prefix[k];
+    a.span = (int64_t)channels * plane;  // a frame
+    a.n_spans = 1;
+    a.channels = 1;
+    int mode = kUniform;
+    if (by_channel && layout == CT_LAYOUT_NCHW) {
+        mode = kPlanes;
+        a.span = plane;
+        a.n_spans = (uint32_t)channels;
+        a.channels = (uint32_t)channels;
+    } else if (by_channel) {
+        mode = layout == CT_LAYOUT_NHWC_BGR ? kPacked3Rev : kPacked3;
+    } else if (n_prefix == 0 && dtype != CT_DTYPE_F32) {
+        mode = kRawCodes;
+    }
+    const int64_t elems_per_trip = (int64_t)kBlock * (16 / (int64_t)src_align) * (mode >= kPacked3 ? 6 : kLoads);
+    const int64_t trips = std::max<int64_t>(1, (a.span + elems_per_trip - 1) / elems_per_trip);
+    const int groups = (int)std::min<int64_t>(extrema_groups_per_frame(n_frames), trips);
+    const dim3 grid((uint32_t)groups, (uint32_t)n_frames);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (mode == kRawCodes) {
+        if (dtype == CT_DTYPE_U8)
+            hipLaunchKernelGGL((ingest_extrema_frames_kernel<uint8_t, kRawCodes>), grid, dim3(kBlock), 0, s, a);
+        else
+            hipLaunchKernelGGL((ingest_extrema_frames_kernel<uint16_t, kRawCodes>), grid, dim3(kBlock), 0, s, a);
+    } else if (dtype == CT_DTYPE_U8) {
+        launch_extrema_frames<uint8_t>(a, mode, grid, s);
+    } else if (dtype == CT_DTYPE_U16) {
+        launch_extrema_frames<uint16_t>(a, mode, grid, s);
+    } else {
+        launch_extrema_frames<float>(a, mode, grid, s);
+    }
+    if (hipGetLastError() != hipSuccess) return CT_ERR_LAUNCH;
+    hipLaunchKernelGGL(ingest_extrema_frames_fold_kernel, dim3((uint32_t)n_frames), dim3(kBlock), 0, s, a.partial, groups, from_data,
+                       fixed_min, fixed_max, consts_dev);
     return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
 }

@@ -22,6 +22,12 @@
 // What precedes the first aligned packet of a plane (slot 0) and what follows the last whole one goes element by element.
 // Every load is that of an element of the thread's own pixels, every store lies in the thread's own [p0, p0 + n).  The
 // stage list travels by value in the kernel arguments; the stage loop is wave-uniform.  No atomics.
+//
+// ct_linearize_ingest_data: the chain may hold one CT_INGEST_AFFINE_DATA stage -- a data-dependent Normalize -- whose sub
+// and div are PER FRAME: consts[4 f], consts[4 f + 1] as ct_ingest_extrema_frames left them.  The frame of a workgroup row
+// is known before the slot loop (planar: (first + blockIdx.y) / channels; interleaved: first + blockIdx.y), so the two
+// floats are one wave-uniform load per workgroup and the select against the stage's own constants is scalar.  The kernels
+// are the same instantiations (as in ct_merge_ingest_kernel.hpp): a NULL consts is the constant chain.
 #include "ct_args.hpp"
 #include "ct_ingest_stages.hpp"
 
@@ -31,6 +37,7 @@ struct LinIngestArgs {
     const void *src;
     const float *std_in;   // EXPLICIT: planar (F, C, plane) float32, like the outputs
     const float *lut;
+    const float *consts;   // (F, 4) per-frame {sub, div, min, max} of a CT_INGEST_AFFINE_DATA stage, or NULL
     float *lin_out;
     float *std_out;
     int64_t image_stride;  // source elements between consecutive frames
@@ -140,6 +147,7 @@ __global__ __launch_bounds__(kBlock) void linearize_ingest_planar_kernel(const L
     [[maybe_unused]] const float *sdi = STD == CT_STD_EXPLICIT ? a.std_in + (int64_t)q * a.plane : nullptr;
     const int64_t head = (int64_t)(((0 - reinterpret_cast<uintptr_t>(lin)) & 15u) / sizeof(float));
     const uint32_t row0 = c * a.plane_global + a.base;  // global flat index of this plane's first local element (< 2^31)
+    const float dsub = a.consts ? a.consts[4 * (int64_t)f] : 0.0f, ddiv = a.consts ? a.consts[4 * (int64_t)f + 1] : 1.0f;
 #pragma unroll 1
     for (int k = 0; k < kLiSlots; ++k) {
         const int64_t slot = ((int64_t)blockIdx.x * kLiSlots + k) * kBlock + threadIdx.x;
@@ -157,7 +165,7 @@ __global__ __launch_bounds__(kBlock) void linearize_ingest_planar_kernel(const L
             for (int e = 0; e < kLiGroup; ++e) v[e] = e < n ? (float)src[p0 + e] : 0.0f;
         }
         if constexpr (STD == CT_STD_EXPLICIT) li_load_std(sdi + p0, n, sg);
-        ingest_stages<false>(v, a, a.by_channel ? c : 0u);
+        ingest_stages<true>(v, a, a.by_channel ? c : 0u, dsub, ddiv);
         const uint32_t qg = row0 + (uint32_t)p0;
         const int r = C == 3 ? (int)(qg % 3u) : (int)(qg % a.channels);
         LinIngestPacket lo, so;
@@ -182,6 +190,7 @@ __global__ __launch_bounds__(kBlock) void linearize_ingest_packed3_kernel(const 
     [[maybe_unused]] const float *sdi = STD == CT_STD_EXPLICIT ? a.std_in + (int64_t)f * C * a.plane : nullptr;
     const int64_t head = (int64_t)(((0 - reinterpret_cast<uintptr_t>(lin)) & 15u) / sizeof(float));
     const uint32_t pg3 = a.plane_global % 3u;
+    const float dsub = a.consts ? a.consts[4 * (int64_t)f] : 0.0f, ddiv = a.consts ? a.consts[4 * (int64_t)f + 1] : 1.0f;
 #pragma unroll 1
     for (int k = 0; k < kLiSlots; ++k) {
         const int64_t slot = ((int64_t)blockIdx.x * kLiSlots + k) * kBlock + threadIdx.x;
@@ -204,7 +213,7 @@ __global__ __launch_bounds__(kBlock) void linearize_ingest_packed3_kernel(const 
             for (int e = 0; e < kLiGroup; ++e) v[e] = (float)in[e * C + cm];
             const int64_t po = (int64_t)c * a.plane + p0;
             if constexpr (STD == CT_STD_EXPLICIT) li_load_std(sdi + po, n, sg);
-            ingest_stages<false>(v, a, a.by_channel ? c : 0u);
+            ingest_stages<true>(v, a, a.by_channel ? c : 0u, dsub, ddiv);
             // row of (plane c, pixel p0): (c * plane_global + base + p0) % 3 (base.py:173-176)
             const int r = (int)((c * pg3 + m3) % 3u);
             LinIngestPacket lo, so;
@@ -261,23 +270,23 @@ static int li_dispatch(const LinIngestArgs &a, bool packed, int64_t rows, int in
     return CT_ERR_INVALID_ARGUMENT;
 }
 
-}  // namespace ct
-
-extern "C" int ct_linearize_ingest(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
-                                   const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,
-                                   float std_value, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev, void *stream)
+// consts_dev NULL: the constant chains of ct_linearize_ingest (no AFFINE_DATA stage); else ct_linearize_ingest_data
+static int linearize_ingest(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
+                            const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode, float std_value,
+                            const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev, const float *consts_dev, void *stream)
 {
-    using namespace ct;
     // everything that needs no pointer into device memory first: geometry (check_ingest_geometry, no empty plane), the stack
-    // and the stage list (ingest_validate, without AFFINE_DATA), the model and the uncertainty mode (icrf_ok, std_mode_ok)
+    // and the stage list (ingest_validate; AFFINE_DATA only with constants), the model and the uncertainty mode (icrf_ok, std_mode_ok)
     if (!geom || !icrf) return CT_ERR_INVALID_ARGUMENT;
     int rc = check_ingest_geometry(geom, false);
     if (rc != CT_OK) return rc;
     const int64_t plane = geom->h_tile * geom->width;
     if (!stride_holds_image(geom)) return CT_ERR_INVALID_ARGUMENT;
     bool by_channel = false;
-    rc = ingest_validate(dtype, geom->layout, n_frames, geom->channels, plane, stages, n_stages, CT_INGEST_MAX_STAGES, 0, by_channel);
+    rc = ingest_validate(dtype, geom->layout, n_frames, geom->channels, plane, stages, n_stages, CT_INGEST_MAX_STAGES,
+                         consts_dev ? 1 : 0, by_channel);
     if (rc != CT_OK) return rc;
+    if (!aligned(consts_dev, sizeof(float))) return CT_ERR_INVALID_ARGUMENT;
     const int interp = icrf->interp;
     if (!icrf_ok(icrf) || !std_mode_ok(std_mode, std_dev)) return CT_ERR_INVALID_ARGUMENT;
     // linearization.py:100-105: autograd.grad raises for LOOKUP (no gradient path) when stds are present
@@ -295,6 +304,7 @@ extern "C" int ct_linearize_ingest(const void *frames_dev, int32_t dtype, int64_
     a.src = frames_dev;
     a.std_in = std_mode == CT_STD_EXPLICIT ? std_dev : nullptr;
     a.lut = icrf->lut_dev;
+    a.consts = consts_dev;
     a.lin_out = lin_out_dev;
     a.std_out = std_out_dev;
     fill_ingest_args(a, geom, icrf_points(icrf), by_channel, stages, n_stages);
@@ -304,4 +314,23 @@ extern "C" int ct_linearize_ingest(const void *frames_dev, int32_t dtype, int64_
     if (dtype == CT_DTYPE_U8) return li_dispatch<uint8_t>(a, packed, rows, interp, std_mode, write_std, s);
     if (dtype == CT_DTYPE_U16) return li_dispatch<uint16_t>(a, packed, rows, interp, std_mode, write_std, s);
     return li_dispatch<float>(a, packed, rows, interp, std_mode, write_std, s);
+}
+
+}  // namespace ct
+
+extern "C" int ct_linearize_ingest(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
+                                   const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,
+                                   float std_value, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev, void *stream)
+{
+    return ct::linearize_ingest(frames_dev, dtype, n_frames, geom, stages, n_stages, std_dev, std_mode, std_value, icrf, lin_out_dev,
+                                std_out_dev, nullptr, stream);
+}
+
+extern "C" int ct_linearize_ingest_data(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
+                                        const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,
+                                        float std_value, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev,
+                                        const float *consts_dev, void *stream)
+{
+    return ct::linearize_ingest(frames_dev, dtype, n_frames, geom, stages, n_stages, std_dev, std_mode, std_value, icrf, lin_out_dev,
+                                std_out_dev, consts_dev, stream);
 }

@@ -18,8 +18,15 @@ codes (folded into ct_linearize_std's load), float32 pixels with no transform li
 route "ingest" without a StridedDownscale -- a black level, a target range, ``ClampAlongDims``, raw BGR frames behind
 ``CvToTorch`` with explicit (planar) uncertainty images.  For the latter the ring slot keeps the RAW frames in their own
 dtype and memory order and ct_linearize_ingest evaluates chain and ICRF in one pass, bit for bit what ct_ingest_transform
-followed by ct_linearize_std gives on the frame-by-frame route.  A dark field, a downscale off the code pair, a
-data-dependent ``Normalize`` and lists that run as torch ops go frame by frame.
+followed by ct_linearize_std gives on the frame-by-frame route.
+
+A list with a data-dependent ``Normalize`` (``max_val`` and / or ``min_val`` None -- ``Normalize()`` is the reference's
+default; every frame is its own batch here, so the bounds are per frame) is ``pipeline_data_route``'s: ONE
+ct_ingest_extrema_frames launch pair leaves four constants per frame of the group in the slot, ct_linearize_ingest_data
+reads them per frame, and the constants ride the device-to-host stage so that the reference's zero-range ValueError is
+raised -- without a synchronisation of its own -- exactly where the frame-by-frame route raises it: after the frames in
+front of the offending one have been yielded.  A dark field, a downscale off the code pair and lists that run as torch
+ops go frame by frame.
 
 ``output_layout="cv"`` (extension): every yielded pair is in the order the reference's ``save_image`` writes -- (H,W,C),
 a 3-channel frame reversed to BGR -- made by two ct_export_cv launches per group before the device-to-host copy, which
@@ -72,7 +79,14 @@ def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRF
         return
     probe = first[1]
     plan = plan_staging(probe, transforms, planar=first[2] is not None)  # explicit uncertainty images are planar
-    if pipeline_route(probe, plan, dark is not None) != "pipelined":
+    route = pipeline_route(probe, plan, dark is not None)
+    if route != "pipelined":
+        # the second, separate decision: a data-dependent Normalize with per-frame constants.  The probe is a host tensor;
+        # the list is planned as stage_images plans it for the batch on the device (route "ingest_data" exists only there)
+        staged = plan_staging(probe, transforms, planar=first[2] is not None, on_device=dev.type == "cuda")
+        route = pipeline_data_route(probe, staged, dark is not None)
+        plan = staged if route == "pipelined" else plan
+    if route != "pipelined":
         yield from _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat, flat_std, dark,
                                    output_layout == "cv")
         return
@@ -85,8 +99,9 @@ def pipeline_route(probe: torch.Tensor, plan, has_dark: bool) -> str:
     ingests from a ring slot: raw integer codes whose normalisation (and OpenCV layout) fold into ct_linearize_std's
     load, float32 pixels with no device transform at all, or -- route "ingest" -- raw frames whose whole chain
     ct_linearize_ingest evaluates.  Anything else goes frame by frame through the generic staging: a dark field
-    (per-frame conditional blur), a StridedDownscale off the code pair, a data-dependent Normalize (its extrema are per
-    frame here, per stack in ct_ingest_extrema), lists that run as torch ops."""
+    (per-frame conditional blur), a StridedDownscale off the code pair, lists that run as torch ops -- and, as far as THIS
+    function is concerned, a data-dependent Normalize: its extrema are per frame here, per stack in ct_ingest_extrema, so
+    it has a decision of its own, ``pipeline_data_route``, which the generator asks when this one said "frame_by_frame"."""
     if has_dark or probe.ndim != 4:
         return "frame_by_frame"
     if plan.route in ("code", "ingest") and plan.step == 1:
@@ -94,6 +109,18 @@ def pipeline_route(probe: torch.Tensor, plan, has_dark: bool) -> str:
     if plan.route == "torch" and plan.no_transforms and probe.dtype == torch.float32:
         return "pipelined"
     return "frame_by_frame"
+
+
+def pipeline_data_route(probe: torch.Tensor, plan, has_dark: bool) -> str:
+    """"pipelined" | "frame_by_frame" for what ``pipeline_route`` declined: route "ingest_data" -- the fused-ingest grammar
+    with ONE data-dependent Normalize -- on uint8 / uint16 / float32 frames without a StridedDownscale and without a dark
+    field takes the pipeline with per-frame constants (ct_ingest_extrema_frames + ct_linearize_ingest_data per group).
+    Measured against the frame-by-frame route in profiles/linearize_ingest_data.md; everything else stays frame by frame."""
+    if has_dark or probe.ndim != 4 or plan.route != "ingest_data" or plan.step != 1:
+        return "frame_by_frame"
+    if probe.dtype not in (torch.uint8, torch.uint16, torch.float32):
+        return "frame_by_frame"
+    return "pipelined"
 
 
 def _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat, flat_std, dark, cv):
@@ -119,7 +146,7 @@ def _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat
 class _Slot:
     """One ring slot: device buffers for a group of frames and the events that order its three stages."""
 
-    def __init__(self, group, frame_shape, dtype, std_shape, chw, dev, cv):
+    def __init__(self, group, frame_shape, dtype, std_shape, chw, dev, cv, data=False):
         self.frames = torch.empty((group,) + tuple(frame_shape), dtype=dtype, device=dev)
         # explicit uncertainty images: frame-shaped beside ct_linearize_std, planar (C,H,W) beside ct_linearize_ingest
         self.std = torch.empty((group,) + tuple(std_shape), dtype=torch.float32, device=dev) if std_shape is not None else None
@@ -128,6 +155,11 @@ class _Slot:
         # output_layout="cv": the (group, H, W, C) exports the device-to-host copy reads instead
         self.lin_cv = torch.empty((group, chw[1], chw[2], chw[0]), dtype=torch.float32, device=dev) if cv else None
         self.std_cv = torch.empty_like(self.lin_cv) if cv else None
+        # a data-dependent Normalize: the (group, 4) constants of ct_ingest_extrema_frames, its workspace, and the pinned
+        # host copy that drain_one reads for the zero-range check (the slot is not re-used before its group is drained)
+        self.consts = torch.empty((group, 4), dtype=torch.float32, device=dev) if data else None
+        self.workspace = ops.ingest_extrema_frames_workspace(group, dev) if data else None
+        self.consts_host = torch.empty((group, 4), dtype=torch.float32, pin_memory=True) if data else None
         self.copied_in, self.computed, self.copied_out = (torch.cuda.Event() for _ in range(3))
         self.busy = False
 
@@ -141,7 +173,8 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
     probe = first[1]
     frame_shape = tuple(probe.shape[1:])
     # an ingest plan: the slot keeps the RAW frames, (H,W,3) behind a folded CvToTorch, and the kernel runs the chain
-    fused = plan.route == "ingest"
+    data = plan.route == "ingest_data"  # per-frame constants of a data-dependent Normalize (pipeline_data_route)
+    fused = plan.route == "ingest" or data
     layout, max_code = (plan.source_layout if fused else plan.layout), plan.max_code
     chw = frame_shape if layout == "nchw" else (frame_shape[2], frame_shape[0], frame_shape[1])
     out_bytes = 2 * 4 * chw[0] * chw[1] * chw[2]
@@ -149,7 +182,7 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
     std_probe, std_mode, std_value = std_arguments(first[2], dataloader.dataset, torch.device("cpu"))
     with_std = std_probe is not None
     std_shape = (chw if fused else frame_shape) if with_std else None
-    slots = [_Slot(group, frame_shape, probe.dtype, std_shape, chw, dev, cv) for _ in range(_SLOTS)]
+    slots = [_Slot(group, frame_shape, probe.dtype, std_shape, chw, dev, cv, data) for _ in range(_SLOTS)]
     compute = torch.cuda.current_stream(dev)
     h2d, d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
     in_flight = deque()  # (slot, n frames, pinned lin, pinned std, metas)
@@ -158,7 +191,10 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
         slot, k, lin_host, std_host, metas = in_flight.popleft()
         slot.copied_out.synchronize()
         slot.busy = False
+        ranges = slot.consts_host[:k, 1].tolist() if data else None
         for i in range(k):
+            if data and ranges[i] == 0.0:  # general_functions.py:377-378, at the frame it belongs to; a NaN range passes
+                raise ValueError(ops.ZERO_RANGE)
             yield lin_host[i].squeeze(), std_host[i].squeeze(), metas[i]
 
     item, g = first, 0
@@ -189,10 +225,14 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
         compute.wait_event(slot.copied_in)
         compute.wait_event(slot.copied_out)  # the slot's output buffers were last read by its previous copy-out
         if fused:
+            consts = None
+            if data:  # two launches for the group's k sets of constants, into the slot's own buffers
+                consts = ops.ingest_extrema_frames(slot.frames[:k], plan.prefix, layout, plan.min_val, plan.max_val,
+                                                   out=slot.consts[:k], workspace=slot.workspace)
             lin, lin_std = ops.linearize_ingest_frames(slot.frames[:k], plan.stages, lut, interp,
                                                        std=slot.std[:k] if with_std else None, std_mode=std_mode,
                                                        std_value=std_value, want_std=True, layout=layout,
-                                                       out=(slot.lin_out[:k], slot.std_out[:k]))
+                                                       out=(slot.lin_out[:k], slot.std_out[:k]), consts=consts)
         else:
             lin, lin_std = ops.linearize_frames(slot.frames[:k], lut, interp, std=slot.std[:k] if with_std else None,
                                                 std_mode=std_mode, std_value=std_value, max_code=max_code, want_std=True,
@@ -205,6 +245,8 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
         slot.computed.record(compute)
         with torch.cuda.stream(d2h):
             d2h.wait_event(slot.computed)
+            if data:  # 16 bytes per frame, in front of copied_out
+                slot.consts_host[:k].copy_(slot.consts[:k], non_blocking=True)
             lin_host = torch.empty(lin.shape, dtype=torch.float32, pin_memory=True)
             std_host = torch.empty(lin.shape, dtype=torch.float32, pin_memory=True)
             lin_host.copy_(lin, non_blocking=True)

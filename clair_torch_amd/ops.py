@@ -834,6 +834,15 @@ def _check_consts(consts, device):
         raise ValueError(f"consts must be the 4-element float32 tensor of ingest_extrema on {device}")
 
 
+def _check_frame_consts(consts, n_frames: int, device):
+    _require_device(consts, "consts")
+    if consts.dtype != torch.float32:
+        raise TypeError(f"consts must be float32, got {consts.dtype}")
+    if tuple(consts.shape) != (n_frames, 4) or consts.device != device or not consts.is_contiguous():
+        raise ValueError(f"consts must be the contiguous ({n_frames}, 4) float32 tensor of ingest_extrema_frames on {device}, "
+                         f"got shape {tuple(consts.shape)}")
+
+
 def ingest_transform(stack: torch.Tensor, stages, layout: str = "nchw", out: Optional[torch.Tensor] = None,
                      consts: Optional[torch.Tensor] = None):
     """ct_ingest_transform: the chain CastTo(float32), Normalize(max, min, range), ClampAlongDims evaluated in one pass
@@ -869,7 +878,8 @@ def ingest_transform(stack: torch.Tensor, stages, layout: str = "nchw", out: Opt
 # ---- such a chain and the linearization in one pass ----------------------------------------------------------------------
 def linearize_ingest_frames(frames: torch.Tensor, stages, lut: Optional[torch.Tensor], interp: Optional[str] = "linear", *,
                             std: Optional[torch.Tensor] = None, std_mode: str = "none", std_value: float = 0.0,
-                            want_std: bool = True, tile: Optional[TileGeometry] = None, layout: str = "nchw", out=None):
+                            want_std: bool = True, tile: Optional[TileGeometry] = None, layout: str = "nchw", out=None,
+                            consts: Optional[torch.Tensor] = None):
     """ct_linearize_ingest: ``linearize_frames(ingest_transform(frames, stages, layout), lut, interp, ...)`` bit for bit,
     in one launch and without the float32 stack in between -> (lin float32, std float32 | None), planar (F,C,H,W).
     ``frames``: a contiguous uint8 / uint16 / float32 device stack, (F,C,H,W) for "nchw" or (F,H,W,3) for "nhwc" /
@@ -877,12 +887,18 @@ def linearize_ingest_frames(frames: torch.Tensor, stages, lut: Optional[torch.Te
     ("affine_data", ...).  ``std``: explicit uncertainties, float32 and PLANAR (F,C,H,W) like the outputs whatever the
     layout of the frames (gpu_transforms never touch the uncertainty images).  ``tile``: the frames are a row band of a
     taller image, as in ``linearize_frames``.  ``out`` = (lin, std | None): caller-owned contiguous float32 (F,C,H,W)
-    device buffers to write into."""
+    device buffers to write into.
+    ``consts``: the (F, 4) tensor ``ingest_extrema_frames`` returned; then (ct_linearize_ingest_data) one stage may be
+    ("affine_data", mul, add) -- a data-dependent Normalize with PER-FRAME bounds, whose sub and div for frame f the kernel
+    reads from ``consts[f, 0:2]`` when it runs: ``linearize_frames(ingest_transform(frames[f:f+1], stages, layout,
+    consts=consts[f]), ...)`` bit for bit.  No zero-range check happens here (``consts[f, 1] == 0``)."""
     _check_ingest_stack(frames, layout)
     shape = ingest_shape(tuple(frames.shape), layout)
     f, c, h, w = shape
     dev = frames.device
-    arr, n_stages = _ingest_stages(stages, c)
+    arr, n_stages = _ingest_stages(stages, c, data=consts is not None)
+    if consts is not None:
+        _check_frame_consts(consts, f, dev)
     if std is not None:
         std_mode, std = "explicit", _planar_std(std, shape, dev, "outputs")
     if std_mode not in _STD:
@@ -893,10 +909,15 @@ def linearize_ingest_frames(frames: torch.Tensor, stages, lut: Optional[torch.Te
     if frames.numel() == 0:
         return lin, std_out
     with torch.cuda.device(dev):
-        rc = nv.load().ct_linearize_ingest(_ptr(frames), _DTYPE[frames.dtype], f, ctypes.byref(geom), arr, n_stages, _ptr(std),
-                                           _STD[std_mode], float(std_value), ctypes.byref(icrf), _ptr(lin), _ptr(std_out),
-                                           _stream(dev))
-    nv.check(rc, "ct_linearize_ingest")
+        if consts is None:
+            rc = nv.load().ct_linearize_ingest(_ptr(frames), _DTYPE[frames.dtype], f, ctypes.byref(geom), arr, n_stages, _ptr(std),
+                                               _STD[std_mode], float(std_value), ctypes.byref(icrf), _ptr(lin), _ptr(std_out),
+                                               _stream(dev))
+        else:
+            rc = nv.load().ct_linearize_ingest_data(_ptr(frames), _DTYPE[frames.dtype], f, ctypes.byref(geom), arr, n_stages,
+                                                    _ptr(std), _STD[std_mode], float(std_value), ctypes.byref(icrf), _ptr(lin),
+                                                    _ptr(std_out), _ptr(consts), _stream(dev))
+    nv.check(rc, "ct_linearize_ingest" if consts is None else "ct_linearize_ingest_data")
     del lut_keep
     return lin, std_out
 
@@ -1063,6 +1084,58 @@ def ingest_extrema(stack: torch.Tensor, prefix_stages=(), layout: str = "nchw", 
                                    _stream(stack.device))
     nv.check(rc, "ct_ingest_extrema")
     return consts
+
+
+def ingest_extrema_frames_workspace(n_frames: int, device) -> torch.Tensor:
+    """A float32 device tensor that serves ``ingest_extrema_frames`` as ``workspace`` for every stack of 1 to ``n_frames``
+    frames (a ring slot's last group is shorter than the others): the largest ct_ingest_extrema_frames_workspace(k) over
+    k <= n_frames, since that size is not monotone in k."""
+    lib = nv.load()
+    ws_bytes = max(int(lib.ct_ingest_extrema_frames_workspace(k)) for k in range(1, max(int(n_frames), 1) + 1))
+    return torch.empty((max(ws_bytes, 16) // 4,), dtype=torch.float32, device=device)
+
+
+def ingest_extrema_frames(frames: torch.Tensor, prefix_stages=(), layout: str = "nchw", min_val=None, max_val=None, *,
+                          out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """ct_ingest_extrema_frames: ``ingest_extrema`` of every frame of ``frames`` on its own -- the constants of a
+    data-dependent Normalize that sees one frame per batch -- as an (F, 4) float32 device tensor whose row f is bit for bit
+    ``ingest_extrema(frames[f:f+1], prefix_stages, layout, min_val, max_val)``: [sub, div, data min, data max], both extrema
+    NaN when that frame holds a NaN.  Two launches whatever F is, no synchronisation; ``consts[f, 1] == 0``, where the
+    reference raises, is for the caller to check.  ``out``: a contiguous (F, 4) float32 device tensor to write into;
+    ``workspace``: a float32 device tensor of at least the library's workspace size (``ingest_extrema_frames_workspace``);
+    without them both are allocated here.  An empty stack raises, as torch's ``x.min()`` does."""
+    _check_ingest_stack(frames, layout)
+    if min_val is not None and max_val is not None:
+        raise ValueError("min_val and max_val are both given: nothing depends on the data (use ingest_transform)")
+    shape = ingest_shape(tuple(frames.shape), layout)
+    arr, n_prefix = _ingest_stages(prefix_stages, shape[1], limit=nv.EXTREMA_MAX_PREFIX)
+    from_data = (nv.EXTREMA_MIN if min_val is None else 0) | (nv.EXTREMA_MAX if max_val is None else 0)
+    fixed_min = 0.0 if min_val is None else _number(min_val, "min_val")
+    fixed_max = 0.0 if max_val is None else _number(max_val, "max_val")
+    if frames.numel() == 0:
+        raise RuntimeError("ingest_extrema_frames: the stack is empty (the extrema of an empty tensor are undefined)")
+    dev = frames.device
+    lib = nv.load()
+    ws_bytes = int(lib.ct_ingest_extrema_frames_workspace(shape[0]))
+    if ws_bytes == 0:
+        raise ValueError(f"ingest_extrema_frames: {shape[0]} frames are more than one call takes (65535)")
+    if workspace is None:
+        workspace = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=dev)
+    else:
+        _require_device(workspace, "workspace")
+        if (workspace.dtype != torch.float32 or workspace.device != dev or not workspace.is_contiguous()
+                or workspace.numel() * 4 < ws_bytes):
+            raise ValueError(f"workspace must be a contiguous float32 tensor of at least {ws_bytes} bytes on {dev}")
+    if out is None:
+        out = torch.empty((shape[0], 4), dtype=torch.float32, device=dev)
+    else:
+        _check_frame_consts(out, shape[0], dev)
+    with torch.cuda.device(dev):
+        rc = lib.ct_ingest_extrema_frames(_ptr(frames), _DTYPE[frames.dtype], _LAYOUT[layout], shape[0], shape[1],
+                                          shape[2] * shape[3], arr, n_prefix, from_data, fixed_min, fixed_max, _ptr(workspace),
+                                          workspace.numel() * 4, _ptr(out), _stream(dev))
+    nv.check(rc, "ct_ingest_extrema_frames")
+    return out
 
 
 def data_stage_prefix(stages):

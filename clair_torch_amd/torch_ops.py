@@ -25,6 +25,11 @@ and pair lists are passed as their component tensors / scalars.
                                   likewise; an explicit std is planar (F,C,H,W) like the outputs)
     torch.ops.clair_hip.ingest_extrema(stack, prefix, layout, min_val?, max_val?) -> Tensor   (4 floats: sub, div, data
                                   min, data max of a data-dependent Normalize behind the constant ``prefix`` stages)
+    torch.ops.clair_hip.ingest_extrema_frames(frames, prefix, layout, min_val?, max_val?) -> Tensor   ((F, 4): row f is
+                                  ingest_extrema of frame f alone, in two launches for the whole stack)
+    torch.ops.clair_hip.linearize_ingest_data(frames, stages, consts, lut, interp, std?, std_mode, std_value, layout,
+                                  h_global, row_offset) -> (lin, std)   (linearize_ingest whose chain may hold one stage of
+                                  kind 2, the data-dependent Normalize with per-frame sub / div = consts[f, 0:2])
     torch.ops.clair_hip.hdr_merge_ingest_batch(frames, stages, exposures, lut?, interp, gaussian, std?, std_mode, std_value,
                                   layout, h_global, row_offset, closed_form, consts?) -> (mean float64, std float32)   (such
                                   a chain and hdr_merge in one pass over the raw frames; with ``consts`` a stage of kind 2 is
@@ -260,6 +265,36 @@ def ingest_extrema(stack: torch.Tensor, prefix: Sequence[float], layout: str = "
 @ingest_extrema.register_fake
 def _(stack, prefix, layout="nchw", min_val=None, max_val=None):
     return stack.new_empty((4,), dtype=torch.float32)
+
+
+@torch.library.custom_op(f"{_LIB}::ingest_extrema_frames", mutates_args=())
+def ingest_extrema_frames(frames: torch.Tensor, prefix: Sequence[float], layout: str = "nchw", min_val: Optional[float] = None,
+                          max_val: Optional[float] = None) -> torch.Tensor:
+    """ct_ingest_extrema_frames: (F, 4), row f = [sub, div, data min, data max] of frame f alone behind the constant
+    ``prefix`` stages (flattened as for ``ingest_transform``); a bound that is None comes from the data."""
+    return ops.ingest_extrema_frames(frames, _listed_ingest_stages(frames, prefix, layout), layout, min_val, max_val)
+
+
+@ingest_extrema_frames.register_fake
+def _(frames, prefix, layout="nchw", min_val=None, max_val=None):
+    return frames.new_empty((frames.shape[0], 4), dtype=torch.float32)
+
+
+@torch.library.custom_op(f"{_LIB}::linearize_ingest_data", mutates_args=())
+def linearize_ingest_data(frames: torch.Tensor, stages: Sequence[float], consts: torch.Tensor, lut: torch.Tensor, interp: str,
+                          std: Optional[torch.Tensor], std_mode: str, std_value: float, layout: str = "nchw", h_global: int = 0,
+                          row_offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ct_linearize_ingest_data: ``linearize_ingest`` with the per-frame constants of ``ingest_extrema_frames`` for one
+    data-dependent Normalize in the chain (a stage of kind 2: kind, 0, 0, mul, add)."""
+    return ops.linearize_ingest_frames(frames, _listed_ingest_stages(frames, stages, layout), lut, interp, std=std,
+                                       std_mode=std_mode, std_value=std_value, want_std=True, tile=_tile(h_global, row_offset),
+                                       layout=layout, consts=consts)
+
+
+@linearize_ingest_data.register_fake
+def _(frames, stages, consts, lut, interp, std, std_mode, std_value, layout="nchw", h_global=0, row_offset=0):
+    shape = ops.ingest_shape(tuple(frames.shape), layout)
+    return frames.new_empty(shape, dtype=torch.float32), frames.new_empty(shape, dtype=torch.float32)
 
 
 @torch.library.custom_op(f"{_LIB}::hdr_merge_ingest_batch", mutates_args=())

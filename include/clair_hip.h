@@ -404,6 +404,24 @@ int ct_ingest_transform_data(const void *src_dev, int32_t dtype, int32_t layout,
                              const float *consts_dev, void *stream);
 
 /*
+ * ct_ingest_extrema_frames -- ct_ingest_extrema with one set of constants PER FRAME of a dense stack, for consumers whose
+ * frames are batches of their own (linearize_dataset_generator: batch size 1, so Normalize() sees one frame at a time).
+ * The n_frames frames lie channels*plane elements apart; consts_dev holds (n_frames, 4) floats and
+ * consts_dev[4 f .. 4 f + 3] is bit for bit what ct_ingest_extrema writes when called with n_images = 1 on frame f alone:
+ * {sub, div = fl32(top - sub), data min, data max}, both extrema NaN when THAT frame holds a NaN (its neighbours' constants
+ * are untouched by it).  Two launches whatever n_frames is: the frame is a grid dimension of the reduction, the fold runs
+ * one workgroup per frame; no atomics.  workspace_dev: at least ct_ingest_extrema_frames_workspace(n_frames) bytes,
+ * 16-byte aligned.  Refusals as ct_ingest_extrema's (from_data = 0, an empty stack, NULL or misaligned pointers, a short
+ * workspace: CT_ERR_INVALID_ARGUMENT); n_frames > 65535 is CT_ERR_TOO_LARGE (and its workspace size is 0).  Allocates
+ * nothing, synchronises nothing, reads nothing outside the frames, writes only the workspace and consts_dev.
+ */
+int64_t ct_ingest_extrema_frames_workspace(int64_t n_frames);
+int ct_ingest_extrema_frames(const void *src_dev, int32_t dtype, int32_t layout, int64_t n_frames, int32_t channels,
+                             int64_t plane, const ct_ingest_stage *prefix, int32_t n_prefix, int32_t from_data,
+                             float fixed_min, float fixed_max, void *workspace_dev, int64_t workspace_bytes,
+                             float *consts_dev /* (n_frames, 4) */, void *stream);
+
+/*
  * ct_linearize_ingest -- such a chain and the body of linearize_dataset_generator in ONE pass over F independent frames:
  * the outputs are bit for bit those of ct_ingest_transform followed by ct_linearize_std on its float32 result,
  *   x   = the stage list applied to (float)sample (CT_INGEST_AFFINE / CT_INGEST_CLAMP only, at most
@@ -428,6 +446,19 @@ int ct_ingest_transform_data(const void *src_dev, int32_t dtype, int32_t layout,
 int ct_linearize_ingest(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
                         const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,
                         float std_value, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev, void *stream);
+
+/*
+ * ct_linearize_ingest_data -- ct_linearize_ingest whose chain may hold at most one CT_INGEST_AFFINE_DATA stage with PER-FRAME
+ * constants: sub and div of frame f are consts_dev[4 f] and consts_dev[4 f + 1] (consts_dev: (n_frames, 4) floats as
+ * ct_ingest_extrema_frames leaves them, 4-byte aligned, read when the kernel runs).  For every frame the outputs are bit for
+ * bit those of ct_ingest_transform_data on that frame with its four constants followed by ct_linearize_std on the float32
+ * result.  A row band is normalised by the constants it is given (the band's own extrema on every route of the project).
+ * consts_dev NULL: ct_linearize_ingest, which refuses that kind.  Everything else as ct_linearize_ingest.
+ */
+int ct_linearize_ingest_data(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
+                             const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,
+                             float std_value, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev,
+                             const float *consts_dev, void *stream);
 
 /*
  * ct_hdr_merge_ingest_batch -- such a chain and one batch of compute_hdr_image's loop body in ONE pass over B raw frames:
