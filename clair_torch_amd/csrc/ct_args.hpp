@@ -51,6 +51,9 @@ static inline int check_ingest_geometry(const ct_geometry *g, bool allow_empty)
 // NULL is aligned: a pointer that is not there is not used.  Where NULL is a fault the caller tests the pointer itself.
 static inline bool aligned(const void *p, size_t bytes) { return reinterpret_cast<uintptr_t>(p) % bytes == 0; }
 
+// the bytes of an element of a stack of a (validated) CT_DTYPE_*, which is also the alignment of its pointer
+static inline size_t dtype_bytes(int32_t dtype) { return dtype == CT_DTYPE_U8 ? 1 : (dtype == CT_DTYPE_U16 ? 2 : 4); }
+
 // ---- model and uncertainty mode ---------------------------------------------------------------------------------------
 // allow_none: CT_INTERP_NONE (no LUT) is a model
 static inline bool icrf_ok(const ct_icrf *icrf, bool allow_none = true)

@@ -2,35 +2,36 @@
 //
 // Normalize() with max_val and / or min_val None normalises a batch by its own extrema (normalize_tensor,
 // clair_torch/common/general_functions.py:373-376): x.max() / x.min() of the whole tensor the transform receives, i.e. of
-// the raw stack after the constant stages that stand in front of it.  ingest_extrema_kernel is that reduction as a
-// read-only streaming pass over the raw stack: it evaluates the prefix per element with the ingest kernels' own
-// ingest_stages, and reduces min, max and "any NaN" (torch's extrema propagate NaN, v_min_f32 / v_max_f32 drop it).
-// ingest_extrema_fold_kernel folds the workgroups' partials -- no atomics, so the result does not depend on the order the
-// workgroups ran in -- and forms sub, top and div = fl32(top - sub) for the CT_INGEST_AFFINE_DATA stage of ct_ingest.hip.
+// a raw frame (or stack) after the constant stages that stand in front of it.  ingest_extrema_kernel is that reduction as a
+// read-only streaming pass, with one set of constants PER FRAME of a dense stack: it evaluates the prefix per element with
+// the ingest kernels' own ingest_stages, and reduces min, max and "any NaN" (torch's extrema propagate NaN, v_min_f32 /
+// v_max_f32 drop it).  The frame is the grid's y index, so it is workgroup-uniform; a frame's gridDim.x workgroups walk that
+// frame alone and leave partial[frame][blockIdx.x].  ingest_extrema_fold_kernel, one workgroup per frame, folds the frame's
+// partials -- no atomics, so the result does not depend on the order the workgroups ran in -- and forms sub, top and
+// div = fl32(top - sub) for the CT_INGEST_AFFINE_DATA stage of ct_ingest.hip: two launches whatever the number of frames.
+// ct_ingest_extrema_frames gives every frame of its stack constants of its own (a consumer whose frames are batches of their
+// own: linearize_dataset_generator); ct_ingest_extrema is the same call with the whole stack as its one frame (grid y = 1),
+// and since min, max and the NaN flag are exact and order-independent, the four floats of frame f are those
+// ct_ingest_extrema gives for that frame alone.
 //
 // Roofline: HBM, sizeof(T) bytes read per sample, every byte once; nothing written but 16 bytes per workgroup.
 //
 // A span is a run of elements that share the clamp pair.  When no prefix stage depends on the channel (the empty prefix
-// included) the whole stack is ONE span, whatever its layout.  Otherwise: PLANES, each plane is a span (channel = plane
-// index % channels, wave-uniform); PACKED3, the interleaved stack is one span whose element e belongs to memory channel
+// included) a frame is ONE span, whatever its layout.  Otherwise: PLANES, each plane of the frame is a span (channel = plane
+// index % channels, wave-uniform); PACKED3, the interleaved frame is one span whose element e belongs to memory channel
 // e % 3 (BGR: plane 2 - e % 3).  A span is read as
 //   head     the elements in front of the first 16-byte boundary                        (thread t of the grid: element t)
 //   packets  16-byte aligned loads, kLoads per thread in flight; a workgroup owns kBlock * kLoads consecutive packets per
-//            trip (lanes side by side in each of the kLoads rows), the grid strides over the trips (persistent workgroups)
+//            trip (lanes side by side in each of the kLoads rows), the frame's workgroups stride over the trips (persistent
+//            workgroups)
 //   rest     what follows the last whole packet (PACKED3: the last whole triple)         (thread t: element rest0 + t)
+// The walk starts at the frame's own base address -- the head length and, for PACKED3, the channel phase of the registers
+// follow from that address, so they are per frame (a frame's byte size need not be a multiple of 16).
 // PACKED3 with channel-dependent stages reads three consecutive packets per thread: 3 * 16 bytes hold a whole number of
 // pixels, so the channel of every register is the same for all lanes (it depends on head % 3 alone).
 // Integer codes with an empty prefix are reduced as integers (packed 16-bit min / max: the cast to float32 is exact and
 // monotone) and converted once per workgroup.
-// Every load is that of an element of [src, src + n); nothing is written except partial[blockIdx.x].
-//
-// ct_ingest_extrema_frames is the same reduction with one set of constants PER FRAME of a dense stack, for a consumer whose
-// frames are batches of their own (linearize_dataset_generator).  The frame is the grid's y index, so it is
-// workgroup-uniform; a frame's workgroups walk that frame alone with the span walk above, which starts at the frame's own
-// base address -- the head length and, for PACKED3, the channel phase of the registers follow from that address, so they
-// are per frame (a frame's byte size need not be a multiple of 16).  Partials go to workspace[frame][group], the fold
-// kernel runs one workgroup per frame: two launches for the whole stack, and since min, max and the NaN flag are exact and
-// order-independent the four floats of frame f are those ct_ingest_extrema gives for that frame alone.
+// Every load is that of an element of the workgroup's frame; nothing is written except the workgroup's partial.
 #include <algorithm>
 
 #include "ct_ingest_stages.hpp"
@@ -248,10 +249,13 @@ __device__ __forceinline__ bool extrema_block_fold(FloatAcc &s)
     return true;
 }
 
+// Frame blockIdx.y of a dense stack: a.span * a.n_spans elements per frame (PLANES: n_spans planes of a.span elements,
+// plane q of channel q % a.channels; else one span).  Workgroup blockIdx.x of gridDim.x walks that frame and leaves
+// partial[frame][blockIdx.x].
 template <typename T, int MODE>
 __global__ __launch_bounds__(kBlock) void ingest_extrema_kernel(const ExtremaArgs a)
 {
-    const T *src = static_cast<const T *>(a.src);
+    const T *src = static_cast<const T *>(a.src) + (int64_t)blockIdx.y * ((int64_t)a.n_spans * a.span);
     FloatAcc acc;
     if constexpr (MODE == kRawCodes) {
         CodeAcc codes;
@@ -267,14 +271,17 @@ __global__ __launch_bounds__(kBlock) void ingest_extrema_kernel(const ExtremaArg
     }
     if (extrema_block_fold(acc)) {
         u32x4_t out = {__float_as_uint(acc.lo), __float_as_uint(acc.hi), acc.nan, 0u};
-        *reinterpret_cast<u32x4_t *>(&a.partial[blockIdx.x]) = out;
+        *reinterpret_cast<u32x4_t *>(&a.partial[(int64_t)blockIdx.y * gridDim.x + blockIdx.x]) = out;
     }
 }
 
-// one workgroup: consts = {sub, div, data min, data max}
-__device__ __forceinline__ void extrema_fold_partials(const ExtremaPartial *__restrict__ partial, int n_partials, int from_data,
-                                                      float fixed_min, float fixed_max, float *__restrict__ consts)
+// workgroup f: the n_partials partials of frame f -> consts[4 f .. 4 f + 3] = {sub, div, data min, data max}
+__global__ __launch_bounds__(kBlock) void ingest_extrema_fold_kernel(const ExtremaPartial *__restrict__ partial, int n_partials,
+                                                                     int from_data, float fixed_min, float fixed_max,
+                                                                     float *__restrict__ consts)
 {
+    partial += (int64_t)blockIdx.x * n_partials;
+    consts += 4 * (int64_t)blockIdx.x;
     FloatAcc acc;
     for (int k = threadIdx.x; k < n_partials; k += kBlock) {
         FloatAcc p;
@@ -293,73 +300,20 @@ __device__ __forceinline__ void extrema_fold_partials(const ExtremaPartial *__re
     consts[3] = hi;
 }
 
-__global__ __launch_bounds__(kBlock) void ingest_extrema_fold_kernel(const ExtremaPartial *__restrict__ partial, int n_partials,
-                                                                     int from_data, float fixed_min, float fixed_max,
-                                                                     float *__restrict__ consts)
-{
-    extrema_fold_partials(partial, n_partials, from_data, fixed_min, fixed_max, consts);
-}
-
-// ---- one set of constants per frame ------------------------------------------------------------------------------------
-// Frame blockIdx.y of a dense stack: a.span * a.n_spans elements per frame (PLANES: n_spans = channels planes of a.span
-// elements; else one span).  Workgroup blockIdx.x of gridDim.x walks that frame and leaves partial[frame][blockIdx.x].
-template <typename T, int MODE>
-__global__ __launch_bounds__(kBlock) void ingest_extrema_frames_kernel(const ExtremaArgs a)
-{
-    const T *src = static_cast<const T *>(a.src) + (int64_t)blockIdx.y * ((int64_t)a.n_spans * a.span);
-    FloatAcc acc;
-    if constexpr (MODE == kRawCodes) {
-        CodeAcc codes;
-        extrema_span<T, false, false>(a, src, a.span, 0u, codes);
-        acc = codes.as_float();
-    } else if constexpr (MODE == kUniform) {
-        extrema_span<T, false, false>(a, src, a.span, 0u, acc);
-    } else if constexpr (MODE == kPlanes) {
-        for (uint32_t q = 0; q < a.n_spans; ++q) extrema_span<T, false, false>(a, src + (int64_t)q * a.span, a.span, q, acc);
-    } else {
-        extrema_span<T, true, MODE == kPacked3Rev>(a, src, a.span, 0u, acc);
-    }
-    if (extrema_block_fold(acc)) {
-        u32x4_t out = {__float_as_uint(acc.lo), __float_as_uint(acc.hi), acc.nan, 0u};
-        *reinterpret_cast<u32x4_t *>(&a.partial[(int64_t)blockIdx.y * gridDim.x + blockIdx.x]) = out;
-    }
-}
-
-// workgroup f: the n_partials partials of frame f -> consts[4 f .. 4 f + 3]
-__global__ __launch_bounds__(kBlock) void ingest_extrema_frames_fold_kernel(const ExtremaPartial *__restrict__ partial,
-                                                                            int n_partials, int from_data, float fixed_min,
-                                                                            float fixed_max, float *__restrict__ consts)
-{
-    extrema_fold_partials(partial + (int64_t)blockIdx.x * n_partials, n_partials, from_data, fixed_min, fixed_max,
-                          consts + 4 * (int64_t)blockIdx.x);
-}
-
 template <typename T>
-static void launch_extrema(const ExtremaArgs &a, int mode, int groups, hipStream_t s)
+static void launch_extrema(const ExtremaArgs &a, int mode, dim3 grid, hipStream_t s)
 {
-    const dim3 grid(groups), block(kBlock);
+    const dim3 block(kBlock);
     if (mode == kUniform)
         hipLaunchKernelGGL((ingest_extrema_kernel<T, kUniform>), grid, block, 0, s, a);
     else if (mode == kPlanes)
         hipLaunchKernelGGL((ingest_extrema_kernel<T, kPlanes>), grid, block, 0, s, a);
     else if (mode == kPacked3)
         hipLaunchKernelGGL((ingest_extrema_kernel<T, kPacked3>), grid, block, 0, s, a);
-    else
+    else if (mode == kPacked3Rev)
         hipLaunchKernelGGL((ingest_extrema_kernel<T, kPacked3Rev>), grid, block, 0, s, a);
-}
-
-template <typename T>
-static void launch_extrema_frames(const ExtremaArgs &a, int mode, dim3 grid, hipStream_t s)
-{
-    const dim3 block(kBlock);
-    if (mode == kUniform)
-        hipLaunchKernelGGL((ingest_extrema_frames_kernel<T, kUniform>), grid, block, 0, s, a);
-    else if (mode == kPlanes)
-        hipLaunchKernelGGL((ingest_extrema_frames_kernel<T, kPlanes>), grid, block, 0, s, a);
-    else if (mode == kPacked3)
-        hipLaunchKernelGGL((ingest_extrema_frames_kernel<T, kPacked3>), grid, block, 0, s, a);
-    else
-        hipLaunchKernelGGL((ingest_extrema_frames_kernel<T, kPacked3Rev>), grid, block, 0, s, a);
+    else if constexpr (sizeof(T) < sizeof(float))  // kRawCodes: integer codes only
+        hipLaunchKernelGGL((ingest_extrema_kernel<T, kRawCodes>), grid, block, 0, s, a);
 }
 
 // Partials (= most workgroups) per frame of an n_frames launch: together about kExtremaGroups, which is what fills the
@@ -371,135 +325,91 @@ static inline int64_t extrema_groups_per_frame(int64_t n_frames)
 
 constexpr int64_t kExtremaMaxFrames = 65535;  // a grid's y extent
 
+// bytes of the partials of an n_frames launch; 0: one call does not take that many frames
+static inline int64_t extrema_workspace(int64_t n_frames)
+{
+    if (n_frames < 1 || n_frames > kExtremaMaxFrames) return 0;
+    return n_frames * extrema_groups_per_frame(n_frames) * (int64_t)sizeof(ExtremaPartial);
+}
+
+// Both entry points.  per_frame: every image of the stack is a frame with constants of its own (consts_dev holds four floats
+// per image); else the whole stack is the one frame.  The two test workspace and size in opposite orders, which decides the
+// status of a call with both faults: the whole-stack call tests its workspace first, the per-frame call the size.
+static int ingest_extrema(const void *src_dev, int32_t dtype, int32_t layout, int64_t n_images, bool per_frame, int32_t channels,
+                          int64_t plane, const ct_ingest_stage *prefix, int32_t n_prefix, int32_t from_data, float fixed_min,
+                          float fixed_max, void *workspace_dev, int64_t workspace_bytes, float *consts_dev, void *stream)
+{
+    bool by_channel = false;
+    const int rc = ingest_validate(dtype, layout, n_images, channels, plane, prefix, n_prefix, CT_EXTREMA_MAX_PREFIX, 0, by_channel);
+    if (rc != CT_OK) return rc;
+    if (from_data < CT_EXTREMA_MIN || from_data > (CT_EXTREMA_MIN | CT_EXTREMA_MAX)) return CT_ERR_INVALID_ARGUMENT;
+    if (n_images == 0 || plane == 0) return CT_ERR_INVALID_ARGUMENT;  // torch raises on the extrema of an empty tensor
+    if (!src_dev || !aligned(src_dev, dtype_bytes(dtype))) return CT_ERR_INVALID_ARGUMENT;
+    if (!consts_dev || !aligned(consts_dev, sizeof(float))) return CT_ERR_INVALID_ARGUMENT;
+    const int64_t n_frames = per_frame ? n_images : 1;
+    const bool workspace_ok = workspace_dev && workspace_bytes >= extrema_workspace(n_frames) && aligned(workspace_dev, 16);
+    if (!per_frame && !workspace_ok) return CT_ERR_INVALID_ARGUMENT;
+    int64_t rows, total;
+    if (__builtin_mul_overflow(n_images, (int64_t)channels, &rows) || __builtin_mul_overflow(rows, plane, &total) ||
+        total > (INT64_MAX >> 4) || rows > 0x7fffffff || n_frames > kExtremaMaxFrames)
+        return CT_ERR_TOO_LARGE;
+    if (!workspace_ok) return CT_ERR_INVALID_ARGUMENT;
+    ExtremaArgs a = {};
+    a.src = src_dev;
+    a.partial = static_cast<ExtremaPartial *>(workspace_dev);
+    a.n_stages = (uint32_t)n_prefix;
+    for (int32_t k = 0; k < n_prefix; ++k) a.stage[k] = prefix[k];
+    a.span = total / n_frames;  // a frame
+    a.n_spans = 1;
+    a.channels = 1;
+    int mode = kUniform;
+    if (by_channel && layout == CT_LAYOUT_NCHW) {
+        mode = kPlanes;
+        a.span = plane;
+        a.n_spans = (uint32_t)(rows / n_frames);
+        a.channels = (uint32_t)channels;
+    } else if (by_channel) {
+        mode = layout == CT_LAYOUT_NHWC_BGR ? kPacked3Rev : kPacked3;
+    } else if (n_prefix == 0 && dtype != CT_DTYPE_F32) {
+        mode = kRawCodes;
+    }
+    const int64_t elems_per_trip = (int64_t)kBlock * (16 / (int64_t)dtype_bytes(dtype)) * (mode >= kPacked3 ? 6 : kLoads);
+    const int64_t trips = std::max<int64_t>(1, (a.span + elems_per_trip - 1) / elems_per_trip);
+    const int groups = (int)std::min<int64_t>(extrema_groups_per_frame(n_frames), trips);
+    const dim3 grid((uint32_t)groups, (uint32_t)n_frames);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dtype == CT_DTYPE_U8)
+        launch_extrema<uint8_t>(a, mode, grid, s);
+    else if (dtype == CT_DTYPE_U16)
+        launch_extrema<uint16_t>(a, mode, grid, s);
+    else
+        launch_extrema<float>(a, mode, grid, s);
+    if (hipGetLastError() != hipSuccess) return CT_ERR_LAUNCH;
+    hipLaunchKernelGGL(ingest_extrema_fold_kernel, dim3((uint32_t)n_frames), dim3(kBlock), 0, s, a.partial, groups, from_data,
+                       fixed_min, fixed_max, consts_dev);
+    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
+}
+
 }  // namespace ct
 
-extern "C" int64_t ct_ingest_extrema_workspace(void) { return (int64_t)ct::kExtremaGroups * (int64_t)sizeof(ct::ExtremaPartial); }
+extern "C" int64_t ct_ingest_extrema_workspace(void) { return ct::extrema_workspace(1); }
 
 extern "C" int ct_ingest_extrema(const void *src_dev, int32_t dtype, int32_t layout, int64_t n_images, int32_t channels,
                                  int64_t plane, const ct_ingest_stage *prefix, int32_t n_prefix, int32_t from_data,
                                  float fixed_min, float fixed_max, void *workspace_dev, int64_t workspace_bytes,
                                  float *consts_dev, void *stream)
 {
-    using namespace ct;
-    bool by_channel = false;
-    const int rc = ingest_validate(dtype, layout, n_images, channels, plane, prefix, n_prefix, CT_EXTREMA_MAX_PREFIX, 0, by_channel);
-    if (rc != CT_OK) return rc;
-    if (from_data < CT_EXTREMA_MIN || from_data > (CT_EXTREMA_MIN | CT_EXTREMA_MAX)) return CT_ERR_INVALID_ARGUMENT;
-    if (n_images == 0 || plane == 0) return CT_ERR_INVALID_ARGUMENT;  // torch raises on the extrema of an empty tensor
-    const uintptr_t src_align = dtype == CT_DTYPE_U8 ? 1 : (dtype == CT_DTYPE_U16 ? 2 : 4);
-    if (!src_dev || reinterpret_cast<uintptr_t>(src_dev) % src_align != 0) return CT_ERR_INVALID_ARGUMENT;
-    if (!consts_dev || reinterpret_cast<uintptr_t>(consts_dev) % sizeof(float) != 0) return CT_ERR_INVALID_ARGUMENT;
-    if (!workspace_dev || workspace_bytes < ct_ingest_extrema_workspace() || reinterpret_cast<uintptr_t>(workspace_dev) % 16 != 0)
-        return CT_ERR_INVALID_ARGUMENT;
-    int64_t rows, total;
-    if (__builtin_mul_overflow(n_images, (int64_t)channels, &rows) || __builtin_mul_overflow(rows, plane, &total) ||
-        total > (INT64_MAX >> 4) || rows > 0x7fffffff)
-        return CT_ERR_TOO_LARGE;
-    ExtremaArgs a = {};
-    a.src = src_dev;
-    a.partial = static_cast<ExtremaPartial *>(workspace_dev);
-    a.n_stages = (uint32_t)n_prefix;
-    for (int32_t k = 0; k < n_prefix; ++k) a.stage[k] = prefix[k];
-    a.span = total;
-    a.n_spans = 1;
-    a.channels = 1;
-    int mode = kUniform;
-    if (by_channel && layout == CT_LAYOUT_NCHW) {
-        mode = kPlanes;
-        a.span = plane;
-        a.n_spans = (uint32_t)rows;
-        a.channels = (uint32_t)channels;
-    } else if (by_channel) {
-        mode = layout == CT_LAYOUT_NHWC_BGR ? kPacked3Rev : kPacked3;
-    } else if (n_prefix == 0 && dtype != CT_DTYPE_F32) {
-        mode = kRawCodes;
-    }
-    const int64_t elems_per_trip = (int64_t)kBlock * (16 / (int64_t)src_align) * (mode >= kPacked3 ? 6 : kLoads);
-    const int groups = (int)std::min<int64_t>(kExtremaGroups, std::max<int64_t>(1, (a.span + elems_per_trip - 1) / elems_per_trip));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (mode == kRawCodes) {
-        if (dtype == CT_DTYPE_U8)
-            hipLaunchKernelGGL((ingest_extrema_kernel<uint8_t, kRawCodes>), dim3(groups), dim3(kBlock), 0, s, a);
-        else
-            hipLaunchKernelGGL((ingest_extrema_kernel<uint16_t, kRawCodes>), dim3(groups), dim3(kBlock), 0, s, a);
-    } else if (dtype == CT_DTYPE_U8) {
-        launch_extrema<uint8_t>(a, mode, groups, s);
-    } else if (dtype == CT_DTYPE_U16) {
-        launch_extrema<uint16_t>(a, mode, groups, s);
-    } else {
-        launch_extrema<float>(a, mode, groups, s);
-    }
-    if (hipGetLastError() != hipSuccess) return CT_ERR_LAUNCH;
-    hipLaunchKernelGGL(ingest_extrema_fold_kernel, dim3(1), dim3(kBlock), 0, s, a.partial, groups, from_data, fixed_min, fixed_max,
-                       consts_dev);
-    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
+    return ct::ingest_extrema(src_dev, dtype, layout, n_images, false, channels, plane, prefix, n_prefix, from_data, fixed_min,
+                              fixed_max, workspace_dev, workspace_bytes, consts_dev, stream);
 }
 
-extern "C" int64_t ct_ingest_extrema_frames_workspace(int64_t n_frames)
-{
-    if (n_frames < 1 || n_frames > ct::kExtremaMaxFrames) return 0;
-    return n_frames * ct::extrema_groups_per_frame(n_frames) * (int64_t)sizeof(ct::ExtremaPartial);
-}
+extern "C" int64_t ct_ingest_extrema_frames_workspace(int64_t n_frames) { return ct::extrema_workspace(n_frames); }
 
 extern "C" int ct_ingest_extrema_frames(const void *src_dev, int32_t dtype, int32_t layout, int64_t n_frames, int32_t channels,
                                         int64_t plane, const ct_ingest_stage *prefix, int32_t n_prefix, int32_t from_data,
                                         float fixed_min, float fixed_max, void *workspace_dev, int64_t workspace_bytes,
                                         float *consts_dev, void *stream)
 {
-    using namespace ct;
-    bool by_channel = false;
-    const int rc = ingest_validate(dtype, layout, n_frames, channels, plane, prefix, n_prefix, CT_EXTREMA_MAX_PREFIX, 0, by_channel);
-    if (rc != CT_OK) return rc;
-    if (from_data < CT_EXTREMA_MIN || from_data > (CT_EXTREMA_MIN | CT_EXTREMA_MAX)) return CT_ERR_INVALID_ARGUMENT;
-    if (n_frames == 0 || plane == 0) return CT_ERR_INVALID_ARGUMENT;  // torch raises on the extrema of an empty tensor
-    const uintptr_t src_align = dtype == CT_DTYPE_U8 ? 1 : (dtype == CT_DTYPE_U16 ? 2 : 4);
-    if (!src_dev || reinterpret_cast<uintptr_t>(src_dev) % src_align != 0) return CT_ERR_INVALID_ARGUMENT;
-    if (!consts_dev || reinterpret_cast<uintptr_t>(consts_dev) % sizeof(float) != 0) return CT_ERR_INVALID_ARGUMENT;
-    int64_t rows, total;
-    if (__builtin_mul_overflow(n_frames, (int64_t)channels, &rows) || __builtin_mul_overflow(rows, plane, &total) ||
-        total > (INT64_MAX >> 4) || rows > 0x7fffffff || n_frames > kExtremaMaxFrames)
-        return CT_ERR_TOO_LARGE;
-    if (!workspace_dev || workspace_bytes < ct_ingest_extrema_frames_workspace(n_frames) ||
-        reinterpret_cast<uintptr_t>(workspace_dev) % 16 != 0)
-        return CT_ERR_INVALID_ARGUMENT;
-    ExtremaArgs a = {};
-    a.src = src_dev;
-    a.partial = static_cast<ExtremaPartial *>(workspace_dev);
-    a.n_stages = (uint32_t)n_prefix;
-    for (int32_t k = 0; k < n_prefix; ++k) a.stage[k] = prefix[k];
-    a.span = (int64_t)channels * plane;  // a frame
-    a.n_spans = 1;
-    a.channels = 1;
-    int mode = kUniform;
-    if (by_channel && layout == CT_LAYOUT_NCHW) {
-        mode = kPlanes;
-        a.span = plane;
-        a.n_spans = (uint32_t)channels;
-        a.channels = (uint32_t)channels;
-    } else if (by_channel) {
-        mode = layout == CT_LAYOUT_NHWC_BGR ? kPacked3Rev : kPacked3;
-    } else if (n_prefix == 0 && dtype != CT_DTYPE_F32) {
-        mode = kRawCodes;
-    }
-    const int64_t elems_per_trip = (int64_t)kBlock * (16 / (int64_t)src_align) * (mode >= kPacked3 ? 6 : kLoads);
-    const int64_t trips = std::max<int64_t>(1, (a.span + elems_per_trip - 1) / elems_per_trip);
-    const int groups = (int)std::min<int64_t>(extrema_groups_per_frame(n_frames), trips);
-    const dim3 grid((uint32_t)groups, (uint32_t)n_frames);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (mode == kRawCodes) {
-        if (dtype == CT_DTYPE_U8)
-            hipLaunchKernelGGL((ingest_extrema_frames_kernel<uint8_t, kRawCodes>), grid, dim3(kBlock), 0, s, a);
-        else
-            hipLaunchKernelGGL((ingest_extrema_frames_kernel<uint16_t, kRawCodes>), grid, dim3(kBlock), 0, s, a);
-    } else if (dtype == CT_DTYPE_U8) {
-        launch_extrema_frames<uint8_t>(a, mode, grid, s);
-    } else if (dtype == CT_DTYPE_U16) {
-        launch_extrema_frames<uint16_t>(a, mode, grid, s);
-    } else {
-        launch_extrema_frames<float>(a, mode, grid, s);
-    }
-    if (hipGetLastError() != hipSuccess) return CT_ERR_LAUNCH;
-    hipLaunchKernelGGL(ingest_extrema_frames_fold_kernel, dim3((uint32_t)n_frames), dim3(kBlock), 0, s, a.partial, groups, from_data,
-                       fixed_min, fixed_max, consts_dev);
-    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
+    return ct::ingest_extrema(src_dev, dtype, layout, n_frames, true, channels, plane, prefix, n_prefix, from_data, fixed_min,
+                              fixed_max, workspace_dev, workspace_bytes, consts_dev, stream);
 }

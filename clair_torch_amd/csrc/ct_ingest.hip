@@ -201,11 +201,9 @@ static int ingest_transform(const void *src_dev, int32_t dtype, int32_t layout, 
     const int rc = ingest_validate(dtype, layout, n_images, channels, plane, stages, n_stages, CT_INGEST_MAX_STAGES, data ? 1 : 0,
                                    by_channel);
     if (rc != CT_OK) return rc;
-    if (data && (!consts_dev || reinterpret_cast<uintptr_t>(consts_dev) % sizeof(float) != 0)) return CT_ERR_INVALID_ARGUMENT;
+    if (data && (!consts_dev || !aligned(consts_dev, sizeof(float)))) return CT_ERR_INVALID_ARGUMENT;
     if (n_images == 0 || plane == 0) return CT_OK;
-    const uintptr_t src_align = dtype == CT_DTYPE_U8 ? 1 : (dtype == CT_DTYPE_U16 ? 2 : 4);
-    if (!src_dev || !dst_dev || reinterpret_cast<uintptr_t>(src_dev) % src_align != 0 ||
-        reinterpret_cast<uintptr_t>(dst_dev) % sizeof(float) != 0)
+    if (!src_dev || !dst_dev || !aligned(src_dev, dtype_bytes(dtype)) || !aligned(dst_dev, sizeof(float)))
         return CT_ERR_INVALID_ARGUMENT;
     // elements and byte offsets are 64-bit; planes / images are counted with 32 bits, a plane's packets with a grid's x
     int64_t rows, total;

@@ -296,8 +296,7 @@ static int linearize_ingest(const void *frames_dev, int32_t dtype, int64_t n_fra
     int64_t rows = n_frames;
     if ((!packed && __builtin_mul_overflow(n_frames, (int64_t)geom->channels, &rows)) || rows > 0x7fffffff) return CT_ERR_TOO_LARGE;
     if (n_frames == 0) return CT_OK;
-    const uintptr_t src_align = dtype == CT_DTYPE_U8 ? 1 : (dtype == CT_DTYPE_U16 ? 2 : 4);
-    if (!frames_dev || !lin_out_dev || !aligned(frames_dev, src_align) || !aligned(lin_out_dev, sizeof(float)) ||
+    if (!frames_dev || !lin_out_dev || !aligned(frames_dev, dtype_bytes(dtype)) || !aligned(lin_out_dev, sizeof(float)) ||
         !aligned(std_out_dev, sizeof(float)) || !aligned(std_dev, sizeof(float)))
         return CT_ERR_INVALID_ARGUMENT;
     LinIngestArgs a = {};

@@ -1056,14 +1056,9 @@ def hdr_merge_ingest_batches(frames_list, stages, exposures_list, *, lut: Option
 ZERO_RANGE = "Normalization range is zero (min == max); cannot normalize."  # general_functions.py:378
 
 
-def ingest_extrema(stack: torch.Tensor, prefix_stages=(), layout: str = "nchw", min_val=None, max_val=None):
-    """ct_ingest_extrema: the constants of a data-dependent Normalize (reference general_functions.py:373-376), as a
-    4-element float32 device tensor ``consts`` = [sub, div, data min, data max].  The extrema are those of the whole
-    ``stack`` (as ``ingest_transform`` takes it) after the up to 3 constant ``prefix_stages`` that stand in front of the
-    Normalize; a NaN anywhere makes both NaN.  ``min_val`` / ``max_val``: None takes that bound from the data (at least
-    one must be None), a number fixes it: sub = min, div = fl32(max - min) in float32, as torch forms them.  One
-    streaming pass plus a fold, no synchronisation: ``div == 0``, where the reference raises, is for the caller to
-    check (``ingest_transform_data``).  An empty stack raises, as torch's ``x.min()`` does."""
+def _extrema_call(front, stack, prefix_stages, layout, min_val, max_val):
+    """What ``ingest_extrema`` and ``ingest_extrema_frames`` (``front``: which of them, for the message) check and build
+    alike: the planar shape and the arguments of the entry points from ``prefix`` to ``fixed_max``."""
     _check_ingest_stack(stack, layout)
     if min_val is not None and max_val is not None:
         raise ValueError("min_val and max_val are both given: nothing depends on the data (use ingest_transform)")
@@ -1073,15 +1068,26 @@ def ingest_extrema(stack: torch.Tensor, prefix_stages=(), layout: str = "nchw", 
     fixed_min = 0.0 if min_val is None else _number(min_val, "min_val")
     fixed_max = 0.0 if max_val is None else _number(max_val, "max_val")
     if stack.numel() == 0:
-        raise RuntimeError("ingest_extrema: the stack is empty (the extrema of an empty tensor are undefined)")
+        raise RuntimeError(f"{front}: the stack is empty (the extrema of an empty tensor are undefined)")
+    return shape, (arr, n_prefix, from_data, fixed_min, fixed_max)
+
+
+def ingest_extrema(stack: torch.Tensor, prefix_stages=(), layout: str = "nchw", min_val=None, max_val=None):
+    """ct_ingest_extrema: the constants of a data-dependent Normalize (reference general_functions.py:373-376), as a
+    4-element float32 device tensor ``consts`` = [sub, div, data min, data max].  The extrema are those of the whole
+    ``stack`` (as ``ingest_transform`` takes it) after the up to 3 constant ``prefix_stages`` that stand in front of the
+    Normalize; a NaN anywhere makes both NaN.  ``min_val`` / ``max_val``: None takes that bound from the data (at least
+    one must be None), a number fixes it: sub = min, div = fl32(max - min) in float32, as torch forms them.  One
+    streaming pass plus a fold, no synchronisation: ``div == 0``, where the reference raises, is for the caller to
+    check (``ingest_transform_data``).  An empty stack raises, as torch's ``x.min()`` does."""
+    shape, args = _extrema_call("ingest_extrema", stack, prefix_stages, layout, min_val, max_val)
     lib = nv.load()
     ws_bytes = int(lib.ct_ingest_extrema_workspace())
     ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=stack.device)
     consts = torch.empty((4,), dtype=torch.float32, device=stack.device)
     with torch.cuda.device(stack.device):
         rc = lib.ct_ingest_extrema(_ptr(stack), _DTYPE[stack.dtype], _LAYOUT[layout], shape[0], shape[1], shape[2] * shape[3],
-                                   arr, n_prefix, from_data, fixed_min, fixed_max, _ptr(ws), ws_bytes, _ptr(consts),
-                                   _stream(stack.device))
+                                   *args, _ptr(ws), ws_bytes, _ptr(consts), _stream(stack.device))
     nv.check(rc, "ct_ingest_extrema")
     return consts
 
@@ -1104,16 +1110,7 @@ def ingest_extrema_frames(frames: torch.Tensor, prefix_stages=(), layout: str = 
     reference raises, is for the caller to check.  ``out``: a contiguous (F, 4) float32 device tensor to write into;
     ``workspace``: a float32 device tensor of at least the library's workspace size (``ingest_extrema_frames_workspace``);
     without them both are allocated here.  An empty stack raises, as torch's ``x.min()`` does."""
-    _check_ingest_stack(frames, layout)
-    if min_val is not None and max_val is not None:
-        raise ValueError("min_val and max_val are both given: nothing depends on the data (use ingest_transform)")
-    shape = ingest_shape(tuple(frames.shape), layout)
-    arr, n_prefix = _ingest_stages(prefix_stages, shape[1], limit=nv.EXTREMA_MAX_PREFIX)
-    from_data = (nv.EXTREMA_MIN if min_val is None else 0) | (nv.EXTREMA_MAX if max_val is None else 0)
-    fixed_min = 0.0 if min_val is None else _number(min_val, "min_val")
-    fixed_max = 0.0 if max_val is None else _number(max_val, "max_val")
-    if frames.numel() == 0:
-        raise RuntimeError("ingest_extrema_frames: the stack is empty (the extrema of an empty tensor are undefined)")
+    shape, args = _extrema_call("ingest_extrema_frames", frames, prefix_stages, layout, min_val, max_val)
     dev = frames.device
     lib = nv.load()
     ws_bytes = int(lib.ct_ingest_extrema_frames_workspace(shape[0]))
@@ -1132,8 +1129,8 @@ def ingest_extrema_frames(frames: torch.Tensor, prefix_stages=(), layout: str = 
         _check_frame_consts(out, shape[0], dev)
     with torch.cuda.device(dev):
         rc = lib.ct_ingest_extrema_frames(_ptr(frames), _DTYPE[frames.dtype], _LAYOUT[layout], shape[0], shape[1],
-                                          shape[2] * shape[3], arr, n_prefix, from_data, fixed_min, fixed_max, _ptr(workspace),
-                                          workspace.numel() * 4, _ptr(out), _stream(dev))
+                                          shape[2] * shape[3], *args, _ptr(workspace), workspace.numel() * 4, _ptr(out),
+                                          _stream(dev))
     nv.check(rc, "ct_ingest_extrema_frames")
     return out
 

@@ -1,7 +1,8 @@
 """The data-dependent Normalize of the streamed linearization on the device.  Every specification here is an equality of bit
-patterns with launches the project already had, and the comparand is never the new kernel:
+patterns, with launches the project already had or with the CPU:
   1. ``ops.ingest_extrema_frames(x)[f]``  ==  ``ops.ingest_extrema(x[f:f+1])`` -- min, max and the NaN flag are exact and
-     order-independent, so the partition of the work cannot show;
+     order-independent, so the partition of the work cannot show -- and, since both run one kernel, == the extrema of
+     frame f behind the prefix as the transform classes give them on the CPU;
   2. ``ops.linearize_ingest_frames(frames, stages, ..., consts=K)[f]``  ==  ``ops.linearize_frames(ops.ingest_transform(
      frames[f:f+1], stages, consts=K[f]), ...)``;
   3. the pipelined route of linearize_dataset_generator  ==  its frame-by-frame route  ==  the CPU classes' chain applied
@@ -110,6 +111,33 @@ def _prefixes(dtype):
             "clamp": [("clamp", [(-1e30, 1e30), (60 * s, 200 * s), (50 * s, 190 * s)])]}
 
 
+def _planar(mem, layout):
+    """Host frames in memory order -> the planar (B,C,H,W) float32 tensor the chain receives."""
+    x = mem.to(torch.float32)  # (exact for every code; torch flips no uint16)
+    if layout != "nchw":
+        x = x.permute(0, 3, 1, 2)
+        x = x.flip(1) if layout == "nhwc_bgr" else x
+    return x.contiguous()
+
+
+def _cpu_extrema(planar, prefix):
+    """x.min(), x.max() (0-dim float32) of ``planar`` behind the prefix stages, applied on the CPU by the project's own
+    classes: ("affine", sub, div, mul, add) is Normalize(sub + div, sub, (add, add + mul)) -- every constant of _prefixes is
+    exact in float32, so the class forms the same sub, div, mul and add -- and ("clamp", pairs) is ClampAlongDims(1, pairs)."""
+    T = _T()
+    classes = [T.Normalize(st[1] + st[2], st[1], (st[4], st[4] + st[3])) if st[0] == "affine" else T.ClampAlongDims(1, st[1])
+               for st in prefix]
+    x = _cpu_chain(planar, classes)
+    return x.min(), x.max()
+
+
+def _cpu_consts(lo, hi, mn, mx):
+    """[sub, div = fl32(top - sub), data min, data max], formed in float32 as torch forms them."""
+    sub = lo if mn is None else torch.tensor(mn, dtype=torch.float32)
+    top = hi if mx is None else torch.tensor(mx, dtype=torch.float32)
+    return torch.stack([sub, top - sub, lo, hi])
+
+
 # 3x1x1: less than one packet; 3x5x7: 105 elements, so frame sizes are no multiples of 16 bytes and the heads differ per
 # frame; 3x97x101: 29 391 elements, more than one workgroup trip per frame in every mode (the largest is 24 576 uint8
 # elements for packed3)
@@ -119,6 +147,8 @@ _EXTREMA_SHAPES = [(3, 1, 1), (3, 5, 7), (3, 97, 101)]
 @pytest.mark.parametrize("layout", ["nchw", "nhwc", "nhwc_bgr"])
 @pytest.mark.parametrize("dtype", [torch.uint8, torch.uint16, torch.float32])
 def test_extrema_per_frame_equal_single_frame_calls(dev, dtype, layout):
+    """Both calls run one kernel, so their equality checks the frame base, the per-frame head and the indexing of the
+    partials; the values themselves are checked against the CPU, frame by frame."""
     from clair_torch_amd import ops
     rng = np.random.default_rng(101)
     s = float(_SCALE[dtype])
@@ -127,11 +157,14 @@ def test_extrema_per_frame_equal_single_frame_calls(dev, dtype, layout):
         host, lo, hi = _bordered_frames(rng, mem_shape, dtype)
         x = host.to(dev)
         for kind, prefix in _prefixes(dtype).items():
+            cpu = [_cpu_extrema(_planar(host[f:f + 1], layout), prefix) for f in range(F)]
             for mn, mx in ((None, None), (None, 300 * s), (-5 * s, None)):  # both, the minimum, the maximum from the data
                 got = ops.ingest_extrema_frames(x, prefix, layout, mn, mx)
                 assert tuple(got.shape) == (F, 4) and got.dtype == torch.float32 and got.device == x.device
                 want = torch.stack([ops.ingest_extrema(x[f:f + 1], prefix, layout, mn, mx) for f in range(F)])
                 assert _same_bits(got, want), (chw, kind, mn, mx, got.cpu(), want.cpu())
+                ref = torch.stack([_cpu_consts(*cpu[f], mn, mx) for f in range(F)])
+                assert _same_bits(got, ref), (chw, kind, mn, mx, got.cpu(), ref)
                 if kind == "none":  # ... and what was planted
                     data = got.cpu().numpy()
                     assert np.array_equal(data[:, 2], lo) and np.array_equal(data[:, 3], hi), (chw, data)
@@ -158,6 +191,27 @@ def test_a_nan_stays_in_its_frame(dev, layout, kind):
     # a fixed bound is no NaN; the data extrema of that frame still are
     fixed = ops.ingest_extrema_frames(x, prefix, layout, -5.0, None).cpu()
     assert float(fixed[2, 0]) == -5.0 and torch.isnan(fixed[2, 1:]).all() and not torch.isnan(fixed[[0, 1, 3, 4]]).any()
+
+
+def test_planes_of_a_second_image_take_their_channels_clamp(dev):
+    """(2,3,5,7) uint16 planar behind the per-channel clamp: the whole-stack call walks six planes as one frame, and planes
+    3 to 5 are channels 0 to 2 again (plane index % channels; the plane index alone would read pairs that are not there).
+    The stack's extrema lie in the second image, where only its channel's pair cuts them.  Against the CPU, and the same
+    stack through the per-frame call, where each image is a frame of three planes."""
+    from clair_torch_amd import ops
+    rng = np.random.default_rng(163)
+    s = _SCALE[torch.uint16]
+    host = rng.integers(70, 181, size=(2, 3, 5, 7))
+    host[1, 2, 2, 3], host[1, 1, 4, 6] = 10, 240  # below plane 2's lower bound 50, above plane 1's upper bound 200
+    host = torch.from_numpy((host * s).astype(np.uint16))
+    prefix = _prefixes(torch.uint16)["clamp"]
+    x = host.to(dev)
+    lo, hi = _cpu_extrema(_planar(host, "nchw"), prefix)
+    assert float(lo) == 50 * s and float(hi) == 200 * s
+    for mn, mx in ((None, None), (None, 300.0 * s), (-5.0 * s, None)):
+        assert _same_bits(ops.ingest_extrema(x, prefix, "nchw", mn, mx), _cpu_consts(lo, hi, mn, mx)), (mn, mx)
+        ref = torch.stack([_cpu_consts(*_cpu_extrema(_planar(host[f:f + 1], "nchw"), prefix), mn, mx) for f in range(2)])
+        assert _same_bits(ops.ingest_extrema_frames(x, prefix, "nchw", mn, mx), ref), (mn, mx)
 
 
 def test_extrema_front_end_buffers_and_custom_op(dev):
