@@ -30,7 +30,7 @@ EXPORTS = ("ct_abi_version", "ct_error_string", "ct_hdr_merge_batch", "ct_hdr_me
            "ct_strided_downscale", "ct_export_cv", "ct_ingest_transform", "ct_ingest_extrema_workspace", "ct_ingest_extrema",
            "ct_ingest_transform_data", "ct_linearize_ingest", "ct_hdr_merge_ingest_batch", "ct_video_stats_ingest_batch",
            "ct_hdr_merge_ingest_batches", "ct_ingest_extrema_frames_workspace", "ct_ingest_extrema_frames",
-           "ct_linearize_ingest_data")
+           "ct_linearize_ingest_data", "ct_pair_residual_ingest_fwd", "ct_pair_residual_ingest_bwd")
 
 
 class Geometry(ctypes.Structure):
@@ -147,6 +147,12 @@ def load():
                                                 vp, vp, vp, vp, u32, vp]
     lib.ct_video_stats_ingest_batch.restype = i32
     lib.ct_video_stats_ingest_batch.argtypes = [vp, i32, i32, gp, ctypes.POINTER(IngestStage), i32, vp, ip, f32, vp, vp, vp]
+    stages = ctypes.POINTER(IngestStage)
+    lib.ct_pair_residual_ingest_fwd.restype = i32
+    lib.ct_pair_residual_ingest_fwd.argtypes = [vp, i32, stages, i32, vp, i32, gp, vp, ip, vp, vp, vp, i32, pp, i32, vp, vp, vp]
+    lib.ct_pair_residual_ingest_bwd.restype = i32
+    lib.ct_pair_residual_ingest_bwd.argtypes = [vp, i32, stages, i32, vp, i32, gp, vp, ip, vp, i32, vp, vp, vp, pp, vp, vp, vp, vp,
+                                                i64, vp]
     lib.ct_video_stats_batch.restype = i32
     lib.ct_video_stats_batch.argtypes = [vp, i32, f32, i32, gp, ip, f32, vp, vp, vp]
     if lib.ct_abi_version() != ABI_VERSION:

@@ -1219,3 +1219,101 @@ def video_stats_ingest_batch(frames: torch.Tensor, stages, mean_state: torch.Ten
                                                    _ptr(m2_state), _stream(dev))
     nv.check(rc, "ct_video_stats_ingest_batch")
     del lut_keep
+
+
+# ---- a gpu_transforms chain and the exposure-pair residual in one pass -------------------------------------------------------
+_PAIR_INGEST_CODES = ("pair_residual_ingest takes uint8 / uint16 codes (float32 pixels: ingest_transform + "
+                      "pair_residual_sums / pair_residual_lut_grad)")
+
+
+def _pair_ingest_setup(frames, stages, pairs, consts, layout, std, std_mode, lut, interp, tile):
+    """What the two pair ingest fronts share: the checks of ``video_stats_ingest_batch`` and the structs of the call."""
+    _check_ingest_stack(frames, layout, codes_only=_PAIR_INGEST_CODES)
+    shape = ingest_shape(tuple(frames.shape), layout)
+    n, c = shape[0], shape[1]
+    dev = frames.device
+    if n != pairs.n_images:
+        raise ValueError(f"pair list was built for {pairs.n_images} images, stack has {n}")
+    arr, n_stages = _ingest_stages(stages, c, data=consts is not None)
+    if consts is not None:
+        _check_consts(consts, dev)
+    if std is not None:
+        std_mode, std = "explicit", _planar_std(std, shape, dev, "ingested stack")
+    if std_mode not in _STD:
+        raise ValueError(f"unknown std_mode {std_mode}")
+    icrf, lut_keep = _icrf_struct(lut, interp, c)
+    return shape, arr, n_stages, std, std_mode, icrf, lut_keep, _ingest_geometry(shape, tile, layout)
+
+
+def pair_residual_ingest_sums(frames: torch.Tensor, stages, pairs: PairList, *, lut: Optional[torch.Tensor], interp: Optional[str],
+                              lower: float, upper: float, use_relative: bool, use_unc_weight: bool,
+                              consts: Optional[torch.Tensor] = None, std: Optional[torch.Tensor] = None, std_mode: str = "none",
+                              std_value: float = 0.0, level: int = 1, tile: Optional[TileGeometry] = None,
+                              center: Optional[torch.Tensor] = None, layout: str = "nchw"):
+    """ct_pair_residual_ingest_fwd: ``pair_residual_sums(ingest_transform(frames, stages, layout, consts=consts), pairs, ...)``
+    in one launch and without the float32 stack in between -> (P, C, 5) float64 sums; every staged sample has the bits of that
+    route, the sums differ by the order of the float64 additions alone.
+
+    ``frames``: a contiguous uint8 / uint16 device stack, (N,C,H,W) for "nchw" or (N,H,W,3) for "nhwc" / "nhwc_bgr" (the
+    order of the source: a folded CvToTorch).  ``stages``: as ``ingest_transform`` takes them; with ``consts`` (the tensor
+    ``ingest_extrema`` returned) one of them may be ("affine_data", mul, add).  ``std``: explicit uncertainties, float32 and
+    PLANAR (N,C,H,W) whatever the layout of the frames.  Everything else as in ``pair_residual_sums``."""
+    shape, arr, n_stages, std, std_mode, icrf, lut_keep, geom = _pair_ingest_setup(frames, stages, pairs, consts, layout, std,
+                                                                                  std_mode, lut, interp, tile)
+    n, c = shape[0], shape[1]
+    dev = frames.device
+    prm = _pair_params(lower, upper, use_relative, use_unc_weight, std_mode, std_value)
+    sums = torch.zeros((pairs.n_pairs, c, 5), dtype=torch.float64, device=dev)
+    if center is not None:
+        center = center.to(device=dev, dtype=torch.float64).contiguous()
+        if center.shape != (pairs.n_pairs, c):
+            raise ValueError(f"center must be (P={pairs.n_pairs}, C={c})")
+    if pairs.n_pairs:
+        with torch.cuda.device(dev):
+            rc = nv.load().ct_pair_residual_ingest_fwd(_ptr(frames), _DTYPE[frames.dtype], arr, n_stages, _ptr(consts), n,
+                                                       ctypes.byref(geom), _ptr(std), ctypes.byref(icrf), _ptr(pairs.i),
+                                                       _ptr(pairs.j), _ptr(pairs.ratio), pairs.n_pairs, ctypes.byref(prm),
+                                                       int(level), _ptr(center), _ptr(sums), _stream(dev))
+        nv.check(rc, "ct_pair_residual_ingest_fwd")
+    del lut_keep
+    return sums
+
+
+def pair_residual_ingest_lut_grad(frames: torch.Tensor, stages, pairs: PairList, coef: torch.Tensor, *, lut: torch.Tensor,
+                                  interp: str, lower: float, upper: float, use_relative: bool,
+                                  consts: Optional[torch.Tensor] = None, tile: Optional[TileGeometry] = None,
+                                  use_unc_weight: bool = False, std: Optional[torch.Tensor] = None, std_mode: str = "none",
+                                  std_value: float = 0.0, smean: Optional[torch.Tensor] = None, lane_kernel: bool = True,
+                                  layout: str = "nchw"):
+    """ct_pair_residual_ingest_bwd: ``pair_residual_lut_grad(ingest_transform(frames, stages, layout, consts=consts), pairs,
+    coef, ...)`` in one launch sequence and without the float32 stack -> (C, L) float64 LUT gradient.  ``frames``, ``stages``,
+    ``consts`` and ``std`` as in ``pair_residual_ingest_sums``, everything else as in ``pair_residual_lut_grad``."""
+    if not use_unc_weight:
+        std, std_mode = None, "none"
+    shape, arr, n_stages, std, std_mode, icrf, lut_keep, geom = _pair_ingest_setup(frames, stages, pairs, consts, layout, std,
+                                                                                  std_mode, lut, interp, tile)
+    n, c = shape[0], shape[1]
+    dev = frames.device
+    prm = _pair_params(lower, upper, use_relative, use_unc_weight, std_mode, std_value,
+                       pair_band=pairs.band if lane_kernel else 0)
+    if std_mode != "none":
+        if smean is None:
+            raise ValueError("the uncertainty-weighted backward needs the forward's spatial means")
+        smean = smean.to(device=dev, dtype=torch.float64).contiguous()
+    else:
+        smean = None
+    coef = coef.to(device=dev, dtype=torch.float64).contiguous()
+    if coef.shape != (pairs.n_pairs, c):
+        raise ValueError(f"coef must be (P={pairs.n_pairs}, C={c}), got {tuple(coef.shape)}")
+    grad = torch.zeros((c, lut.shape[1]), dtype=torch.float64, device=dev)
+    if pairs.n_pairs:
+        ws = pairs.workspace(c)
+        with torch.cuda.device(dev):
+            rc = nv.load().ct_pair_residual_ingest_bwd(_ptr(frames), _DTYPE[frames.dtype], arr, n_stages, _ptr(consts), n,
+                                                       ctypes.byref(geom), _ptr(std), ctypes.byref(icrf), _ptr(pairs.ratio),
+                                                       pairs.n_pairs, _ptr(pairs.part_off), _ptr(pairs.part_sample),
+                                                       _ptr(pairs.part_pair), ctypes.byref(prm), _ptr(coef), _ptr(smean),
+                                                       _ptr(grad), _ptr(ws), ws.numel(), _stream(dev))
+        nv.check(rc, "ct_pair_residual_ingest_bwd")
+    del lut_keep
+    return grad

@@ -15,6 +15,11 @@ and pair lists are passed as their component tensors / scalars.
                                            unc_weight, std_mode, std_value, max_code, level) -> (P, C, 5) float64
     torch.ops.clair_hip.pair_residual_lut_grad(stack, i_idx, j_idx, ratio, coef, lut, interp, lower, upper, relative,
                                                max_code) -> (C, L) float64
+    torch.ops.clair_hip.pair_residual_ingest_sums(frames, stages, i_idx, j_idx, ratio, lut?, interp, lower, upper, relative,
+                                  unc_weight, std?, std_mode, std_value, level, layout, consts?) -> (P, C, 5) float64
+    torch.ops.clair_hip.pair_residual_ingest_lut_grad(frames, stages, i_idx, j_idx, ratio, coef, lut, interp, lower, upper,
+                                  relative, layout, consts?) -> (C, L) float64   (a chain -- stages flattened as for
+                                  ingest_transform -- and the two pair ops above in one pass over raw uint8 / uint16 frames)
 
     torch.ops.clair_hip.strided_downscale(stack, step, layout) -> Tensor   (x[..., ::step, ::step], same dtype / layout)
     torch.ops.clair_hip.export_cv(x, to_f64) -> Tensor   (planar result -> the (H,W,C) BGR array save_image writes)
@@ -153,6 +158,43 @@ def pair_residual_lut_grad(stack: torch.Tensor, i_idx: torch.Tensor, j_idx: torc
 
 @pair_residual_lut_grad.register_fake
 def _(stack, i_idx, j_idx, ratio, coef, lut, interp, lower, upper, relative, max_code):
+    return lut.new_empty(lut.shape, dtype=torch.float64)
+
+
+@torch.library.custom_op(f"{_LIB}::pair_residual_ingest_sums", mutates_args=())
+def pair_residual_ingest_sums(frames: torch.Tensor, stages: Sequence[float], i_idx: torch.Tensor, j_idx: torch.Tensor,
+                              ratio: torch.Tensor, lut: Optional[torch.Tensor], interp: str, lower: float, upper: float,
+                              relative: bool, unc_weight: bool, std: Optional[torch.Tensor], std_mode: str, std_value: float,
+                              level: int = 1, layout: str = "nchw", consts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ct_pair_residual_ingest_fwd: ingest_transform followed by pair_residual_sums in one pass over the raw frames
+    (stages flattened as for ``ingest_transform``; an explicit std is planar (N,C,H,W))."""
+    pairs = ops.PairList(i_idx, j_idx, ratio, frames.shape[0], frames.device)
+    return ops.pair_residual_ingest_sums(frames, _listed_ingest_stages(frames, stages, layout), pairs, lut=lut,
+                                         interp=interp if lut is not None else None, lower=lower, upper=upper,
+                                         use_relative=relative, use_unc_weight=unc_weight, consts=consts, std=std,
+                                         std_mode=std_mode, std_value=std_value, level=level, layout=layout)
+
+
+@pair_residual_ingest_sums.register_fake
+def _(frames, stages, i_idx, j_idx, ratio, lut, interp, lower, upper, relative, unc_weight, std, std_mode, std_value, level=1,
+      layout="nchw", consts=None):
+    return frames.new_empty((i_idx.shape[0], ops.ingest_shape(tuple(frames.shape), layout)[1], 5), dtype=torch.float64)
+
+
+@torch.library.custom_op(f"{_LIB}::pair_residual_ingest_lut_grad", mutates_args=())
+def pair_residual_ingest_lut_grad(frames: torch.Tensor, stages: Sequence[float], i_idx: torch.Tensor, j_idx: torch.Tensor,
+                                  ratio: torch.Tensor, coef: torch.Tensor, lut: torch.Tensor, interp: str, lower: float,
+                                  upper: float, relative: bool, layout: str = "nchw",
+                                  consts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ct_pair_residual_ingest_bwd: ingest_transform followed by pair_residual_lut_grad in one pass over the raw frames."""
+    pairs = ops.PairList(i_idx, j_idx, ratio, frames.shape[0], frames.device)
+    return ops.pair_residual_ingest_lut_grad(frames, _listed_ingest_stages(frames, stages, layout), pairs, coef, lut=lut,
+                                             interp=interp, lower=lower, upper=upper, use_relative=relative, consts=consts,
+                                             layout=layout)
+
+
+@pair_residual_ingest_lut_grad.register_fake
+def _(frames, stages, i_idx, j_idx, ratio, coef, lut, interp, lower, upper, relative, layout="nchw", consts=None):
     return lut.new_empty(lut.shape, dtype=torch.float64)
 
 

@@ -17,10 +17,9 @@ from torch.utils.data import DataLoader
 from .. import ops
 from ..common.general_functions import get_valid_exposure_pairs
 from ..common.typecheck import expect
-from ..inference._staging import (normalise_transform_list, refuse_tile_with_downscale, resolve_device, stage_images,
-                                  std_arguments)
+from ..inference._staging import normalise_transform_list, refuse_tile_with_downscale, resolve_device, std_arguments
 from ..models.base import ICRFModelBase
-from .linearity import linearity_loss
+from .linearity import linearity_loss, stage_pair_images
 from .losses import (compute_endpoint_penalty, compute_monotonicity_penalty, compute_range_penalty,
                      compute_smoothness_penalty)
 
@@ -30,9 +29,13 @@ def train_icrf(dataloader: DataLoader, batch_size: int, device, icrf_model: ICRF
                use_relative_linearity_loss: bool = True, use_uncertainty_weighting: bool = True, epochs: int = 150,
                patience: int = 300, alpha: float = 1.0, beta: float = 1.0, gamma: float = 1.0, delta: float = 1.0,
                lower_valid_threshold: float = 1 / 255, upper_valid_threshold: float = 254 / 255,
-               exposure_ratio_threshold: float = 0.1, gpu_transforms=None, tile=None, group=None, verbose: bool = True):
+               exposure_ratio_threshold: float = 0.1, gpu_transforms=None, tile=None, group=None, verbose: bool = True,
+               fused_ingest: bool = True):
     """Returns the trained model.  Extensions over the reference: ``gpu_transforms`` (raw integer codes in the
-    DataLoader), ``tile`` / ``group`` (row-band sharding over ranks with exact all-reduced statistics), ``verbose``."""
+    DataLoader), ``tile`` / ``group`` (row-band sharding over ranks with exact all-reduced statistics), ``verbose``,
+    ``fused_ingest`` (raw uint8 / uint16 frames behind a recognised ``gpu_transforms`` chain -- a black level, a target
+    range, a clamp, one data-dependent Normalize, raw BGR frames -- are read by the pair kernels themselves in forward and
+    backward, no float32 stack per step; False runs ct_ingest_transform first, as do float32 frames and every other route)."""
     expect(dataloader, DataLoader, "dataloader")
     expect(batch_size, int, "batch_size")
     expect(device, (str, torch.device), "device")
@@ -110,16 +113,16 @@ def train_icrf(dataloader: DataLoader, batch_size: int, device, icrf_model: ICRF
         running_loss = torch.zeros(channels, device=dev, dtype=torch.float64)
         for _, val_batch, std_batch, meta_batch in dataloader:
             # explicit uncertainty images are planar
-            images, max_code, layout = stage_images(val_batch, dev, transforms, planar=std_batch is not None)
+            images, max_code, layout, n_frames = stage_pair_images(val_batch, dev, transforms, std_batch is not None, fused_ingest)
             std, std_mode, std_value = std_arguments(std_batch, dataloader.dataset, dev)
-            if images.shape[0] < 2:
+            if n_frames < 2:
                 print("Skipped batch due to single image.")
                 continue
             exposures = meta_batch["exposure_time"].to(torch.float64)
             key = (tuple(exposures.tolist()), exposure_ratio_threshold)
             if key not in pair_cache:
                 i_idx, j_idx, ratio = get_valid_exposure_pairs(exposures, exposure_ratio_threshold)
-                pair_cache[key] = ops.PairList(i_idx, j_idx, ratio, images.shape[0], dev)
+                pair_cache[key] = ops.PairList(i_idx, j_idx, ratio, n_frames, dev)
             pairs = pair_cache[key]
 
             for optimizer in optimizers:

@@ -560,6 +560,43 @@ int ct_video_stats_ingest_batch(const void *frames_dev, int32_t dtype, int32_t b
                                 void *stream);
 
 /*
+ * ct_pair_residual_ingest_fwd / ct_pair_residual_ingest_bwd -- such a chain and ct_pair_residual_fwd / _bwd in ONE pass over
+ * N raw frames: the sums (the LUT gradient) are those of ct_ingest_transform (with consts_dev: ct_ingest_transform_data) into
+ * a dense planar float32 (N, C, H_tile, W) stack followed by ct_pair_residual_fwd (_bwd) on that stack with CT_DTYPE_F32 and
+ * the same geometry with layout CT_LAYOUT_NCHW.  Every staged sample has the bits of that route -- x = the stage list applied
+ * to (float)code, then the ICRF of a float32 pixel (LUT coordinate clamped on both sides), the Gaussian weight, the validity
+ * mask lower <= x <= upper and sigma (CT_STD_CONSTANT / MULTIPLIER on x) -- and for contiguous allocations of one shape the
+ * tiles are walked alike, so the results differ by the order of the float64 atomic additions alone.  No float32 stack exists:
+ * sizeof(code) bytes are read per sample and launch where the float32 stack costs 4, and the ct_ingest_transform pass
+ * (sizeof(code) read, 4 written per sample) is gone.
+ *   frames_dev   CT_DTYPE_U8 / U16 codes aligned to their element (CT_DTYPE_F32 is CT_ERR_UNSUPPORTED: such a stack has no
+ *                copy to save); geom->layout CT_LAYOUT_NCHW (any C) or, with C == 3, CT_LAYOUT_NHWC / NHWC_BGR: the order of
+ *                the SOURCE (a folded CvToTorch); frames image_stride elements apart
+ *   stages, n_stages, consts_dev   as ct_video_stats_ingest_batch takes them (at most one CT_INGEST_AFFINE_DATA stage, and
+ *                only with consts_dev, whose first two floats are read when the kernel runs)
+ *   std_dev      CT_STD_EXPLICIT: PLANAR float32 (N, C, H_tile, W), dense, whatever the layout of the frames (gpu_transforms
+ *                never touch the uncertainty images); else NULL
+ *   every other argument as ct_pair_residual_fwd / ct_pair_residual_bwd take it; the backward's workspace is that of
+ *   ct_pair_residual_bwd_workspace.
+ * Validation needs no device memory and comes first: the geometry, the stack and the stage list, the dtype, the constants'
+ * alignment and the model as ct_video_stats_ingest_batch judges them, then everything ct_pair_residual_fwd / _bwd refuse
+ * (n_images < 2, an empty plane, CT_INTERP_LOOKUP with a std mode: CT_ERR_NO_GRADIENT_PATH, ...).  Allocates nothing,
+ * synchronises nothing, reads nothing back, never writes the frames.
+ */
+int ct_pair_residual_ingest_fwd(const void *frames_dev, int32_t dtype, const ct_ingest_stage *stages, int32_t n_stages,
+                                const float *consts_dev, int32_t n_images, const ct_geometry *geom, const float *std_dev,
+                                const ct_icrf *icrf, const int32_t *i_idx_dev, const int32_t *j_idx_dev, const double *ratio_dev,
+                                int32_t n_pairs, const ct_pair_params *params, int32_t level, const double *center_dev,
+                                double *sums_dev, void *stream);
+int ct_pair_residual_ingest_bwd(const void *frames_dev, int32_t dtype, const ct_ingest_stage *stages, int32_t n_stages,
+                                const float *consts_dev, int32_t n_images, const ct_geometry *geom, const float *std_dev,
+                                const ct_icrf *icrf, const double *ratio_dev, int32_t n_pairs,
+                                const int32_t *partner_offsets_dev, const int32_t *partner_sample_dev,
+                                const int32_t *partner_pair_dev, const ct_pair_params *params, const double *coef_dev,
+                                const double *smean_dev, double *lut_grad_dev, void *workspace_dev, int64_t workspace_bytes,
+                                void *stream);
+
+/*
  * ct_export_cv -- the array save_image hands to cv.imwrite (clair_torch/common/data_io.py:228-234: astype, transpose to
  * (H, W, C), channel reversal of a 3-channel image), made on the device from planar results:
  *   dst[f][p][c'] = (dst type) src[f][c][p],  p < plane = H*W,  c' = channels-1-c when reverse_channels, else c
