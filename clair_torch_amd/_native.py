@@ -30,7 +30,7 @@ EXPORTS = ("ct_abi_version", "ct_error_string", "ct_hdr_merge_batch", "ct_hdr_me
            "ct_strided_downscale", "ct_export_cv", "ct_ingest_transform", "ct_ingest_extrema_workspace", "ct_ingest_extrema",
            "ct_ingest_transform_data", "ct_linearize_ingest", "ct_hdr_merge_ingest_batch", "ct_video_stats_ingest_batch",
            "ct_hdr_merge_ingest_batches", "ct_ingest_extrema_frames_workspace", "ct_ingest_extrema_frames",
-           "ct_linearize_ingest_data", "ct_pair_residual_ingest_fwd", "ct_pair_residual_ingest_bwd")
+           "ct_linearize_ingest_data", "ct_pair_residual_ingest_fwd", "ct_pair_residual_ingest_bwd", "ct_linearize_ingest_strided")
 
 
 class Geometry(ctypes.Structure):
@@ -139,6 +139,8 @@ def load():
                                              vp]
     lib.ct_linearize_ingest_data.restype = i32
     lib.ct_linearize_ingest_data.argtypes = [vp, i32, i64, gp, ctypes.POINTER(IngestStage), i32, vp, i32, f32, ip, vp, vp, vp, vp]
+    lib.ct_linearize_ingest_strided.restype = i32
+    lib.ct_linearize_ingest_strided.argtypes = [vp, i32, i64, gp, i32, ctypes.POINTER(IngestStage), i32, vp, i32, f32, ip, vp, vp, vp, vp]
     lib.ct_hdr_merge_ingest_batch.restype = i32
     lib.ct_hdr_merge_ingest_batch.argtypes = [vp, i32, i32, gp, ctypes.POINTER(IngestStage), i32, vp, vp, i32, f32, vp, ip, i32, vp, vp,
                                               vp, vp, vp, u32, vp]

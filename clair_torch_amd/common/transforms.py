@@ -38,7 +38,7 @@ interleaved frames as they are (layout "nhwc_bgr") and the fused ingest reads th
 stack (``planar=True``: explicit std and dark-field images are planar) gets no "nhwc_bgr": such a list goes to route 3.
 """
 import ctypes
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Optional
 
 import torch
@@ -234,7 +234,9 @@ class StagingPlan:
     ``source_layout``: how the fused ingest reads the batch ("nhwc_bgr": raw frames behind a leading CvToTorch);
     ``step``: the StridedDownscale to apply to the raw stack (1 = none); ``max_code``: of the code route; ``stages``,
     ``step_first``, ``prefix``, ``min_val`` / ``max_val``: as in ``IngestPlan`` / ``DataIngestPlan``; ``no_transforms``: the
-    list is empty (route "torch" with nothing to run)."""
+    list is empty (route "torch" with nothing to run); ``step_in_kernel``: the consumer asked ``plan_staging`` for a plan
+    whose ``step > 1`` its own kernel applies to the raw stack (ct_linearize_ingest_strided) instead of the staging's
+    ct_strided_downscale -- never set on a plan nobody asked that of."""
     route: str
     layout: str = "nchw"
     step: int = 1
@@ -246,6 +248,7 @@ class StagingPlan:
     max_val: Optional[float] = None
     source_layout: str = "nchw"
     no_transforms: bool = False
+    step_in_kernel: bool = False
 
 
 def _recognise_ingest(images: torch.Tensor, transforms) -> Optional[StagingPlan]:
@@ -341,10 +344,21 @@ def fusable_ingest_data(images: torch.Tensor, transforms) -> Optional[DataIngest
     return DataIngestPlan(p.source_layout, p.step, p.step_first, p.stages, p.prefix, p.min_val, p.max_val)
 
 
-def plan_staging(images: torch.Tensor, transforms, planar: bool = False, on_device: bool = False) -> StagingPlan:
+def plan_staging(images: torch.Tensor, transforms, planar: bool = False, on_device: bool = False,
+                 step_in_kernel: bool = False) -> StagingPlan:
     """The route ``transforms`` take on ``images``, read off the batch's shape, dtype, contiguity and device type alone
     (no device call).  ``planar``: the caller cannot take an interleaved stack; the layout is then always "nchw".
-    ``on_device``: ``images`` is a host probe of batches that are staged on a CUDA device: plan as for a batch there."""
+    ``on_device``: ``images`` is a host probe of batches that are staged on a CUDA device: plan as for a batch there.
+    ``step_in_kernel``: the caller has a kernel that applies a plan's ``step > 1`` to the raw stack itself
+    (linearize_dataset_generator: ct_linearize_ingest_strided); such a plan of route "code", "ingest" or "ingest_data" then
+    says so, and nothing else about it changes."""
+    plan = _plan_staging(images, transforms, planar, on_device)
+    if step_in_kernel and plan.step > 1 and plan.route in ("code", "ingest", "ingest_data"):
+        return replace(plan, step_in_kernel=True)
+    return plan
+
+
+def _plan_staging(images: torch.Tensor, transforms, planar: bool, on_device: bool) -> StagingPlan:
     ts = [t for t in transforms if t is not None]
     # 1, 2: the code pair, behind one StridedDownscale (4-D batches) or alone; raw frames stay interleaved unless ``planar``
     step, rest = fusable_downscale(ts)

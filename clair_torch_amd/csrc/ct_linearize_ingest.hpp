@@ -1,0 +1,194 @@
+// ct_linearize_ingest.hpp -- what the fused chain + linearization kernels share (ct_linearize_ingest.hip on dense frames,
+// ct_linearize_ingest_strided.hip on every step-th row and column of them): the argument block, the slot / span scheme of
+// a thread's 4 output elements, the sample step behind the chain (li_sample4), the packet store, and the host-side launch
+// loop and dispatch over element type, interpolation and uncertainty mode.  One copy of each: the outputs of the two files
+// agree bit for bit because they run the same device functions.
+#pragma once
+#include "ct_args.hpp"
+#include "ct_ingest_stages.hpp"
+
+namespace ct {
+
+struct LinIngestArgs {
+    const void *src;
+    const float *std_in;   // EXPLICIT: planar (F, C, plane) float32, like the outputs
+    const float *lut;
+    const float *consts;   // (F, 4) per-frame {sub, div, min, max} of a CT_INGEST_AFFINE_DATA stage, or NULL
+    float *lin_out;
+    float *std_out;
+    int64_t image_stride;  // source elements between consecutive frames
+    int64_t plane;         // H_tile * W
+    uint32_t first;        // first plane / frame of this launch (a grid's y extent is 65535)
+    uint32_t channels, n_points;
+    uint32_t plane_global;  // H_global * W: global flat index of (c, local p) = c * plane_global + base + p
+    uint32_t base;          // row_offset * W
+    uint32_t reversed;      // PACKED3: memory channel cm feeds plane 2 - cm (BGR)
+    uint32_t by_channel;    // some clamp holds different pairs for different channels (then C <= CT_INGEST_MAX_CHANNELS);
+                            // else every channel takes pair 0, whatever C is
+    float std_value;
+    uint32_t n_stages;
+    ct_ingest_stage stage[CT_INGEST_MAX_STAGES];
+};
+
+struct alignas(16) LinIngestPacket {
+    float v[4];
+};
+
+constexpr int kLiGroup = 4;     // output elements per packet
+constexpr int kLiSlots = 4;     // slots per thread
+constexpr uint32_t kLiMaxRows = 65535;
+
+// slot 0 -> the elements in front of the first aligned packet, slot s >= 1 -> packet s - 1; false when there is nothing
+__device__ __forceinline__ bool li_span(int64_t head, int64_t slot, int64_t plane, int64_t &p0, int &n)
+{
+    if (slot == 0) {
+        p0 = 0;
+        n = (int)(head < plane ? head : plane);
+        return n > 0;
+    }
+    p0 = head + (slot - 1) * kLiGroup;
+    if (p0 >= plane) return false;
+    n = plane - p0 < kLiGroup ? (int)(plane - p0) : kLiGroup;
+    return true;
+}
+
+// four samples behind the chain -> (lin, std); `r` is the LINEAR / CATMULL row of the first one, `c` the channel
+template <int INTERP, int STD, bool WRITE_STD>
+__device__ __forceinline__ void li_sample4(const float (&x)[kLiGroup], const float (&sg)[kLiGroup], const char *lds, int L, int C,
+                                           int c, int r, float std_value, LinIngestPacket &lo, LinIngestPacket &so)
+{
+    constexpr int kEntry = lut_entry_bytes(INTERP);
+    const float top = (float)(L - 1);
+    [[maybe_unused]] bool tiny = false;  // some 0 < |grad * std| < 1e-18 among these
+#pragma unroll
+    for (int e = 0; e < kLiGroup; ++e) {
+        float dfdx;
+        lo.v[e] = icrf_sample<INTERP, true, false>(x[e], lds + (INTERP == CT_INTERP_LOOKUP ? c : r) * L * kEntry, top, dfdx);
+        so.v[e] = 0.0f;
+        if constexpr (WRITE_STD && STD != CT_STD_NONE) {
+            float sigma = std_value;                                        // CONSTANT
+            if constexpr (STD == CT_STD_EXPLICIT) sigma = sg[e];
+            if constexpr (STD == CT_STD_MULTIPLIER) sigma = x[e] * std_value;  // datasets/base.py:133, x behind the chain
+            const float ags = fabsf(dfdx * sigma);  // sqrt((grad * std)^2) = |grad * std| unless the square underflows
+            so.v[e] = ags;
+            tiny |= ags < 1e-18f && ags != 0.0f;
+        }
+        ++r;
+        r = r >= C ? r - C : r;
+    }
+    if constexpr (WRITE_STD && STD != CT_STD_NONE) {
+        if (__builtin_expect(__any(tiny), 0)) {  // wave-uniform, practically never taken (ct_linearize.hip)
+#pragma unroll
+            for (int e = 0; e < kLiGroup; ++e)
+                if (so.v[e] < 1e-18f && so.v[e] != 0.0f) so.v[e] = sqrtf(so.v[e] * so.v[e]);
+        }
+    }
+}
+
+// n <= 4 results to dp[0..n): one packet when all four are there and dp is 16-byte aligned, else element by element
+__device__ __forceinline__ void li_store(float *dp, const LinIngestPacket &v, int n)
+{
+    if (n == kLiGroup && (reinterpret_cast<uintptr_t>(dp) & 15u) == 0) {
+        store_stream(reinterpret_cast<LinIngestPacket *>(dp), v);
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < kLiGroup; ++k)
+        if (k < n) dp[k] = v.v[k];
+}
+
+// n <= 4 floats from sp[0..n) (any alignment), zeros behind them
+__device__ __forceinline__ void li_load_std(const float *sp, int n, float (&sg)[kLiGroup])
+{
+    if (n == kLiGroup) {
+        __builtin_memcpy(sg, sp, sizeof(sg));
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < kLiGroup; ++k) sg[k] = k < n ? sp[k] : 0.0f;
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------------
+// `rows` workgroup rows (planes or frames) of `kernel`, at most kLiMaxRows per launch; Args is LinIngestArgs or derives from it
+template <typename Args>
+static int li_launch_rows(void (*kernel)(const Args), Args a, int interp, int64_t rows, hipStream_t s)
+{
+    const int64_t slots = 1 + (a.plane + kLiGroup - 1) / kLiGroup;
+    const int64_t per_block = (int64_t)kBlock * kLiSlots;
+    const size_t lds = lut_lds_bytes(interp, a.channels, a.n_points);
+    const dim3 block(kBlock);
+    for (int64_t first = 0; first < rows; first += kLiMaxRows) {
+        a.first = (uint32_t)first;
+        const dim3 grid((uint32_t)((slots + per_block - 1) / per_block), (uint32_t)(rows - first < kLiMaxRows ? rows - first : kLiMaxRows));
+        hipLaunchKernelGGL(kernel, grid, block, lds, s, a);
+        if (hipGetLastError() != hipSuccess) return CT_ERR_LAUNCH;
+    }
+    return CT_OK;
+}
+
+// Launch<T, INTERP, STD, WRITE_STD>::run(a, packed, rows, s) picks the kernel of a file
+template <template <typename, int, int, bool> class Launch, typename T, int INTERP, typename Args>
+static int li_dispatch_std(const Args &a, bool packed, int64_t rows, int std_mode, bool write_std, hipStream_t s)
+{
+    if (!write_std) return Launch<T, INTERP, CT_STD_NONE, false>::run(a, packed, rows, s);
+    if (std_mode == CT_STD_NONE) return Launch<T, INTERP, CT_STD_NONE, true>::run(a, packed, rows, s);
+    if constexpr (INTERP != CT_INTERP_LOOKUP) {  // (LOOKUP with uncertainties has no gradient path: refused by the caller)
+        switch (std_mode) {
+            case CT_STD_CONSTANT: return Launch<T, INTERP, CT_STD_CONSTANT, true>::run(a, packed, rows, s);
+            case CT_STD_MULTIPLIER: return Launch<T, INTERP, CT_STD_MULTIPLIER, true>::run(a, packed, rows, s);
+            case CT_STD_EXPLICIT: return Launch<T, INTERP, CT_STD_EXPLICIT, true>::run(a, packed, rows, s);
+        }
+    }
+    return CT_ERR_INVALID_ARGUMENT;
+}
+
+template <template <typename, int, int, bool> class Launch, typename T, typename Args>
+static int li_dispatch_interp(const Args &a, bool packed, int64_t rows, int interp, int std_mode, bool write_std, hipStream_t s)
+{
+    switch (interp) {
+        case CT_INTERP_LOOKUP: return li_dispatch_std<Launch, T, CT_INTERP_LOOKUP>(a, packed, rows, std_mode, write_std, s);
+        case CT_INTERP_LINEAR: return li_dispatch_std<Launch, T, CT_INTERP_LINEAR>(a, packed, rows, std_mode, write_std, s);
+        case CT_INTERP_CATMULL: return li_dispatch_std<Launch, T, CT_INTERP_CATMULL>(a, packed, rows, std_mode, write_std, s);
+        case CT_INTERP_NONE: return li_dispatch_std<Launch, T, CT_INTERP_NONE>(a, packed, rows, std_mode, write_std, s);
+    }
+    return CT_ERR_INVALID_ARGUMENT;
+}
+
+template <template <typename, int, int, bool> class Launch, typename Args>
+static int li_dispatch(const Args &a, int32_t dtype, bool packed, int64_t rows, int interp, int std_mode, bool write_std, hipStream_t s)
+{
+    if (dtype == CT_DTYPE_U8) return li_dispatch_interp<Launch, uint8_t>(a, packed, rows, interp, std_mode, write_std, s);
+    if (dtype == CT_DTYPE_U16) return li_dispatch_interp<Launch, uint16_t>(a, packed, rows, interp, std_mode, write_std, s);
+    return li_dispatch_interp<Launch, float>(a, packed, rows, interp, std_mode, write_std, s);
+}
+
+// What the entry points check in this order, before any pointer into device memory: the stack and the stage list
+// (ingest_validate over `plane` elements per channel; AFFINE_DATA only with constants), the constants' alignment, the model and
+// the uncertainty mode, LOOKUP with uncertainties (linearization.py:100-105: autograd.grad raises, no gradient path), the LDS
+// budget, the row count.  `rows`: workgroup rows of the launch.
+static inline int li_check_call(int32_t dtype, int64_t n_frames, const ct_geometry *geom, int64_t plane, const ct_ingest_stage *stages,
+                                int32_t n_stages, const float *std_dev, int32_t std_mode, const ct_icrf *icrf, const float *consts_dev,
+                                bool &by_channel, int64_t &rows)
+{
+    int rc = ingest_validate(dtype, geom->layout, n_frames, geom->channels, plane, stages, n_stages, CT_INGEST_MAX_STAGES,
+                             consts_dev ? 1 : 0, by_channel);
+    if (rc != CT_OK) return rc;
+    if (!aligned(consts_dev, sizeof(float))) return CT_ERR_INVALID_ARGUMENT;
+    if (!icrf_ok(icrf) || !std_mode_ok(std_mode, std_dev)) return CT_ERR_INVALID_ARGUMENT;
+    if (std_mode != CT_STD_NONE && icrf->interp == CT_INTERP_LOOKUP) return CT_ERR_NO_GRADIENT_PATH;
+    if (lut_lds_bytes(icrf->interp, geom->channels, icrf->n_points) > kLdsBudget) return CT_ERR_TOO_LARGE;
+    rows = n_frames;
+    if ((geom->layout == CT_LAYOUT_NCHW && __builtin_mul_overflow(n_frames, (int64_t)geom->channels, &rows)) || rows > 0x7fffffff)
+        return CT_ERR_TOO_LARGE;
+    return CT_OK;
+}
+
+// ... and after them the pointers: frames and lin_out are required, everything is aligned to its element
+static inline bool li_pointers_ok(const void *frames_dev, int32_t dtype, const float *std_dev, const float *lin_out_dev,
+                                  const float *std_out_dev)
+{
+    return frames_dev && lin_out_dev && aligned(frames_dev, dtype_bytes(dtype)) && aligned(lin_out_dev, sizeof(float)) &&
+           aligned(std_out_dev, sizeof(float)) && aligned(std_dev, sizeof(float));
+}
+
+}  // namespace ct

@@ -15,18 +15,26 @@ LINEAR / LOOKUP std bit for bit -- but the frames move through a three-stage pip
 
 Which inputs take the pipeline is ``pipeline_route``'s answer: the code pair ``[CastTo(float32), Normalize(max, 0)]`` on raw
 codes (folded into ct_linearize_std's load), float32 pixels with no transform list, and every list of ``plan_staging``'s
-route "ingest" without a StridedDownscale -- a black level, a target range, ``ClampAlongDims``, raw BGR frames behind
-``CvToTorch`` with explicit (planar) uncertainty images.  For the latter the ring slot keeps the RAW frames in their own
-dtype and memory order and ct_linearize_ingest evaluates chain and ICRF in one pass, bit for bit what ct_ingest_transform
-followed by ct_linearize_std gives on the frame-by-frame route.
+route "ingest" -- a black level, a target range, ``ClampAlongDims``, raw BGR frames behind ``CvToTorch`` with explicit
+(planar) uncertainty images.  For the latter the ring slot keeps the RAW frames in their own dtype and memory order and
+ct_linearize_ingest evaluates chain and ICRF in one pass, bit for bit what ct_ingest_transform followed by
+ct_linearize_std gives on the frame-by-frame route.
+
+A ``StridedDownscale`` in such a list -- or beside the code pair, which then runs as the one-stage chain x / max_code --
+keeps the pipeline: the slot still holds the raw full-size frames, ct_linearize_ingest_strided reads every step-th row and
+column of them, and outputs, exports, pinned host tensors and the group size follow the downscaled shape.  Explicit
+uncertainty images must arrive at that shape (the reference applies gpu_transforms to the value images only); another
+shape is a ValueError before anything is queued.
 
 A list with a data-dependent ``Normalize`` (``max_val`` and / or ``min_val`` None -- ``Normalize()`` is the reference's
 default; every frame is its own batch here, so the bounds are per frame) is ``pipeline_data_route``'s: ONE
 ct_ingest_extrema_frames launch pair leaves four constants per frame of the group in the slot, ct_linearize_ingest_data
 reads them per frame, and the constants ride the device-to-host stage so that the reference's zero-range ValueError is
 raised -- without a synchronisation of its own -- exactly where the frame-by-frame route raises it: after the frames in
-front of the offending one have been yielded.  A dark field, a downscale off the code pair and lists that run as torch
-ops go frame by frame.
+front of the offending one have been yielded.  A StridedDownscale BEHIND that Normalize keeps this route (the extrema are
+those of the full frames, which ct_ingest_extrema_frames reads; the strided kernel takes the constants); one in FRONT of it
+needs the extrema of the selected pixels and stays frame by frame.  A dark field and lists that run as torch ops go frame
+by frame.
 
 ``output_layout="cv"`` (extension): every yielded pair is in the order the reference's ``save_image`` writes -- (H,W,C),
 a 3-channel frame reversed to BGR -- made by two ct_export_cv launches per group before the device-to-host copy, which
@@ -78,12 +86,13 @@ def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRF
     if first is None:
         return
     probe = first[1]
-    plan = plan_staging(probe, transforms, planar=first[2] is not None)  # explicit uncertainty images are planar
+    # explicit uncertainty images are planar; a StridedDownscale is ct_linearize_ingest_strided's to apply (step_in_kernel)
+    plan = plan_staging(probe, transforms, planar=first[2] is not None, step_in_kernel=True)
     route = pipeline_route(probe, plan, dark is not None)
     if route != "pipelined":
         # the second, separate decision: a data-dependent Normalize with per-frame constants.  The probe is a host tensor;
         # the list is planned as stage_images plans it for the batch on the device (route "ingest_data" exists only there)
-        staged = plan_staging(probe, transforms, planar=first[2] is not None, on_device=dev.type == "cuda")
+        staged = plan_staging(probe, transforms, planar=first[2] is not None, on_device=dev.type == "cuda", step_in_kernel=True)
         route = pipeline_data_route(probe, staged, dark is not None)
         plan = staged if route == "pipelined" else plan
     if route != "pipelined":
@@ -98,13 +107,17 @@ def pipeline_route(probe: torch.Tensor, plan, has_dark: bool) -> str:
     will do) and whose transform list ``plan_staging`` planned as ``plan``.  The pipeline ingests what one kernel
     ingests from a ring slot: raw integer codes whose normalisation (and OpenCV layout) fold into ct_linearize_std's
     load, float32 pixels with no device transform at all, or -- route "ingest" -- raw frames whose whole chain
-    ct_linearize_ingest evaluates.  Anything else goes frame by frame through the generic staging: a dark field
-    (per-frame conditional blur), a StridedDownscale off the code pair, lists that run as torch ops -- and, as far as THIS
+    ct_linearize_ingest evaluates; with a StridedDownscale in the list (``plan.step > 1``) and a plan made for a consumer
+    that applies the step in its kernel (``plan.step_in_kernel``, which the generator asks ``plan_staging`` for; a plan
+    without it leaves the step to the staging and goes frame by frame, as ever) ct_linearize_ingest_strided
+    reads every step-th row and column of the raw frames, the code pair then as the one-stage chain x / max_code (measured
+    in profiles/linearize_ingest_strided.md).  Anything else goes frame by frame through the generic staging: a dark field
+    (per-frame conditional blur), lists that run as torch ops -- and, as far as THIS
     function is concerned, a data-dependent Normalize: its extrema are per frame here, per stack in ct_ingest_extrema, so
     it has a decision of its own, ``pipeline_data_route``, which the generator asks when this one said "frame_by_frame"."""
     if has_dark or probe.ndim != 4:
         return "frame_by_frame"
-    if plan.route in ("code", "ingest") and plan.step == 1:
+    if plan.route in ("code", "ingest") and (plan.step == 1 or plan.step_in_kernel):
         return "pipelined"
     if plan.route == "torch" and plan.no_transforms and probe.dtype == torch.float32:
         return "pipelined"
@@ -113,10 +126,16 @@ def pipeline_route(probe: torch.Tensor, plan, has_dark: bool) -> str:
 
 def pipeline_data_route(probe: torch.Tensor, plan, has_dark: bool) -> str:
     """"pipelined" | "frame_by_frame" for what ``pipeline_route`` declined: route "ingest_data" -- the fused-ingest grammar
-    with ONE data-dependent Normalize -- on uint8 / uint16 / float32 frames without a StridedDownscale and without a dark
-    field takes the pipeline with per-frame constants (ct_ingest_extrema_frames + ct_linearize_ingest_data per group).
-    Measured against the frame-by-frame route in profiles/linearize_ingest_data.md; everything else stays frame by frame."""
-    if has_dark or probe.ndim != 4 or plan.route != "ingest_data" or plan.step != 1:
+    with ONE data-dependent Normalize -- on uint8 / uint16 / float32 frames without a dark field takes the pipeline with
+    per-frame constants (ct_ingest_extrema_frames + ct_linearize_ingest_data per group).  A StridedDownscale BEHIND the
+    Normalize keeps it when the plan says ``step_in_kernel`` (see ``pipeline_route``): the extrema are those of the full
+    frames and ct_linearize_ingest_strided takes the constants.  One in
+    FRONT of it (``plan.step_first``) needs the extrema of the selected pixels, which no kernel here reduces from the raw
+    frames, and stays frame by frame.  Measured against the frame-by-frame route in profiles/linearize_ingest_data.md;
+    everything else stays frame by frame."""
+    if has_dark or probe.ndim != 4 or plan.route != "ingest_data":
+        return "frame_by_frame"
+    if plan.step != 1 and (plan.step_first or not plan.step_in_kernel):
         return "frame_by_frame"
     if probe.dtype not in (torch.uint8, torch.uint16, torch.float32):
         return "frame_by_frame"
@@ -174,14 +193,23 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
     frame_shape = tuple(probe.shape[1:])
     # an ingest plan: the slot keeps the RAW frames, (H,W,3) behind a folded CvToTorch, and the kernel runs the chain
     data = plan.route == "ingest_data"  # per-frame constants of a data-dependent Normalize (pipeline_data_route)
-    fused = plan.route == "ingest" or data
+    # a StridedDownscale: the slot still keeps the raw full-size frames, ct_linearize_ingest_strided reads every step-th row
+    # and column of them, and everything behind the kernel -- outputs, exports, pinned host tensors, the group size -- has
+    # the downscaled shape.  The code pair then runs as the one-stage chain x / max_code (the same correctly rounded division)
+    step = plan.step
+    fused = plan.route == "ingest" or data or step > 1
+    stages = (("affine", 0, plan.max_code, 1, 0),) if plan.route == "code" else plan.stages
     layout, max_code = (plan.source_layout if fused else plan.layout), plan.max_code
     chw = frame_shape if layout == "nchw" else (frame_shape[2], frame_shape[0], frame_shape[1])
+    chw = (chw[0], -(-chw[1] // step), -(-chw[2] // step))
     out_bytes = 2 * 4 * chw[0] * chw[1] * chw[2]
     group = max(1, min(16, _GROUP_BYTES // out_bytes))
     std_probe, std_mode, std_value = std_arguments(first[2], dataloader.dataset, torch.device("cpu"))
     with_std = std_probe is not None
     std_shape = (chw if fused else frame_shape) if with_std else None
+    if with_std and step > 1 and tuple(std_probe.shape[1:]) != chw:
+        # gpu_transforms are applied to the value images only: explicit uncertainties arrive at the downscaled size
+        raise ValueError(f"uncertainty images must have the downscaled shape {chw}, got {tuple(std_probe.shape[1:])}")
     slots = [_Slot(group, frame_shape, probe.dtype, std_shape, chw, dev, cv, data) for _ in range(_SLOTS)]
     compute = torch.cuda.current_stream(dev)
     h2d, d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
@@ -217,6 +245,8 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
                     # and without an uncertainty image is refused rather than silently ignoring some of them
                     raise ValueError("uncertainty images present for some frames only")
                 if with_std:
+                    if step > 1 and tuple(std_batch.shape[1:]) != chw:
+                        raise ValueError(f"uncertainty images must have the downscaled shape {chw}, got {tuple(std_batch.shape[1:])}")
                     slot.std[k].copy_(std_batch[0], non_blocking=True)
                 metas.append(meta_batch)
                 k += 1
@@ -229,10 +259,12 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
             if data:  # two launches for the group's k sets of constants, into the slot's own buffers
                 consts = ops.ingest_extrema_frames(slot.frames[:k], plan.prefix, layout, plan.min_val, plan.max_val,
                                                    out=slot.consts[:k], workspace=slot.workspace)
-            lin, lin_std = ops.linearize_ingest_frames(slot.frames[:k], plan.stages, lut, interp,
-                                                       std=slot.std[:k] if with_std else None, std_mode=std_mode,
-                                                       std_value=std_value, want_std=True, layout=layout,
-                                                       out=(slot.lin_out[:k], slot.std_out[:k]), consts=consts)
+            args = dict(std=slot.std[:k] if with_std else None, std_mode=std_mode, std_value=std_value, want_std=True,
+                        layout=layout, out=(slot.lin_out[:k], slot.std_out[:k]), consts=consts)
+            if step > 1:
+                lin, lin_std = ops.linearize_ingest_frames_strided(slot.frames[:k], step, stages, lut, interp, **args)
+            else:
+                lin, lin_std = ops.linearize_ingest_frames(slot.frames[:k], stages, lut, interp, **args)
         else:
             lin, lin_std = ops.linearize_frames(slot.frames[:k], lut, interp, std=slot.std[:k] if with_std else None,
                                                 std_mode=std_mode, std_value=std_value, max_code=max_code, want_std=True,

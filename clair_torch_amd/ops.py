@@ -922,6 +922,47 @@ def linearize_ingest_frames(frames: torch.Tensor, stages, lut: Optional[torch.Te
     return lin, std_out
 
 
+def linearize_ingest_frames_strided(frames: torch.Tensor, step: int, stages, lut: Optional[torch.Tensor],
+                                    interp: Optional[str] = "linear", *, std: Optional[torch.Tensor] = None,
+                                    std_mode: str = "none", std_value: float = 0.0, want_std: bool = True,
+                                    tile: Optional[TileGeometry] = None, layout: str = "nchw", out=None,
+                                    consts: Optional[torch.Tensor] = None):
+    """ct_linearize_ingest_strided: ``linearize_ingest_frames(strided_downscale(frames, step, layout), stages, ...)`` bit for
+    bit, in one launch and without the compacted frames in between -> (lin float32, std float32 | None), planar
+    (F,C,ho,wo) with ho = ceil(H/step), wo = ceil(W/step).  ``frames``, ``stages``, ``layout``, ``consts`` as
+    ``linearize_ingest_frames`` takes them; ``consts`` are those of the frames as given (``ingest_extrema_frames`` on the
+    full frames: a data-dependent Normalize in FRONT of the downscale).  ``std``: explicit uncertainties, float32 and
+    planar (F,C,ho,wo) -- already of the output shape, because gpu_transforms are applied to the value images only.
+    ``out`` = (lin, std | None): contiguous float32 (F,C,ho,wo) device buffers.  ``tile``: with ``step == 1`` only (a row
+    band behind a downscale is refused: the phase of the band is not carried)."""
+    _check_ingest_stack(frames, layout)
+    if isinstance(step, bool) or not isinstance(step, int) or step < 1:
+        raise ValueError(f"step must be an int >= 1, got {step!r}")
+    src_shape = ingest_shape(tuple(frames.shape), layout)
+    f, c = src_shape[:2]
+    shape = downscaled_shape(src_shape, step)
+    dev = frames.device
+    arr, n_stages = _ingest_stages(stages, c, data=consts is not None)
+    if consts is not None:
+        _check_frame_consts(consts, f, dev)
+    if std is not None:
+        std_mode, std = "explicit", _planar_std(std, shape, dev, "outputs")
+    if std_mode not in _STD:
+        raise ValueError(f"unknown std_mode {std_mode}")
+    icrf, lut_keep = _icrf_struct(lut, interp, c)
+    geom = _ingest_geometry(src_shape, tile, layout)
+    lin, std_out = _lin_std_out(out, shape, dev, want_std, lin_required=True)
+    if frames.numel() == 0:
+        return lin, std_out
+    with torch.cuda.device(dev):
+        rc = nv.load().ct_linearize_ingest_strided(_ptr(frames), _DTYPE[frames.dtype], f, ctypes.byref(geom), min(step, 0x7fffffff), arr,
+                                                   n_stages, _ptr(std), _STD[std_mode], float(std_value), ctypes.byref(icrf), _ptr(lin),
+                                                   _ptr(std_out), _ptr(consts), _stream(dev))
+    nv.check(rc, "ct_linearize_ingest_strided")
+    del lut_keep
+    return lin, std_out
+
+
 # ---- such a chain and one batch of the HDR merge in one pass ---------------------------------------------------------------
 def hdr_merge_ingest_batch(frames: torch.Tensor, stages, exposures: torch.Tensor, *, lut: Optional[torch.Tensor] = None,
                            interp: Optional[str] = "linear", gaussian_weight: bool = True, std: Optional[torch.Tensor] = None,

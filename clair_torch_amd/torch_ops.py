@@ -296,6 +296,22 @@ def _(frames, stages, lut, interp, std, std_mode, std_value, layout="nchw", h_gl
     return frames.new_empty(shape, dtype=torch.float32), frames.new_empty(shape, dtype=torch.float32)
 
 
+@torch.library.custom_op(f"{_LIB}::linearize_ingest_strided", mutates_args=())
+def linearize_ingest_strided(frames: torch.Tensor, step: int, stages: Sequence[float], lut: torch.Tensor, interp: str,
+                             std: Optional[torch.Tensor], std_mode: str, std_value: float, layout: str = "nchw",
+                             consts: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ct_linearize_ingest_strided: strided_downscale followed by linearize_ingest (with ``consts``: linearize_ingest_data),
+    bit for bit, in one pass over the raw frames; an explicit std is planar and of the downscaled shape."""
+    return ops.linearize_ingest_frames_strided(frames, step, _listed_ingest_stages(frames, stages, layout), lut, interp, std=std,
+                                               std_mode=std_mode, std_value=std_value, want_std=True, layout=layout, consts=consts)
+
+
+@linearize_ingest_strided.register_fake
+def _(frames, step, stages, lut, interp, std, std_mode, std_value, layout="nchw", consts=None):
+    shape = ops.downscaled_shape(ops.ingest_shape(tuple(frames.shape), layout), step)
+    return frames.new_empty(shape, dtype=torch.float32), frames.new_empty(shape, dtype=torch.float32)
+
+
 @torch.library.custom_op(f"{_LIB}::ingest_extrema", mutates_args=())
 def ingest_extrema(stack: torch.Tensor, prefix: Sequence[float], layout: str = "nchw", min_val: Optional[float] = None,
                    max_val: Optional[float] = None) -> torch.Tensor:

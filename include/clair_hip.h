@@ -461,6 +461,30 @@ int ct_linearize_ingest_data(const void *frames_dev, int32_t dtype, int64_t n_fr
                              const float *consts_dev, void *stream);
 
 /*
+ * ct_linearize_ingest_strided -- StridedDownscale(step), such a chain and the linearization in ONE pass: every step-th row and
+ * column of the raw frames in, dense planar float32 (F, C, ho, wo) out, ho = ceil(H_tile / step), wo = ceil(W / step).  Bit
+ * for bit ct_strided_downscale followed by ct_linearize_ingest (consts_dev NULL) or ct_linearize_ingest_data on the
+ * compacted frames, without the compacted copy; step == 1 is those two entry points themselves.
+ *   geom         of the SOURCE frames (layout, H, W, image_stride) as ct_linearize_ingest takes it.  With step > 1 a row band
+ *                (row_offset != 0 or h_tile != h_global) is CT_ERR_INVALID_ARGUMENT: which rows of a band a downscale selects
+ *                depends on row_offset % step, a phase that is not carried
+ *   step         >= 1, else CT_ERR_INVALID_ARGUMENT
+ *   lin_out_dev, std_out_dev   planar (F, C, ho, wo) float32, dense, aligned to 4 bytes; std_out_dev may be NULL
+ *   std_dev      EXPLICIT: planar (F, C, ho, wo) float32, dense -- already of the OUTPUT shape: gpu_transforms are applied to
+ *                the value images only, so explicit uncertainties arrive at the downscaled size
+ *   consts_dev   NULL, or (n_frames, 4) per-frame constants of one CT_INGEST_AFFINE_DATA stage as ct_linearize_ingest_data
+ *                reads them (ct_ingest_extrema_frames on the FULL frames: a Normalize in front of the downscale)
+ * The LINEAR / CATMULL LUT row is the flat NCHW index of the DOWNSCALED frame modulo C, (c * ho * wo + i * wo + j) % C.
+ * Everything else -- stage checks, CT_ERR_UNSUPPORTED, CT_ERR_NO_GRADIENT_PATH, CT_ERR_TOO_LARGE, validation before anything
+ * touches the device, n_frames == 0 -- as ct_linearize_ingest.  Reads only selected elements of the frames, touches nothing
+ * outside F*C*ho*wo elements of the outputs.
+ */
+int ct_linearize_ingest_strided(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom, int32_t step,
+                                const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,
+                                float std_value, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev,
+                                const float *consts_dev /* may be NULL */, void *stream);
+
+/*
  * ct_hdr_merge_ingest_batch -- such a chain and one batch of compute_hdr_image's loop body in ONE pass over B raw frames:
  * state and outputs are bit for bit those of ct_ingest_transform (with consts_dev: ct_ingest_transform_data) into a dense
  * planar float32 (B, C, H_tile, W) stack followed by ct_hdr_merge_batch on that stack with CT_DTYPE_F32, the same geometry
