@@ -158,6 +158,37 @@ __device__ __forceinline__ float icrf_sample(float x, const char *row_lds, float
     }
 }
 
+// The sample step of the linearization (linearization.py:95-106,132): lin = f(x) in the reference's float32 order and the
+// propagated uncertainty sd = sqrt((f'(x) * sigma)^2), where sigma is `sigma` (EXPLICIT; not read otherwise), x * std_value
+// (MULTIPLIER, datasets/base.py:133) or std_value (CONSTANT); sd = 0 when there is none to write.  In binary floating point
+// the correctly rounded square root of a correctly rounded square is |.| exactly unless the square underflows, so sd is
+// |f'(x) * sigma| and the sqrtf expansion (~18 instructions) is only needed for 0 < sd < 1e-18: `tiny`.  The caller ORs
+// `tiny` over its samples and replaces such sd by sqrtf(sd * sd) behind ONE wave-uniform branch, if (__any(tiny)), which is
+// practically never taken; written as a per-element `if` here the compiler if-converts it and every sample pays for the
+// expansion (a third of linearize_kernel's VALU work).  Returned by value: with reference outputs some kernels schedule
+// differently (profiles/linearize_refactor_ab.md).
+struct LinSample {
+    float lin, sd;
+    bool tiny;
+};
+template <int INTERP, int STD, bool WRITE_STD, bool RANGED>
+__device__ __forceinline__ LinSample linearize_sample(float x, const char *row_lds, float top, float sigma, float std_value)
+{
+    float dfdx;
+    LinSample r;
+    r.lin = icrf_sample<INTERP, true, RANGED>(x, row_lds, top, dfdx);
+    r.sd = 0.0f;
+    r.tiny = false;
+    if constexpr (WRITE_STD && STD != CT_STD_NONE) {
+        if constexpr (STD == CT_STD_CONSTANT) sigma = std_value;
+        if constexpr (STD == CT_STD_MULTIPLIER) sigma = x * std_value;
+        const float ags = fabsf(dfdx * sigma);
+        r.sd = ags;
+        r.tiny = ags < 1e-18f && ags != 0.0f;
+    }
+    return r;
+}
+
 // d(G * f(x))/dx for float32 x in autograd's operation order (the upstream gradient multiplies the LUT taps FIRST):
 // what ICRFModelBase.forward's backward hands to the image (clair_torch/models/base.py:160-226), bit for bit.
 template <int INTERP>
@@ -398,6 +429,16 @@ static int with_enum(int value, F &&f)
     int rc = CT_ERR_INVALID_ARGUMENT;
     (void)((value == VALUES ? (rc = f(std::integral_constant<int, VALUES>{}), true) : false) || ...);
     return rc;
+}
+
+// (STD, WRITE_STD) of a linearization kernel: f(integral_constant<int, STD>, integral_constant<bool, WRITE_STD>).  Without
+// a std output the kernel is the CT_STD_NONE one, whatever std_mode says; with one, STDS are the uncertainty modes the
+// kernel has besides CT_STD_NONE, and CT_ERR_INVALID_ARGUMENT answers every other.
+template <int... STDS, typename F>
+static int with_linearize_std(int std_mode, bool write_std, F &&f)
+{
+    if (!write_std) return f(std::integral_constant<int, CT_STD_NONE>{}, std::false_type{});
+    return with_enum<CT_STD_NONE, STDS...>(std_mode, [&](auto S) { return f(S, std::true_type{}); });
 }
 
 }  // namespace ct

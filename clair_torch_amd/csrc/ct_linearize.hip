@@ -12,6 +12,11 @@
 //                       flush negligible).
 //
 // Roofline: HBM (sizeof(T) read + 4 or 8 B written per sample).  No reuse between workgroups, so no XCD remap.
+//
+// The sample step (icrf_sample, sigma, |f'(x) sigma|, the `tiny` corner) is linearize_sample of ct_device.hpp, explained
+// there; linearize_rgb_kernel calls it, linearize_kernel and linearize_planar_kernel spell the same expressions out (through
+// the call some of their instantiations compile differently: profiles/linearize_refactor_ab.md).  load_frame4 is the load
+// of four elements as floats; lin_dispatch / lin_launch / lin_launch_grid are the one host path of the four routes.
 #include <algorithm>
 #include "ct_args.hpp"
 
@@ -37,6 +42,22 @@ struct LinArgs {
     NormConst norm;
     float std_value;
 };
+
+// Four elements of a frame as floats: those at element offset q of the frame that starts `frame_off` elements into `frames`.
+// Integer frames: one typed buffer load delivers the codes as floats (ct_device.hpp) -- frame base in SGPRs, 32-bit per-thread
+// byte offset, no v_cvt; float frames: one 16-byte packet.
+template <typename T>
+__device__ __forceinline__ void load_frame4(const void *frames, int64_t frame_off, uint64_t q, float (&out)[4])
+{
+    if constexpr (sizeof(T) != 4) {
+        const uint64_t base = reinterpret_cast<uint64_t>(frames) + (uint64_t)(frame_off * (int64_t)sizeof(T));
+        load_codes_as_float<T, 4>(base, (uint32_t)q * (uint32_t)sizeof(T), out);
+    } else {
+        const LPacket<T, 4> pk = *reinterpret_cast<const LPacket<T, 4> *>(static_cast<const T *>(frames) + frame_off + q);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) out[k] = pk.v[k];
+    }
+}
 
 // grid.x covers the packets of one frame, grid.y walks frames
 template <typename T, int V, int INTERP, int STD, bool WRITE_STD>
@@ -150,7 +171,7 @@ __global__ __launch_bounds__(kBlock) void linearize_kernel(const LinArgs a)
 // flight per thread.  The 8-elements-per-thread mapping of linearize_kernel writes 32 bytes per lane with two half-dense
 // store instructions; the pixel-owning RGB kernel below, whose stores are dense, ran the same C4 workload in 0.70 ms
 // against 0.84 ms (profiles/r03_layout_ingest.md) -- this kernel gives the planar layout the same access shape.
-// Per-element arithmetic is the same function call as everywhere else (bit-identical results).  q_count: a multiple of 4.
+// Per-element arithmetic is that of linearize_sample, spelled out (bit-identical results).  q_count: a multiple of 4.
 template <typename T, int K, int INTERP, int STD, bool WRITE_STD>
 __global__ __launch_bounds__(kBlock) void linearize_planar_kernel(const LinArgs a)
 {
@@ -195,14 +216,7 @@ __global__ __launch_bounds__(kBlock) void linearize_planar_kernel(const LinArgs 
         LPacket<float, 4> sp[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {  // all loads first
-            if constexpr (sizeof(T) != 4) {
-                const uint64_t base = reinterpret_cast<uint64_t>(a.frames) + (uint64_t)((int64_t)f * a.image_stride * (int64_t)sizeof(T));
-                load_codes_as_float<T, 4>(base, q0[k] * (uint32_t)sizeof(T), xin[k]);
-            } else {
-                const LPacket<T, 4> pk = *reinterpret_cast<const LPacket<T, 4> *>(static_cast<const T *>(a.frames) + (int64_t)f * a.image_stride + q0[k]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) xin[k][e] = pk.v[e];
-            }
+            load_frame4<T>(a.frames, (int64_t)f * a.image_stride, q0[k], xin[k]);
             if constexpr (STD == CT_STD_EXPLICIT) sp[k] = *reinterpret_cast<const LPacket<float, 4> *>(a.std_stack + (int64_t)f * a.image_stride + q0[k]);
         }
         LPacket<float, 4> lo[K], so[K];
@@ -244,53 +258,12 @@ __global__ __launch_bounds__(kBlock) void linearize_planar_kernel(const LinArgs 
     }
 }
 
-constexpr int kLinPackets = 3;  // packets per thread of linearize_planar_kernel (12 elements, like the RGB kernel)
-
-template <typename T, int INTERP, int STD, bool WRITE_STD>
-static int lin_launch_planar(const LinArgs &a, hipStream_t s)
-{
-    if (a.q_count == 0 || a.n_frames == 0) return CT_OK;
-    const uint32_t packets = a.q_count / 4, gx = (packets + kBlock * kLinPackets - 1) / (kBlock * kLinPackets);
-    uint32_t gy = (a.n_frames + 1) / 2;
-    if (gy < 1) gy = 1;
-    if (gy > 65535) gy = 65535;
-    const size_t lds = lut_lds_bytes(INTERP, a.channels, a.n_points);
-    if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;
-    hipLaunchKernelGGL((linearize_planar_kernel<T, kLinPackets, INTERP, STD, WRITE_STD>), dim3(gx, gy), dim3(kBlock), lds, s, a);
-    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
-}
-
-template <typename T, int INTERP>
-static int lin_dispatch_planar_std(const LinArgs &a, int std_mode, bool write_std, hipStream_t s)
-{
-    if (!write_std) return lin_launch_planar<T, INTERP, CT_STD_NONE, false>(a, s);
-    switch (std_mode) {
-        case CT_STD_NONE: return lin_launch_planar<T, INTERP, CT_STD_NONE, true>(a, s);
-        case CT_STD_CONSTANT: return lin_launch_planar<T, INTERP, CT_STD_CONSTANT, true>(a, s);
-        case CT_STD_MULTIPLIER: return lin_launch_planar<T, INTERP, CT_STD_MULTIPLIER, true>(a, s);
-        case CT_STD_EXPLICIT: return lin_launch_planar<T, INTERP, CT_STD_EXPLICIT, true>(a, s);
-    }
-    return CT_ERR_INVALID_ARGUMENT;
-}
-
-template <typename T>
-static int lin_dispatch_planar(const LinArgs &a, int interp, int std_mode, bool write_std, hipStream_t s)
-{
-    switch (interp) {
-        case CT_INTERP_LOOKUP: return lin_dispatch_planar_std<T, CT_INTERP_LOOKUP>(a, std_mode, write_std, s);
-        case CT_INTERP_LINEAR: return lin_dispatch_planar_std<T, CT_INTERP_LINEAR>(a, std_mode, write_std, s);
-        case CT_INTERP_CATMULL: return lin_dispatch_planar_std<T, CT_INTERP_CATMULL>(a, std_mode, write_std, s);
-        case CT_INTERP_NONE: return lin_dispatch_planar_std<T, CT_INTERP_NONE>(a, std_mode, write_std, s);
-    }
-    return CT_ERR_INVALID_ARGUMENT;
-}
-
 // Interleaved RGB / BGR frames (C == 3: what OpenCV decodes to, clair_torch/common/data_io.py:125-154): a thread owns four
 // consecutive PIXELS = 12 memory elements (three typed loads of four codes each, or three 16-byte loads of float pixels),
 // so every channel plane of the planar outputs receives its four consecutive pixels as ONE 16-byte streaming store.  The
 // element-per-thread mapping of linearize_kernel scatters 4-byte stores over three planes and pays three runtime divisions
 // per element: 2.09 ms against 0.85 ms for the planar layout on C4 (profiles/r03_layout_ingest.md).  Per-element arithmetic
-// is the same function call, so results are bit-identical to the planar path.  q_begin / q_count are multiples of 12.
+// is linearize_sample, so results are bit-identical to the planar path.  q_begin / q_count are multiples of 12.
 template <typename T, int INTERP, int STD, bool WRITE_STD>
 __global__ __launch_bounds__(kBlock) void linearize_rgb_kernel(const LinArgs a)
 {
@@ -330,17 +303,7 @@ __global__ __launch_bounds__(kBlock) void linearize_rgb_kernel(const LinArgs a)
 #pragma unroll
             for (int h = 0; h < 3; ++h) {
                 const uint32_t rel = wave_first + 4u * ((uint32_t)h * 64u + lane);  // this lane's packet of dense load h
-                if (rel < a.q_count) {
-                    if constexpr (sizeof(T) != 4) {
-                        const uint64_t base = reinterpret_cast<uint64_t>(a.frames) + (uint64_t)((int64_t)f * a.image_stride * (int64_t)sizeof(T));
-                        load_codes_as_float<T, 4>(base, (a.q_begin + rel) * (uint32_t)sizeof(T), got[h].v);
-                    } else {
-                        const T *src = static_cast<const T *>(a.frames) + (int64_t)f * a.image_stride + a.q_begin + rel;
-                        const LPacket<T, 4> pk = *reinterpret_cast<const LPacket<T, 4> *>(src);
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) got[h].v[k] = pk.v[k];
-                    }
-                }
+                if (rel < a.q_count) load_frame4<T>(a.frames, (int64_t)f * a.image_stride, (uint64_t)a.q_begin + rel, got[h].v);
             }
 #pragma unroll
             for (int h = 0; h < 3; ++h) *reinterpret_cast<LPacket<float, 4> *>(stage + 4u * ((uint32_t)h * 64u + lane)) = got[h];
@@ -353,20 +316,14 @@ __global__ __launch_bounds__(kBlock) void linearize_rgb_kernel(const LinArgs a)
         }
         if (!active) continue;  // lanes past the end helped with the loads only
         float lin[12], sd[12];
-        [[maybe_unused]] bool tiny = false;
+        bool tiny = false;
 #pragma unroll
         for (int k = 0; k < 12; ++k) {
             const float x = sizeof(T) != 4 ? code_to_pixel(xin[k], a.norm) : xin[k];
-            float dfdx;
-            lin[k] = icrf_sample<INTERP, true, kRanged>(x, lds + row_off[k], top, dfdx);
-            sd[k] = 0.0f;
-            if constexpr (WRITE_STD && STD != CT_STD_NONE) {
-                float sigma = a.std_value;                                          // CONSTANT
-                if constexpr (STD == CT_STD_MULTIPLIER) sigma = x * a.std_value;    // datasets/base.py:133
-                const float ags = fabsf(dfdx * sigma);  // sqrt((grad * std)^2) = |grad * std| unless the square underflows
-                sd[k] = ags;
-                tiny |= ags < 1e-18f && ags != 0.0f;
-            }
+            const LinSample r = linearize_sample<INTERP, STD, WRITE_STD, kRanged>(x, lds + row_off[k], top, 0.0f, a.std_value);
+            lin[k] = r.lin;
+            sd[k] = r.sd;
+            tiny |= r.tiny;
         }
         if constexpr (WRITE_STD && STD != CT_STD_NONE) {
             if (__builtin_expect(__any(tiny), 0)) {
@@ -392,86 +349,56 @@ __global__ __launch_bounds__(kBlock) void linearize_rgb_kernel(const LinArgs a)
     }
 }
 
-template <typename T, int INTERP, int STD, bool WRITE_STD>
-static int lin_launch_rgb(const LinArgs &a, hipStream_t s)
+// ---- host: launch and dispatch ----------------------------------------------------------------------------------------
+enum LinRoute { kLinElement, kLinPacket, kLinPlanar, kLinRgb };  // linearize_kernel<T, 1>, <T, kLinV>, the planar and the RGB kernel
+constexpr int kLinV = 8;        // elements per thread of linearize_kernel's packets (lin_typed)
+constexpr int kLinPackets = 3;  // packets per thread of linearize_planar_kernel (12 elements, like the RGB kernel)
+
+// What every launch shares; `per_block`: elements of one frame per workgroup (q_count is a multiple of a thread's share)
+template <typename Kernel>
+static int lin_launch_grid(Kernel kernel, const LinArgs &a, uint32_t per_block, size_t lds, hipStream_t s)
 {
     if (a.q_count == 0 || a.n_frames == 0) return CT_OK;
-    const uint32_t vecs = a.q_count / 12, gx = (vecs + kBlock - 1) / kBlock;
-    uint32_t gy = (a.n_frames + 1) / 2;
-    if (gy < 1) gy = 1;
-    if (gy > 65535) gy = 65535;
-    const size_t lds = (lut_lds_bytes(INTERP, 3, a.n_points) + 15 & ~(size_t)15) +
-                       (size_t)(kBlock / 64) * 768 * sizeof(float);  // LUT | 3 KB of exchange space per wavefront
-    if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;
-    hipLaunchKernelGGL((linearize_rgb_kernel<T, INTERP, STD, WRITE_STD>), dim3(gx, gy), dim3(kBlock), lds, s, a);
-    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
-}
-
-template <typename T, int INTERP>
-static int lin_dispatch_rgb_std(const LinArgs &a, int std_mode, bool write_std, hipStream_t s)
-{
-    if (!write_std) return lin_launch_rgb<T, INTERP, CT_STD_NONE, false>(a, s);
-    switch (std_mode) {
-        case CT_STD_NONE: return lin_launch_rgb<T, INTERP, CT_STD_NONE, true>(a, s);
-        case CT_STD_CONSTANT: return lin_launch_rgb<T, INTERP, CT_STD_CONSTANT, true>(a, s);
-        case CT_STD_MULTIPLIER: return lin_launch_rgb<T, INTERP, CT_STD_MULTIPLIER, true>(a, s);
-    }
-    return CT_ERR_UNSUPPORTED;  // explicit std stacks with interleaved frames go through the element-wise kernel
-}
-
-template <typename T>
-static int lin_dispatch_rgb(const LinArgs &a, int interp, int std_mode, bool write_std, hipStream_t s)
-{
-    switch (interp) {
-        case CT_INTERP_LOOKUP: return lin_dispatch_rgb_std<T, CT_INTERP_LOOKUP>(a, std_mode, write_std, s);
-        case CT_INTERP_LINEAR: return lin_dispatch_rgb_std<T, CT_INTERP_LINEAR>(a, std_mode, write_std, s);
-        case CT_INTERP_CATMULL: return lin_dispatch_rgb_std<T, CT_INTERP_CATMULL>(a, std_mode, write_std, s);
-        case CT_INTERP_NONE: return lin_dispatch_rgb_std<T, CT_INTERP_NONE>(a, std_mode, write_std, s);
-    }
-    return CT_ERR_INVALID_ARGUMENT;
-}
-
-template <typename T, int V, int INTERP, int STD, bool WRITE_STD>
-static int lin_launch(const LinArgs &a, hipStream_t s)
-{
-    if (a.q_count == 0 || a.n_frames == 0) return CT_OK;
-    const uint32_t vecs = a.q_count / V, gx = (vecs + kBlock - 1) / kBlock;
+    const uint32_t gx = (uint32_t)(((uint64_t)a.q_count + per_block - 1) / per_block);
     // Two frames per workgroup (grid.y = F/2): measured best on C4 (64 frames: 57 % of the HBM peak vs 52 % with one
     // frame and 49 % with sixteen frames per workgroup); the LUT staging is amortised over two packets and the grid
     // stays far larger than the machine.  A write-heavy stream with the same ingredients and no frame loop reaches
-    // 5.2-5.5 TB/s on the same device (tools/stream_write_heavy.hip), so this kernel is at ~85 % of what is achievable.
-    uint32_t gy = (a.n_frames + 1) / 2;
-    if (gy < 1) gy = 1;
-    if (gy > 65535) gy = 65535;
-    const size_t lds = lut_lds_bytes(INTERP, a.channels, a.n_points);
+    // 5.2-5.5 TB/s on the same device (tools/stream_write_heavy.hip), so linearize_kernel is at ~85 % of what is achievable.
+    const uint32_t gy = std::min(std::max((a.n_frames + 1) / 2, 1u), 65535u);
     if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;
-    hipLaunchKernelGGL((linearize_kernel<T, V, INTERP, STD, WRITE_STD>), dim3(gx, gy), dim3(kBlock), lds, s, a);
+    hipLaunchKernelGGL(kernel, dim3(gx, gy), dim3(kBlock), lds, s, a);
     return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
 }
 
-template <typename T, int V, int INTERP>
-static int lin_dispatch_std(const LinArgs &a, int std_mode, bool write_std, hipStream_t s)
+template <typename T, int ROUTE, int INTERP, int STD, bool WRITE_STD>
+static int lin_launch(const LinArgs &a, hipStream_t s)
 {
-    if (!write_std) return lin_launch<T, V, INTERP, CT_STD_NONE, false>(a, s);
-    switch (std_mode) {
-        case CT_STD_NONE: return lin_launch<T, V, INTERP, CT_STD_NONE, true>(a, s);
-        case CT_STD_CONSTANT: return lin_launch<T, V, INTERP, CT_STD_CONSTANT, true>(a, s);
-        case CT_STD_MULTIPLIER: return lin_launch<T, V, INTERP, CT_STD_MULTIPLIER, true>(a, s);
-        case CT_STD_EXPLICIT: return lin_launch<T, V, INTERP, CT_STD_EXPLICIT, true>(a, s);
+    const size_t lut = lut_lds_bytes(INTERP, a.channels, a.n_points);
+    if constexpr (ROUTE == kLinRgb) {  // (channels == 3)  LUT | 3 KB of exchange space per wavefront
+        const size_t lds = (lut + 15 & ~(size_t)15) + (size_t)(kBlock / 64) * 768 * sizeof(float);
+        return lin_launch_grid(linearize_rgb_kernel<T, INTERP, STD, WRITE_STD>, a, 12 * kBlock, lds, s);
+    } else if constexpr (ROUTE == kLinPlanar) {
+        return lin_launch_grid(linearize_planar_kernel<T, kLinPackets, INTERP, STD, WRITE_STD>, a, 4 * kLinPackets * kBlock, lut, s);
+    } else {
+        constexpr int V = ROUTE == kLinPacket ? kLinV : 1;
+        return lin_launch_grid(linearize_kernel<T, V, INTERP, STD, WRITE_STD>, a, V * kBlock, lut, s);
     }
-    return CT_ERR_INVALID_ARGUMENT;
 }
 
-template <typename T, int V>
+// interp / std_mode / write_std -> template arguments.  The RGB kernel has no CT_STD_EXPLICIT (explicit std stacks with
+// interleaved frames go through the element-wise kernel, lin_typed): it answers CT_ERR_UNSUPPORTED for a mode it does not hold.
+template <typename T, int ROUTE>
 static int lin_dispatch(const LinArgs &a, int interp, int std_mode, bool write_std, hipStream_t s)
 {
-    switch (interp) {
-        case CT_INTERP_LOOKUP: return lin_dispatch_std<T, V, CT_INTERP_LOOKUP>(a, std_mode, write_std, s);
-        case CT_INTERP_LINEAR: return lin_dispatch_std<T, V, CT_INTERP_LINEAR>(a, std_mode, write_std, s);
-        case CT_INTERP_CATMULL: return lin_dispatch_std<T, V, CT_INTERP_CATMULL>(a, std_mode, write_std, s);
-        case CT_INTERP_NONE: return lin_dispatch_std<T, V, CT_INTERP_NONE>(a, std_mode, write_std, s);
-    }
-    return CT_ERR_INVALID_ARGUMENT;
+    return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
+        auto launch = [&](auto S, auto W) { return lin_launch<T, ROUTE, I, S, W>(a, s); };
+        if constexpr (ROUTE == kLinRgb) {
+            const int rc = with_linearize_std<CT_STD_CONSTANT, CT_STD_MULTIPLIER>(std_mode, write_std, launch);
+            return rc == CT_ERR_INVALID_ARGUMENT ? (int)CT_ERR_UNSUPPORTED : rc;  // (no launch returns INVALID_ARGUMENT)
+        } else {
+            return with_linearize_std<CT_STD_CONSTANT, CT_STD_MULTIPLIER, CT_STD_EXPLICIT>(std_mode, write_std, launch);
+        }
+    });
 }
 
 template <typename T>
@@ -480,10 +407,7 @@ static int lin_typed(LinArgs a, uint32_t Q, int interp, int std_mode, bool write
     // Elements per thread: 8 integer codes (two typed loads) or 8 float pixels (two 16-byte loads).  16 codes per thread was
     // measured 2.6x SLOWER on C4 (2.21 against 0.85 ms, profiles/r03_layout_ingest.md) although the pixel-owning RGB kernel
     // with 12 codes per thread is the fastest of all (0.68 ms).
-#ifndef CT_LINEARIZE_V_INT
-#define CT_LINEARIZE_V_INT 8
-#endif
-    constexpr int V = sizeof(T) == 4 ? 8 : CT_LINEARIZE_V_INT;
+    constexpr int V = kLinV;
     // Packets of V are for interleaved frames, whose outputs are stored element by element.  Planar frames with whole packets
     // go to linearize_planar_kernel below; what it refuses (Q % 4 != 0: output frames out_stride = Q apart are 4-byte aligned
     // only, whatever image_stride is) goes element by element.
@@ -496,29 +420,29 @@ static int lin_typed(LinArgs a, uint32_t Q, int interp, int std_mode, bool write
         aligned(a.frames, 16) && (a.image_stride % 4) == 0 && aligned(a.lin_out, 16) && aligned(a.std_out, 16) && a.out_stride % 4 == 0) {
         a.q_begin = 0;
         a.q_count = Q;  // 3 * plane_local: a multiple of 12
-        return lin_dispatch_rgb<T>(a, interp, std_mode, write_std, s);
+        return lin_dispatch<T, kLinRgb>(a, interp, std_mode, write_std, s);
     }
     // planar frames with whole packets of four everywhere: the dense-access kernel (K packets per thread)
     if (a.tile.layout == CT_LAYOUT_NCHW && Q >= 4 && aligned(a.frames, sizeof(T) * 4) && (a.image_stride % 4) == 0 &&
         aligned(a.std_stack, 16) && aligned(a.lin_out, 16) && aligned(a.std_out, 16) && a.out_stride % 4 == 0) {
         a.q_begin = 0;
         a.q_count = (Q / 4) * 4;
-        rc = lin_dispatch_planar<T>(a, interp, std_mode, write_std, s);
+        rc = lin_dispatch<T, kLinPlanar>(a, interp, std_mode, write_std, s);
         if (rc != CT_OK || a.q_count == Q) return rc;
         a.q_begin = a.q_count;
         a.q_count = Q - a.q_begin;
-        return lin_dispatch<T, 1>(a, interp, std_mode, write_std, s);
+        return lin_dispatch<T, kLinElement>(a, interp, std_mode, write_std, s);
     }
     if (q_vec) {
         a.q_begin = 0;
         a.q_count = q_vec;
-        rc = lin_dispatch<T, V>(a, interp, std_mode, write_std, s);
+        rc = lin_dispatch<T, kLinPacket>(a, interp, std_mode, write_std, s);
         if (rc != CT_OK) return rc;
     }
     if (q_vec < Q) {
         a.q_begin = q_vec;
         a.q_count = Q - q_vec;
-        rc = lin_dispatch<T, 1>(a, interp, std_mode, write_std, s);
+        rc = lin_dispatch<T, kLinElement>(a, interp, std_mode, write_std, s);
     }
     return rc;
 }
@@ -696,10 +620,5 @@ extern "C" int ct_linearize_bwd(const float *x_dev, const float *grad_out_dev, i
     a.channels = geom->channels;
     a.n_points = icrf->n_points;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (interp) {
-        case CT_INTERP_LOOKUP: return bwd_launch<CT_INTERP_LOOKUP>(a, s);
-        case CT_INTERP_LINEAR: return bwd_launch<CT_INTERP_LINEAR>(a, s);
-        case CT_INTERP_CATMULL: return bwd_launch<CT_INTERP_CATMULL>(a, s);
-    }
-    return CT_ERR_INVALID_ARGUMENT;
+    return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL>(interp, [&](auto I) { return bwd_launch<I>(a, s); });
 }

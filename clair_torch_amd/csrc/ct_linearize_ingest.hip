@@ -1,9 +1,10 @@
 // ct_linearize_ingest.hip -- a recognised gpu_transforms chain and the ICRF linearization in ONE pass (gfx950): raw codes /
 // pixels in, planar float32 (lin, std) out.  The outputs are bit for bit those of ct_ingest_transform (ct_ingest.hip)
 // followed by ct_linearize_std (ct_linearize.hip) on its float32 result -- the same two device functions run here on a
-// value that never leaves the registers: ct::ingest_stages (ct_ingest_stages.hpp) and icrf_sample<INTERP, true, false>
-// (ct_device.hpp; RANGED = false, the clamp mask, the reference-order CATMULL derivative), then std = |f'(x) * sigma|
-// with the sqrtf of the rounded square behind a wave-uniform branch where the square underflows (linearization.py:106,132).
+// value that never leaves the registers: ct::ingest_stages (ct_ingest_stages.hpp) and linearize_sample (ct_device.hpp:
+// icrf_sample<INTERP, true, false> -- RANGED = false, the clamp mask, the reference-order CATMULL derivative -- then
+// std = |f'(x) * sigma|), with the sqrtf of the rounded square behind a wave-uniform branch where the square underflows
+// (linearization.py:106,132; li_sample4 of ct_linearize_ingest.hpp).
 //
 // Roofline: HBM, sizeof(T) bytes read and 4 or 8 written per sample (+ 4 read with explicit uncertainties), every byte
 // once: 10 B per uint16 sample where the two launches move 18.

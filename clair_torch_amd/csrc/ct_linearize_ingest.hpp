@@ -1,8 +1,9 @@
 // ct_linearize_ingest.hpp -- what the fused chain + linearization kernels share (ct_linearize_ingest.hip on dense frames,
 // ct_linearize_ingest_strided.hip on every step-th row and column of them): the argument block, the slot / span scheme of
-// a thread's 4 output elements, the sample step behind the chain (li_sample4), the packet store, and the host-side launch
-// loop and dispatch over element type, interpolation and uncertainty mode.  One copy of each: the outputs of the two files
-// agree bit for bit because they run the same device functions.
+// a thread's 4 output elements, the sample step behind the chain (li_sample4: four linearize_sample of ct_device.hpp, the
+// step ct_linearize.hip runs, and their `tiny` fix-up), the packet store, and the host-side launch loop and dispatch over
+// element type, interpolation and uncertainty mode (with_enum, with_linearize_std).  One copy of each: the outputs of the
+// two files agree bit for bit because they run the same device functions.
 #pragma once
 #include "ct_args.hpp"
 #include "ct_ingest_stages.hpp"
@@ -62,22 +63,17 @@ __device__ __forceinline__ void li_sample4(const float (&x)[kLiGroup], const flo
     [[maybe_unused]] bool tiny = false;  // some 0 < |grad * std| < 1e-18 among these
 #pragma unroll
     for (int e = 0; e < kLiGroup; ++e) {
-        float dfdx;
-        lo.v[e] = icrf_sample<INTERP, true, false>(x[e], lds + (INTERP == CT_INTERP_LOOKUP ? c : r) * L * kEntry, top, dfdx);
-        so.v[e] = 0.0f;
-        if constexpr (WRITE_STD && STD != CT_STD_NONE) {
-            float sigma = std_value;                                        // CONSTANT
-            if constexpr (STD == CT_STD_EXPLICIT) sigma = sg[e];
-            if constexpr (STD == CT_STD_MULTIPLIER) sigma = x[e] * std_value;  // datasets/base.py:133, x behind the chain
-            const float ags = fabsf(dfdx * sigma);  // sqrt((grad * std)^2) = |grad * std| unless the square underflows
-            so.v[e] = ags;
-            tiny |= ags < 1e-18f && ags != 0.0f;
-        }
+        // RANGED = false: x is a float behind the chain (and so is the x of MULTIPLIER)
+        const LinSample s = linearize_sample<INTERP, STD, WRITE_STD, false>(x[e], lds + (INTERP == CT_INTERP_LOOKUP ? c : r) * L * kEntry,
+                                                                            top, sg[e], std_value);
+        lo.v[e] = s.lin;
+        so.v[e] = s.sd;
+        tiny |= s.tiny;
         ++r;
         r = r >= C ? r - C : r;
     }
     if constexpr (WRITE_STD && STD != CT_STD_NONE) {
-        if (__builtin_expect(__any(tiny), 0)) {  // wave-uniform, practically never taken (ct_linearize.hip)
+        if (__builtin_expect(__any(tiny), 0)) {  // wave-uniform, practically never taken (linearize_sample)
 #pragma unroll
             for (int e = 0; e < kLiGroup; ++e)
                 if (so.v[e] < 1e-18f && so.v[e] != 0.0f) so.v[e] = sqrtf(so.v[e] * so.v[e]);
@@ -126,40 +122,26 @@ static int li_launch_rows(void (*kernel)(const Args), Args a, int interp, int64_
     return CT_OK;
 }
 
-// Launch<T, INTERP, STD, WRITE_STD>::run(a, packed, rows, s) picks the kernel of a file
-template <template <typename, int, int, bool> class Launch, typename T, int INTERP, typename Args>
-static int li_dispatch_std(const Args &a, bool packed, int64_t rows, int std_mode, bool write_std, hipStream_t s)
-{
-    if (!write_std) return Launch<T, INTERP, CT_STD_NONE, false>::run(a, packed, rows, s);
-    if (std_mode == CT_STD_NONE) return Launch<T, INTERP, CT_STD_NONE, true>::run(a, packed, rows, s);
-    if constexpr (INTERP != CT_INTERP_LOOKUP) {  // (LOOKUP with uncertainties has no gradient path: refused by the caller)
-        switch (std_mode) {
-            case CT_STD_CONSTANT: return Launch<T, INTERP, CT_STD_CONSTANT, true>::run(a, packed, rows, s);
-            case CT_STD_MULTIPLIER: return Launch<T, INTERP, CT_STD_MULTIPLIER, true>::run(a, packed, rows, s);
-            case CT_STD_EXPLICIT: return Launch<T, INTERP, CT_STD_EXPLICIT, true>::run(a, packed, rows, s);
-        }
-    }
-    return CT_ERR_INVALID_ARGUMENT;
-}
-
+// dtype / interp / std_mode / write_std -> template arguments; Launch<T, INTERP, STD, WRITE_STD>::run(a, packed, rows, s) picks
+// the kernel of a file.  LOOKUP with uncertainties has no gradient path (refused by the caller) and no kernel.
 template <template <typename, int, int, bool> class Launch, typename T, typename Args>
-static int li_dispatch_interp(const Args &a, bool packed, int64_t rows, int interp, int std_mode, bool write_std, hipStream_t s)
+static int li_dispatch_typed(const Args &a, bool packed, int64_t rows, int interp, int std_mode, bool write_std, hipStream_t s)
 {
-    switch (interp) {
-        case CT_INTERP_LOOKUP: return li_dispatch_std<Launch, T, CT_INTERP_LOOKUP>(a, packed, rows, std_mode, write_std, s);
-        case CT_INTERP_LINEAR: return li_dispatch_std<Launch, T, CT_INTERP_LINEAR>(a, packed, rows, std_mode, write_std, s);
-        case CT_INTERP_CATMULL: return li_dispatch_std<Launch, T, CT_INTERP_CATMULL>(a, packed, rows, std_mode, write_std, s);
-        case CT_INTERP_NONE: return li_dispatch_std<Launch, T, CT_INTERP_NONE>(a, packed, rows, std_mode, write_std, s);
-    }
-    return CT_ERR_INVALID_ARGUMENT;
+    return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
+        auto run = [&](auto S, auto W) { return Launch<T, I, S, W>::run(a, packed, rows, s); };
+        if constexpr (I == CT_INTERP_LOOKUP)
+            return with_linearize_std<>(std_mode, write_std, run);
+        else
+            return with_linearize_std<CT_STD_CONSTANT, CT_STD_MULTIPLIER, CT_STD_EXPLICIT>(std_mode, write_std, run);
+    });
 }
 
 template <template <typename, int, int, bool> class Launch, typename Args>
 static int li_dispatch(const Args &a, int32_t dtype, bool packed, int64_t rows, int interp, int std_mode, bool write_std, hipStream_t s)
 {
-    if (dtype == CT_DTYPE_U8) return li_dispatch_interp<Launch, uint8_t>(a, packed, rows, interp, std_mode, write_std, s);
-    if (dtype == CT_DTYPE_U16) return li_dispatch_interp<Launch, uint16_t>(a, packed, rows, interp, std_mode, write_std, s);
-    return li_dispatch_interp<Launch, float>(a, packed, rows, interp, std_mode, write_std, s);
+    if (dtype == CT_DTYPE_U8) return li_dispatch_typed<Launch, uint8_t>(a, packed, rows, interp, std_mode, write_std, s);
+    if (dtype == CT_DTYPE_U16) return li_dispatch_typed<Launch, uint16_t>(a, packed, rows, interp, std_mode, write_std, s);
+    return li_dispatch_typed<Launch, float>(a, packed, rows, interp, std_mode, write_std, s);
 }
 
 // What the entry points check in this order, before any pointer into device memory: the stack and the stage list

@@ -3,7 +3,7 @@
 // (F, C, ho, wo), ho = ceil(H / step), wo = ceil(W / step), out.  Bit for bit ct_strided_downscale (ct_downscale.hip)
 // followed by ct_linearize_ingest / ct_linearize_ingest_data (ct_linearize_ingest.hip) on the compacted frames: selecting
 // pixels commutes with the per-sample chain, and the sample step is the same code (ct_linearize_ingest.hpp: ingest_stages,
-// li_sample4 = icrf_sample<INTERP, true, false> and |f'(x) sigma| with its wave-uniform sqrtf branch).
+// li_sample4 = linearize_sample of ct_device.hpp four times and the wave-uniform sqrtf branch of the `tiny` corner).
 //
 // Roofline: HBM.  Only every step-th source row is touched; within such a row whole 128-byte lines arrive whenever
 // step * pixel_bytes is below the line size, so the floor is (selected rows at full width) + 4 or 8 bytes written per output

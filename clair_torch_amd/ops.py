@@ -876,6 +876,42 @@ def ingest_transform(stack: torch.Tensor, stages, layout: str = "nchw", out: Opt
 
 
 # ---- such a chain and the linearization in one pass ----------------------------------------------------------------------
+def _linearize_ingest(strided, frames, step, stages, lut, interp, std, std_mode, std_value, want_std, tile, layout, out, consts):
+    """The two fronts below: ct_linearize_ingest_strided with ``strided``, else ct_linearize_ingest / ct_linearize_ingest_data."""
+    _check_ingest_stack(frames, layout)
+    if strided and (isinstance(step, bool) or not isinstance(step, int) or step < 1):
+        raise ValueError(f"step must be an int >= 1, got {step!r}")
+    src_shape = ingest_shape(tuple(frames.shape), layout)
+    f, c = src_shape[:2]
+    shape = downscaled_shape(src_shape, step) if strided else src_shape
+    dev = frames.device
+    arr, n_stages = _ingest_stages(stages, c, data=consts is not None)
+    if consts is not None:
+        _check_frame_consts(consts, f, dev)
+    if std is not None:
+        std_mode, std = "explicit", _planar_std(std, shape, dev, "outputs")
+    if std_mode not in _STD:
+        raise ValueError(f"unknown std_mode {std_mode}")
+    icrf, lut_keep = _icrf_struct(lut, interp, c)
+    geom = _ingest_geometry(src_shape, tile, layout)
+    lin, std_out = _lin_std_out(out, shape, dev, want_std, lin_required=True)
+    if frames.numel() == 0:
+        return lin, std_out
+    head = (_ptr(frames), _DTYPE[frames.dtype], f, ctypes.byref(geom))
+    tail = (arr, n_stages, _ptr(std), _STD[std_mode], float(std_value), ctypes.byref(icrf), _ptr(lin), _ptr(std_out))
+    with torch.cuda.device(dev):
+        if strided:
+            name, rc = "ct_linearize_ingest_strided", nv.load().ct_linearize_ingest_strided(*head, min(step, 0x7fffffff), *tail,
+                                                                                           _ptr(consts), _stream(dev))
+        elif consts is None:
+            name, rc = "ct_linearize_ingest", nv.load().ct_linearize_ingest(*head, *tail, _stream(dev))
+        else:
+            name, rc = "ct_linearize_ingest_data", nv.load().ct_linearize_ingest_data(*head, *tail, _ptr(consts), _stream(dev))
+    nv.check(rc, name)
+    del lut_keep
+    return lin, std_out
+
+
 def linearize_ingest_frames(frames: torch.Tensor, stages, lut: Optional[torch.Tensor], interp: Optional[str] = "linear", *,
                             std: Optional[torch.Tensor] = None, std_mode: str = "none", std_value: float = 0.0,
                             want_std: bool = True, tile: Optional[TileGeometry] = None, layout: str = "nchw", out=None,
@@ -892,34 +928,7 @@ def linearize_ingest_frames(frames: torch.Tensor, stages, lut: Optional[torch.Te
     ("affine_data", mul, add) -- a data-dependent Normalize with PER-FRAME bounds, whose sub and div for frame f the kernel
     reads from ``consts[f, 0:2]`` when it runs: ``linearize_frames(ingest_transform(frames[f:f+1], stages, layout,
     consts=consts[f]), ...)`` bit for bit.  No zero-range check happens here (``consts[f, 1] == 0``)."""
-    _check_ingest_stack(frames, layout)
-    shape = ingest_shape(tuple(frames.shape), layout)
-    f, c, h, w = shape
-    dev = frames.device
-    arr, n_stages = _ingest_stages(stages, c, data=consts is not None)
-    if consts is not None:
-        _check_frame_consts(consts, f, dev)
-    if std is not None:
-        std_mode, std = "explicit", _planar_std(std, shape, dev, "outputs")
-    if std_mode not in _STD:
-        raise ValueError(f"unknown std_mode {std_mode}")
-    icrf, lut_keep = _icrf_struct(lut, interp, c)
-    geom = _ingest_geometry(shape, tile, layout)
-    lin, std_out = _lin_std_out(out, shape, dev, want_std, lin_required=True)
-    if frames.numel() == 0:
-        return lin, std_out
-    with torch.cuda.device(dev):
-        if consts is None:
-            rc = nv.load().ct_linearize_ingest(_ptr(frames), _DTYPE[frames.dtype], f, ctypes.byref(geom), arr, n_stages, _ptr(std),
-                                               _STD[std_mode], float(std_value), ctypes.byref(icrf), _ptr(lin), _ptr(std_out),
-                                               _stream(dev))
-        else:
-            rc = nv.load().ct_linearize_ingest_data(_ptr(frames), _DTYPE[frames.dtype], f, ctypes.byref(geom), arr, n_stages,
-                                                    _ptr(std), _STD[std_mode], float(std_value), ctypes.byref(icrf), _ptr(lin),
-                                                    _ptr(std_out), _ptr(consts), _stream(dev))
-    nv.check(rc, "ct_linearize_ingest" if consts is None else "ct_linearize_ingest_data")
-    del lut_keep
-    return lin, std_out
+    return _linearize_ingest(False, frames, 1, stages, lut, interp, std, std_mode, std_value, want_std, tile, layout, out, consts)
 
 
 def linearize_ingest_frames_strided(frames: torch.Tensor, step: int, stages, lut: Optional[torch.Tensor],
@@ -935,32 +944,7 @@ def linearize_ingest_frames_strided(frames: torch.Tensor, step: int, stages, lut
     planar (F,C,ho,wo) -- already of the output shape, because gpu_transforms are applied to the value images only.
     ``out`` = (lin, std | None): contiguous float32 (F,C,ho,wo) device buffers.  ``tile``: with ``step == 1`` only (a row
     band behind a downscale is refused: the phase of the band is not carried)."""
-    _check_ingest_stack(frames, layout)
-    if isinstance(step, bool) or not isinstance(step, int) or step < 1:
-        raise ValueError(f"step must be an int >= 1, got {step!r}")
-    src_shape = ingest_shape(tuple(frames.shape), layout)
-    f, c = src_shape[:2]
-    shape = downscaled_shape(src_shape, step)
-    dev = frames.device
-    arr, n_stages = _ingest_stages(stages, c, data=consts is not None)
-    if consts is not None:
-        _check_frame_consts(consts, f, dev)
-    if std is not None:
-        std_mode, std = "explicit", _planar_std(std, shape, dev, "outputs")
-    if std_mode not in _STD:
-        raise ValueError(f"unknown std_mode {std_mode}")
-    icrf, lut_keep = _icrf_struct(lut, interp, c)
-    geom = _ingest_geometry(src_shape, tile, layout)
-    lin, std_out = _lin_std_out(out, shape, dev, want_std, lin_required=True)
-    if frames.numel() == 0:
-        return lin, std_out
-    with torch.cuda.device(dev):
-        rc = nv.load().ct_linearize_ingest_strided(_ptr(frames), _DTYPE[frames.dtype], f, ctypes.byref(geom), min(step, 0x7fffffff), arr,
-                                                   n_stages, _ptr(std), _STD[std_mode], float(std_value), ctypes.byref(icrf), _ptr(lin),
-                                                   _ptr(std_out), _ptr(consts), _stream(dev))
-    nv.check(rc, "ct_linearize_ingest_strided")
-    del lut_keep
-    return lin, std_out
+    return _linearize_ingest(True, frames, step, stages, lut, interp, std, std_mode, std_value, want_std, tile, layout, out, consts)
 
 
 # ---- such a chain and one batch of the HDR merge in one pass ---------------------------------------------------------------
