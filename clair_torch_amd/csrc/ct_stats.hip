@@ -14,22 +14,9 @@
 // Interleaved (F, H, W, C) frames as OpenCV decodes them (IL instantiations): a thread still owns V consecutive MEMORY
 // elements -- the frame loads stay packets -- and only the LUT row and the position in the planar (C, H, W) state follow
 // from TileMap::planar_index; the state is touched element by element, once per batch of frames.
-#include "ct_args.hpp"
-#include "ct_stats_merge.hpp"
+#include "ct_stats_kernel.hpp"
 
 namespace ct {
-
-struct StatsArgs {
-    const void *frames;
-    const float *lut;
-    float *mean_state, *m2_state;
-    int64_t image_stride;
-    uint32_t q_begin, q_count;
-    TileMap tile;
-    int32_t batch, channels, n_points;
-    NormConst norm;
-    float count_before;  // W_A (number of frames merged so far)
-};
 
 template <typename T, int V, int INTERP, bool IL>
 __global__ __launch_bounds__(kBlock) void video_stats_kernel(const StatsArgs a)
@@ -174,45 +161,33 @@ static int stats_dispatch(const StatsArgs &a, int interp, hipStream_t s)
     return CT_ERR_INVALID_ARGUMENT;
 }
 
+
 template <typename T>
-static int stats_typed(StatsArgs a, uint32_t Q, int interp, hipStream_t s)
+static int stats_typed(const StatsArgs &a, uint32_t Q, int interp, hipStream_t s)
 {
-    constexpr int V = 4;  // 4 elements per thread: 32 frames x 4 values fit the register file
-    const bool vec_ok = aligned(a.frames, sizeof(T) * V) && (a.image_stride % V) == 0 && aligned(a.mean_state, 4 * V) &&
-                        aligned(a.m2_state, 4 * V);
-    const uint32_t q_vec = vec_ok ? (Q / V) * V : 0;
-    int rc = CT_OK;
-    if (q_vec) {
-        a.q_begin = 0;
-        a.q_count = q_vec;
-        rc = stats_dispatch<T, V>(a, interp, s);
-        if (rc != CT_OK) return rc;
-    }
-    if (q_vec < Q) {
-        a.q_begin = q_vec;
-        a.q_count = Q - q_vec;
-        rc = stats_dispatch<T, 1>(a, interp, s);
-    }
-    return rc;
+    return stats_split(a, Q, stats_frames_vec_ok<T>(a.frames, a.image_stride),
+                       [&](const StatsArgs &part, auto V) { return stats_dispatch<T, decltype(V)::value>(part, interp, s); });
 }
 
 }  // namespace ct
 
 extern "C" int ct_norm_constants(float max_code, float *hi, float *lo);
 
-extern "C" int ct_video_stats_batch(const void *frames_dev, int32_t dtype, float max_code, int32_t batch,
-                                    const ct_geometry *geom, const ct_icrf *icrf, float frames_before,
-                                    float *mean_state_dev, float *m2_state_dev, void *stream)
+namespace ct {
+
+// Everything ct_video_stats_batch refuses, in its order, and its argument block.  in_list: the batch is one of
+// ct_video_stats_batches', where a size of 0 is a batch to skip (nothing of it is dereferenced, so neither its frames nor the
+// state need to be there) and the LUT is tested against the LDS here, before any launch of the call.
+static int stats_prepare(const void *frames_dev, int32_t dtype, float max_code, int32_t batch, const ct_geometry *geom,
+                         const ct_icrf *icrf, float frames_before, float *mean_state_dev, float *m2_state_dev, bool in_list, StatsArgs &a)
 {
-    using namespace ct;
-    if (!frames_dev || !geom || !icrf || !mean_state_dev || !m2_state_dev || batch <= 0 || frames_before < 0.0f)
+    const bool skipped = in_list && batch == 0;
+    if (!geom || !icrf || (!skipped && (!frames_dev || !mean_state_dev || !m2_state_dev || batch <= 0)) || frames_before < 0.0f)
         return CT_ERR_INVALID_ARGUMENT;
     if (!shape_positive(geom) || !band_fits(geom) || !icrf_ok(icrf)) return CT_ERR_INVALID_ARGUMENT;
     if (!global_below_2_31(geom)) return CT_ERR_TOO_LARGE;
     if (!stride_holds_image(geom) || !layout_ok(geom)) return CT_ERR_INVALID_ARGUMENT;
-    const int interp = icrf->interp;
-    const int64_t Ql = local_elements(geom);
-    StatsArgs a{};
+    a = StatsArgs{};
     a.frames = frames_dev;
     a.lut = icrf->lut_dev;
     a.mean_state = mean_state_dev;
@@ -223,15 +198,80 @@ extern "C" int ct_video_stats_batch(const void *frames_dev, int32_t dtype, float
     a.channels = geom->channels;
     a.n_points = icrf_points(icrf);
     a.count_before = frames_before;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case CT_DTYPE_U8:
-            if (ct_norm_constants(max_code, &a.norm.hi, &a.norm.lo) != CT_OK) return CT_ERR_UNSUPPORTED;
-            return stats_typed<uint8_t>(a, (uint32_t)Ql, interp, s);
-        case CT_DTYPE_U16:
-            if (ct_norm_constants(max_code, &a.norm.hi, &a.norm.lo) != CT_OK) return CT_ERR_UNSUPPORTED;
-            return stats_typed<uint16_t>(a, (uint32_t)Ql, interp, s);
-        case CT_DTYPE_F32: return stats_typed<float>(a, (uint32_t)Ql, interp, s);
+    if (dtype == CT_DTYPE_U8 || dtype == CT_DTYPE_U16) {
+        if (ct_norm_constants(max_code, &a.norm.hi, &a.norm.lo) != CT_OK) return CT_ERR_UNSUPPORTED;
+    } else if (dtype != CT_DTYPE_F32) {
+        return CT_ERR_UNSUPPORTED;
     }
-    return CT_ERR_UNSUPPORTED;
+    if (in_list && lut_lds_bytes(icrf->interp, a.channels, a.n_points) > kLdsBudget) return CT_ERR_TOO_LARGE;
+    return CT_OK;
+}
+
+static int stats_run(const StatsArgs &a, int32_t dtype, const ct_geometry *geom, int interp, hipStream_t s)
+{
+    const uint32_t Q = (uint32_t)local_elements(geom);
+    switch (dtype) {
+        case CT_DTYPE_U8: return stats_typed<uint8_t>(a, Q, interp, s);
+        case CT_DTYPE_U16: return stats_typed<uint16_t>(a, Q, interp, s);
+    }
+    return stats_typed<float>(a, Q, interp, s);
+}
+
+}  // namespace ct
+
+extern "C" int ct_video_stats_batch(const void *frames_dev, int32_t dtype, float max_code, int32_t batch,
+                                    const ct_geometry *geom, const ct_icrf *icrf, float frames_before,
+                                    float *mean_state_dev, float *m2_state_dev, void *stream)
+{
+    using namespace ct;
+    StatsArgs a;
+    if (const int rc = stats_prepare(frames_dev, dtype, max_code, batch, geom, icrf, frames_before, mean_state_dev, m2_state_dev, false, a);
+        rc != CT_OK)
+        return rc;
+    return stats_run(a, dtype, geom, icrf->interp, static_cast<hipStream_t>(stream));
+}
+
+// Several consecutive batches: ONE launch of the MULTI kernels (ct_stats_multi.hip) where every batch fits a register-cached
+// walk; otherwise one launch per batch with the state in memory, exactly what the caller would have done.
+extern "C" int ct_video_stats_batches(const void *const *frames_devs, const int32_t *batch_sizes, int32_t n_batches, int32_t dtype,
+                                      float max_code, const ct_geometry *geom, const ct_icrf *icrf, float frames_before,
+                                      float *mean_state_dev, float *m2_state_dev, uint32_t flags, void *stream)
+{
+    using namespace ct;
+    if (n_batches < 1 || n_batches > kMaxStatsBatches || !frames_devs || !batch_sizes) return CT_ERR_INVALID_ARGUMENT;
+    if (n_batches == 1 && batch_sizes[0] != 0)
+        return ct_video_stats_batch(frames_devs[0], dtype, max_code, batch_sizes[0], geom, icrf, frames_before, mean_state_dev,
+                                    m2_state_dev, stream);
+    // every batch as the single-batch entry point would judge it, with the frame count its caller would pass; nothing has
+    // touched the device when one of them is refused
+    StatsBatches mb = {};
+    StatsArgs a, first = {};
+    int64_t before = 0;
+    int n = 0;
+    for (int b = 0; b < n_batches; ++b) {
+        // the float of the exact count (frames_before is one already; a sum of integers below 2^53 is exact in double)
+        const float count = before == 0 ? frames_before : (float)((double)frames_before + (double)before);
+        if (const int rc = stats_prepare(frames_devs[b], dtype, max_code, batch_sizes[b], geom, icrf, count, mean_state_dev, m2_state_dev, true, a);
+            rc != CT_OK)
+            return rc;
+        if (batch_sizes[b] == 0) continue;
+        if (n == 0) first = a;
+        mb.frames[n] = frames_devs[b];
+        mb.batch[n] = batch_sizes[b];
+        mb.count_before[n] = count;
+        mb.batch_max = batch_sizes[b] > mb.batch_max ? batch_sizes[b] : mb.batch_max;
+        before += batch_sizes[b];
+        ++n;
+    }
+    mb.n_batches = n;
+    if (n == 0) return CT_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n >= 2 && mb.batch_max <= kStatsCachedMax) return stats_multi(first, mb, dtype, (uint32_t)local_elements(geom), icrf->interp, s);
+    if (n >= 2 && (flags & CT_STATS_REQUIRE_ONE_LAUNCH)) return CT_ERR_UNSUPPORTED;  // (tests: make the route explicit)
+    for (int b = 0; b < n; ++b) {
+        const int rc = ct_video_stats_batch(mb.frames[b], dtype, max_code, mb.batch[b], geom, icrf, mb.count_before[b], mean_state_dev,
+                                            m2_state_dev, stream);
+        if (rc != CT_OK) return rc;
+    }
+    return CT_OK;
 }

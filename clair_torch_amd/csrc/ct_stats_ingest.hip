@@ -33,45 +33,10 @@
 // Every load is that of a code of the thread's own elements (pixels) in one of the B frames, every store lies in the
 // thread's own elements of mean_state and m2_state.  The consts of a CT_INGEST_AFFINE_DATA stage are read once per thread,
 // before anything is stored.  No atomics, no LDS traffic besides the LUT, the frames are read only.
-#include "ct_args.hpp"
 #include "ct_ingest_stages.hpp"
-#include "ct_stats_merge.hpp"
+#include "ct_stats_kernel.hpp"
 
 namespace ct {
-
-struct StatsIngestArgs {
-    const void *frames;
-    const float *consts;    // sub, div of a CT_INGEST_AFFINE_DATA stage (ct_ingest_extrema), or NULL
-    const float *lut;
-    float *mean_state, *m2_state;
-    int64_t image_stride;   // source elements between consecutive frames
-    uint32_t plane;         // H_tile * W
-    uint32_t plane_global;  // H_global * W: global flat index of (c, local p) = c * plane_global + base + p
-    uint32_t base;          // row_offset * W
-    int32_t batch, channels, n_points;
-    uint32_t reversed;      // PACKED3: memory channel cm feeds plane 2 - cm (BGR)
-    uint32_t by_channel;    // some clamp holds different pairs for different channels (then C <= CT_INGEST_MAX_CHANNELS)
-    uint32_t state_lead;    // PLANAR: (mean_state address / 4) % 4, or kSiNoPackets: every element goes through G = 1
-    float count_before;     // W_A (number of frames merged so far)
-    uint32_t n_stages;
-    ct_ingest_stage stage[CT_INGEST_MAX_STAGES];
-};
-
-constexpr int kSiGroup = 4;  // PLANAR: elements per thread of the vector body, one 16-byte state packet
-constexpr uint32_t kSiNoPackets = 4;
-
-template <typename T, int N>
-struct SiRaw {
-    T v[N];
-};
-
-// elements in front of a plane's first aligned state packet, and the end of its last whole one
-__device__ __forceinline__ void si_body(const StatsIngestArgs &a, uint32_t c, uint32_t &head, uint32_t &body_end)
-{
-    head = a.state_lead == kSiNoPackets ? a.plane : (0u - (a.state_lead + c * a.plane)) & (uint32_t)(kSiGroup - 1);
-    head = head < a.plane ? head : a.plane;
-    body_end = head + ((a.plane - head) & ~(uint32_t)(kSiGroup - 1));
-}
 
 // One thread: G consecutive elements of every plane it owns, the whole batch and the state.  (The walk stands in the kernel
 // itself and not in a device function of its own: a callee is unrolled before it is inlined, and the kernel would then meet
@@ -216,11 +181,12 @@ __global__ __launch_bounds__(kBlock) void video_stats_ingest_kernel(const StatsI
     }
 }
 
+
 template <typename T, bool PACKED, int G, int INTERP, bool DATA>
 static int si_launch(const StatsIngestArgs &a, uint32_t threads_x, hipStream_t s)
 {
     const size_t lds = lut_lds_bytes(INTERP, a.channels, a.n_points);
-    const dim3 grid((threads_x + kBlock - 1) / kBlock, PACKED ? 1u : (uint32_t)a.channels), block(kBlock);
+    const dim3 grid = si_grid(a, PACKED, threads_x), block(kBlock);
     if (a.batch <= 16)
         hipLaunchKernelGGL((video_stats_ingest_kernel<T, PACKED, G, INTERP, 16, DATA>), grid, block, lds, s, a);
     else if (a.batch <= 32)
@@ -230,29 +196,37 @@ static int si_launch(const StatsIngestArgs &a, uint32_t threads_x, hipStream_t s
     return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
 }
 
-template <typename T, int INTERP, bool DATA>
-static int si_layout(StatsIngestArgs a, bool packed, hipStream_t s)
-{
-    if (packed) return si_launch<T, true, 1, INTERP, DATA>(a, a.plane, s);
-    auto lead = [](const void *p) { return (uint32_t)((reinterpret_cast<uintptr_t>(p) / sizeof(float)) % kSiGroup); };
-    // packets only where mean and m2 are equally aligned (always, for two allocations); else element by element
-    const bool packets = lead(a.mean_state) == lead(a.m2_state) && a.plane >= (uint32_t)kSiGroup;
-    a.state_lead = packets ? lead(a.mean_state) : kSiNoPackets;
-    if (packets) {
-        const int rc = si_launch<T, false, kSiGroup, INTERP, DATA>(a, a.plane / kSiGroup, s);  // (a thread per possible packet)
-        if (rc != CT_OK) return rc;
-        if (a.state_lead == 0 && a.plane % kSiGroup == 0) return CT_OK;  // every plane is whole packets
-        return si_launch<T, false, 1, INTERP, DATA>(a, 2 * (kSiGroup - 1), s);
-    }
-    return si_launch<T, false, 1, INTERP, DATA>(a, a.plane, s);
-}
-
 template <typename T>
 static int si_dispatch(const StatsIngestArgs &a, bool packed, int interp, hipStream_t s)
 {
     return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
-        return a.consts ? si_layout<T, I, true>(a, packed, s) : si_layout<T, I, false>(a, packed, s);
+        constexpr int kI = decltype(I)::value;
+        return si_layout(a, packed, [&](const StatsIngestArgs &part, auto P, auto G, uint32_t threads_x) {
+            constexpr bool kP = decltype(P)::value;
+            constexpr int kG = decltype(G)::value;
+            return a.consts ? si_launch<T, kP, kG, kI, true>(part, threads_x, s) : si_launch<T, kP, kG, kI, false>(part, threads_x, s);
+        });
     });
+}
+
+// What ct_video_stats_ingest_batch refuses without looking at a pointer into device memory, in its order: geometry (an empty
+// plane allowed), the stack and the stage list of 8-bit / 16-bit codes, the model (check_code_ingest, which
+// ct_hdr_merge_ingest_batch shares), the count, the stride, the LDS and the grid.
+static int si_validate(int32_t dtype, int32_t batch, const ct_geometry *geom, const ct_ingest_stage *stages, int32_t n_stages,
+                       const float *consts_dev, const ct_icrf *icrf, float frames_before, bool &by_channel)
+{
+    if (const int rc = check_code_ingest(dtype, batch, geom, stages, n_stages, consts_dev, icrf, by_channel); rc != CT_OK) return rc;
+    if (!(frames_before >= 0.0f) || !stride_holds_image(geom)) return CT_ERR_INVALID_ARGUMENT;
+    if (lut_lds_bytes(icrf->interp, geom->channels, icrf->n_points) > kLdsBudget) return CT_ERR_TOO_LARGE;
+    if (geom->layout == CT_LAYOUT_NCHW && geom->channels > 65535) return CT_ERR_TOO_LARGE;  // a plane is a row of the grid
+    return CT_OK;
+}
+
+// the pointers of a batch that has something to do: present and aligned to their element
+static bool si_pointers_ok(const void *frames_dev, int32_t dtype, const float *mean_state_dev, const float *m2_state_dev)
+{
+    if (!frames_dev || !mean_state_dev || !m2_state_dev) return false;
+    return aligned(frames_dev, dtype == CT_DTYPE_U16 ? 2 : 1) && aligned(mean_state_dev, sizeof(float)) && aligned(m2_state_dev, sizeof(float));
 }
 
 }  // namespace ct
@@ -263,20 +237,10 @@ extern "C" int ct_video_stats_ingest_batch(const void *frames_dev, int32_t dtype
                                            void *stream)
 {
     using namespace ct;
-    // everything that needs no pointer into device memory first: geometry (an empty plane allowed), the stack and the stage
-    // list of 8-bit / 16-bit codes, the model (check_code_ingest, which ct_hdr_merge_ingest_batch shares)
     bool by_channel = false;
-    if (const int rc = check_code_ingest(dtype, batch, geom, stages, n_stages, consts_dev, icrf, by_channel); rc != CT_OK) return rc;
-    const int64_t plane = geom->h_tile * geom->width;
-    const int interp = icrf->interp;
-    if (!(frames_before >= 0.0f) || !stride_holds_image(geom)) return CT_ERR_INVALID_ARGUMENT;
-    if (lut_lds_bytes(interp, geom->channels, icrf->n_points) > kLdsBudget) return CT_ERR_TOO_LARGE;
-    const bool packed = geom->layout != CT_LAYOUT_NCHW;
-    if (!packed && geom->channels > 65535) return CT_ERR_TOO_LARGE;  // a plane is a row of the grid
-    if (batch == 0 || plane == 0) return CT_OK;
-    if (!frames_dev || !mean_state_dev || !m2_state_dev) return CT_ERR_INVALID_ARGUMENT;
-    if (!aligned(frames_dev, dtype == CT_DTYPE_U16 ? 2 : 1) || !aligned(mean_state_dev, sizeof(float)) || !aligned(m2_state_dev, sizeof(float)))
-        return CT_ERR_INVALID_ARGUMENT;
+    if (const int rc = si_validate(dtype, batch, geom, stages, n_stages, consts_dev, icrf, frames_before, by_channel); rc != CT_OK) return rc;
+    if (batch == 0 || geom->h_tile * geom->width == 0) return CT_OK;
+    if (!si_pointers_ok(frames_dev, dtype, mean_state_dev, m2_state_dev)) return CT_ERR_INVALID_ARGUMENT;
     StatsIngestArgs a = {};
     a.frames = frames_dev;
     a.consts = consts_dev;
@@ -286,6 +250,65 @@ extern "C" int ct_video_stats_ingest_batch(const void *frames_dev, int32_t dtype
     fill_ingest_args(a, geom, icrf_points(icrf), by_channel, stages, n_stages);
     a.batch = batch;
     a.count_before = frames_before;
+    const bool packed = geom->layout != CT_LAYOUT_NCHW;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == CT_DTYPE_U8 ? si_dispatch<uint8_t>(a, packed, interp, s) : si_dispatch<uint16_t>(a, packed, interp, s);
+    return dtype == CT_DTYPE_U8 ? si_dispatch<uint8_t>(a, packed, icrf->interp, s) : si_dispatch<uint16_t>(a, packed, icrf->interp, s);
+}
+
+// Several consecutive batches behind one chain: ONE launch of the MULTI kernels (ct_stats_ingest_multi.hip) where every batch
+// fits a register-cached walk and the batches agree on having constants; otherwise one launch per batch with the state in
+// memory, exactly what the caller would have done.
+extern "C" int ct_video_stats_ingest_batches(const void *const *frames_devs, const int32_t *batch_sizes, int32_t n_batches,
+                                             int32_t dtype, const ct_geometry *geom, const ct_ingest_stage *stages,
+                                             int32_t n_stages, const float *const *consts_devs, const ct_icrf *icrf,
+                                             float frames_before, float *mean_state_dev, float *m2_state_dev, uint32_t flags,
+                                             void *stream)
+{
+    using namespace ct;
+    if (n_batches < 1 || n_batches > kMaxStatsBatches || !frames_devs || !batch_sizes) return CT_ERR_INVALID_ARGUMENT;
+    if (n_batches == 1)
+        return ct_video_stats_ingest_batch(frames_devs[0], dtype, batch_sizes[0], geom, stages, n_stages, consts_devs ? consts_devs[0] : nullptr,
+                                           icrf, frames_before, mean_state_dev, m2_state_dev, stream);
+    // every batch as the single-batch entry point would judge it, with the frame count its caller would pass; nothing has
+    // touched the device when one of them is refused
+    StatsBatches mb = {};
+    bool by_channel = false;
+    int64_t before = 0;
+    int n = 0, n_consts = 0;
+    for (int b = 0; b < n_batches; ++b) {
+        // the float of the exact count (frames_before is one already; a sum of integers below 2^53 is exact in double)
+        const float count = before == 0 ? frames_before : (float)((double)frames_before + (double)before);
+        const float *consts = consts_devs ? consts_devs[b] : nullptr;
+        if (const int rc = si_validate(dtype, batch_sizes[b], geom, stages, n_stages, consts, icrf, count, by_channel); rc != CT_OK) return rc;
+        if (batch_sizes[b] == 0) continue;
+        mb.frames[n] = frames_devs[b];
+        mb.consts[n] = consts;
+        mb.batch[n] = batch_sizes[b];
+        mb.count_before[n] = count;
+        mb.batch_max = batch_sizes[b] > mb.batch_max ? batch_sizes[b] : mb.batch_max;
+        n_consts += consts ? 1 : 0;
+        before += batch_sizes[b];
+        ++n;
+    }
+    mb.n_batches = n;
+    if (n == 0 || geom->h_tile * geom->width == 0) return CT_OK;
+    for (int b = 0; b < n; ++b)
+        if (!si_pointers_ok(mb.frames[b], dtype, mean_state_dev, m2_state_dev)) return CT_ERR_INVALID_ARGUMENT;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n >= 2 && mb.batch_max <= kStatsCachedMax && (n_consts == 0 || n_consts == n)) {
+        StatsIngestArgs a = {};
+        a.consts = mb.consts[0];  // (only whether there are any: the kernel reads each batch's own)
+        a.lut = icrf->lut_dev;
+        a.mean_state = mean_state_dev;
+        a.m2_state = m2_state_dev;
+        fill_ingest_args(a, geom, icrf_points(icrf), by_channel, stages, n_stages);
+        return stats_ingest_multi(a, mb, dtype, geom->layout != CT_LAYOUT_NCHW, icrf->interp, s);
+    }
+    if (n >= 2 && (flags & CT_STATS_REQUIRE_ONE_LAUNCH)) return CT_ERR_UNSUPPORTED;  // (tests: make the route explicit)
+    for (int b = 0; b < n; ++b) {
+        const int rc = ct_video_stats_ingest_batch(mb.frames[b], dtype, mb.batch[b], geom, stages, n_stages, mb.consts[b], icrf,
+                                                   mb.count_before[b], mean_state_dev, m2_state_dev, stream);
+        if (rc != CT_OK) return rc;
+    }
+    return CT_OK;
 }

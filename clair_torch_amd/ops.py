@@ -1193,29 +1193,122 @@ def ingest_transform_data(stack: torch.Tensor, stages, layout: str = "nchw", min
 
 
 # ---- streaming video statistics -----------------------------------------------------------------------------------
+MAX_STATS_BATCHES = 16  # batches one ct_video_stats_batches call takes (the kernel's argument block holds 16 pointers)
+
+
+def _stats_batch_list(frames_list, consts=None):
+    """The batches of one ``video_stats_*_batches`` call: a non-empty list of at most MAX_STATS_BATCHES tensors."""
+    if not isinstance(frames_list, (list, tuple)) or len(frames_list) == 0 or (consts is not None and len(consts) != len(frames_list)):
+        raise ValueError("frames / consts must be non-empty lists of equal length")
+    if len(frames_list) > MAX_STATS_BATCHES:
+        raise ValueError(f"at most {MAX_STATS_BATCHES} batches per call")
+    return list(frames_list)
+
+
+def _same_batches(frames_list):
+    f0 = frames_list[0]
+    for t in frames_list:
+        if t.dtype != f0.dtype or t.shape[1:] != f0.shape[1:] or t.device != f0.device:
+            raise ValueError("all batches of one call must share dtype, image shape and device")
+
+
+def _batch_arrays(frames_list, consts=None):
+    """The HOST arrays of a ``*_batches`` entry point: frame pointers, batch sizes, and the constants' pointers or None."""
+    k = len(frames_list)
+    ptr_arr = (ctypes.c_void_p * k)(*[t.data_ptr() for t in frames_list])
+    size_arr = (ctypes.c_int32 * k)(*[int(t.shape[0]) for t in frames_list])
+    consts_arr = None if consts is None else (ctypes.c_void_p * k)(*[None if t is None else t.data_ptr() for t in consts])
+    return ptr_arr, size_arr, consts_arr
+
+
+def _video_stats(frames_list, mean_state, m2_state, frames_before, lut, interp, max_code, tile, layout, flags=None):
+    """``video_stats_batch`` (``flags`` None: one batch, ct_video_stats_batch) and ``video_stats_batches``."""
+    for t in frames_list:
+        _check_stack(t, "frames")
+    _same_batches(frames_list)
+    f0 = frames_list[0]
+    c, h, w = _chw(f0, layout)
+    dev = f0.device
+    frames_list = [t.contiguous() for t in frames_list]
+    max_code = _default_max_code(f0, max_code)
+    _check_stats_state(mean_state, m2_state, (c, h, w))
+    icrf, lut_keep = _icrf_struct(lut, interp, c)
+    geom = _geometry(frames_list[0], tile, layout)
+    lib = nv.load()
+    with torch.cuda.device(dev):
+        if flags is None:
+            rc = lib.ct_video_stats_batch(_ptr(frames_list[0]), _DTYPE[f0.dtype], float(max_code or 1.0), f0.shape[0],
+                                          ctypes.byref(geom), ctypes.byref(icrf), float(frames_before),
+                                          _ptr(mean_state), _ptr(m2_state), _stream(dev))
+        else:
+            geom.image_stride = c * h * w  # contiguous batches: one stride for all (that of a 1-frame batch is arbitrary)
+            ptr_arr, size_arr, _ = _batch_arrays(frames_list)
+            rc = lib.ct_video_stats_batches(ptr_arr, size_arr, len(frames_list), _DTYPE[f0.dtype], float(max_code or 1.0),
+                                            ctypes.byref(geom), ctypes.byref(icrf), float(frames_before), _ptr(mean_state),
+                                            _ptr(m2_state), flags, _stream(dev))
+    nv.check(rc, "ct_video_stats_batch" if flags is None else "ct_video_stats_batches")
+    del lut_keep
+
+
 def video_stats_batch(frames: torch.Tensor, mean_state: torch.Tensor, m2_state: torch.Tensor, frames_before: int, *,
                       lut: Optional[torch.Tensor] = None, interp: Optional[str] = None,
                       max_code: Optional[float] = None, tile: Optional[TileGeometry] = None, layout: str = "nchw"):
     """ct_video_stats_batch: merge one batch of frames into the running (mean, m2) float32 state in place.
     ``layout`` "nhwc" / "nhwc_bgr": frames are (F,H,W,C) as OpenCV decodes them; the state stays planar (C,H,W)."""
-    _check_stack(frames, "frames")
-    b = frames.shape[0]
-    c, h, w = _chw(frames, layout)
-    dev = frames.device
-    frames = frames.contiguous()
-    max_code = _default_max_code(frames, max_code)
-    _check_stats_state(mean_state, m2_state, (c, h, w))
-    icrf, lut_keep = _icrf_struct(lut, interp, c)
-    geom = _geometry(frames, tile, layout)
-    with torch.cuda.device(dev):
-        rc = nv.load().ct_video_stats_batch(_ptr(frames), _DTYPE[frames.dtype], float(max_code or 1.0), b,
-                                            ctypes.byref(geom), ctypes.byref(icrf), float(frames_before),
-                                            _ptr(mean_state), _ptr(m2_state), _stream(dev))
-    nv.check(rc, "ct_video_stats_batch")
-    del lut_keep
+    _video_stats([frames], mean_state, m2_state, frames_before, lut, interp, max_code, tile, layout)
+
+
+def video_stats_batches(frames_list, mean_state: torch.Tensor, m2_state: torch.Tensor, frames_before: int, *,
+                        lut: Optional[torch.Tensor] = None, interp: Optional[str] = None, max_code: Optional[float] = None,
+                        tile: Optional[TileGeometry] = None, layout: str = "nchw", require_one_launch: bool = False):
+    """Several CONSECUTIVE batches of one video in one call (ct_video_stats_batches): the same state, bit for bit, as
+    ``video_stats_batch`` on each of them in turn with the frame count carried along -- but where every batch has at most 32
+    frames one launch walks them all with (mean, m2) in registers in between (no state traffic between the batches).
+
+    ``frames_list``: list of at most MAX_STATS_BATCHES device stacks of one dtype, image shape and device, each as
+    ``video_stats_batch`` takes it (separate allocations are fine; an empty batch is skipped); ``frames_before``: the frames
+    merged before the first of them.  ``require_one_launch`` (tests): raise instead of falling back to one launch per batch
+    (a batch of more than 32 frames).  Everything else as in ``video_stats_batch``."""
+    _video_stats(_stats_batch_list(frames_list), mean_state, m2_state, frames_before, lut, interp, max_code, tile, layout,
+                 nv.STATS_REQUIRE_ONE_LAUNCH if require_one_launch else 0)
 
 
 # ---- a gpu_transforms chain and the streaming video statistics in one pass ------------------------------------------------
+def _video_stats_ingest(front, frames_list, stages, mean_state, m2_state, frames_before, lut, interp, tile, layout, consts, flags=None):
+    """``video_stats_ingest_batch`` (``flags`` None: one batch, ct_video_stats_ingest_batch) and ``video_stats_ingest_batches``;
+    ``consts``: a list like ``frames_list``, or None."""
+    for t in frames_list:
+        _check_ingest_stack(t, layout, codes_only=f"{front} takes uint8 / uint16 codes (float32 pixels: "
+                                                  f"ingest_transform + {front.replace('_ingest', '')})")
+    _same_batches(frames_list)
+    f0 = frames_list[0]
+    shape = ingest_shape(tuple(f0.shape), layout)
+    _, c, h, w = shape
+    dev = f0.device
+    has_consts = consts is not None and any(t is not None for t in consts)
+    arr, n_stages = _ingest_stages(stages, c, data=has_consts)
+    if consts is not None:
+        for t in consts:
+            if t is not None:
+                _check_consts(t, dev)
+    _check_stats_state(mean_state, m2_state, (c, h, w), dev)
+    icrf, lut_keep = _icrf_struct(lut, interp, c)
+    geom = _ingest_geometry(shape, tile, layout)
+    lib = nv.load()
+    with torch.cuda.device(dev):
+        if flags is None:
+            rc = lib.ct_video_stats_ingest_batch(_ptr(f0), _DTYPE[f0.dtype], shape[0], ctypes.byref(geom), arr, n_stages,
+                                                 _ptr(consts[0]) if consts is not None else None, ctypes.byref(icrf),
+                                                 float(frames_before), _ptr(mean_state), _ptr(m2_state), _stream(dev))
+        else:
+            ptr_arr, size_arr, consts_arr = _batch_arrays(frames_list, consts)
+            rc = lib.ct_video_stats_ingest_batches(ptr_arr, size_arr, len(frames_list), _DTYPE[f0.dtype], ctypes.byref(geom), arr,
+                                                   n_stages, consts_arr, ctypes.byref(icrf), float(frames_before),
+                                                   _ptr(mean_state), _ptr(m2_state), flags, _stream(dev))
+    nv.check(rc, "ct_video_stats_ingest_batch" if flags is None else "ct_video_stats_ingest_batches")
+    del lut_keep
+
+
 def video_stats_ingest_batch(frames: torch.Tensor, stages, mean_state: torch.Tensor, m2_state: torch.Tensor, frames_before: int, *,
                              lut: Optional[torch.Tensor] = None, interp: Optional[str] = None,
                              tile: Optional[TileGeometry] = None, layout: str = "nchw", consts: Optional[torch.Tensor] = None):
@@ -1227,23 +1320,27 @@ def video_stats_ingest_batch(frames: torch.Tensor, stages, mean_state: torch.Ten
     ``ingest_extrema`` returned) one of them may be ("affine_data", mul, add).  ``mean_state``, ``m2_state``: contiguous
     float32 (C,H,W), planar whatever the layout of the frames (``ingest_shape(frames.shape, layout)[1:]``).
     ``frames_before``, ``lut``, ``interp``, ``tile``: as in ``video_stats_batch``."""
-    _check_ingest_stack(frames, layout, codes_only="video_stats_ingest_batch takes uint8 / uint16 codes (float32 pixels: "
-                                                   "ingest_transform + video_stats_batch)")
-    shape = ingest_shape(tuple(frames.shape), layout)
-    b, c, h, w = shape
-    dev = frames.device
-    arr, n_stages = _ingest_stages(stages, c, data=consts is not None)
-    if consts is not None:
-        _check_consts(consts, dev)
-    _check_stats_state(mean_state, m2_state, (c, h, w), dev)
-    icrf, lut_keep = _icrf_struct(lut, interp, c)
-    geom = _ingest_geometry(shape, tile, layout)
-    with torch.cuda.device(dev):
-        rc = nv.load().ct_video_stats_ingest_batch(_ptr(frames), _DTYPE[frames.dtype], b, ctypes.byref(geom), arr, n_stages,
-                                                   _ptr(consts), ctypes.byref(icrf), float(frames_before), _ptr(mean_state),
-                                                   _ptr(m2_state), _stream(dev))
-    nv.check(rc, "ct_video_stats_ingest_batch")
-    del lut_keep
+    _video_stats_ingest("video_stats_ingest_batch", [frames], stages, mean_state, m2_state, frames_before, lut, interp, tile, layout,
+                        None if consts is None else [consts])
+
+
+def video_stats_ingest_batches(frames_list, stages, mean_state: torch.Tensor, m2_state: torch.Tensor, frames_before: int, *,
+                               lut: Optional[torch.Tensor] = None, interp: Optional[str] = None,
+                               tile: Optional[TileGeometry] = None, layout: str = "nchw", consts=None,
+                               require_one_launch: bool = False):
+    """Several CONSECUTIVE batches of one video behind one chain in one call (ct_video_stats_ingest_batches): the same state,
+    bit for bit, as ``video_stats_ingest_batch`` on each of them in turn with the frame count carried along -- but where every
+    batch has at most 32 frames one launch walks them all with (mean, m2) in registers in between.
+
+    ``frames_list``: list of at most MAX_STATS_BATCHES uint8 / uint16 device stacks of one dtype, image shape and device, each
+    as ``video_stats_ingest_batch`` takes it (separate allocations are fine; an empty batch is skipped); ``consts``: list of
+    the tensors ``ingest_extrema`` returned for each batch -- every batch has its own data-dependent Normalize constants --
+    or None; a list may hold None for a batch without constants.  ``require_one_launch`` (tests): raise instead of falling
+    back to one launch per batch (a batch of more than 32 frames; batches with and without constants mixed).  Everything
+    else as in ``video_stats_ingest_batch``."""
+    _video_stats_ingest("video_stats_ingest_batches", _stats_batch_list(frames_list, consts), stages, mean_state, m2_state,
+                        frames_before, lut, interp, tile, layout, consts,
+                        nv.STATS_REQUIRE_ONE_LAUNCH if require_one_launch else 0)
 
 
 # ---- a gpu_transforms chain and the exposure-pair residual in one pass -------------------------------------------------------

@@ -76,6 +76,10 @@ extern "C" {
                                         back, common/general_functions.py:338-358) -- and the merge stores dense packets
                                         without regrouping.  Use the same flag on every batch of a merge. */
 
+/* ct_video_stats_batches, ct_video_stats_ingest_batches */
+#define CT_STATS_MAX_BATCHES 16
+#define CT_STATS_REQUIRE_ONE_LAUNCH 1u /* CT_ERR_UNSUPPORTED instead of one launch per batch */
+
 /* Memory layout of one image of a stack.  Outputs and state are always planar (C, H, W) like the reference's tensors.
  * NHWC = the interleaved layout OpenCV decodes to (clair_torch/common/data_io.py:125-154); NHWC_BGR additionally
  * reverses the channel order on the fly, i.e. folds cv_to_torch (clair_torch/common/general_functions.py:315-335)
@@ -582,6 +586,47 @@ int ct_video_stats_ingest_batch(const void *frames_dev, int32_t dtype, int32_t b
                                 const ct_ingest_stage *stages, int32_t n_stages, const float *consts_dev,
                                 const ct_icrf *icrf, float frames_before, float *mean_state_dev, float *m2_state_dev,
                                 void *stream);
+
+/*
+ * ct_video_stats_batches / ct_video_stats_ingest_batches -- n_batches consecutive batches of one video in one call: exactly
+ * ct_video_stats_batch / ct_video_stats_ingest_batch applied to batch 0 .. n_batches - 1 in turn, bit for bit in mean_state
+ * and m2_state -- but where it can, ONE launch walks all of them with (mean, m2) in registers in between: the state arrays are
+ * read at most once (not at all with frames_before == 0) and written once, where a launch per batch reads 8 B and writes 8 B
+ * per element and batch beside B * sizeof(code) bytes of samples (at the reference's batch_size of 4: 80 % of the traffic of
+ * uint8 frames, 67 % of uint16 frames).
+ *   frames_devs, batch_sizes   HOST arrays of n_batches (1 .. CT_STATS_MAX_BATCHES) device pointers / batch sizes, read during
+ *                the call: batch b is batch_sizes[b] frames at frames_devs[b], each as the single-batch entry point takes it.
+ *                The batches may be separate allocations; they share one dtype, one geometry (image_stride included), one
+ *                layout and one stage list.  A batch of size 0 is skipped (a negative size is CT_ERR_INVALID_ARGUMENT).
+ *   consts_devs  HOST array of n_batches device pointers, each the 4 floats ct_ingest_extrema left for that batch (its own
+ *                data-dependent Normalize constants, read when the kernel runs), or NULL as a whole
+ *   frames_before   the frames merged before batch 0.  Batch b is merged into a state of frames_before plus the sizes of the
+ *                batches in front of it: the float of that exact integer count, formed on the host -- what a caller of the
+ *                single-batch entry point would pass -- and handed to the kernel by value; nothing is summed in float32 on the
+ *                device.
+ *   flags        CT_STATS_REQUIRE_ONE_LAUNCH: CT_ERR_UNSUPPORTED instead of one launch per batch.
+ * n_batches outside 1 .. 16 is CT_ERR_INVALID_ARGUMENT; n_batches == 1 is the single-batch entry point (flags ignored; one
+ * batch of size 0 is CT_OK for both).  Every batch is judged as the single-batch entry point judges it (the same status
+ * codes, the first refusal wins; an empty batch needs neither its frames nor the state) before anything touches the device.
+ * If all batches are empty, or the image of the ingest form is, the call is CT_OK without a launch.
+ * One pass: where every non-empty batch has at most 32 frames (the register-cached walks, BMAX 16 / 32 chosen from the
+ * largest batch) and, for the ingest form, every batch or none has constants, one launch walks all batches -- plus the scalar
+ * launch for heads and tails the single-batch entry points have.  Each thread owns the same elements for every batch, each
+ * frame byte is read once.  ct_video_stats_batches reads the frames as 4-element packets only where EVERY batch is aligned
+ * to them (and the state to 16 bytes); a misaligned frame pointer in any batch sends all batches down the element-wise form,
+ * which gives the same bits.  The ingest form reads codes at any alignment, as ct_video_stats_ingest_batch does.
+ * Fallback: a batch of more than 32 frames, or batches with and without constants mixed, run one launch per batch through the
+ * single-batch kernels; with CT_STATS_REQUIRE_ONE_LAUNCH that is CT_ERR_UNSUPPORTED and nothing is launched.
+ * Allocates nothing, synchronises nothing, reads nothing back, never writes the frames, touches nothing outside C*H_tile*W
+ * elements of the two state arrays.
+ */
+int ct_video_stats_batches(const void *const *frames_devs, const int32_t *batch_sizes, int32_t n_batches, int32_t dtype,
+                           float max_code, const ct_geometry *geom, const ct_icrf *icrf, float frames_before,
+                           float *mean_state_dev, float *m2_state_dev, uint32_t flags, void *stream);
+int ct_video_stats_ingest_batches(const void *const *frames_devs, const int32_t *batch_sizes, int32_t n_batches, int32_t dtype,
+                                  const ct_geometry *geom, const ct_ingest_stage *stages, int32_t n_stages,
+                                  const float *const *consts_devs, const ct_icrf *icrf, float frames_before,
+                                  float *mean_state_dev, float *m2_state_dev, uint32_t flags, void *stream);
 
 /*
  * ct_pair_residual_ingest_fwd / ct_pair_residual_ingest_bwd -- such a chain and ct_pair_residual_fwd / _bwd in ONE pass over
