@@ -14,6 +14,10 @@
 // Interleaved (F, H, W, C) frames as OpenCV decodes them (IL instantiations): a thread still owns V consecutive MEMORY
 // elements -- the frame loads stay packets -- and only the LUT row and the position in the planar (C, H, W) state follow
 // from TileMap::planar_index; the state is touched element by element, once per batch of frames.
+//
+// Host: stats_prepare is everything ct_video_stats_batch refuses and its argument block; dispatch, BMAX pick, launch and the
+// walk over the batch list of ct_video_stats_batches are ct_stats_kernel.hpp's (stats_dispatch, with_stats_bmax,
+// stats_launch_grid, stats_batches), shared with ct_stats_multi.hip and the two ingest files.
 #include "ct_stats_kernel.hpp"
 
 namespace ct {
@@ -23,7 +27,6 @@ __global__ __launch_bounds__(kBlock) void video_stats_kernel(const StatsArgs a)
 {
     extern __shared__ __align__(16) char lds[];
     constexpr bool kRanged = sizeof(T) != 4;
-    constexpr int kEntry = lut_entry_bytes(INTERP);
     const int C = a.channels, L = a.n_points, B = a.batch;
     stage_lut<INTERP>(lds, a.lut, C, L);
     __syncthreads();
@@ -35,11 +38,9 @@ __global__ __launch_bounds__(kBlock) void video_stats_kernel(const StatsArgs a)
     uint32_t pq[V];  // position in the planar state (== q0 + e unless the frames are interleaved)
 #pragma unroll
     for (int e = 0; e < V; ++e) {
-        int ch;
-        uint32_t qg;
-        pq[e] = IL ? a.tile.planar_index(q0 + e) : q0 + e;
-        a.tile.locate(pq[e], ch, qg);
-        row_off[e] = lut_row<INTERP>(qg, ch, C) * L * kEntry;
+        const StatsOwn own = stats_own<INTERP, IL>(a.tile, q0 + e, C, L);
+        pq[e] = own.pq;
+        row_off[e] = own.row_off;
     }
     const T *src = static_cast<const T *>(a.frames) + q0;
     float sum[V], m2[V];
@@ -75,7 +76,6 @@ __global__ __launch_bounds__(kBlock) void video_stats_cached_kernel(const StatsA
 {
     extern __shared__ __align__(16) char lds[];
     constexpr bool kRanged = sizeof(T) != 4;
-    constexpr int kEntry = lut_entry_bytes(INTERP);
     const int C = a.channels, L = a.n_points, B = a.batch;
     stage_lut<INTERP>(lds, a.lut, C, L);
     __syncthreads();
@@ -87,11 +87,9 @@ __global__ __launch_bounds__(kBlock) void video_stats_cached_kernel(const StatsA
     uint32_t pq[V];  // position in the planar state (== q0 + e unless the frames are interleaved)
 #pragma unroll
     for (int e = 0; e < V; ++e) {
-        int ch;
-        uint32_t qg;
-        pq[e] = IL ? a.tile.planar_index(q0 + e) : q0 + e;
-        a.tile.locate(pq[e], ch, qg);
-        row_off[e] = lut_row<INTERP>(qg, ch, C) * L * kEntry;
+        const StatsOwn own = stats_own<INTERP, IL>(a.tile, q0 + e, C, L);
+        pq[e] = own.pq;
+        row_off[e] = own.row_off;
     }
     const T *src = static_cast<const T *>(a.frames) + q0;
     SPacket<T, V> raw[BMAX];
@@ -125,48 +123,6 @@ __global__ __launch_bounds__(kBlock) void video_stats_cached_kernel(const StatsA
         }
     }
     merge_state<V, IL>(a, q0, pq, mean_b, m2);
-}
-
-template <typename T, int V, int INTERP, bool IL>
-static int stats_launch_layout(const StatsArgs &a, hipStream_t s)
-{
-    if (a.q_count == 0) return CT_OK;
-    const uint32_t vecs = a.q_count / V, grid = (vecs + kBlock - 1) / kBlock;
-    const size_t lds = lut_lds_bytes(INTERP, a.channels, a.n_points);
-    if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;
-    if (a.batch <= 16)
-        hipLaunchKernelGGL((video_stats_cached_kernel<T, V, INTERP, 16, IL>), dim3(grid), dim3(kBlock), lds, s, a);
-    else if (a.batch <= 32)
-        hipLaunchKernelGGL((video_stats_cached_kernel<T, V, INTERP, 32, IL>), dim3(grid), dim3(kBlock), lds, s, a);
-    else
-        hipLaunchKernelGGL((video_stats_kernel<T, V, INTERP, IL>), dim3(grid), dim3(kBlock), lds, s, a);
-    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
-}
-
-template <typename T, int V, int INTERP>
-static int stats_launch(const StatsArgs &a, hipStream_t s)
-{
-    return a.tile.layout == CT_LAYOUT_NCHW ? stats_launch_layout<T, V, INTERP, false>(a, s) : stats_launch_layout<T, V, INTERP, true>(a, s);
-}
-
-template <typename T, int V>
-static int stats_dispatch(const StatsArgs &a, int interp, hipStream_t s)
-{
-    switch (interp) {
-        case CT_INTERP_LOOKUP: return stats_launch<T, V, CT_INTERP_LOOKUP>(a, s);
-        case CT_INTERP_LINEAR: return stats_launch<T, V, CT_INTERP_LINEAR>(a, s);
-        case CT_INTERP_CATMULL: return stats_launch<T, V, CT_INTERP_CATMULL>(a, s);
-        case CT_INTERP_NONE: return stats_launch<T, V, CT_INTERP_NONE>(a, s);
-    }
-    return CT_ERR_INVALID_ARGUMENT;
-}
-
-
-template <typename T>
-static int stats_typed(const StatsArgs &a, uint32_t Q, int interp, hipStream_t s)
-{
-    return stats_split(a, Q, stats_frames_vec_ok<T>(a.frames, a.image_stride),
-                       [&](const StatsArgs &part, auto V) { return stats_dispatch<T, decltype(V)::value>(part, interp, s); });
 }
 
 }  // namespace ct
@@ -207,14 +163,18 @@ static int stats_prepare(const void *frames_dev, int32_t dtype, float max_code, 
     return CT_OK;
 }
 
+// The launches of one batch: dtype / V / interp / layout by ct::stats_dispatch, then the walk that takes a.batch frames.
 static int stats_run(const StatsArgs &a, int32_t dtype, const ct_geometry *geom, int interp, hipStream_t s)
 {
-    const uint32_t Q = (uint32_t)local_elements(geom);
-    switch (dtype) {
-        case CT_DTYPE_U8: return stats_typed<uint8_t>(a, Q, interp, s);
-        case CT_DTYPE_U16: return stats_typed<uint16_t>(a, Q, interp, s);
-    }
-    return stats_typed<float>(a, Q, interp, s);
+    return stats_dispatch(a, &a.frames, 1, dtype, (uint32_t)local_elements(geom), interp, [&](const StatsArgs &part, auto t, auto V, auto I, auto IL) {
+        using T = decltype(t);
+        return with_stats_bmax<true>(part.batch, [&](auto BMAX) {
+            if constexpr (BMAX == 0)
+                return stats_launch_grid(video_stats_kernel<T, V, I, IL>, stats_grid<V>(part), I, s, part);
+            else
+                return stats_launch_grid(video_stats_cached_kernel<T, V, I, BMAX, IL>, stats_grid<V>(part), I, s, part);
+        });
+    });
 }
 
 }  // namespace ct
@@ -238,40 +198,20 @@ extern "C" int ct_video_stats_batches(const void *const *frames_devs, const int3
                                       float *mean_state_dev, float *m2_state_dev, uint32_t flags, void *stream)
 {
     using namespace ct;
-    if (n_batches < 1 || n_batches > kMaxStatsBatches || !frames_devs || !batch_sizes) return CT_ERR_INVALID_ARGUMENT;
-    if (n_batches == 1 && batch_sizes[0] != 0)
-        return ct_video_stats_batch(frames_devs[0], dtype, max_code, batch_sizes[0], geom, icrf, frames_before, mean_state_dev,
-                                    m2_state_dev, stream);
-    // every batch as the single-batch entry point would judge it, with the frame count its caller would pass; nothing has
-    // touched the device when one of them is refused
-    StatsBatches mb = {};
-    StatsArgs a, first = {};
-    int64_t before = 0;
-    int n = 0;
-    for (int b = 0; b < n_batches; ++b) {
-        // the float of the exact count (frames_before is one already; a sum of integers below 2^53 is exact in double)
-        const float count = before == 0 ? frames_before : (float)((double)frames_before + (double)before);
-        if (const int rc = stats_prepare(frames_devs[b], dtype, max_code, batch_sizes[b], geom, icrf, count, mean_state_dev, m2_state_dev, true, a);
-            rc != CT_OK)
-            return rc;
-        if (batch_sizes[b] == 0) continue;
-        if (n == 0) first = a;
-        mb.frames[n] = frames_devs[b];
-        mb.batch[n] = batch_sizes[b];
-        mb.count_before[n] = count;
-        mb.batch_max = batch_sizes[b] > mb.batch_max ? batch_sizes[b] : mb.batch_max;
-        before += batch_sizes[b];
-        ++n;
-    }
-    mb.n_batches = n;
-    if (n == 0) return CT_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (n >= 2 && mb.batch_max <= kStatsCachedMax) return stats_multi(first, mb, dtype, (uint32_t)local_elements(geom), icrf->interp, s);
-    if (n >= 2 && (flags & CT_STATS_REQUIRE_ONE_LAUNCH)) return CT_ERR_UNSUPPORTED;  // (tests: make the route explicit)
-    for (int b = 0; b < n; ++b) {
-        const int rc = ct_video_stats_batch(mb.frames[b], dtype, max_code, mb.batch[b], geom, icrf, mb.count_before[b], mean_state_dev,
-                                            m2_state_dev, stream);
-        if (rc != CT_OK) return rc;
-    }
-    return CT_OK;
+    return stats_batches(
+        frames_devs, nullptr, batch_sizes, n_batches, frames_before, flags, false,
+        [&](int b, float count) {
+            StatsArgs a;
+            return stats_prepare(frames_devs[b], dtype, max_code, batch_sizes[b], geom, icrf, count, mean_state_dev, m2_state_dev, true, a);
+        },
+        [&](const StatsBatches &mb, bool cached) {
+            if (!cached) return kStatsPerBatch;
+            StatsArgs first;  // (judged above: the block of the first batch with frames)
+            stats_prepare(mb.frames[0], dtype, max_code, mb.batch[0], geom, icrf, mb.count_before[0], mean_state_dev, m2_state_dev, true, first);
+            return stats_multi(first, mb, dtype, (uint32_t)local_elements(geom), icrf->interp, s);
+        },
+        [&](const void *frames, const float *, int32_t batch, float count) {
+            return ct_video_stats_batch(frames, dtype, max_code, batch, geom, icrf, count, mean_state_dev, m2_state_dev, stream);
+        });
 }

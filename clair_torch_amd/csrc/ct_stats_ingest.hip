@@ -33,14 +33,19 @@
 // Every load is that of a code of the thread's own elements (pixels) in one of the B frames, every store lies in the
 // thread's own elements of mean_state and m2_state.  The consts of a CT_INGEST_AFFINE_DATA stage are read once per thread,
 // before anything is stored.  No atomics, no LDS traffic besides the LUT, the frames are read only.
+//
+// Host: si_validate and si_pointers_ok are what the entry points refuse; dispatch, BMAX pick, launch and the walk over the
+// batch list of ct_video_stats_ingest_batches are ct_stats_kernel.hpp's (si_dispatch, with_stats_bmax, stats_launch_grid,
+// stats_batches), shared with the other three files.
 #include "ct_ingest_stages.hpp"
 #include "ct_stats_kernel.hpp"
 
 namespace ct {
 
-// One thread: G consecutive elements of every plane it owns, the whole batch and the state.  (The walk stands in the kernel
-// itself and not in a device function of its own: a callee is unrolled before it is inlined, and the kernel would then meet
-// its by-value argument block with more users than the optimizer follows and keep a copy of it in scratch.)
+// One thread: G consecutive elements of every plane it owns, the whole batch and the state.  (Location, load, sample and walk
+// stand in the kernel itself, here and in ct_stats_ingest_multi.hip: the thread's location as a function returning a struct
+// changed the assembly of 128 of the 240 kernels of the two files, load_raw and sample as functions that of 180 -- no
+// scratch, other instruction order and registers.  profiles/stats_refactor_ab.md.)
 template <typename T, bool PACKED, int G, int INTERP, int BMAX, bool DATA>
 __global__ __launch_bounds__(kBlock) void video_stats_ingest_kernel(const StatsIngestArgs a)
 {
@@ -182,29 +187,12 @@ __global__ __launch_bounds__(kBlock) void video_stats_ingest_kernel(const StatsI
 }
 
 
-template <typename T, bool PACKED, int G, int INTERP, bool DATA>
-static int si_launch(const StatsIngestArgs &a, uint32_t threads_x, hipStream_t s)
+// The launches of one batch: dtype / interp / layout / constants by ct::si_dispatch, then the walk that takes a.batch frames.
+static int si_run(const StatsIngestArgs &a, int dtype, bool packed, int interp, hipStream_t s)
 {
-    const size_t lds = lut_lds_bytes(INTERP, a.channels, a.n_points);
-    const dim3 grid = si_grid(a, PACKED, threads_x), block(kBlock);
-    if (a.batch <= 16)
-        hipLaunchKernelGGL((video_stats_ingest_kernel<T, PACKED, G, INTERP, 16, DATA>), grid, block, lds, s, a);
-    else if (a.batch <= 32)
-        hipLaunchKernelGGL((video_stats_ingest_kernel<T, PACKED, G, INTERP, 32, DATA>), grid, block, lds, s, a);
-    else
-        hipLaunchKernelGGL((video_stats_ingest_kernel<T, PACKED, G, INTERP, 0, DATA>), grid, block, lds, s, a);
-    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
-}
-
-template <typename T>
-static int si_dispatch(const StatsIngestArgs &a, bool packed, int interp, hipStream_t s)
-{
-    return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
-        constexpr int kI = decltype(I)::value;
-        return si_layout(a, packed, [&](const StatsIngestArgs &part, auto P, auto G, uint32_t threads_x) {
-            constexpr bool kP = decltype(P)::value;
-            constexpr int kG = decltype(G)::value;
-            return a.consts ? si_launch<T, kP, kG, kI, true>(part, threads_x, s) : si_launch<T, kP, kG, kI, false>(part, threads_x, s);
+    return si_dispatch(a, dtype, packed, interp, [&](const StatsIngestArgs &part, dim3 grid, auto t, auto P, auto G, auto I, auto DATA) {
+        return with_stats_bmax<true>(part.batch, [&](auto BMAX) {
+            return stats_launch_grid(video_stats_ingest_kernel<decltype(t), P, G, I, BMAX, DATA>, grid, I, s, part);
         });
     });
 }
@@ -250,9 +238,7 @@ extern "C" int ct_video_stats_ingest_batch(const void *frames_dev, int32_t dtype
     fill_ingest_args(a, geom, icrf_points(icrf), by_channel, stages, n_stages);
     a.batch = batch;
     a.count_before = frames_before;
-    const bool packed = geom->layout != CT_LAYOUT_NCHW;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == CT_DTYPE_U8 ? si_dispatch<uint8_t>(a, packed, icrf->interp, s) : si_dispatch<uint16_t>(a, packed, icrf->interp, s);
+    return si_run(a, dtype, geom->layout != CT_LAYOUT_NCHW, icrf->interp, static_cast<hipStream_t>(stream));
 }
 
 // Several consecutive batches behind one chain: ONE launch of the MULTI kernels (ct_stats_ingest_multi.hip) where every batch
@@ -265,50 +251,30 @@ extern "C" int ct_video_stats_ingest_batches(const void *const *frames_devs, con
                                              void *stream)
 {
     using namespace ct;
-    if (n_batches < 1 || n_batches > kMaxStatsBatches || !frames_devs || !batch_sizes) return CT_ERR_INVALID_ARGUMENT;
-    if (n_batches == 1)
-        return ct_video_stats_ingest_batch(frames_devs[0], dtype, batch_sizes[0], geom, stages, n_stages, consts_devs ? consts_devs[0] : nullptr,
-                                           icrf, frames_before, mean_state_dev, m2_state_dev, stream);
-    // every batch as the single-batch entry point would judge it, with the frame count its caller would pass; nothing has
-    // touched the device when one of them is refused
-    StatsBatches mb = {};
     bool by_channel = false;
-    int64_t before = 0;
-    int n = 0, n_consts = 0;
-    for (int b = 0; b < n_batches; ++b) {
-        // the float of the exact count (frames_before is one already; a sum of integers below 2^53 is exact in double)
-        const float count = before == 0 ? frames_before : (float)((double)frames_before + (double)before);
-        const float *consts = consts_devs ? consts_devs[b] : nullptr;
-        if (const int rc = si_validate(dtype, batch_sizes[b], geom, stages, n_stages, consts, icrf, count, by_channel); rc != CT_OK) return rc;
-        if (batch_sizes[b] == 0) continue;
-        mb.frames[n] = frames_devs[b];
-        mb.consts[n] = consts;
-        mb.batch[n] = batch_sizes[b];
-        mb.count_before[n] = count;
-        mb.batch_max = batch_sizes[b] > mb.batch_max ? batch_sizes[b] : mb.batch_max;
-        n_consts += consts ? 1 : 0;
-        before += batch_sizes[b];
-        ++n;
-    }
-    mb.n_batches = n;
-    if (n == 0 || geom->h_tile * geom->width == 0) return CT_OK;
-    for (int b = 0; b < n; ++b)
-        if (!si_pointers_ok(mb.frames[b], dtype, mean_state_dev, m2_state_dev)) return CT_ERR_INVALID_ARGUMENT;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (n >= 2 && mb.batch_max <= kStatsCachedMax && (n_consts == 0 || n_consts == n)) {
-        StatsIngestArgs a = {};
-        a.consts = mb.consts[0];  // (only whether there are any: the kernel reads each batch's own)
-        a.lut = icrf->lut_dev;
-        a.mean_state = mean_state_dev;
-        a.m2_state = m2_state_dev;
-        fill_ingest_args(a, geom, icrf_points(icrf), by_channel, stages, n_stages);
-        return stats_ingest_multi(a, mb, dtype, geom->layout != CT_LAYOUT_NCHW, icrf->interp, s);
-    }
-    if (n >= 2 && (flags & CT_STATS_REQUIRE_ONE_LAUNCH)) return CT_ERR_UNSUPPORTED;  // (tests: make the route explicit)
-    for (int b = 0; b < n; ++b) {
-        const int rc = ct_video_stats_ingest_batch(mb.frames[b], dtype, mb.batch[b], geom, stages, n_stages, mb.consts[b], icrf,
-                                                   mb.count_before[b], mean_state_dev, m2_state_dev, stream);
-        if (rc != CT_OK) return rc;
-    }
-    return CT_OK;
+    return stats_batches(
+        frames_devs, consts_devs, batch_sizes, n_batches, frames_before, flags, true,
+        [&](int b, float count) {
+            return si_validate(dtype, batch_sizes[b], geom, stages, n_stages, consts_devs ? consts_devs[b] : nullptr, icrf, count, by_channel);
+        },
+        [&](const StatsBatches &mb, bool cached) {
+            if (geom->h_tile * geom->width == 0) return (int)CT_OK;
+            int n_consts = 0;
+            for (int b = 0; b < mb.n_batches; ++b) {
+                if (!si_pointers_ok(mb.frames[b], dtype, mean_state_dev, m2_state_dev)) return (int)CT_ERR_INVALID_ARGUMENT;
+                n_consts += mb.consts[b] ? 1 : 0;
+            }
+            if (!cached || (n_consts != 0 && n_consts != mb.n_batches)) return kStatsPerBatch;
+            StatsIngestArgs a = {};
+            a.consts = mb.consts[0];  // (only whether there are any: the kernel reads each batch's own)
+            a.lut = icrf->lut_dev;
+            a.mean_state = mean_state_dev;
+            a.m2_state = m2_state_dev;
+            fill_ingest_args(a, geom, icrf_points(icrf), by_channel, stages, n_stages);
+            return stats_ingest_multi(a, mb, dtype, geom->layout != CT_LAYOUT_NCHW, icrf->interp, static_cast<hipStream_t>(stream));
+        },
+        [&](const void *frames, const float *consts, int32_t batch, float count) {
+            return ct_video_stats_ingest_batch(frames, dtype, batch, geom, stages, n_stages, consts, icrf, count, mean_state_dev, m2_state_dev,
+                                               stream);
+        });
 }

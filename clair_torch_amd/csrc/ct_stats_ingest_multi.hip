@@ -13,12 +13,14 @@
 // came before it, and written once, after the last batch.  The counts travel by value (StatsBatches::count_before, the float
 // of the exact integer, formed on the host): the result is that of one launch per batch, bit for bit.  HBM-bound; no
 // atomics, no LDS traffic besides the LUT, the frames are read only.
+// Host: ct::stats_ingest_multi is ct_stats_ingest.hip's dispatch and launch (ct::si_dispatch, ct_stats_kernel.hpp) with the
+// batches as a second argument.
 #include "ct_ingest_stages.hpp"
 #include "ct_stats_kernel.hpp"
 
 namespace ct {
 
-// (The walk stands in the kernel itself, as in video_stats_ingest_kernel: see the remark there.)
+// (Location, load, sample and walk stand in the kernel itself, as in video_stats_ingest_kernel: see the remark there.)
 template <typename T, bool PACKED, int G, int INTERP, int BMAX, bool DATA>
 __global__ __launch_bounds__(kBlock) void video_stats_ingest_multi_kernel(const StatsIngestArgs a, const StatsBatches mb)
 {
@@ -175,38 +177,14 @@ __global__ __launch_bounds__(kBlock) void video_stats_ingest_multi_kernel(const 
     }
 }
 
-template <typename T, bool PACKED, int G, int INTERP, bool DATA>
-static int si_launch_multi(const StatsIngestArgs &a, const StatsBatches &mb, uint32_t threads_x, hipStream_t s)
-{
-    const size_t lds = lut_lds_bytes(INTERP, a.channels, a.n_points);
-    const dim3 grid = si_grid(a, PACKED, threads_x), block(kBlock);
-    if (mb.batch_max <= 16)
-        hipLaunchKernelGGL((video_stats_ingest_multi_kernel<T, PACKED, G, INTERP, 16, DATA>), grid, block, lds, s, a, mb);
-    else
-        hipLaunchKernelGGL((video_stats_ingest_multi_kernel<T, PACKED, G, INTERP, kStatsCachedMax, DATA>), grid, block, lds, s, a, mb);
-    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
-}
-
-template <typename T>
-static int si_dispatch_multi(const StatsIngestArgs &a, const StatsBatches &mb, bool packed, int interp, hipStream_t s)
-{
-    return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
-        constexpr int kI = decltype(I)::value;
-        return si_layout(a, packed, [&](const StatsIngestArgs &part, auto P, auto G, uint32_t threads_x) {
-            constexpr bool kP = decltype(P)::value;
-            constexpr int kG = decltype(G)::value;
-            return a.consts ? si_launch_multi<T, kP, kG, kI, true>(part, mb, threads_x, s)
-                            : si_launch_multi<T, kP, kG, kI, false>(part, mb, threads_x, s);
-        });
-    });
-}
-
 int stats_ingest_multi(const StatsIngestArgs &a, const StatsBatches &mb, int dtype, bool packed, int interp, hipStream_t s)
 {
     if (mb.n_batches < 2 || mb.n_batches > kMaxStatsBatches || mb.batch_max > kStatsCachedMax) return CT_ERR_INVALID_ARGUMENT;
-    if (dtype == CT_DTYPE_U8) return si_dispatch_multi<uint8_t>(a, mb, packed, interp, s);
-    if (dtype == CT_DTYPE_U16) return si_dispatch_multi<uint16_t>(a, mb, packed, interp, s);
-    return CT_ERR_UNSUPPORTED;
+    return si_dispatch(a, dtype, packed, interp, [&](const StatsIngestArgs &part, dim3 grid, auto t, auto P, auto G, auto I, auto DATA) {
+        return with_stats_bmax<false>(mb.batch_max, [&](auto BMAX) {
+            return stats_launch_grid(video_stats_ingest_multi_kernel<decltype(t), P, G, I, BMAX, DATA>, grid, I, s, part, mb);
+        });
+    });
 }
 
 }  // namespace ct

@@ -1,9 +1,13 @@
 // ct_stats_kernel.hpp -- what the one-batch-per-launch statistics kernels (ct_stats.hip, ct_stats_ingest.hip) and their
 // several-batches-per-launch forms (ct_stats_multi.hip, ct_stats_ingest_multi.hip) share: the argument blocks, the rules that
-// say which thread owns which element (the host side of them: stats_split, si_layout) and the entry points of the MULTI
-// translation units.  The kernels themselves stay in their .hip files; the MULTI kernels repeat the register-cached walk
-// around a loop over the batches instead of sharing a device function with the single-batch kernels, whose code is left as
-// it was (a walk in a callee costs ct_stats_ingest.hip's kernel a scratch copy of its argument block, see there).
+// say which thread owns which element (the host side of them: stats_split, si_layout), the entry points of the MULTI
+// translation units and the one host path in front of every launch: the walk over a batch list (stats_batches), the dispatch
+// on dtype / interpolation / layout (stats_dispatch, si_dispatch), the BMAX pick (with_stats_bmax) and the launch itself
+// (stats_launch_grid).  The kernels stay in their .hip files.  Device code is shared only where every kernel's gfx950
+// assembly stayed byte for byte what the copies gave (tools/compare_kernel_asm.py): stats_own below did.  The register-cached
+// walk, the merge on registers, the ingest form's thread location and its load and sample step did not -- a shared form of
+// each changed 128 to 207 of the 240 kernels that see it (instruction order, operand order, register numbers; no scratch) --
+// so the MULTI kernels repeat them.  The table: profiles/stats_refactor_ab.md.
 #pragma once
 #include "ct_args.hpp"
 #include "ct_stats_merge.hpp"
@@ -62,6 +66,73 @@ struct StatsBatches {
 int stats_multi(const StatsArgs &a, const StatsBatches &mb, int dtype, uint32_t Q, int interp, hipStream_t stream);
 int stats_ingest_multi(const StatsIngestArgs &a, const StatsBatches &mb, int dtype, bool packed, int interp, hipStream_t stream);
 
+// ---- host: the launch, one copy for the four translation units ----------------------------------------------------------
+// BMAX of the walk for batches of at most `batch` frames: f(integral_constant<int, BMAX>), the register-cached walks of 16 and
+// of kStatsCachedMax frames.  STREAMED: the single-batch launches, which walk a larger batch out of memory (BMAX = 0).
+template <bool STREAMED, typename F>
+static int with_stats_bmax(int32_t batch, F &&f)
+{
+    if constexpr (STREAMED)
+        if (batch > kStatsCachedMax) return f(std::integral_constant<int, 0>{});
+    return batch <= 16 ? f(std::integral_constant<int, 16>{}) : f(std::integral_constant<int, kStatsCachedMax>{});
+}
+
+// kernel(a, mb...) on `grid`: an empty grid is nothing to do, the LUT has to fit the LDS (the ingest entry points have refused
+// that one before they come here, si_validate: for them it cannot fire), the launch and its error.
+template <typename Kernel, typename Args, typename... Batches>
+static int stats_launch_grid(Kernel kernel, dim3 grid, int interp, hipStream_t s, const Args &a, const Batches &...mb)
+{
+    if (grid.x == 0) return CT_OK;
+    const size_t lds = lut_lds_bytes(interp, a.channels, a.n_points);
+    if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, s, a, mb...);
+    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
+}
+
+// ---- host: the batch list of ct_video_stats_batches and ct_video_stats_ingest_batches ---------------------------------------
+constexpr int kStatsPerBatch = 1;  // one_launch's answer where the list is not one launch (no CT_* status is positive)
+
+// Every batch judged as the single-batch entry point would judge it, with the frame count its caller would pass -- nothing has
+// touched the device when one of them is refused -- then ONE launch where the list allows it, else one single-batch call per
+// batch with frames, exactly what the caller would have done (CT_STATS_REQUIRE_ONE_LAUNCH: refused instead).
+//   validate(b, count)                  the status of batch b of the arguments, with `count` frames in front of it
+//   one_launch(mb, cached)              the batches with frames (at least one).  cached: two or more, each within a register-
+//                                       cached walk.  The status of the call, or kStatsPerBatch
+//   single(frames, consts, batch, count)   the single-batch entry point
+// forward_lone_empty: a list of one batch of size 0 goes to `single` as a list of one batch with frames does; else it is a list.
+template <typename Validate, typename OneLaunch, typename Single>
+static int stats_batches(const void *const *frames_devs, const float *const *consts_devs, const int32_t *batch_sizes, int32_t n_batches,
+                         float frames_before, uint32_t flags, bool forward_lone_empty, Validate &&validate, OneLaunch &&one_launch,
+                         Single &&single)
+{
+    if (n_batches < 1 || n_batches > kMaxStatsBatches || !frames_devs || !batch_sizes) return CT_ERR_INVALID_ARGUMENT;
+    if (n_batches == 1 && (forward_lone_empty || batch_sizes[0] != 0))
+        return single(frames_devs[0], consts_devs ? consts_devs[0] : nullptr, batch_sizes[0], frames_before);
+    StatsBatches mb = {};
+    int64_t before = 0;
+    int n = 0;
+    for (int b = 0; b < n_batches; ++b) {
+        // the float of the exact count (frames_before is one already; a sum of integers below 2^53 is exact in double)
+        const float count = before == 0 ? frames_before : (float)((double)frames_before + (double)before);
+        if (const int rc = validate(b, count); rc != CT_OK) return rc;
+        if (batch_sizes[b] == 0) continue;
+        mb.frames[n] = frames_devs[b];
+        mb.consts[n] = consts_devs ? consts_devs[b] : nullptr;
+        mb.batch[n] = batch_sizes[b];
+        mb.count_before[n] = count;
+        mb.batch_max = batch_sizes[b] > mb.batch_max ? batch_sizes[b] : mb.batch_max;
+        before += batch_sizes[b];
+        ++n;
+    }
+    mb.n_batches = n;
+    if (n == 0) return CT_OK;
+    if (const int rc = one_launch(mb, n >= 2 && mb.batch_max <= kStatsCachedMax); rc != kStatsPerBatch) return rc;
+    if (n >= 2 && (flags & CT_STATS_REQUIRE_ONE_LAUNCH)) return CT_ERR_UNSUPPORTED;  // (tests: make the route explicit)
+    for (int b = 0; b < n; ++b)
+        if (const int rc = single(mb.frames[b], mb.consts[b], mb.batch[b], mb.count_before[b]); rc != CT_OK) return rc;
+    return CT_OK;
+}
+
 // ---- ct_stats.hip's ownership: V = 4 consecutive memory elements per thread, then a V = 1 tail --------------------------
 constexpr int kStatsV = 4;  // 4 elements per thread: 32 frames x 4 values fit the register file
 
@@ -93,6 +164,54 @@ static int stats_split(StatsArgs a, uint32_t Q, bool frames_vec_ok, Dispatch &&d
         rc = dispatch(a, std::integral_constant<int, 1>{});
     }
     return rc;
+}
+
+// Memory element q of a tile of frames: its position in the planar state (== q unless the frames are interleaved) and the
+// byte offset of its LUT row in the LDS table, from the global flat index.  One element, by value: the only shape of this
+// rule that leaves the three kernels' assembly as it was (profiles/stats_refactor_ab.md).
+struct StatsOwn {
+    uint32_t pq;
+    int row_off;
+};
+
+template <int INTERP, bool IL>
+__device__ __forceinline__ StatsOwn stats_own(const TileMap &tile, uint32_t q, int C, int L)
+{
+    int ch;
+    uint32_t qg;
+    StatsOwn o;
+    o.pq = IL ? tile.planar_index(q) : q;
+    tile.locate(o.pq, ch, qg);
+    o.row_off = lut_row<INTERP>(qg, ch, C) * L * lut_entry_bytes(INTERP);
+    return o;
+}
+
+// grid of a launch of a.q_count elements, V of them per thread
+template <int V>
+static inline dim3 stats_grid(const StatsArgs &a)
+{
+    return dim3((a.q_count / V + kBlock - 1) / kBlock);
+}
+
+// dtype / V / interp / layout -> template arguments, for ct_stats.hip and ct_stats_multi.hip: launch(part, T{}, V, INTERP, IL)
+// for the vector body and the scalar tail of the Q elements; packets where each of the n `frames` can be read as such.
+template <typename Launch>
+static int stats_dispatch(const StatsArgs &a, const void *const *frames, int n, int dtype, uint32_t Q, int interp, Launch &&launch)
+{
+    auto typed = [&](auto t) {
+        using T = decltype(t);
+        bool frames_vec_ok = true;
+        for (int b = 0; b < n; ++b) frames_vec_ok = frames_vec_ok && stats_frames_vec_ok<T>(frames[b], a.image_stride);
+        return stats_split(a, Q, frames_vec_ok, [&](const StatsArgs &part, auto V) {
+            return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
+                return part.tile.layout == CT_LAYOUT_NCHW ? launch(part, T{}, V, I, std::false_type{}) : launch(part, T{}, V, I, std::true_type{});
+            });
+        });
+    };
+    if (dtype == CT_DTYPE_U8) return typed(uint8_t{});
+    if (dtype == CT_DTYPE_U16) return typed(uint16_t{});
+    if (dtype == CT_DTYPE_F32) return typed(float{});
+    return CT_ERR_UNSUPPORTED;
 }
 
 // ---- ct_stats_ingest.hip's ownership (its head describes it) ------------------------------------------------------------
@@ -135,6 +254,25 @@ static int si_layout(StatsIngestArgs a, bool packed, Launch &&launch)
         return launch(a, std::false_type{}, One{}, (uint32_t)(2 * (kSiGroup - 1)));
     }
     return launch(a, std::false_type{}, One{}, a.plane);
+}
+
+// dtype / interp / layout / constants -> template arguments, for ct_stats_ingest.hip and ct_stats_ingest_multi.hip:
+// launch(part, grid, T{}, PACKED, G, INTERP, DATA) for each launch of si_layout.
+template <typename Launch>
+static int si_dispatch(const StatsIngestArgs &a, int dtype, bool packed, int interp, Launch &&launch)
+{
+    auto typed = [&](auto t) {
+        using T = decltype(t);
+        return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
+            return si_layout(a, packed, [&](const StatsIngestArgs &part, auto P, auto G, uint32_t threads_x) {
+                const dim3 grid = si_grid(part, P, threads_x);
+                return a.consts ? launch(part, grid, T{}, P, G, I, std::true_type{}) : launch(part, grid, T{}, P, G, I, std::false_type{});
+            });
+        });
+    };
+    if (dtype == CT_DTYPE_U8) return typed(uint8_t{});
+    if (dtype == CT_DTYPE_U16) return typed(uint16_t{});
+    return CT_ERR_UNSUPPORTED;
 }
 
 }  // namespace ct

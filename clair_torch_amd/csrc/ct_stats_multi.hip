@@ -11,6 +11,7 @@
 // written once, after the last batch.  The count in front of every batch travels by value (StatsBatches::count_before, the
 // float of the exact integer, formed on the host), so every merge_moments call sees the operands a launch of its own sees:
 // the result is that of one launch per batch, bit for bit.  HBM-bound; no atomics, no LDS traffic besides the LUT.
+// Host: ct::stats_multi is ct_stats.hip's dispatch and launch (ct_stats_kernel.hpp) with the batches as a second argument.
 #include "ct_stats_kernel.hpp"
 
 namespace ct {
@@ -20,7 +21,6 @@ __global__ __launch_bounds__(kBlock) void video_stats_multi_kernel(const StatsAr
 {
     extern __shared__ __align__(16) char lds[];
     constexpr bool kRanged = sizeof(T) != 4;
-    constexpr int kEntry = lut_entry_bytes(INTERP);
     const int C = a.channels, L = a.n_points;
     stage_lut<INTERP>(lds, a.lut, C, L);
     __syncthreads();
@@ -32,11 +32,9 @@ __global__ __launch_bounds__(kBlock) void video_stats_multi_kernel(const StatsAr
     uint32_t pq[V];  // position in the planar state (== q0 + e unless the frames are interleaved)
 #pragma unroll
     for (int e = 0; e < V; ++e) {
-        int ch;
-        uint32_t qg;
-        pq[e] = IL ? a.tile.planar_index(q0 + e) : q0 + e;
-        a.tile.locate(pq[e], ch, qg);
-        row_off[e] = lut_row<INTERP>(qg, ch, C) * L * kEntry;
+        const StatsOwn own = stats_own<INTERP, IL>(a.tile, q0 + e, C, L);
+        pq[e] = own.pq;
+        row_off[e] = own.row_off;
     }
 
     // the one read of the state: what batch 0 merges into, unless it is the first of the video
@@ -115,45 +113,15 @@ __global__ __launch_bounds__(kBlock) void video_stats_multi_kernel(const StatsAr
     }
 }
 
-template <typename T, int V, int INTERP, bool IL>
-static int stats_multi_launch(const StatsArgs &a, const StatsBatches &mb, hipStream_t s)
-{
-    if (a.q_count == 0) return CT_OK;
-    const uint32_t vecs = a.q_count / V, grid = (vecs + kBlock - 1) / kBlock;
-    const size_t lds = lut_lds_bytes(INTERP, a.channels, a.n_points);
-    if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;  // (refused by the entry point before it gets here)
-    if (mb.batch_max <= 16)
-        hipLaunchKernelGGL((video_stats_multi_kernel<T, V, INTERP, 16, IL>), dim3(grid), dim3(kBlock), lds, s, a, mb);
-    else
-        hipLaunchKernelGGL((video_stats_multi_kernel<T, V, INTERP, kStatsCachedMax, IL>), dim3(grid), dim3(kBlock), lds, s, a, mb);
-    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
-}
-
-template <typename T>
-static int stats_multi_typed(const StatsArgs &a, const StatsBatches &mb, uint32_t Q, int interp, hipStream_t s)
-{
-    // packets of 4 elements only where every batch can be read as such: one ownership for the whole call
-    bool frames_vec_ok = true;
-    for (int b = 0; b < mb.n_batches; ++b) frames_vec_ok = frames_vec_ok && stats_frames_vec_ok<T>(mb.frames[b], a.image_stride);
-    return stats_split(a, Q, frames_vec_ok, [&](const StatsArgs &part, auto V) {
-        constexpr int kV = decltype(V)::value;
-        return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
-            constexpr int kI = decltype(I)::value;
-            return part.tile.layout == CT_LAYOUT_NCHW ? stats_multi_launch<T, kV, kI, false>(part, mb, s)
-                                                      : stats_multi_launch<T, kV, kI, true>(part, mb, s);
-        });
-    });
-}
-
 int stats_multi(const StatsArgs &a, const StatsBatches &mb, int dtype, uint32_t Q, int interp, hipStream_t s)
 {
     if (mb.n_batches < 2 || mb.n_batches > kMaxStatsBatches || mb.batch_max > kStatsCachedMax) return CT_ERR_INVALID_ARGUMENT;
-    switch (dtype) {
-        case CT_DTYPE_U8: return stats_multi_typed<uint8_t>(a, mb, Q, interp, s);
-        case CT_DTYPE_U16: return stats_multi_typed<uint16_t>(a, mb, Q, interp, s);
-        case CT_DTYPE_F32: return stats_multi_typed<float>(a, mb, Q, interp, s);
-    }
-    return CT_ERR_UNSUPPORTED;
+    // packets of 4 elements only where every batch can be read as such: one ownership for the whole call
+    return stats_dispatch(a, mb.frames, mb.n_batches, dtype, Q, interp, [&](const StatsArgs &part, auto t, auto V, auto I, auto IL) {
+        return with_stats_bmax<false>(mb.batch_max, [&](auto BMAX) {
+            return stats_launch_grid(video_stats_multi_kernel<decltype(t), V, I, BMAX, IL>, stats_grid<V>(part), I, s, part, mb);
+        });
+    });
 }
 
 }  // namespace ct

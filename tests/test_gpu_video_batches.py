@@ -216,6 +216,19 @@ def test_fallback_and_its_refusal(dev, form, dtype):
 
 
 @pytest.mark.parametrize("form,dtype", FORMS, ids=FORM_IDS)
+def test_one_batch_with_frames_is_never_refused(dev, form, dtype):
+    """A single batch with frames among empty ones is one launch of the single-batch kernels, so requiring one launch refuses
+    nothing -- not even 33 frames, which no several-batches kernel takes.  (Only a launch tells the two apart: every status
+    without one is the same.)"""
+    rng = np.random.default_rng(17)
+    host = _draw(rng, (33, 3, 5, 7), dtype)
+    stages = _chains(dtype, 3)["clamp"] if form == "ingest" else None
+    for partition in ([0, 5, 0], [0, 33]):
+        _run(dev, form, host[:sum(partition)], "nchw", partition, _lut(3, 16), "linear", stages=stages, one_launch=True)
+        _run(dev, form, host[:sum(partition)], "nchw", partition, _lut(3, 16), "linear", stages=stages, one_launch=True, frames_before=6)
+
+
+@pytest.mark.parametrize("form,dtype", FORMS, ids=FORM_IDS)
 @pytest.mark.parametrize("layout", ["nchw", "nhwc", "nhwc_bgr"])
 def test_row_band(dev, form, dtype, layout):
     """Rows [2, 7) of a 9-row image: the LINEAR row follows the GLOBAL flat index (h_global > h_tile, row_offset > 0), as in

@@ -137,6 +137,58 @@ def test_batches_validate_before_any_launch(lib, form):
         assert call(sizes=(0, 0, 0), consts=[None, FAKE, None]) == OK
 
 
+def test_the_two_forms_differ_where_their_single_batch_entry_points_do(lib):
+    """What the code form and the ingest form of the batch list do NOT share, told apart by status alone (nothing launches):
+    the code form looks at a batch's pointers before the geometry, batch by batch, and has no empty image; the ingest form
+    judges every batch first, then answers an empty image, and only then looks at pointers."""
+    from clair_torch_amd import _native as nv
+    ONE = nv.STATS_REQUIRE_ONE_LAUNCH
+    linear = nv.Icrf(lut_dev=0x2000, n_points=256, interp=nv.INTERP_LINEAR)
+    above_lds = nv.Icrf(lut_dev=0x2000, n_points=1 << 20, interp=nv.INTERP_CATMULL)
+    huge = _geom(h=1 << 15, w=1 << 15)
+    one = _stages(nv.INGEST_AFFINE)
+
+    def code(sizes, frames, geom=None, model=linear, mean=FAKE, m2=FAKE, flags=ONE):
+        f_arr, s_arr = _arrays(frames, sizes)
+        return lib.ct_video_stats_batches(f_arr, s_arr, len(sizes), nv.DTYPE_U16, 1023.0, ctypes.byref(geom or _geom()), ctypes.byref(model),
+                                          0.0, ctypes.c_void_p(mean), ctypes.c_void_p(m2), flags, None)
+
+    def ingest(sizes, frames, geom=None, model=linear, mean=FAKE, m2=FAKE, flags=ONE):
+        f_arr, s_arr = _arrays(frames, sizes)
+        return lib.ct_video_stats_ingest_batches(f_arr, s_arr, len(sizes), nv.DTYPE_U16, ctypes.byref(geom or _geom()), one, 1, None,
+                                                 ctypes.byref(model), 0.0, ctypes.c_void_p(mean), ctypes.c_void_p(m2), flags, None)
+
+    # a lone empty batch is a list of one in the code form (the single-batch entry point refuses a size of 0), with the list's
+    # LDS test; the ingest form hands it to its single-batch entry point, which takes a size of 0 and tests the LDS itself
+    for flags in (0, ONE):
+        assert code((0,), [None], mean=None, m2=None, flags=flags) == OK and ingest((0,), [None], mean=None, m2=None, flags=flags) == OK
+        assert code((0,), [None], model=above_lds, flags=flags) == TOO_LARGE and ingest((0,), [None], model=above_lds, flags=flags) == TOO_LARGE
+        assert code((0,), [None], geom=_geom(c=0), flags=flags) == INVALID and ingest((0,), [None], geom=_geom(c=0), flags=flags) == INVALID
+    # a lone batch with frames goes to the single-batch entry point in both: its refusals, in its order
+    assert code((2,), [None], geom=huge) == INVALID and ingest((2,), [None], geom=huge) == TOO_LARGE
+    assert code((2,), [FAKE], model=above_lds) == TOO_LARGE and ingest((2,), [FAKE], model=above_lds) == TOO_LARGE
+    # pointers against geometry: the code form refuses the missing pointer of batch 0 before it looks at the image, and the
+    # image (in batch 0's turn) before the missing pointer of batch 1; the ingest form judges every batch before any pointer
+    assert code((2, 3), [None, FAKE], geom=huge) == INVALID and code((2, 3), [FAKE, FAKE], geom=huge, mean=None) == INVALID
+    assert code((2, 3), [FAKE, None], geom=huge) == TOO_LARGE and code((0, 3), [None, None], geom=huge, mean=None) == TOO_LARGE
+    assert code((2, 3), [None, FAKE], model=above_lds) == INVALID and code((2, 3), [FAKE, None], model=above_lds) == TOO_LARGE
+    for frames in ([None, FAKE], [FAKE, None], [None, None]):
+        assert ingest((2, 3), frames, geom=huge) == TOO_LARGE and ingest((2, 3), frames, model=above_lds) == TOO_LARGE
+        assert ingest((2, 3), frames, geom=huge, mean=None, m2=None) == TOO_LARGE
+        assert ingest((2, 3), frames) == INVALID
+    # an empty image: CT_OK in the ingest form before any pointer is looked at, with or without the flag, whatever the sizes
+    # (33 frames included: there is nothing to refuse a launch for); the code form has no empty image
+    for geom in (_geom(h=0), _geom(w=0)):
+        for flags in (0, ONE):
+            for sizes in ((2, 3), (0, 2), (33, 2), (2,), (0, 0)):
+                assert ingest(sizes, [None] * len(sizes), geom=geom, mean=None, m2=None, flags=flags) == OK
+                assert code(sizes, [FAKE] * len(sizes), geom=geom, flags=flags) == INVALID
+    assert ingest((2, -1), [None, None], geom=_geom(h=0), mean=None) == INVALID  # ... but after every batch has been judged
+    # more than 32 frames with the flag: refused only where two batches have frames, and after the pointers
+    assert code((33, 0, 2), [FAKE, None, FAKE]) == UNSUPPORTED and ingest((33, 0, 2), [FAKE, None, FAKE]) == UNSUPPORTED
+    assert code((33, 0, 2), [FAKE, None, None]) == INVALID and ingest((33, 0, 2), [FAKE, None, None]) == INVALID
+
+
 def _T():
     from clair_torch_amd.common import transforms
     return transforms
