@@ -5,7 +5,9 @@ The reference applies conditional_gaussian_blur with the batch's matched dark fi
 (clair_torch/inference/hdr_merge.py:76-92, linearization.py:73-92) and later adds the dark field's variance term by a
 second autograd.grad (hdr_merge.py:117-126, linearization.py:108-116).  Here one kernel (ct_dark_field_blur) produces the
 blurred batch and a per-sample uncertainty that carries both variance terms; the merge / linearize kernels then run
-unchanged on (float32 pixels, explicit uncertainty).
+unchanged on (float32 pixels, explicit uncertainty).  In compute_hdr_image a matched batch in a closed-form mode can
+instead take ct_hdr_merge_dark_batch, which forms both per sample in registers and merges them in the same pass
+(``DarkField.fuses_with_merge`` / ``merge``; bit-identical to the pair).
 
 Row bands: the 3x3 blur needs the rows just above and below a band.  ``exchange_halo`` gets them from the neighbouring
 ranks (one send / receive pair per side over torch.distributed; 2 rows of B x C x W elements, latency-bound on xGMI).
@@ -60,25 +62,56 @@ class DarkField:
     def from_dataset(cls, dataset, main_dataset, device):
         return cls(dataset, main_dataset, device)
 
-    def apply(self, index_batch, images, max_code, std, std_mode, std_value, tile=None, group=None):
-        """-> (blurred float32 batch, explicit per-sample uncertainty | None), or (None, None) when no dark field matches
-        this batch (MissingValMode.SKIP_BATCH: the reference then leaves the batch uncorrected, hdr_merge.py:84).
+    def match(self, index_batch, std, std_mode):
+        """-> (dark, dark std) of the dark fields matched to this batch, or None when none matches
+        (MissingValMode.SKIP_BATCH: the reference then leaves the batch uncorrected, hdr_merge.py:84).
 
         Error behaviour follows the reference: the dark std is dereferenced unconditionally (AttributeError without it),
         and with a dark std but no image uncertainties autograd finds no path to the dark field (RuntimeError)."""
         frames = [self.main_dataset.files[int(i)] for i in index_batch]
         _, dark, dark_std, _ = self.dataset.get_matching_artefact_images(frames)
         if dark is None:
-            return None, None
+            return None
         if dark_std is None:
             raise AttributeError("'NoneType' object has no attribute 'to'")  # hdr_merge.py:87 / linearization.py:86
         if std is None and std_mode == "none":
             # hdr_merge.py:97-99,118: the ICRF runs under set_grad_enabled(stds is not None), so nothing connects the
             # running average to dark_field_val
             raise RuntimeError("element 0 of tensors does not require grad and does not have a grad_fn")
+        return dark, dark_std
+
+    @staticmethod
+    def fuses_with_merge(images, layout, interp, reference_order) -> bool:
+        """The route decision of a matched batch in compute_hdr_image: True = ct_hdr_merge_dark_batch (blur and merge in one
+        pass over the staged images), False = ct_dark_field_blur into float32 stacks, then the float32 merge.  Fused are
+        planar codes or float32 pixels in a closed-form mode -- the rule of the fused ingest: the reference-order kernel
+        (``reference_order=True``, and LOOKUP / CATMULL by default: a matched batch always carries uncertainties) is not
+        fused."""
+        if not isinstance(images, torch.Tensor) or layout != "nchw" or images.ndim != 4:
+            return False
+        if images.dtype not in (torch.uint8, torch.uint16, torch.float32):
+            return False
+        return not (reference_order is True or (interp in ("lookup", "catmull") and reference_order is None))
+
+    def apply(self, index_batch, images, max_code, std, std_mode, std_value, tile=None, group=None, matched=None):
+        """-> (blurred float32 batch, explicit per-sample uncertainty | None), or (None, None) when no dark field matches
+        this batch.  ``matched``: what ``match`` returned for it, where the caller has asked already."""
+        if matched is None:
+            matched = self.match(index_batch, std, std_mode)
+        if matched is None:
+            return None, None
+        dark, dark_std = matched
         halo = exchange_halo(images, tile, group)
         return ops.dark_field_blur(images, dark, dark_std, std=std, std_mode=std_mode, std_value=std_value,
                                    max_code=max_code, tile=tile, halo=halo)
+
+    def merge(self, matched, images, exposures, max_code, std, std_mode, std_value, tile=None, group=None, **merge_args):
+        """The matched batch through ct_hdr_merge_dark_batch: what ``apply`` and ``ops.hdr_merge_batch`` on its two stacks
+        give, bit for bit.  ``merge_args``: lut, interp, gaussian_weight, state, finalize, reference_order."""
+        dark, dark_std = matched
+        halo = exchange_halo(images, tile, group)
+        return ops.hdr_merge_dark_batch(images, exposures, dark, dark_std, std=std, std_mode=std_mode, std_value=std_value,
+                                        max_code=max_code, tile=tile, halo=halo, **merge_args)
 
     def linearize(self, index_batch, images, max_code, std, std_mode, std_value, lut, interp):
         xb, sig = self.apply(index_batch, images, max_code, std, std_mode, std_value)

@@ -629,19 +629,11 @@ def flatfield_correct(value: torch.Tensor, var_or_std: Optional[torch.Tensor], f
 
 
 # ---- dark-field conditional blur -----------------------------------------------------------------------------------
-def dark_field_blur(stack: torch.Tensor, dark: torch.Tensor, dark_std: Optional[torch.Tensor], *,
-                    std: Optional[torch.Tensor] = None, std_mode: str = "none", std_value: float = 0.0,
-                    max_code: Optional[float] = None, tile: Optional[TileGeometry] = None,
-                    halo: Optional[torch.Tensor] = None, threshold: float = 0.05, alpha: float = 50.0):
-    """ct_dark_field_blur: (xb float32 (B,C,H,W), sigma_eff float32 | None).  ``dark`` / ``dark_std`` are (1|B,C,H,W);
-    ``halo`` (B,C,2,W) holds the global rows above / below a row band (see include/clair_hip.h)."""
-    _check_stack(stack)
+def _dark_arguments(stack, dark, dark_std, halo):
+    """What dark_field_blur and hdr_merge_dark_batch check of the dark field, its std and the halo rows of a contiguous
+    (B,C,H,W) ``stack``: (dark, dark_std, halo) as the kernels read them."""
     b, c, h, w = stack.shape
     dev = stack.device
-    if std is not None:
-        std_mode, std = "explicit", _explicit_std(std, stack)
-    stack = stack.contiguous()
-    max_code = _default_max_code(stack, max_code)
     dark = dark.to(device=dev, dtype=torch.float32).contiguous()
     if dark.ndim != 4 or dark.shape[0] not in (1, b) or tuple(dark.shape[1:]) != (c, h, w):
         raise ValueError(f"mask_map batch dimension must be 1 or {b}, got shape {tuple(dark.shape)}")
@@ -658,6 +650,23 @@ def dark_field_blur(stack: torch.Tensor, dark: torch.Tensor, dark_std: Optional[
         halo = halo.to(device=dev, dtype=stack.dtype).contiguous()
         if tuple(halo.shape) != (b, c, 2, w):
             raise ValueError(f"halo must be (B, C, 2, W) = {(b, c, 2, w)}, got {tuple(halo.shape)}")
+    return dark, dark_std, halo
+
+
+def dark_field_blur(stack: torch.Tensor, dark: torch.Tensor, dark_std: Optional[torch.Tensor], *,
+                    std: Optional[torch.Tensor] = None, std_mode: str = "none", std_value: float = 0.0,
+                    max_code: Optional[float] = None, tile: Optional[TileGeometry] = None,
+                    halo: Optional[torch.Tensor] = None, threshold: float = 0.05, alpha: float = 50.0):
+    """ct_dark_field_blur: (xb float32 (B,C,H,W), sigma_eff float32 | None).  ``dark`` / ``dark_std`` are (1|B,C,H,W);
+    ``halo`` (B,C,2,W) holds the global rows above / below a row band (see include/clair_hip.h)."""
+    _check_stack(stack)
+    b, c, h, w = stack.shape
+    dev = stack.device
+    if std is not None:
+        std_mode, std = "explicit", _explicit_std(std, stack)
+    stack = stack.contiguous()
+    max_code = _default_max_code(stack, max_code)
+    dark, dark_std, halo = _dark_arguments(stack, dark, dark_std, halo)
     geom = _geometry(stack, tile)
     xb = torch.empty((b, c, h, w), dtype=torch.float32, device=dev)
     sig = torch.empty_like(xb) if dark_std is not None else None
@@ -668,6 +677,55 @@ def dark_field_blur(stack: torch.Tensor, dark: torch.Tensor, dark_std: Optional[
                                           _stream(dev))
     nv.check(rc, "ct_dark_field_blur")
     return xb, sig
+
+
+def hdr_merge_dark_batch(stack: torch.Tensor, exposures: torch.Tensor, dark: torch.Tensor, dark_std: Optional[torch.Tensor], *,
+                         lut: Optional[torch.Tensor] = None, interp: Optional[str] = "linear", gaussian_weight: bool = True,
+                         std: Optional[torch.Tensor] = None, std_mode: str = "none", std_value: float = 0.0,
+                         max_code: Optional[float] = None, state: Optional[MergeState] = None, finalize: bool = True,
+                         tile: Optional[TileGeometry] = None, halo: Optional[torch.Tensor] = None,
+                         mean_dtype: torch.dtype = torch.float64, reference_order: Optional[bool] = None,
+                         threshold: float = 0.05, alpha: float = 50.0):
+    """ct_hdr_merge_dark_batch: ``xb, sig = dark_field_blur(stack, dark, dark_std, ...)`` followed by
+    ``hdr_merge_batch(xb, exposures, std=sig, ...)`` bit for bit, in one launch and without the two float32 stacks in
+    between.  Returns (mean, std|None), planar (C,H,W), when ``finalize`` else None.
+
+    ``stack`` (B,C,H,W) uint8 / uint16 codes (``max_code``) or float32 pixels; ``dark``, ``dark_std``, ``std``, ``std_mode``,
+    ``std_value``, ``tile``, ``halo``, ``threshold``, ``alpha``: as ``dark_field_blur`` takes them (the uncertainty of the RAW
+    image; without ``dark_std`` no uncertainty is propagated, as ``hdr_merge_batch(xb, ...)`` without one).  ``exposures``,
+    ``lut``, ``interp``, ``gaussian_weight``, ``state``, ``finalize``, ``mean_dtype``: as in ``hdr_merge_batch``; the
+    MergeState is the same, so fused and unfused batches may alternate on one.  ``reference_order``: False = the closed-form
+    kernels for LOOKUP / CATMULL with uncertainties as well (CT_MERGE_CLOSED_FORM); None leaves those two modes, and True
+    every mode, to the reference-order kernel, which this entry point does not have (NativeLibraryError: use
+    ``dark_field_blur`` + ``hdr_merge_batch``)."""
+    _check_stack(stack)
+    b, c, h, w = stack.shape
+    dev = stack.device
+    if b < 1:
+        raise ValueError("empty batch")
+    if std is not None:
+        std_mode, std = "explicit", _explicit_std(std, stack)
+    if std_mode not in _STD:
+        raise ValueError(f"unknown std_mode {std_mode}")
+    stack = stack.contiguous()
+    max_code = _default_max_code(stack, max_code)
+    dark, dark_std, halo = _dark_arguments(stack, dark, dark_std, halo)
+    exposure_dev = _exposures_to_device(exposures, b, dev)
+    icrf, lut_keep = _icrf_struct(lut, interp, c)
+    geom = _geometry(stack, tile)
+    flags, _, mean_out, std_out = _merge_setup_for((c, h, w), dev, "planar", state, finalize, dark_std is not None, mean_dtype,
+                                                   reference_order, 0, "batch")
+    with torch.cuda.device(dev):
+        rc = nv.load().ct_hdr_merge_dark_batch(
+            _ptr(stack), _DTYPE[stack.dtype], float(max_code or 1.0), b, ctypes.byref(geom), _ptr(halo), _ptr(std), _STD[std_mode],
+            float(std_value), _ptr(dark), _ptr(dark_std), dark.shape[0], float(threshold), float(alpha), _ptr(exposure_dev),
+            ctypes.byref(icrf), nv.WEIGHT_GAUSS if gaussian_weight else nv.WEIGHT_NONE, *_state_ptrs(state), _ptr(mean_out),
+            _ptr(std_out), flags, _stream(dev))
+    nv.check(rc, "ct_hdr_merge_dark_batch")
+    del lut_keep
+    if state is not None:
+        state.batches += 1
+    return (mean_out, std_out) if finalize else None
 
 
 # ---- strided downscale of raw codes (StridedDownscale folded in front of the code-domain kernels) -----------------

@@ -321,6 +321,39 @@ int ct_dark_field_blur(const void *stack_dev, int32_t dtype, float max_code, int
                        float *xb_out_dev, float *std_out_dev, void *stream);
 
 /*
+ * ct_hdr_merge_dark_batch -- that blur and one batch of compute_hdr_image's loop body in ONE pass over B raw frames: state
+ * and outputs are bit for bit those of ct_dark_field_blur into dense float32 (B, C, H_tile, W) stacks xb and sigma_eff
+ * followed by ct_hdr_merge_batch on them with CT_DTYPE_F32, CT_STD_EXPLICIT, the same geometry (image_stride C*H_tile*W)
+ * and the same flags with CT_MERGE_CLOSED_FORM -- without the two stacks: sizeof(code) + 8 bytes read per sample (+ 4 with
+ * explicit image uncertainties) where the two launches move 16 B per sample more, and no float32 copy of the batch exists.
+ *   stack_dev .. alpha   as ct_dark_field_blur takes them: codes or float32 pixels, CT_LAYOUT_NCHW only; std_dev (EXPLICIT)
+ *                laid out like the stack (image_stride between frames); std_mode NONE / CONSTANT / MULTIPLIER / EXPLICIT only
+ *                selects how the RAW image's sigma enters sigma_eff; dark_dev / dark_std_dev dense; halo_dev for a row band
+ *   dark_std_dev NULL: there is no sigma_eff, as ct_dark_field_blur with std_out_dev == NULL: the merge then runs as
+ *                ct_hdr_merge_batch with CT_STD_NONE on xb (std_dev / std_mode are still checked, var_state_dev and
+ *                std_out_dev are not used)
+ *   exposure_dev, icrf, weight_mode, state, outputs   as ct_hdr_merge_batch; state and outputs are planar (C, H_tile, W)
+ *   flags        CT_MERGE_FIRST_BATCH, CT_MERGE_FINALIZE, CT_MERGE_MEAN_OUT_F32, CT_MERGE_CLOSED_FORM
+ * Status: whatever ct_dark_field_blur refuses is refused with its status and in its order (a missing stack / geometry / dark
+ * field, width < 2 or h_global < 2, a layout other than NCHW: CT_ERR_UNSUPPORTED, dark_batch outside {1, B}, one shared
+ * dark field with its std for B > 1: CT_ERR_UNSUPPORTED, a bad std mode, a band without its halo, a one-row band at the
+ * image's edge: CT_ERR_UNSUPPORTED, a short image_stride, an unknown dtype or max_code: CT_ERR_UNSUPPORTED), then whatever
+ * ct_hdr_merge_batch refuses for (xb, sigma_eff) with its status (model, weight mode, CT_ERR_NO_GRADIENT_PATH for LOOKUP
+ * with unit weights and a dark std, a missing state on a batch that is not first and final, missing outputs, CT_ERR_TOO_LARGE
+ * for 2^31 elements).  CT_ERR_UNSUPPORTED besides: CT_MERGE_F64_MOMENTS, CT_MERGE_REFERENCE_ORDER, CT_MERGE_OUT_AS_INPUT, and
+ * LOOKUP / CATMULL with a dark std and no CT_MERGE_CLOSED_FORM (ct_hdr_merge_batch sends those to the reference-order kernel,
+ * which is not fused).  CT_ERR_TOO_LARGE: the LUT with 8 B per exposure exceeds 160 KiB of LDS.  Every argument is validated
+ * before anything touches the device.  Allocates nothing, synchronises nothing, reads nothing back, never writes the frames,
+ * touches nothing outside C*H_tile*W elements of the state and the outputs.
+ */
+int ct_hdr_merge_dark_batch(const void *stack_dev, int32_t dtype, float max_code, int32_t batch, const ct_geometry *geom,
+                            const void *halo_dev, const float *std_dev, int32_t std_mode, float std_value,
+                            const float *dark_dev, const float *dark_std_dev, int32_t dark_batch, float threshold, float alpha,
+                            const double *exposure_dev, const ct_icrf *icrf, int32_t weight_mode, double *mean_state_dev,
+                            float *sumw_state_dev, float *var_state_dev, void *mean_out_dev, float *std_out_dev, uint32_t flags,
+                            void *stream);
+
+/*
  * ct_video_stats_batch -- loop body of compute_video_mean_and_std
  * (clair_torch/inference/inferential_statistics.py:38-47): optional ICRF linearization of a batch of frames and the
  * unweighted WBOMeanVar update (clair_torch/common/statistics.py:213-259), float32 like the reference.
