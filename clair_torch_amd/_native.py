@@ -18,6 +18,7 @@ LAYOUT_NCHW, LAYOUT_NHWC, LAYOUT_NHWC_BGR = 0, 1, 2
 MERGE_FIRST_BATCH, MERGE_FINALIZE, MERGE_MEAN_OUT_F32, MERGE_F64_MOMENTS = 1, 2, 4, 8
 MERGE_REFERENCE_ORDER, MERGE_CLOSED_FORM, MERGE_STD_HINT, MERGE_REQUIRE_ONE_LAUNCH, MERGE_OUT_AS_INPUT = 16, 32, 64, 128, 256
 STATS_REQUIRE_ONE_LAUNCH, STATS_MAX_BATCHES = 1, 16
+LINEARIZE_DARK_MAX_FRAMES = 16
 INGEST_AFFINE, INGEST_CLAMP, INGEST_MAX_STAGES, INGEST_MAX_CHANNELS = 0, 1, 4, 4
 INGEST_AFFINE_DATA, EXTREMA_MIN, EXTREMA_MAX, EXTREMA_MAX_PREFIX = 2, 1, 2, 3
 ERR_INVALID_ARGUMENT, ERR_UNSUPPORTED, ERR_LAUNCH, ERR_NO_GRADIENT_PATH, ERR_TOO_LARGE = -1, -2, -3, -4, -5
@@ -32,7 +33,7 @@ EXPORTS = ("ct_abi_version", "ct_error_string", "ct_hdr_merge_batch", "ct_hdr_me
            "ct_ingest_transform_data", "ct_linearize_ingest", "ct_hdr_merge_ingest_batch", "ct_video_stats_ingest_batch",
            "ct_hdr_merge_ingest_batches", "ct_ingest_extrema_frames_workspace", "ct_ingest_extrema_frames",
            "ct_linearize_ingest_data", "ct_pair_residual_ingest_fwd", "ct_pair_residual_ingest_bwd", "ct_linearize_ingest_strided",
-           "ct_video_stats_batches", "ct_video_stats_ingest_batches", "ct_hdr_merge_dark_batch")
+           "ct_video_stats_batches", "ct_video_stats_ingest_batches", "ct_hdr_merge_dark_batch", "ct_linearize_dark")
 
 
 class Geometry(ctypes.Structure):
@@ -119,6 +120,8 @@ def load():
     lib.ct_hdr_merge_dark_batch.restype = i32
     lib.ct_hdr_merge_dark_batch.argtypes = [vp, i32, f32, i32, gp, vp, vp, i32, f32, vp, vp, i32, f32, f32, vp, ip, i32, vp, vp, vp,
                                             vp, vp, u32, vp]
+    lib.ct_linearize_dark.restype = i32
+    lib.ct_linearize_dark.argtypes = [vp, i32, f32, i64, gp, vp, i32, f32, vp, vp, f32, f32, ip, vp, vp, vp]
     lib.ct_band_stats_workspace.restype = i64
     lib.ct_band_stats_workspace.argtypes = [i32]
     lib.ct_band_stats.restype = i32

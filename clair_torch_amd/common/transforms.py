@@ -31,6 +31,8 @@ copy pipeline -- route 3 by ct_linearize_ingest, which evaluates the chain and t
 and float32 batches with an empty list (inference/linearization.py::pipeline_route) -- and route 4 (likewise without a
 downscale or a dark field; ``pipeline_data_route``): every frame is a batch of its own there, so ct_ingest_extrema_frames
 takes the extrema of each frame of a group in one launch pair and ct_linearize_ingest_data reads the constants per frame.
+With a dark field, planar frames on route 2 without a downscale and bare float32 batches keep the pipeline
+(``DarkField.fuses_with_linearize``: ct_linearize_dark blurs and linearizes the matched frames in one pass).
 Everything else goes frame by frame.
 
 A leading ``CvToTorch`` on (B,H,W,3) uint8 / uint16 frames is never executed on routes 1-4: the code-route kernels read the

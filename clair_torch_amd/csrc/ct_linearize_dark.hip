@@ -1,0 +1,255 @@
+// ct_linearize_dark.hip -- the dark-field conditional blur and the ICRF linearization of F independent frames in ONE pass
+// over the raw frames (gfx950).  For every frame the outputs are bit for bit those of ct_dark_field_blur (ct_darkfield.hip)
+// on it as a batch of one with its own matched dark field, into float32 xb and sigma_eff, followed by ct_linearize_std
+// (ct_linearize.hip) on (xb, CT_DTYPE_F32, std = sigma_eff, CT_STD_EXPLICIT): the blur is dark_blur_kernel's expressions in
+// its operation order on values that never leave the registers, and the sample step is li_sample4<INTERP, CT_STD_EXPLICIT,
+// true> of ct_linearize_ingest.hpp (linearize_sample with RANGED = false and its wave-uniform `tiny` fix-up), the step
+// ct_linearize.hip runs on float32 pixels with explicit uncertainties.
+//
+// The window walk and the blur are a second copy of those in md_run (ct_merge_dark.hip): the two must stay
+// expression-identical (and identical to dark_blur_kernel); tests/test_gpu_linearize_dark.py and test_gpu_merge_dark.py hold
+// each of them to the pair of launches bit for bit.
+//
+// Roofline: HBM.  Per sample sizeof(T) bytes of the frame (its neighbours in the 3 x 3 window are L1 / L2 hits: the rows
+// above and below belong to the wavefronts next door), 4 of the dark field and 4 of its std (+ 4 with explicit image
+// uncertainties), 8 written.  The pair moves sizeof(T) + 8 (+ 4) read and 8 written by the blur, then 8 read and 8 written by
+// the linearization: a uint16 frame with derived uncertainties costs 18 B per sample where the pair moves 34, and the two
+// float32 stacks of a group never exist.  (Byte counts from the shapes; see profiles/linearize_dark.md for what was timed.)
+//
+// Ownership: a workgroup row (blockIdx.y) is one (frame, channel) plane, so the frame -- its dark field pointers, which
+// travel in the argument block: at most CT_LINEARIZE_DARK_MAX_FRAMES frames per launch -- and the channel are wave-uniform.
+// A thread owns 4 consecutive columns of ONE image row: 3 x (1 + 4 + 1) window loads (the column left of the group or the
+// reflected one, the group, the column right of it).  What is left of a row whose width is no multiple of 4 goes through the
+// same code one element after the other.  A workgroup walks kLdSlots groups per thread, a workgroup apart, so one staging of
+// the LUT (stage_lut) serves kLdSlots * 1024 elements.  Outputs are one packet where the group is 16-byte aligned in memory
+// (li_store), else elements.  No atomics, no LDS tile; the frames and the dark fields are read only.  No row bands: the
+// generator that calls this has no tile=, so no halo is built here.
+#include <algorithm>
+#include "ct_linearize_ingest.hpp"
+
+namespace ct {
+
+struct LinDarkArgs {
+    const void *frames;      // (F, C, H, W) T, image_stride between frames
+    const float *std_stack;  // explicit sigma of the raw image, laid out like the frames, or NULL
+    const float *lut;
+    float *lin_out;          // (F, C, H, W) dense
+    float *std_out;
+    const float *dark[CT_LINEARIZE_DARK_MAX_FRAMES];      // (C, H, W) each, one per frame of this launch
+    const float *dark_std[CT_LINEARIZE_DARK_MAX_FRAMES];
+    int64_t image_stride;
+    uint32_t plane;          // H * W
+    uint32_t width, height;
+    uint32_t channels, n_points;
+    NormConst norm;
+    int32_t std_mode;        // of the RAW image: how sigma enters sigma_eff
+    float std_value, threshold, alpha;
+    float k0, k1;            // the two distinct taps of the normalised 1-D kernel: k0 (centre), k1 (sides)
+};
+
+constexpr int kLdGroup = kLiGroup;  // columns per thread
+constexpr int kLdSlots = 4;         // groups per thread
+
+// xb and sigma_eff of columns w0 .. w0 + G - 1 of row h of plane c0 of the frame at `frame` (its dark field: dark, dark_std;
+// its explicit sigma: sigma or NULL).  md_run's load_raw and blur for one frame: dark_blur_kernel, expression for expression.
+template <typename T, int G>
+__device__ __forceinline__ void ld_blur(const LinDarkArgs &a, const T *frame, const float *sigma, const float *dark,
+                                        const float *dark_std, uint32_t c0, uint32_t h, uint32_t w0, float *xb, float *sig)
+{
+    const uint32_t W = a.width, H = a.height;
+    const uint32_t q = c0 * a.plane + h * W + w0;  // first element inside the (C, H, W) frame
+    const T *img = frame + (int64_t)c0 * a.plane;
+    const T *mid = img + (int64_t)h * W;
+    const T *up = img + (int64_t)(h > 0 ? h - 1 : 1) * W;          // top: reflect -1 -> 1
+    const T *dn = img + (int64_t)(h + 1 < H ? h + 1 : H - 2) * W;  // bottom: reflect H -> H - 2
+    // column taps with reflect padding (index -1 -> 1, W -> W - 2)
+    const uint32_t cl = w0 > 0 ? w0 - 1 : 1, cr = w0 + G < W ? w0 + G : W - 2;
+    T vu[G + 2], vm[G + 2], vd[G + 2];
+    float d[G], ds[G], sg[G] = {};
+    auto load_row = [&](const T *row, T (&v)[G + 2]) {
+        v[0] = row[cl];
+        __builtin_memcpy(&v[1], row + w0, G * sizeof(T));  // any alignment: rows are only element-aligned in general
+        v[G + 1] = row[cr];
+    };
+    load_row(up, vu);
+    load_row(mid, vm);
+    load_row(dn, vd);
+    __builtin_memcpy(d, dark + q, G * sizeof(float));
+    __builtin_memcpy(ds, dark_std + q, G * sizeof(float));
+    const bool explicit_sigma = a.std_mode == CT_STD_EXPLICIT;
+    if (explicit_sigma) __builtin_memcpy(sg, sigma + q, G * sizeof(float));
+
+    float ru[G + 2], rm[G + 2], rd[G + 2];
+#pragma unroll
+    for (int j = 0; j < G + 2; ++j) {
+        ru[j] = to_pixel<T>(vu[j], a.norm);
+        rm[j] = to_pixel<T>(vm[j], a.norm);
+        rd[j] = to_pixel<T>(vd[j], a.norm);
+    }
+#pragma unroll
+    for (int e = 0; e < G; ++e) {
+        const float bu = (a.k1 * ru[e] + a.k0 * ru[e + 1]) + a.k1 * ru[e + 2];
+        const float bm = (a.k1 * rm[e] + a.k0 * rm[e + 1]) + a.k1 * rm[e + 2];
+        const float bd = (a.k1 * rd[e] + a.k0 * rd[e + 1]) + a.k1 * rd[e + 2];
+        const float x = rm[e + 1];
+        const float blurred = (a.k1 * bu + a.k0 * bm) + a.k1 * bd;
+        const float m = 1.0f / (1.0f + expf(-(d[e] - a.threshold) * a.alpha));  // torch.sigmoid
+        xb[e] = m * blurred + (1.0f - m) * x;
+        float s = 0.0f;
+        if (explicit_sigma) s = sg[e];
+        if (a.std_mode == CT_STD_CONSTANT) s = a.std_value;
+        if (a.std_mode == CT_STD_MULTIPLIER) s = a.std_value * x;  // the dataset derives sigma from the RAW image
+        const float dterm = (blurred - x) * (a.alpha * m * (1.0f - m));
+        const float dsv = dterm * ds[e];
+        sig[e] = sqrtf(s * s + dsv * dsv);
+    }
+}
+
+// groups of kLdGroup columns in a row, the last one possibly short
+static inline __host__ __device__ uint32_t ld_groups_per_row(uint32_t width) { return (width + kLdGroup - 1) / kLdGroup; }
+
+template <typename T, int INTERP>
+__global__ __launch_bounds__(kBlock) void linearize_dark_kernel(const LinDarkArgs a)
+{
+    extern __shared__ __align__(16) char lds[];
+    const int C = (int)a.channels, L = (int)a.n_points;
+    stage_lut<INTERP>(lds, a.lut, C, L);
+    __syncthreads();
+    const uint32_t f = blockIdx.y / a.channels, c0 = blockIdx.y - f * a.channels;  // frame of this launch, channel
+    const T *frame = static_cast<const T *>(a.frames) + (int64_t)f * a.image_stride;
+    const float *sigma = a.std_stack ? a.std_stack + (int64_t)f * a.image_stride : nullptr;
+    const float *dark = a.dark[f], *dark_std = a.dark_std[f];
+    const int64_t out0 = (int64_t)f * C * a.plane;  // the frame inside the dense outputs
+    const uint32_t W = a.width;
+    const uint32_t gpr = ld_groups_per_row(W);
+    const uint64_t n_slots = (uint64_t)gpr * a.height;
+#pragma unroll 1
+    for (int k = 0; k < kLdSlots; ++k) {
+        const uint64_t slot = ((uint64_t)blockIdx.x * kLdSlots + k) * kBlock + threadIdx.x;
+        if (slot >= n_slots) break;
+        const uint32_t h = (uint32_t)(slot / gpr);
+        const uint32_t w0 = ((uint32_t)slot - h * gpr) * kLdGroup;
+        float xb[kLdGroup] = {0.0f, 0.0f, 0.0f, 0.0f}, sig[kLdGroup] = {0.0f, 0.0f, 0.0f, 0.0f};
+        int n = kLdGroup;
+        if (W - w0 >= (uint32_t)kLdGroup) {
+            ld_blur<T, kLdGroup>(a, frame, sigma, dark, dark_std, c0, h, w0, xb, sig);
+        } else {
+            // the end of a row whose width is no multiple of the group (at most kLdGroup - 1 elements): one lane, one element
+            // after the other, each with its own window
+            n = (int)(W - w0);
+#pragma unroll
+            for (int e = 0; e < kLdGroup - 1; ++e)
+                if (e < n) ld_blur<T, 1>(a, frame, sigma, dark, dark_std, c0, h, w0 + e, &xb[e], &sig[e]);
+        }
+        // the frame is batch element 0 of its own batch: the LINEAR / CATMULL row is the flat (C, H, W) index modulo C
+        const uint32_t q = c0 * a.plane + h * W + w0;
+        const int r = C == 3 ? (int)(q % 3u) : (int)(q % a.channels);
+        LinIngestPacket lo, so;
+        li_sample4<INTERP, CT_STD_EXPLICIT, true>(xb, sig, lds, L, C, (int)c0, r, 0.0f, lo, so);
+        li_store(a.lin_out + out0 + q, lo, n);
+        li_store(a.std_out + out0 + q, so, n);
+    }
+}
+
+template <typename T, int INTERP>
+static int ld_launch(const LinDarkArgs &a, int n_frames, hipStream_t s)
+{
+    const size_t lds = lut_lds_bytes(INTERP, (int)a.channels, (int)a.n_points);
+    const uint64_t slots = (uint64_t)ld_groups_per_row(a.width) * a.height;
+    const uint64_t per_block = (uint64_t)kBlock * kLdSlots;
+    const dim3 grid((uint32_t)((slots + per_block - 1) / per_block), (uint32_t)n_frames * a.channels);
+    hipLaunchKernelGGL((linearize_dark_kernel<T, INTERP>), grid, dim3(kBlock), lds, s, a);
+    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
+}
+
+template <typename T>
+static int ld_dispatch(const LinDarkArgs &a, int interp, int n_frames, hipStream_t s)
+{
+    // (LOOKUP has no gradient path: refused by the entry point, no kernel)
+    return with_enum<CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) { return ld_launch<T, I>(a, n_frames, s); });
+}
+
+}  // namespace ct
+
+extern "C" int ct_norm_constants(float max_code, float *hi, float *lo);
+
+extern "C" int ct_linearize_dark(const void *frames_dev, int32_t dtype, float max_code, int64_t n_frames, const ct_geometry *geom,
+                                 const float *std_dev, int32_t std_mode, float std_value, const float *const *dark_devs,
+                                 const float *const *dark_std_devs, float threshold, float alpha, const ct_icrf *icrf,
+                                 float *lin_out_dev, float *std_out_dev, void *stream)
+{
+    using namespace ct;
+    // ---- what ct_dark_field_blur refuses for each frame as a batch of one, in its order (ct_darkfield.hip) ----
+    if (!frames_dev || !geom || !dark_devs || !dark_std_devs || !lin_out_dev || !std_out_dev || n_frames <= 0 || n_frames > 0x7fffffff)
+        return CT_ERR_INVALID_ARGUMENT;
+    for (int64_t k = 0; k < n_frames; ++k)
+        if (!dark_devs[k] || !dark_std_devs[k]) return CT_ERR_INVALID_ARGUMENT;
+    if (!shape_positive(geom) || geom->width < 2 || geom->h_global < 2 || !band_fits(geom)) return CT_ERR_INVALID_ARGUMENT;
+    if (geom->layout != CT_LAYOUT_NCHW) return CT_ERR_UNSUPPORTED;
+    if (!std_mode_ok(std_mode, std_dev)) return CT_ERR_INVALID_ARGUMENT;
+    // a row band would need the rows above and below it; the streamed generator has no tile=, so no halo is built here
+    if (geom->row_offset != 0 || geom->h_tile != geom->h_global) return CT_ERR_UNSUPPORTED;
+    if (!stride_holds_image(geom)) return CT_ERR_INVALID_ARGUMENT;
+    NormConst norm{1.0f, 0.0f};
+    if (dtype == CT_DTYPE_U8 || dtype == CT_DTYPE_U16) {
+        if (ct_norm_constants(max_code, &norm.hi, &norm.lo) != CT_OK) return CT_ERR_UNSUPPORTED;
+    } else if (dtype != CT_DTYPE_F32) {
+        return CT_ERR_UNSUPPORTED;
+    }
+    // ---- what ct_linearize_std refuses for (xb, sigma_eff): float32 pixels with explicit uncertainties ----
+    if (!icrf || !icrf_ok(icrf)) return CT_ERR_INVALID_ARGUMENT;
+    const int interp = icrf->interp;
+    // linearization.py:100-105: uncertainties are always propagated here, and LOOKUP has no gradient path (li_check_call)
+    if (interp == CT_INTERP_LOOKUP) return CT_ERR_NO_GRADIENT_PATH;
+    if (!global_below_2_31(geom)) return CT_ERR_TOO_LARGE;
+    const int n_points = icrf_points(icrf);
+    if (lut_lds_bytes(interp, geom->channels, n_points) > kLdsBudget) return CT_ERR_TOO_LARGE;
+    // frames per launch: what the argument block holds, and a grid's y extent (65535) in (frame, channel) planes
+    const int64_t per_launch = std::min<int64_t>(CT_LINEARIZE_DARK_MAX_FRAMES, (int64_t)kLiMaxRows / geom->channels);
+    if (per_launch < 1) return CT_ERR_TOO_LARGE;
+    const size_t elem = dtype_bytes(dtype);
+    if (!aligned(frames_dev, elem) || !aligned(std_dev, sizeof(float)) || !aligned(lin_out_dev, sizeof(float)) ||
+        !aligned(std_out_dev, sizeof(float)))
+        return CT_ERR_INVALID_ARGUMENT;
+    for (int64_t k = 0; k < n_frames; ++k)
+        if (!aligned(dark_devs[k], sizeof(float)) || !aligned(dark_std_devs[k], sizeof(float))) return CT_ERR_INVALID_ARGUMENT;
+
+    const int64_t plane = geom->h_tile * geom->width;
+    LinDarkArgs a{};
+    a.lut = icrf->lut_dev;
+    a.image_stride = geom->image_stride;
+    a.plane = (uint32_t)plane;
+    a.width = (uint32_t)geom->width;
+    a.height = (uint32_t)geom->h_tile;
+    a.channels = (uint32_t)geom->channels;
+    a.n_points = (uint32_t)n_points;
+    a.norm = norm;
+    a.std_mode = std_mode;
+    a.std_value = std_value;
+    a.threshold = threshold;
+    a.alpha = alpha;
+    // torchvision _get_gaussian_kernel1d(3, 1.0): pdf = exp(-0.5 x^2), x = -1, 0, 1; normalised in float32
+    const float side = expf(-0.5f), sum = (side + 1.0f) + side;
+    a.k0 = 1.0f / sum;
+    a.k1 = side / sum;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    for (int64_t first = 0; first < n_frames; first += per_launch) {
+        const int nf = (int)std::min<int64_t>(per_launch, n_frames - first);
+        a.frames = static_cast<const char *>(frames_dev) + first * geom->image_stride * (int64_t)elem;
+        a.std_stack = std_mode == CT_STD_EXPLICIT ? std_dev + first * geom->image_stride : nullptr;
+        a.lin_out = lin_out_dev + first * geom->channels * plane;
+        a.std_out = std_out_dev + first * geom->channels * plane;
+        for (int k = 0; k < nf; ++k) {
+            a.dark[k] = dark_devs[first + k];
+            a.dark_std[k] = dark_std_devs[first + k];
+        }
+        int rc;
+        switch (dtype) {
+            case CT_DTYPE_U8: rc = ld_dispatch<uint8_t>(a, interp, nf, s); break;
+            case CT_DTYPE_U16: rc = ld_dispatch<uint16_t>(a, interp, nf, s); break;
+            default: rc = ld_dispatch<float>(a, interp, nf, s); break;
+        }
+        if (rc != CT_OK) return rc;
+    }
+    return CT_OK;
+}

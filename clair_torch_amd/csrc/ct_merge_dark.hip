@@ -139,7 +139,8 @@ __device__ __forceinline__ void md_run(const MergeDarkArgs &a, const char *lds, 
         }
         return r;
     };
-    // xb and sigma_eff of the G elements: dark_blur_kernel, expression for expression
+    // xb and sigma_eff of the G elements: dark_blur_kernel, expression for expression.  ld_blur of ct_linearize_dark.hip is a
+    // second copy of load_raw and this: the two must stay expression-identical
     auto blur = [&](const MdRaw<T, G> &r, float (&xb)[G], float (&sig)[G]) {
         float ru[G + 2], rm[G + 2], rd[G + 2];
 #pragma unroll

@@ -7,11 +7,15 @@ second autograd.grad (hdr_merge.py:117-126, linearization.py:108-116).  Here one
 blurred batch and a per-sample uncertainty that carries both variance terms; the merge / linearize kernels then run
 unchanged on (float32 pixels, explicit uncertainty).  In compute_hdr_image a matched batch in a closed-form mode can
 instead take ct_hdr_merge_dark_batch, which forms both per sample in registers and merges them in the same pass
-(``DarkField.fuses_with_merge`` / ``merge``; bit-identical to the pair).
+(``DarkField.fuses_with_merge`` / ``merge``; bit-identical to the pair).  linearize_dataset_generator does the same for its
+frames: where ``DarkField.fuses_with_linearize`` says so, the streamed pipeline hands each run of matched frames of a group to
+ct_linearize_dark (blur and ICRF in one pass, bit-identical to the pair) with the matched dark fields uploaded once and kept in
+a small device cache (``device_pair``).
 
 Row bands: the 3x3 blur needs the rows just above and below a band.  ``exchange_halo`` gets them from the neighbouring
 ranks (one send / receive pair per side over torch.distributed; 2 rows of B x C x W elements, latency-bound on xGMI).
 """
+from collections import OrderedDict
 from typing import Optional
 
 import torch
@@ -55,8 +59,11 @@ def exchange_halo(images: torch.Tensor, tile: Optional[ops.TileGeometry], group=
 class DarkField:
     """The dark-field dataset of one compute_hdr_image / linearize_dataset_generator call."""
 
+    CACHE_PAIRS = 4  # matched (dark, dark std) pairs kept on the device by ``device_pair``
+
     def __init__(self, dataset, main_dataset, device):
         self.dataset, self.main_dataset, self.device = dataset, main_dataset, device
+        self._cache = OrderedDict()  # cache_key -> (host dark, host std, device dark, device std), least recently used first
 
     @classmethod
     def from_dataset(cls, dataset, main_dataset, device):
@@ -92,6 +99,47 @@ class DarkField:
         if images.dtype not in (torch.uint8, torch.uint16, torch.float32):
             return False
         return not (reference_order is True or (interp in ("lookup", "catmull") and reference_order is None))
+
+    @staticmethod
+    def fuses_with_linearize(images_or_probe, plan, interp) -> bool:
+        """The route decision of linearize_dataset_generator with a dark-field dataset: True = the streamed pipeline with
+        ct_linearize_dark on the matched frames (blur and ICRF in one pass over the slot's raw frames), False = frame by
+        frame through ct_dark_field_blur and ct_linearize_std.  ``images_or_probe``: the first value batch (shape and dtype
+        only: a CPU tensor will do); ``plan``: its ``plan_staging`` plan with ``planar=True``.  Fused are planar 4-D frames
+        on route "code" without a StridedDownscale (raw uint8 / uint16 codes and their max_code) and float32 pixels with no
+        transform list.  LOOKUP (no gradient path: the frame-by-frame route raises at the first matched frame), routes
+        "ingest", "ingest_data" and "torch" with transforms, and any StridedDownscale stay frame by frame."""
+        t = images_or_probe
+        if not isinstance(t, torch.Tensor) or t.ndim != 4 or interp not in ("linear", "catmull"):
+            return False
+        if plan.route == "code":
+            return plan.step == 1 and plan.layout == "nchw" and t.dtype in (torch.uint8, torch.uint16)
+        return plan.route == "torch" and plan.no_transforms and t.dtype == torch.float32
+
+    @staticmethod
+    def cache_key(dark, dark_std):
+        """What identifies the contents of a matched host pair: address, in-place version counter, shape and dtype of both
+        (an in-place edit bumps ``_version``; the cache holds the host tensors, so an address is not re-used while its
+        entry lives)."""
+        return tuple((t.data_ptr(), t._version, tuple(t.shape), t.dtype) for t in (dark, dark_std))
+
+    def device_pair(self, dark, dark_std):
+        """-> (dark, dark std) of ``match`` as contiguous float32 device tensors, uploaded on the CURRENT stream (the
+        pipeline's copy stream) the first time a pair is seen and kept for the next frames: get_matching_artefact_images
+        usually hands the same host tensors back for many frames, and 8 B per element per frame would triple the copy-in.
+        At most CACHE_PAIRS pairs are kept, the least recently used one goes first; the caller keeps what it got alive for
+        as long as queued work reads it (the pipeline: in the group's in_flight record)."""
+        key = self.cache_key(dark, dark_std)
+        entry = self._cache.get(key)
+        if entry is None:
+            dev_pair = tuple(t.to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous() for t in (dark, dark_std))
+            entry = (dark, dark_std) + dev_pair
+            self._cache[key] = entry
+            while len(self._cache) > self.CACHE_PAIRS:
+                self._cache.popitem(last=False)
+        else:
+            self._cache.move_to_end(key)
+        return entry[2], entry[3]
 
     def apply(self, index_batch, images, max_code, std, std_mode, std_value, tile=None, group=None, matched=None):
         """-> (blurred float32 batch, explicit per-sample uncertainty | None), or (None, None) when no dark field matches

@@ -33,8 +33,16 @@ reads them per frame, and the constants ride the device-to-host stage so that th
 raised -- without a synchronisation of its own -- exactly where the frame-by-frame route raises it: after the frames in
 front of the offending one have been yielded.  A StridedDownscale BEHIND that Normalize keeps this route (the extrema are
 those of the full frames, which ct_ingest_extrema_frames reads; the strided kernel takes the constants); one in FRONT of it
-needs the extrema of the selected pixels and stays frame by frame.  A dark field and lists that run as torch ops go frame
-by frame.
+needs the extrema of the selected pixels and stays frame by frame.  Lists that run as torch ops go frame by frame.
+
+A dark-field dataset is ``DarkField.fuses_with_linearize``'s to decide (inference/dark_field.py), not ``pipeline_route``'s:
+with ``fused_dark=True`` planar raw codes behind the code pair and bare float32 pixels (LINEAR / CATMULL) take the pipeline.
+Every frame is matched on the host when it is copied into the slot, the matched dark fields are uploaded once on the copy
+stream (a device cache of 4 pairs) and each group is cut into maximal runs of matched frames -- ONE ct_linearize_dark launch
+on that range of the slot's raw frames: conditional blur and ICRF in one pass, bit for bit what ct_dark_field_blur followed
+by ct_linearize_std gives frame by frame -- and unmatched ones (ct_linearize_std).  An exception of the match (no dark std,
+no image uncertainties) is raised where the frame-by-frame route raises it: after the frames in front have been yielded.
+Everything else with a dark field, and ``fused_dark=False``, goes frame by frame as ever.
 
 ``output_layout="cv"`` (extension): every yielded pair is in the order the reference's ``save_image`` writes -- (H,W,C),
 a 3-channel frame reversed to BGR -- made by two ct_export_cv launches per group before the device-to-host copy, which
@@ -57,10 +65,21 @@ from ..common.transforms import plan_staging
 
 _GROUP_BYTES = 256 << 20  # device-to-host bytes per group (two float32 planes per frame): ~5 frames of 1080p RGB
 _SLOTS = 3                # ring slots = groups in flight (copy-in | compute | copy-out)
+# linearize_dataset_generator(fused_dark=...).  The rule, set before measuring (profiles/linearize_dark.md): True only if, end
+# to end on 64 uint16 1080p frames from pinned memory, every fused run was faster than every frame-by-frame run.  Measured:
+# 1037 [715 .. 1041] frames/s fused against 456 [388 .. 461] frame by frame, 2.27x at the medians, the slowest fused run (89 ms)
+# ahead of the fastest frame-by-frame run (139 ms): True.
+FUSED_DARK_DEFAULT = True
 
 
 def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRFModelBase, flatfield_dataset=None,
-                                gpu_transforms=None, dark_field_dataset=None, output_layout: str = "planar"):
+                                gpu_transforms=None, dark_field_dataset=None, output_layout: str = "planar",
+                                fused_dark: bool = FUSED_DARK_DEFAULT):
+    """``fused_dark`` (extension; only read with a ``dark_field_dataset``): True lets inputs that
+    ``DarkField.fuses_with_linearize`` accepts take the streamed pipeline with ct_linearize_dark; False is the frame-by-frame
+    route through ct_dark_field_blur and ct_linearize_std.  The yielded values are the same bit for bit.  The default and the
+    measurement behind it: FUSED_DARK_DEFAULT above (True: 2.27x the frames/s of the frame-by-frame route on 64 uint16 1080p
+    frames, every fused run faster than every frame-by-frame run; profiles/linearize_dark.md)."""
     if output_layout not in ("planar", "cv"):
         raise ValueError(f"unknown output_layout {output_layout!r} (planar, cv)")
     expect(dataloader, DataLoader, "dataloader")
@@ -89,6 +108,12 @@ def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRF
     # explicit uncertainty images are planar; a StridedDownscale is ct_linearize_ingest_strided's to apply (step_in_kernel)
     plan = plan_staging(probe, transforms, planar=first[2] is not None, step_in_kernel=True)
     route = pipeline_route(probe, plan, dark is not None)
+    if dark is not None and fused_dark:
+        # the dark field's own decision, on the first frame planned as _frame_by_frame plans it (dark images are planar)
+        dark_plan = plan_staging(probe, transforms, planar=True)
+        if dark.fuses_with_linearize(probe, dark_plan, interp):
+            yield from _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, dark_plan, output_layout == "cv", dark)
+            return
     if route != "pipelined":
         # the second, separate decision: a data-dependent Normalize with per-frame constants.  The probe is a host tensor;
         # the list is planned as stage_images plans it for the batch on the device (route "ingest_data" exists only there)
@@ -111,8 +136,9 @@ def pipeline_route(probe: torch.Tensor, plan, has_dark: bool) -> str:
     that applies the step in its kernel (``plan.step_in_kernel``, which the generator asks ``plan_staging`` for; a plan
     without it leaves the step to the staging and goes frame by frame, as ever) ct_linearize_ingest_strided
     reads every step-th row and column of the raw frames, the code pair then as the one-stage chain x / max_code (measured
-    in profiles/linearize_ingest_strided.md).  Anything else goes frame by frame through the generic staging: a dark field
-    (per-frame conditional blur), lists that run as torch ops -- and, as far as THIS
+    in profiles/linearize_ingest_strided.md).  Anything else goes frame by frame through the generic staging: lists that run
+    as torch ops, a dark field as far as THIS function is concerned (``has_dark``: the generator asks
+    ``DarkField.fuses_with_linearize`` first when ``fused_dark`` is on, and comes here only for what that declined) -- and, as far as THIS
     function is concerned, a data-dependent Normalize: its extrema are per frame here, per stack in ct_ingest_extrema, so
     it has a decision of its own, ``pipeline_data_route``, which the generator asks when this one said "frame_by_frame"."""
     if has_dark or probe.ndim != 4:
@@ -131,7 +157,8 @@ def pipeline_data_route(probe: torch.Tensor, plan, has_dark: bool) -> str:
     Normalize keeps it when the plan says ``step_in_kernel`` (see ``pipeline_route``): the extrema are those of the full
     frames and ct_linearize_ingest_strided takes the constants.  One in
     FRONT of it (``plan.step_first``) needs the extrema of the selected pixels, which no kernel here reduces from the raw
-    frames, and stays frame by frame.  Measured against the frame-by-frame route in profiles/linearize_ingest_data.md;
+    frames, and stays frame by frame.  A dark field always does here: ``DarkField.fuses_with_linearize``, the only decision
+    that sends a dark-field run to the pipeline, declines every data-dependent Normalize.  Measured against the frame-by-frame route in profiles/linearize_ingest_data.md;
     everything else stays frame by frame."""
     if has_dark or probe.ndim != 4 or plan.route != "ingest_data":
         return "frame_by_frame"
@@ -183,7 +210,7 @@ class _Slot:
         self.busy = False
 
 
-def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan, cv):
+def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan, cv, dark=None):
     # Memory note for consumers: the yielded CPU tensors of one group (up to _GROUP_BYTES = 256 MB of output, 5 frames of
     # 1080p RGB) are views of two pinned host tensors, so keeping ONE frame alive keeps its group's pinned pages, and
     # list(generator) page-locks the whole output.  The reference hands out independent pageable .cpu() copies; copying
@@ -213,10 +240,11 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
     slots = [_Slot(group, frame_shape, probe.dtype, std_shape, chw, dev, cv, data) for _ in range(_SLOTS)]
     compute = torch.cuda.current_stream(dev)
     h2d, d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
-    in_flight = deque()  # (slot, n frames, pinned lin, pinned std, metas)
+    in_flight = deque()  # (slot, n frames, pinned lin, pinned std, metas, device dark fields the group's launches read)
+    pending = None       # what dark.match raised for a frame: raised once the frames in front of it have been yielded
 
     def drain_one():
-        slot, k, lin_host, std_host, metas = in_flight.popleft()
+        slot, k, lin_host, std_host, metas, _ = in_flight.popleft()
         slot.copied_out.synchronize()
         slot.busy = False
         ranges = slot.consts_host[:k, 1].tolist() if data else None
@@ -231,14 +259,22 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
         if slot.busy:  # its previous group is the oldest in flight: hand those frames over first
             yield from drain_one()
         g += 1
-        k, metas = 0, []
+        k, metas, pairs = 0, [], []
         with torch.cuda.stream(h2d):
             # the slot's input buffers were last read by the kernel of its previous group
             h2d.wait_event(slot.computed)
             while item is not None and k < group:
-                _, val_batch, std_batch, meta_batch = item
+                index_batch, val_batch, std_batch, meta_batch = item
                 if tuple(val_batch.shape[1:]) != frame_shape or val_batch.dtype != probe.dtype:
                     raise ValueError("all frames of one linearization run must share shape and dtype")
+                if dark is not None:
+                    try:
+                        matched = dark.match(index_batch, std_batch, std_mode)
+                    except Exception as exc:  # stop queueing here; the frames in front are still handed over first
+                        pending, item = exc, None
+                        break
+                    # (uploaded on this copy stream when the cache does not hold the pair)
+                    pairs.append(None if matched is None else dark.device_pair(*matched))
                 slot.frames[k].copy_(val_batch[0], non_blocking=True)
                 if with_std != (std_batch is not None):
                     # the pipeline's buffers and kernel variant follow the FIRST frame; a stream that mixes frames with
@@ -252,6 +288,8 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
                 k += 1
                 item = next(items, None)
             slot.copied_in.record(h2d)
+        if k == 0:  # (the match of the group's first frame raised)
+            break
         compute.wait_event(slot.copied_in)
         compute.wait_event(slot.copied_out)  # the slot's output buffers were last read by its previous copy-out
         if fused:
@@ -265,6 +303,8 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
                 lin, lin_std = ops.linearize_ingest_frames_strided(slot.frames[:k], step, stages, lut, interp, **args)
             else:
                 lin, lin_std = ops.linearize_ingest_frames(slot.frames[:k], stages, lut, interp, **args)
+        elif dark is not None:
+            lin, lin_std = _linearize_dark_runs(slot, k, pairs, with_std, lut, interp, std_mode, std_value, max_code)
         else:
             lin, lin_std = ops.linearize_frames(slot.frames[:k], lut, interp, std=slot.std[:k] if with_std else None,
                                                 std_mode=std_mode, std_value=std_value, max_code=max_code, want_std=True,
@@ -285,6 +325,27 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
             std_host.copy_(lin_std, non_blocking=True)
             slot.copied_out.record(d2h)
         slot.busy = True
-        in_flight.append((slot, k, lin_host, std_host, metas))
+        in_flight.append((slot, k, lin_host, std_host, metas, pairs))
     while in_flight:
         yield from drain_one()
+    if pending is not None:
+        raise pending
+
+
+def _linearize_dark_runs(slot, k, pairs, with_std, lut, interp, std_mode, std_value, max_code):
+    """The first ``k`` planar frames of ``slot`` into its output buffers, cut into maximal runs of frames with a matched dark
+    field (``pairs[i]``: its device (dark, dark std); one ct_linearize_dark launch on that range of the raw frames) and
+    without one (None: MissingValMode.SKIP_BATCH leaves the frame uncorrected; one ct_linearize_std launch)."""
+    a = 0
+    while a < k:
+        b = a + 1
+        while b < k and (pairs[b] is None) == (pairs[a] is None):
+            b += 1
+        args = dict(std=slot.std[a:b] if with_std else None, std_mode=std_mode, std_value=std_value, max_code=max_code,
+                    out=(slot.lin_out[a:b], slot.std_out[a:b]))
+        if pairs[a] is None:
+            ops.linearize_frames(slot.frames[a:b], lut, interp, want_std=True, **args)
+        else:
+            ops.linearize_dark_frames(slot.frames[a:b], [p[0] for p in pairs[a:b]], [p[1] for p in pairs[a:b]], lut, interp, **args)
+        a = b
+    return slot.lin_out[:k], slot.std_out[:k]

@@ -728,6 +728,80 @@ def hdr_merge_dark_batch(stack: torch.Tensor, exposures: torch.Tensor, dark: tor
     return (mean_out, std_out) if finalize else None
 
 
+MAX_LINEARIZE_DARK_FRAMES = nv.LINEARIZE_DARK_MAX_FRAMES  # frames one ct_linearize_dark launch takes (longer stacks: several)
+
+
+def _dark_per_frame(frames, darks, dark_stds):
+    """The dark fields and their stds of ``linearize_dark_frames`` as two lists of F contiguous float32 (C,H,W) device
+    tensors: each frame is a batch of one, so every entry passes ``_dark_arguments`` with B = 1."""
+    f = frames.shape[0]
+    if dark_stds is None:
+        raise ValueError("linearize_dark_frames propagates the dark field's uncertainty: dark_stds is required")
+    lists = []
+    for name, v in (("darks", darks), ("dark_stds", dark_stds)):
+        if isinstance(v, torch.Tensor):
+            if v.ndim != 4 or v.shape[0] != f:
+                raise ValueError(f"{name} must be (F, C, H, W) with F = {f} or a sequence of F tensors, got shape {tuple(v.shape)}")
+            v = [v[k:k + 1] for k in range(f)]
+        elif len(v) != f:
+            raise ValueError(f"{len(v)} {name} for {f} frames")
+        lists.append(v)
+    out, seen = ([], []), {}
+    for d, s in zip(*lists):
+        key = (id(d), id(s))
+        if key not in seen:  # a dark field shared between frames is checked (and made contiguous) once
+            for name, t in (("darks", d), ("dark_stds", s)):
+                if not isinstance(t, torch.Tensor):
+                    raise TypeError(f"{name} must hold torch.Tensors, got {type(t)}")
+            d4, s4 = (t if t.ndim == 4 else t.unsqueeze(0) for t in (d, s))
+            seen[key] = _dark_arguments(frames[:1], d4, s4, None)[:2]
+        out[0].append(seen[key][0])
+        out[1].append(seen[key][1])
+    return out
+
+
+def linearize_dark_frames(frames: torch.Tensor, darks, dark_stds, lut: Optional[torch.Tensor], interp: Optional[str] = "linear", *,
+                          std: Optional[torch.Tensor] = None, std_mode: str = "none", std_value: float = 0.0,
+                          max_code: Optional[float] = None, threshold: float = 0.05, alpha: float = 50.0, out=None):
+    """ct_linearize_dark on (F,C,H,W) frames -> (lin, std) float32 (F,C,H,W): for every frame k, bit for bit
+    ``xb, sig = dark_field_blur(frames[k:k+1], darks[k], dark_stds[k], ...)`` followed by
+    ``linearize_frames(xb, lut, interp, std=sig)``, in one launch per MAX_LINEARIZE_DARK_FRAMES frames and without the two
+    float32 stacks in between.
+
+    ``frames``: planar uint8 / uint16 codes (``max_code``) or float32 pixels; a view whose frames are contiguous but further
+    apart than C*H*W is read in place unless ``std`` is given.  ``darks`` / ``dark_stds``: sequences of F device tensors
+    (C,H,W) or (1,C,H,W), the dark field matched to each frame and its std (repeats allowed), or one (F,C,H,W) tensor each.
+    ``std`` / ``std_mode`` / ``std_value``: the uncertainty of the RAW image as ``dark_field_blur`` takes it.  ``out`` =
+    (lin, std): as in ``linearize_frames``.  LOOKUP has no gradient path to the image (RuntimeError, as ``linearize_frames``
+    with uncertainties)."""
+    _check_stack(frames, "frames")
+    f, c, h, w = frames.shape
+    dev = frames.device
+    if f < 1:
+        raise ValueError("no frames")
+    if std is not None:
+        # (explicit uncertainties are dense: so are the frames then, the kernel strides both alike)
+        std_mode, std, frames = "explicit", _explicit_std(std, frames, "frames"), frames.contiguous()
+    if std_mode not in _STD:
+        raise ValueError(f"unknown std_mode {std_mode}")
+    max_code = _default_max_code(frames, max_code)
+    dark_list, dark_std_list = _dark_per_frame(frames, darks, dark_stds)
+    icrf, lut_keep = _icrf_struct(lut, interp, c)
+    geom = _geometry(frames, None)
+    if f == 1:  # (the stride of a single frame means nothing)
+        geom.image_stride = c * h * w
+    lin, std_out = _lin_std_out(out, (f, c, h, w), dev, True, lin_required=True)
+    dark_arr = (ctypes.c_void_p * f)(*[t.data_ptr() for t in dark_list])
+    dark_std_arr = (ctypes.c_void_p * f)(*[t.data_ptr() for t in dark_std_list])
+    with torch.cuda.device(dev):
+        rc = nv.load().ct_linearize_dark(_ptr(frames), _DTYPE[frames.dtype], float(max_code or 1.0), f, ctypes.byref(geom), _ptr(std),
+                                         _STD[std_mode], float(std_value), dark_arr, dark_std_arr, float(threshold), float(alpha),
+                                         ctypes.byref(icrf), _ptr(lin), _ptr(std_out), _stream(dev))
+    nv.check(rc, "ct_linearize_dark")
+    del lut_keep, dark_list, dark_std_list
+    return lin, std_out
+
+
 # ---- strided downscale of raw codes (StridedDownscale folded in front of the code-domain kernels) -----------------
 def downscaled_shape(shape, step: int, layout: str = "nchw"):
     """Shape of ``x[..., ::step, ::step]`` taken on the spatial axes of a 4-D stack in ``layout``."""

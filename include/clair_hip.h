@@ -354,6 +354,34 @@ int ct_hdr_merge_dark_batch(const void *stack_dev, int32_t dtype, float max_code
                             void *stream);
 
 /*
+ * ct_linearize_dark -- that blur and the body of linearize_dataset_generator in ONE pass over F independent raw frames, each
+ * its own batch of one (linearization.py:42) with its own matched dark field: for every frame lin_out and std_out are bit for
+ * bit those of ct_dark_field_blur on it (batch = 1, dark_batch = 1) into float32 xb and sigma_eff followed by
+ * ct_linearize_std on (xb, CT_DTYPE_F32, std = sigma_eff, CT_STD_EXPLICIT) -- without the two stacks: sizeof(code) + 8 bytes
+ * read per sample (+ 4 with explicit image uncertainties) and 8 written, where the two launches move 16 B per sample more.
+ *   frames_dev   (F, C, H, W) codes (max_code) or float32 pixels, CT_LAYOUT_NCHW only, geom->image_stride between frames; the
+ *                whole image (no row band: row_offset 0, h_tile == h_global)
+ *   std_dev / std_mode / std_value   sigma of the RAW image as ct_dark_field_blur takes it (EXPLICIT: laid out like the
+ *                frames; CT_STD_MULTIPLIER multiplies the raw x, not xb)
+ *   dark_devs, dark_std_devs   HOST arrays of n_frames device pointers, read during the call: the (C, H, W) float32 dark field
+ *                and its std matched to each frame; pointers may repeat.  They travel in the kernel's argument block,
+ *                CT_LINEARIZE_DARK_MAX_FRAMES per launch; longer lists are walked in launches of that many
+ *   lin_out_dev, std_out_dev   (F, C, H, W) float32, dense; both required (uncertainties are always propagated here)
+ * Status: what ct_dark_field_blur refuses with its status and in its order (a missing pointer, n_frames <= 0 or a NULL entry
+ * of either array, width < 2 or h_global < 2, a layout other than NCHW: CT_ERR_UNSUPPORTED, a bad std mode, a row band:
+ * CT_ERR_UNSUPPORTED, a short image_stride, an unknown dtype or max_code: CT_ERR_UNSUPPORTED), then what ct_linearize_std
+ * refuses for (xb, sigma_eff): the model, CT_ERR_NO_GRADIENT_PATH for LOOKUP, CT_ERR_TOO_LARGE for 2^31 elements per frame
+ * or a LUT beyond 160 KiB of LDS; last, CT_ERR_INVALID_ARGUMENT for a pointer not aligned to its element.  Every argument is
+ * validated before anything touches the device.  Allocates nothing, synchronises nothing, reads nothing back, never writes
+ * the frames or the dark fields.
+ */
+#define CT_LINEARIZE_DARK_MAX_FRAMES 16
+int ct_linearize_dark(const void *frames_dev, int32_t dtype, float max_code, int64_t n_frames, const ct_geometry *geom,
+                      const float *std_dev, int32_t std_mode, float std_value, const float *const *dark_devs,
+                      const float *const *dark_std_devs, float threshold, float alpha, const ct_icrf *icrf,
+                      float *lin_out_dev, float *std_out_dev, void *stream);
+
+/*
  * ct_video_stats_batch -- loop body of compute_video_mean_and_std
  * (clair_torch/inference/inferential_statistics.py:38-47): optional ICRF linearization of a batch of frames and the
  * unweighted WBOMeanVar update (clair_torch/common/statistics.py:213-259), float32 like the reference.
