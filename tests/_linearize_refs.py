@@ -39,12 +39,24 @@ TOL = {
     ("lut_grad", "lookup"): (1.8e-6, 5.1e-7),   # measured 4.271e-7, 1.267e-7 (bw_lookup_c4 band0 / bw_lookup_c1 whole)
     ("lut_grad", "linear"): (9.9e-6, 5.3e-7),   # measured 2.467e-6, 1.322e-7 (bw_repeat_linear_c3 whole: 2048 bins of a few +- terms)
     ("lut_grad", "catmull"): (3.2e-6, 7.3e-7),  # measured 7.811e-7, 1.821e-7 (bw_catmull_c1 band0 / bw_catmull_c3 whole)
+    # The cases in which some order of the kernel's float32 flushes leaves less than the factor 4 of the three entries above
+    # (FLUSH_SHARE_OF_TOL below): element-wise they are held to order_bound (inf here), norm-wise to 4x the worst error of
+    # the orders of the flush-order study against the float64 reference -- measured on the restatement bwd_partials /
+    # flush_in_order, not on the kernel -- rounded up.  Measured norm-wise in the comments.
+    ("lut_grad any order", "bw_catmull_c3"): (np.inf, 7.9e-7),            # 1.958e-7 (whole, descending value reversed)
+    ("lut_grad any order", "bw_repeat_linear_c3"): (np.inf, 4.3e-6),      # 1.060e-6 (whole, descending value reversed)
+    ("lut_grad any order", "bw_hot_lookup_c1"): (np.inf, 6.8e-6),         # 1.699e-6 (whole, positive first)
+    ("lut_grad any order", "bw_hot_linear_c3"): (np.inf, 3.5e-6),         # 8.686e-7 (whole, positive first reversed)
+    ("lut_grad any order", "bw_hot_catmull_c2"): (np.inf, 2.5e-6),        # 6.067e-7 (whole, descending value reversed)
+    ("lut_grad any order", "bw_cancel_linear_c3"): (np.inf, 1.7e-6),      # 4.149e-7 (whole, descending value)
+    ("lut_grad any order", "bw_untouched_catmull_c4"): (np.inf, 6.5e-7),  # 1.624e-7 (band1, descending value)
 }
 
 def check(got, ref, key, what):
     """got against the float64 reference at TOL[key] in both measures of _util.assert_parity; exactly where TOL is 0."""
     from _util import assert_parity
     elem, norm = TOL[key]
+    assert np.isfinite(elem), key     # ("lut_grad any order": check_lut_grad)
     if elem == 0.0:
         assert np.array_equal(np.asarray(got, dtype=np.float64), ref), what
     else:
@@ -489,26 +501,54 @@ BACKWARD_CASES = [
     ("bw_catmull_c3", "catmull", 3, 17, 13, 7, 8, 33),
     ("bw_catmull_c4", "catmull", 4, 9, 7, 3, 11, 52),
     ("bw_repeat_linear_c3", "linear", 3, 41, 67, 19, 8, 2048),
+    # ---- cases that put weight on the flush of the LUT gradient (BACKWARD_KIND; conditions asserted on the CPU from
+    # bwd_partials by test_linearize_refs_host.py::test_flush_cases_hold_their_conditions)
+    # "hot": L = 9, so 8 workgroups fit a compute unit and grid.x is Q / 256 uncapped; three quarters of the pixels sit at
+    # x = 0.55 (LUT coordinate 4.4), so every one of the gx * 8 >= 64 workgroups flushes a nonzero partial into the same
+    # bins: the largest m the kernel produces at test size
+    ("bw_hot_lookup_c1", "lookup", 1, 32, 64, 13, 8, 9),        # gx = 8: 64 workgroups
+    ("bw_hot_linear_c3", "linear", 3, 24, 32, 11, 8, 9),        # gx = 9: 72 workgroups, one hot interval per LUT row
+    ("bw_hot_catmull_c2", "catmull", 2, 32, 40, 13, 11, 9),     # gx = 10: 80 workgroups, two images per workgroup for some
+    # "cancel": images 4..7 repeat the pixels of images 0..3 (other workgroups: grid.y = 8), and where x < 0.4 their
+    # upstream gradient is minus that of images 0..3 up to 1e-4: the bins below 0.4 (L - 1) cancel to |S| < 1e-3 A
+    ("bw_cancel_linear_c3", "linear", 3, 17, 29, 7, 8, 64),
+    # "untouched": x in [0.3, 0.6], so the bins below and above get nothing; C = 4 and w = 2 with an even h_global, so the
+    # one-row band [0, 1) reaches LUT rows 0 and 1 only (row = 2 ((c h_global + y) % 2) + x) and rows 2, 3 stay empty
+    ("bw_untouched_catmull_c4", "catmull", 4, 64, 2, 1, 8, 64),
 ]
 BACKWARD_NAMES = [c[0] for c in BACKWARD_CASES]
+BACKWARD_KIND = {n: ({"hot": "hot", "cancel": "cancel", "untouched": "untouched"}.get(n.split("_")[1], "plain")) for n in BACKWARD_NAMES}
+HOT_X = np.float32(0.55)
 
 
 @functools.lru_cache(maxsize=None)
 def backward_case(name):
-    """Namespace: mode, C, hg, w, split, N, L, lut, x and grad_out (N, C, hg, w) float32 (x with the float32 edge values,
-    below 0 and above 1 included), seed.  Shared arrays: do not write to them."""
+    """Namespace: mode, C, hg, w, split, N, L, kind, lut, x and grad_out (N, C, hg, w) float32 (x with the float32 edge
+    values, below 0 and above 1 included; not for kind "untouched", whose x stays in [0.3, 0.6]), seed.  Shared arrays: do
+    not write to them."""
     k = BACKWARD_NAMES.index(name)
     _, mode, C, hg, w, split, N, L = BACKWARD_CASES[k]
-    cs = SimpleNamespace(name=name, mode=mode, C=C, hg=hg, w=w, split=split, N=N, L=L, seed=5000 + k)
+    cs = SimpleNamespace(name=name, mode=mode, C=C, hg=hg, w=w, split=split, N=N, L=L, seed=5000 + k, kind=BACKWARD_KIND[name])
     g = np.linspace(0.0, 1.0, L, dtype=np.float64)
     cs.lut = np.stack([g ** p for p in (1.5, 2.0, 2.5, 3.0)[:C]]).astype(np.float32)
     rng = np.random.default_rng(cs.seed)
     x = (rng.random((N, C, hg, w), dtype=np.float32) * np.float32(1.1) - np.float32(0.05)).astype(np.float32)
-    edges = edge_values("f32", None, L)
-    for lo, hi in ((0, split), (split, hg)):
-        _place(x[:, :, lo:hi], edges)
+    go = rng.standard_normal((N, C, hg, w), dtype=np.float32)
+    if cs.kind == "hot":
+        x[rng.random(x.shape) < 0.75] = HOT_X
+    elif cs.kind == "cancel":
+        half = N // 2
+        x[half:] = x[:half]
+        delta = (np.float32(1) + np.float32(1e-4) * rng.standard_normal(x[:half].shape, dtype=np.float32)).astype(np.float32)
+        go[half:] = np.where(x[:half] < np.float32(0.4), -(go[:half] * delta), go[half:]).astype(np.float32)
+    elif cs.kind == "untouched":
+        x = (np.float32(0.3) + np.float32(0.3) * rng.random(x.shape, dtype=np.float32)).astype(np.float32)
+    if cs.kind != "untouched":
+        edges = edge_values("f32", None, L)
+        for lo, hi in ((0, split), (split, hg)):
+            _place(x[:, :, lo:hi], edges)     # (cancel: an edge value breaks its pair, 26 of 5916)
     cs.x = x
-    cs.grad_out = rng.standard_normal((N, C, hg, w), dtype=np.float32)
+    cs.grad_out = go
     for a in (cs.lut, cs.x, cs.grad_out):
         a.setflags(write=False)
     return cs
@@ -546,3 +586,224 @@ def flush_bound(abs_bins, workgroups):
     (workgroups + 1) 2^-24 abs_bins, whatever the order of the flushes.  (1.001: abs_bins comes from the float64
     reference, the products are float32.)"""
     return (workgroups + 1) * 2.0 ** -24 * np.asarray(abs_bins) * 1.001
+
+
+# ---- the summation of linearize_bwd_kernel, restated ---------------------------------------------------------------
+_U = 2.0 ** -24          # unit roundoff of float32
+_CATMULL_COEF = ((-0.5, 1.0, -0.5, 0.0), (1.5, -2.5, 0.0, 1.0), (-1.5, 2.0, 0.5, 0.0), (0.5, -0.5, 0.0, 0.0))   # t^3, t^2, t, 1
+
+
+def _bwd_products(x, go, L, mode):
+    """[(bin index, float32 product, slack, rounding)] per tap, for the samples x / go (any shape, float32), formed as
+    linearize_bwd_kernel forms them.  LOOKUP (go itself) and LINEAR (fl(go fl(1 - t)), fl(go t)) are restated bit for bit:
+    x * top, the clamp, floor, s - floor(s) (exact), 1 - t and the two products are single float32 operations with
+    nothing for the compiler to contract; slack None.  CATMULL: the weights are the float32 left-to-right evaluation of
+    the polynomials, which the compiler may contract into FMAs in several ways; slack bounds |kernel's product - this
+    product| (see order_bound).  rounding bounds |this product - go * (the exact weight of the float32 t)|: 0 for LOOKUP,
+    2 roundings of the product for LINEAR (1 - t and the product), the weight's 6 2^-24 T and the product's own for
+    CATMULL."""
+    top = np.float32(L - 1)
+    s = (x * top).astype(np.float32)
+    if mode == "lookup":
+        r = np.minimum(np.maximum(np.rint(s), np.float32(0)), top)
+        return [(r.astype(np.int64), go, None, np.zeros(go.shape))]
+    s = np.minimum(np.maximum(s, np.float32(0)), top)
+    fl = np.floor(s)
+    i0 = fl.astype(np.int64)
+    t = (s - fl).astype(np.float32)
+    if mode == "linear":
+        p0, p1 = (go * (np.float32(1) - t).astype(np.float32)).astype(np.float32), (go * t).astype(np.float32)
+        return [(i0, p0, None, 2.001 * _U * np.abs(p0.astype(np.float64))),
+                (np.minimum(i0 + 1, L - 1), p1, None, _U * np.abs(p1.astype(np.float64)))]
+    t2 = (t * t).astype(np.float32)
+    t3 = (t2 * t).astype(np.float32)
+    f = np.float32
+    w = ((f(-0.5) * t3 + t2) - f(0.5) * t, (f(1.5) * t3 - f(2.5) * t2) + f(1.0), (f(-1.5) * t3 + f(2.0) * t2) + f(0.5) * t, f(0.5) * t3 - f(0.5) * t2)
+    t64 = t.astype(np.float64)
+    ago = np.abs(go.astype(np.float64))
+    out = []
+    for wk, coef, idx in zip(w, _CATMULL_COEF, (np.maximum(i0 - 1, 0), i0, np.minimum(i0 + 1, L - 1), np.minimum(i0 + 2, L - 1))):
+        assert wk.dtype == np.float32
+        terms = abs(coef[0]) * t64 ** 3 + abs(coef[1]) * t64 ** 2 + abs(coef[2]) * t64 + abs(coef[3])
+        has_sum = sum(c != 0 for c in coef) > 1          # (every weight here is a sum; kept for the derivation's sake)
+        slack = ago * (15 * _U * terms * has_sum) + (ago + 1) * 2.0 ** -126 * (t64 != 0)
+        out.append((idx, (go * wk).astype(np.float32), slack, ago * 7.001 * _U * terms + (ago + 1) * 2.0 ** -126))
+    return out
+
+
+def bwd_partials(cs, r0, rows, tile, compute_units):
+    """What every workgroup of linearize_bwd_kernel flushes into every bin for rows [r0, r0 + rows) of a backward case,
+    restated from the kernel and bwd_launch (bwd_grid_of).  Workgroup (bx, by) owns the elements q = bx 256 + tid,
+    += gx 256 of the images n = by, += gy; the LUT row of an element is lut_rows; the products are those of
+    _bwd_products; a workgroup adds them per bin in float64 (the LDS histogram) and rounds the bin to float32 once.
+    Namespace: grid; partials (gx gy, C, L) float32 in the order by * gx + bx; per bin m (nonzero partials), A (sum
+    |partial|), S (float64 sum of the partials: what the flushes add up to before their own rounding), E (how far S may
+    be from the float64 reference icrf_backward_f64: the roundings of the float32 products, _bwd_products, and 2^-24 A for
+    the rounding of the partials); slack (gx gy, C, L) float64, how far the kernel's partial may be from this one
+    (order_bound)."""
+    x = np.ascontiguousarray(cs.x[:, :, r0:r0 + rows])
+    go = np.ascontiguousarray(cs.grad_out[:, :, r0:r0 + rows])
+    N, C, h, w = x.shape
+    Q, L = C * h * w, cs.L
+    grid = bwd_grid_of(Q, N, C, L, cs.mode, compute_units)
+    W = grid.gx * grid.gy
+    bx = (np.arange(Q, dtype=np.int64) // 256) % grid.gx
+    by = np.arange(N, dtype=np.int64) % grid.gy
+    wg = by[:, None] * grid.gx + bx[None, :]
+    row = lut_rows(C, h, w, cs.mode, tile).reshape(1, Q)
+    base = ((wg * C + row) * L).reshape(-1)
+    size = W * C * L
+    total, absolute, count, loose = np.zeros(size), np.zeros(size), np.zeros(size, dtype=np.int64), np.zeros(size)
+    rounding = np.zeros(C * L)
+    for idx, prod, slack, rnd in _bwd_products(x.reshape(N, Q), go.reshape(N, Q), L, cs.mode):
+        assert prod.dtype == np.float32
+        flat, p64 = base + idx.reshape(-1), prod.reshape(-1).astype(np.float64)
+        total += np.bincount(flat, weights=p64, minlength=size)
+        absolute += np.bincount(flat, weights=np.abs(p64), minlength=size)
+        count += np.bincount(flat, weights=(p64 != 0), minlength=size).astype(np.int64)
+        if slack is not None:
+            loose += np.bincount(flat, weights=slack.reshape(-1), minlength=size)
+        rounding += np.bincount((np.broadcast_to(row, idx.shape) * L + idx).reshape(-1), weights=rnd.reshape(-1), minlength=C * L)
+    partials = total.astype(np.float32)
+    # the float64 LDS atomics are unordered too: a sum of n float32 products moves by at most n 2^-53 of sum |product|, and
+    # the rounding of the bin to float32 turns that (and the CATMULL slack) into at most one float32 spacing more.  One
+    # product is its own sum: exact.
+    moved = loose + 2 * count * 2.0 ** -53 * absolute
+    slack = np.where((count > 1) | (loose > 0), moved + 2.0 ** -23 * (np.abs(partials) + moved) + 2.0 ** -149, 0.0)
+    shape = (W, C, L)
+    partials, slack = partials.reshape(shape), slack.reshape(shape)
+    p64 = partials.astype(np.float64)
+    A = np.abs(p64).sum(axis=0)
+    E = rounding.reshape(C, L) + _U * A + N * Q * 2.0 ** -51 * absolute.reshape(shape).sum(axis=0)
+    return SimpleNamespace(grid=grid, partials=partials, slack=slack, m=(partials != 0).sum(axis=0), A=A, S=p64.sum(axis=0), E=E)
+
+
+def flush_in_order(partials, order):
+    """The float32 lut_grad that the flushes of `partials` (workgroups, C, L) give in a given order: np.float32 adds to a
+    zero-filled output, zero partials skipped as the kernel skips them (adding them would change nothing).  order: a
+    permutation of the workgroups, or a (workgroups, C, L) integer array holding one permutation per bin."""
+    order = np.asarray(order)
+    p = partials[order] if order.ndim == 1 else np.take_along_axis(partials, order, axis=0)
+    assert p.dtype == np.float32
+    acc = np.zeros(p.shape[1:], dtype=np.float32)
+    for k in range(p.shape[0]):
+        acc = acc + p[k]
+    return acc
+
+
+# The flush-order study of test_linearize_refs_host.py (test_every_flush_order_stays_within_order_bound): the whole image
+# and both bands of every backward case on 256 compute units; the workgroups ascending and descending, 24 seeded random
+# orders of the workgroups, 8 seeded random orders per bin, and per bin the adversarial orders (positive partials first,
+# ascending magnitude, descending value, and the reverse of each).  The study re-measures these figures (to 2 %).
+# ORDER_BOUND_USED: the largest |flush_in_order - S| / order_bound: the bound is not vacuous, an order uses this share of
+# it.  (0: one workgroup, nothing to order.  CATMULL and m >= 64 use least: 15 roundings of slack per product where one or
+# two occur, and a bound linear in m.)
+ORDER_BOUND_USED = {
+    "bw_lookup_c1": 0.6406, "bw_lookup_c3": 0.3385, "bw_lookup_c4": 0.0,           # band0 ascending / band0 per bin#2 / -
+    "bw_linear_c1": 0.2915, "bw_linear_c3": 0.9026, "bw_linear_c4": 0.9784,        # band0 / band1 / band0, all ascending
+    "bw_catmull_c1": 0.0, "bw_catmull_c3": 0.0345, "bw_catmull_c4": 0.0747,        # - / band1 descending magnitude / band0 ascending value
+    "bw_repeat_linear_c3": 0.9549,                                                 # band0 ascending
+    "bw_hot_lookup_c1": 0.0981, "bw_hot_linear_c3": 0.0913, "bw_hot_catmull_c2": 0.0257,   # descending / ascending / descending value
+    "bw_cancel_linear_c3": 0.2278, "bw_untouched_catmull_c4": 0.0405,              # band1 descending value / band0 workgroups#18
+}
+# FLUSH_SHARE_OF_TOL: the largest share of TOL[("lut_grad", mode)] (element, norm-wise) that some order uses against the
+# float64 reference.  TOL is 4x the error of ONE order (the sequential scatter-add of the CPU oracle); a case whose worst
+# order leaves less than that factor 4 (a share above 0.25) is not compared at TOL on the GPU, where the order is the
+# scheduler's, but by assert_flush and norm-wise at TOL[("lut_grad any order", case)] (flush_keeps_margin).
+# bw_repeat_linear_c3, whole image: per bin positive partials first gives an element error of 3.202e-5 = 3.23 TOL (the bins
+# at both ends of the LUT, where the 5 % of samples below 0 and above 1 pile up 250 sign-mixed partials that cancel
+# 30-fold); descending value, reversed, a norm-wise error of 1.060e-6 = 2.0 TOL; the worst of the 32 random orders 6.1e-6 =
+# 0.62 TOL.  bw_untouched_catmull_c4: the median |ref| is 0, so the element measure is relative to |ref| alone.
+FLUSH_SHARE_OF_TOL = {
+    "bw_lookup_c1": (0.1347, 0.1902), "bw_lookup_c3": (0.2296, 0.2025), "bw_lookup_c4": (0.0316, 0.0520),
+    "bw_linear_c1": (0.0318, 0.2015), "bw_linear_c3": (0.0208, 0.0914), "bw_linear_c4": (0.0283, 0.1615),
+    "bw_catmull_c1": (0.2478, 0.1016), "bw_catmull_c3": (0.3014, 0.2682), "bw_catmull_c4": (0.1360, 0.1295),
+    "bw_repeat_linear_c3": (3.2345, 2.0006),
+    "bw_hot_lookup_c1": (0.9695, 3.3307), "bw_hot_linear_c3": (0.1619, 1.6389), "bw_hot_catmull_c2": (0.5371, 0.8311),
+    "bw_cancel_linear_c3": (0.3413, 0.7828), "bw_untouched_catmull_c4": (730.5, 0.2224),
+}
+# Where order_bound replaces the element test of TOL: (least share of the touched bins whose allowance got smaller, largest
+# factor by which one got larger), over the whole image and both bands; old allowance TOL (|ref| + median |ref|).  Bins
+# that nothing reaches had an allowance and now have none.  The large factors are bins whose partials cancel (|ref| far
+# below A: no tolerance relative to |ref| holds in every order there) and, for CATMULL, the contraction slack.
+ALLOWANCE_VS_TOL = {
+    "bw_catmull_c3": (0.0, 14.8), "bw_repeat_linear_c3": (0.996, 248.0), "bw_hot_lookup_c1": (0.0, 43.2),
+    "bw_hot_linear_c3": (0.111, 5.31), "bw_hot_catmull_c2": (0.0, 141.4), "bw_cancel_linear_c3": (0.213, 17.0),
+    "bw_untouched_catmull_c4": (0.0, 7.2e5),
+}
+
+
+def flush_keeps_margin(name):
+    """Whether every studied flush order of a backward case leaves the factor 4 of TOL[("lut_grad", mode)] in both measures."""
+    return max(FLUSH_SHARE_OF_TOL[name]) * 4 <= 1
+
+
+def order_bound(parts):
+    """Per-bin bound on |float32 lut_grad - parts.S| of one launch of linearize_bwd_kernel, whatever the order in which
+    its workgroups flush; parts from bwd_partials.  From the code:
+
+    * lut_grad is zero-filled; a workgroup flushes v = (float)hist[k] with atomicAdd(&lut_grad[k], v) unless v == 0.  With
+      the partials v_1..v_m of a bin given, the first add (to +0.0) is exact and each of the other m - 1 rounds a running
+      sum r to float32: an error of at most 2^-24 |r|, and |r| <= A (1 + 2^-24)^m with A = sum |v_j|, in every order.
+      Hence |lut_grad - sum v_j| <= (m - 1) 2^-24 A (1 + m 2^-24).
+    * What the restatement cannot pin is whether the kernel's v_j are parts.partials (parts.slack, per workgroup and bin):
+      - LOOKUP, LINEAR: the products are restated bit for bit (_bwd_products), so only the order of the float64 LDS atomics
+        is left.  A float64 sum of n float32 products moves by at most n 2^-53 sum |product| between two orders, which
+        changes its float32 rounding only at a rounding tie, and then by one spacing: slack = 2^-23 |v| (+ twice that
+        movement, + 2^-149), and 0 where a workgroup has one nonzero product for the bin (its sum is the product) or none.
+      - CATMULL: with t2 = fl(t t), t3 = fl(t2 t) (relative errors 2^-24 and 2 2^-24; no addition to contract with), a
+        weight sum_k c_k t^k of at most three nonzero terms is evaluated with one rounding per coefficient product (none if
+        it is contracted or c_k is a power of two) and two additions, each rounding a partial sum of at most T = sum_k
+        |c_k| t^k: |w - exact| <= (3 + 2) 2^-24 T, taken as 6 2^-24 T, for every contraction.  Two evaluations differ by at
+        most 12 2^-24 T, their products with go by 12 2^-24 |go| T plus the two product roundings, 2 2^-24 |go| T: taken
+        as 15 2^-24 |go| T per tap, plus (|go| + 1) 2^-126 for t so small that t^2, t^3 or the product underflow.  These
+        add up over a workgroup's samples, and the rounding of the bin adds one spacing as above.
+      A partial that may be nonzero in the kernel (slack > 0) counts in m; A takes the slacks in.
+    * bound = (m - 1) 2^-24 A (1 + m 2^-24) + sum of the slacks.  A bin no workgroup has a nonzero product for has bound 0:
+      the kernel skips zero partials, so the zero-filled +0.0 stays.  A bin with m = 1 has only its slack.
+    Measured use of the bound: ORDER_BOUND_USED above."""
+    live = (parts.partials != 0) | (parts.slack > 0)
+    m = live.sum(axis=0)
+    loose = parts.slack.sum(axis=0)
+    a = parts.A + loose
+    return np.where(m > 0, np.maximum(m - 1, 0) * _U * a * (1 + m * _U) + loose, 0.0)
+
+
+def assert_flush(got, parts, what):
+    """The order-free assertions on a float32 lut_grad of one launch, against bwd_partials: every bin within order_bound of
+    parts.S; a bin no workgroup has a nonzero product for is +0.0 (bound 0, and no sign bit); a bin one workgroup feeds is
+    that workgroup's partial up to its slack (its bound: there is no add to round).  Returns the largest |error| / bound."""
+    got = np.asarray(got)
+    assert got.dtype == np.float32 and got.shape == parts.S.shape, what
+    bound = order_bound(parts)
+    err = np.abs(got.astype(np.float64) - parts.S)
+    live = ((parts.partials != 0) | (parts.slack > 0)).sum(axis=0)
+    empty, single = live == 0, live == 1
+    assert not got[empty].any() and not np.signbit(got[empty]).any(), f"{what}: {int((got[empty] != 0).sum())} untouched bins are not +0.0"
+    one = np.abs(got.astype(np.float64) - parts.partials.astype(np.float64).sum(axis=0))[single]
+    assert np.all(one <= parts.slack.sum(axis=0)[single]), f"{what}: {int((one > parts.slack.sum(axis=0)[single]).sum())} bins of one partial differ from it"
+    bad = err > bound
+    assert not bad.any(), (f"{what}: {int(bad.sum())} of {bad.size} bins beyond order_bound, worst |error| / bound "
+                           f"{float(np.max(err[bad] / bound[bad])) if np.all(bound[bad] > 0) else float('inf'):.3f}")
+    return float(np.max(err / np.where(bound > 0, bound, 1.0)))
+
+
+def check_lut_grad(got, cs, parts, ref, what):
+    """A float32 lut_grad of one launch on a band of a backward case: the order-free assertions (assert_flush, its use of the
+    bound recorded in _util.OBSERVED as "elem" against an "elem_tol" of 1), and against the float64 reference ref at
+    TOL[("lut_grad", mode)] where every flush order keeps that tolerance's margin, else norm-wise at
+    TOL[("lut_grad any order", case)]."""
+    import os
+    from _util import OBSERVED, rel_norm
+    used = assert_flush(got, parts, what)
+    test = os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0].split("::")[-1].split("[")[0]
+    OBSERVED.append({"test": test, "what": what + " |error| / order_bound", "norm": rel_norm(got, parts.S) if parts.S.any() else 0.0, "norm_tol": 0.0,
+                     "elem": used, "elem_tol": 1.0, "n": int(parts.S.size)})
+    if flush_keeps_margin(cs.name):
+        check(got, ref, ("lut_grad", cs.mode), what + " vs f64")
+    else:
+        norm_tol = TOL[("lut_grad any order", cs.name)][1]
+        norm = rel_norm(got, ref)
+        OBSERVED.append({"test": test, "what": what + " vs f64, norm-wise", "norm": norm, "norm_tol": norm_tol, "elem": 0.0, "elem_tol": 1.0, "n": int(ref.size)})
+        assert norm <= norm_tol, f"{what}: norm-wise rel error {norm:.3e} > {norm_tol:.1e}"
+    return used

@@ -15,10 +15,23 @@ checks that every path meets every interpolation mode, dtype and std mode it sup
 | linearize_kernel<8> + <1> behind a padded stride (the C entry point): interleaved C = 4, 1, 3 (plane % 4 != 0) | pt_* |
 | linearize_kernel<1>: nchw with Q % 4 = 1, 2, 3 and every std mode, Q < 4, a frame pointer 1 element into its allocation, frames [1:] of odd Q, several frames of Q % 4 != 0 behind a padded stride of 8 k (sc_band_pad_*); interleaved of Q % 8 != 0 | sc_*, se_* |
 | the frame walk f += gridDim.y three times (131 073 frames), planar and rgb | test_many_frames |
-| ct_linearize_bwd: 3 modes x C = 1, 3, 4 x n_images = 1, 8, 11, whole image and two bands, need_x / need_lut alone, a grid-stride loop that runs twice | test_backward |
+| ct_linearize_bwd: 3 modes x C = 1, 3, 4 x n_images = 1, 8, 11, whole image and two bands, need_x / need_lut alone, a grid-stride loop that runs twice | test_backward: bw_lookup_*, bw_linear_*, bw_catmull_*, bw_repeat_linear_c3 |
+| the flush of the LUT gradient, one hot bin: 64 / 72 / 80 workgroups (8 per compute unit, grid.x uncapped) flush a nonzero partial into the same bins, one case per mode | test_backward: bw_hot_lookup_c1, bw_hot_linear_c3, bw_hot_catmull_c2 |
+| the flush, cancellation: a quarter of the touched bins add up to less than 1e-3 of their partials' magnitudes | test_backward: bw_cancel_linear_c3 |
+| the flush, untouched bins: LUT ranges no sample reaches, and in the one-row band two whole LUT rows; exactly +0.0, with and without grad_x | test_backward: bw_untouched_catmull_c4 |
 | torch.ops.clair_hip.icrf_forward / icrf_backward with h_global, row_offset | test_dispatcher_ops_take_bands |
+
+The LUT gradient is the one result here that float32 global atomics add up, so its last bits follow the order in which the
+workgroups flush.  Order-free, and so the same in every run: grad_x bit for bit; _linearize_refs.assert_flush (every bin
+within order_bound of the restated sum of the workgroups' partials, untouched bins +0.0, bins of one partial equal to it);
+the additivity over the bands at flush_bound (order_bound is not uniformly tighter than flush_bound: CATMULL carries a
+contraction slack); the dispatcher's 2 flush_bound.  The comparison of lut_grad with the float64 reference at
+TOL[("lut_grad", mode)] is four times ONE order's error and is kept only for the cases in which every order of the CPU
+study (test_linearize_refs_host.py) leaves that factor (flush_keeps_margin); the others are compared norm-wise at
+TOL[("lut_grad any order", case)].
 """
 import ctypes
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -191,8 +204,11 @@ def test_many_frames(dev, name):
 @pytest.mark.parametrize("name", lr.BACKWARD_NAMES)
 def test_backward(dev, name):
     """The whole image and its two bands.  grad_x: bit for bit with autograd of the eager oracle (signed zeros aside; LOOKUP:
-    zeros), the same bits with and without the LUT gradient.  lut_grad: within the measured tolerance of the float64
-    reference, with and without grad_x, and additive over the two bands up to the flush order (_linearize_refs.flush_bound)."""
+    zeros), the same bits with and without the LUT gradient.  lut_grad, with and without grad_x: per bin within order_bound
+    of the sum of the partials that the workgroups of the device's grid flush, untouched bins +0.0, bins of one partial
+    equal to it (_linearize_refs.check_lut_grad; the share of the bound used goes to parity_observed.json); against the
+    float64 reference at the measured tolerance where every flush order keeps its margin, else norm-wise; and additive
+    over the two bands up to the flush order (_linearize_refs.flush_bound)."""
     from clair_torch_amd import ops
     cs = lr.backward_case(name)
     cus = torch.cuda.get_device_properties(dev).multi_processor_count
@@ -214,8 +230,10 @@ def test_backward(dev, name):
         else:
             assert np.array_equal(gx.cpu().numpy(), gx_o), what + " grad_x vs autograd"
             lr.check(gx.cpu().numpy(), ref_gx, ("grad_x", cs.mode), f"lin {what} grad_x vs f64")
+        parts = lr.bwd_partials(cs, r0, rows, tile, cus)
         for g, form in ((gl, "both"), (gl_only, "lut only")):
-            lr.check(g.cpu().numpy(), ref_gl, ("lut_grad", cs.mode), f"lin {what} lut_grad ({form}) vs f64")
+            used = lr.check_lut_grad(g.cpu().numpy(), cs, parts, ref_gl, f"lin {what} lut_grad ({form})")
+            print(f"{what} lut_grad ({form}): worst |error| / order_bound {used:.4f}, {parts.grid.gx} x {parts.grid.gy} workgroups, m <= {int(parts.m.max())}")
         got[label] = gl.cpu().numpy().astype(np.float64)
         grid = lr.bwd_grid_of(cs.C * rows * cs.w, cs.N, cs.C, cs.L, cs.mode, cus)
         groups[label] = grid.gx * grid.gy
@@ -243,6 +261,9 @@ def test_dispatcher_ops_take_bands(dev):
         gx, gl = torch.ops.clair_hip.icrf_backward(x, go, lut, mode, True, True, cs.hg, r0)
         rx, rl = ops.icrf_backward(x, go, lut, mode, True, True, tile=tile)
         assert torch.equal(gx, rx)
+        parts = lr.bwd_partials(SimpleNamespace(**{**vars(cs), "mode": mode}), r0, rows, (cs.hg, r0), torch.cuda.get_device_properties(dev).multi_processor_count)
+        for g, via in ((gl, "dispatcher"), (rl, "ops")):
+            lr.assert_flush(g.cpu().numpy(), parts, f"{via} {mode} lut_grad")
         scale = lr.icrf_backward_f64(cs.x[:, :, r0:], cs.grad_out[:, :, r0:], cs.lut, mode, (cs.hg, r0), absolute=True)[1]
         grid = lr.bwd_grid_of(cs.C * rows * cs.w, cs.N, cs.C, cs.L, mode, torch.cuda.get_device_properties(dev).multi_processor_count)
         assert np.all(np.abs(gl.cpu().numpy().astype(np.float64) - rl.cpu().numpy()) <= 2 * lr.flush_bound(scale, grid.gx * grid.gy))
@@ -251,5 +272,5 @@ def test_dispatcher_ops_take_bands(dev):
     ax, al = torch.autograd.grad(torch.ops.clair_hip.icrf_forward(xg, lg, "catmull", cs.hg, r0), (xg, lg), go)
     rx, rl = ops.icrf_backward(x, go, lut, "catmull", True, True, tile=tile)
     assert torch.equal(ax, rx)
-    lr.check(al.cpu().numpy(), lr.icrf_backward_f64(cs.x[:, :, r0:], cs.grad_out[:, :, r0:], cs.lut, "catmull", (cs.hg, r0))[1],
-             ("lut_grad", "catmull"), "lin dispatcher lut_grad vs f64")
+    lr.check_lut_grad(al.cpu().numpy(), cs, lr.bwd_partials(cs, r0, rows, (cs.hg, r0), torch.cuda.get_device_properties(dev).multi_processor_count),
+                      lr.icrf_backward_f64(cs.x[:, :, r0:], cs.grad_out[:, :, r0:], cs.lut, "catmull", (cs.hg, r0))[1], "lin dispatcher lut_grad")
