@@ -3,6 +3,7 @@
 // order decides which status a call with two faults gets (pinned by tests/test_malformed_calls_host.py and the merge / pair
 // tables of tests/test_abi_and_host.py).  No __device__ code: including this header changes no kernel.
 #pragma once
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -92,7 +93,58 @@ static inline bool std_mode_ok(int32_t std_mode, const void *std_dev)
     return std_mode_in_range(std_mode) && (std_mode != CT_STD_EXPLICIT || std_dev);
 }
 
+// The fl(u / max_code) constants of a stack of `dtype`; float32 pixels take none.
+static inline int norm_for_dtype(int32_t dtype, float max_code, NormConst *norm)
+{
+    *norm = NormConst{1.0f, 0.0f};
+    if (dtype == CT_DTYPE_F32) return CT_OK;
+    if (dtype != CT_DTYPE_U8 && dtype != CT_DTYPE_U16) return CT_ERR_UNSUPPORTED;
+    return ct_norm_constants(max_code, &norm->hi, &norm->lo) == CT_OK ? CT_OK : CT_ERR_UNSUPPORTED;
+}
+
+// ---- dark field: what ct_dark_field_blur refuses, for it and for the two entry points that fuse it ------------------------
+// Two runs of its order; what an entry point tests in between, before and after stays with it.  First the frames: shape (the
+// 3 x 3 blur reflects at the borders: two columns and two global rows at least), layout, the dark fields (one per frame or one
+// for all), the std mode.  ct_linearize_dark's frames are batches of one with a dark field each.
+static inline int check_dark_frames(const ct_geometry *g, int32_t batch, int32_t dark_batch, bool propagates, int32_t std_mode,
+                                    const void *std_dev)
+{
+    if (!shape_positive(g) || g->width < 2 || g->h_global < 2 || !band_fits(g)) return CT_ERR_INVALID_ARGUMENT;
+    if (g->layout != CT_LAYOUT_NCHW) return CT_ERR_UNSUPPORTED;
+    if (dark_batch != 1 && dark_batch != batch) return CT_ERR_INVALID_ARGUMENT;
+    // One SHARED dark field for several frames with its uncertainty propagated: the reference's autograd on a (1, C, H, W)
+    // mask_map sums the gradient over the frames BEFORE squaring, (sum_n g_n)^2 sigma_D^2, which a per-frame effective
+    // sigma cannot express (it would give sum_n (g_n sigma_D)^2).  Not built; refuse rather than return the other quantity.
+    if (dark_batch == 1 && batch > 1 && propagates) return CT_ERR_UNSUPPORTED;
+    return std_mode_ok(std_mode, std_dev) ? CT_OK : CT_ERR_INVALID_ARGUMENT;
+}
+
+// ... then the row band: one that does not touch the global top / bottom needs its neighbours' rows in `halo`; so does a
+// one-row band's reflection.  Last the stride.
+static inline int check_dark_band(const ct_geometry *g, const void *halo_dev)
+{
+    const bool top = g->row_offset == 0, bottom = g->row_offset + g->h_tile == g->h_global;
+    if ((!top || !bottom) && !halo_dev) return CT_ERR_INVALID_ARGUMENT;
+    if ((top || bottom) && g->h_tile < 2 && !(top && bottom)) return CT_ERR_UNSUPPORTED;
+    return stride_holds_image(g) ? CT_OK : CT_ERR_INVALID_ARGUMENT;
+}
+
 // ---- argument blocks --------------------------------------------------------------------------------------------------
+// What DarkArgs, MergeDarkArgs and LinDarkArgs have in common (each keeps its own layout): the blur's parameters.
+template <typename Args>
+static inline void fill_blur_args(Args &a, NormConst norm, int32_t std_mode, float std_value, float threshold, float alpha)
+{
+    a.norm = norm;
+    a.std_mode = std_mode;
+    a.std_value = std_value;
+    a.threshold = threshold;
+    a.alpha = alpha;
+    // torchvision _get_gaussian_kernel1d(3, 1.0): pdf = exp(-0.5 x^2), x = -1, 0, 1; normalised in float32
+    const float side = expf(-0.5f), sum = (side + 1.0f) + side;
+    a.k0 = 1.0f / sum;
+    a.k1 = side / sum;
+}
+
 static inline TileMap make_tile(const ct_geometry *g)
 {
     TileMap t;

@@ -104,8 +104,6 @@ __global__ __launch_bounds__(kBlock) void dark_blur_kernel(const DarkArgs a)
 
 }  // namespace ct
 
-extern "C" int ct_norm_constants(float max_code, float *hi, float *lo);
-
 extern "C" int ct_dark_field_blur(const void *stack_dev, int32_t dtype, float max_code, int32_t batch,
                                   const ct_geometry *geom, const void *halo_dev, const float *std_dev, int32_t std_mode,
                                   float std_value, const float *dark_dev, const float *dark_std_dev, int32_t dark_batch,
@@ -113,22 +111,10 @@ extern "C" int ct_dark_field_blur(const void *stack_dev, int32_t dtype, float ma
 {
     using namespace ct;
     if (!stack_dev || !geom || !dark_dev || !xb_out_dev || batch <= 0) return CT_ERR_INVALID_ARGUMENT;
-    // (the 3 x 3 blur reflects at the borders: two columns and two global rows at least)
-    if (!shape_positive(geom) || geom->width < 2 || geom->h_global < 2 || !band_fits(geom)) return CT_ERR_INVALID_ARGUMENT;
-    if (geom->layout != CT_LAYOUT_NCHW) return CT_ERR_UNSUPPORTED;
-    if (dark_batch != 1 && dark_batch != batch) return CT_ERR_INVALID_ARGUMENT;
-    // One SHARED dark field for several frames with its uncertainty propagated: the reference's autograd on a (1, C, H, W)
-    // mask_map sums the gradient over the frames BEFORE squaring, (sum_n g_n)^2 sigma_D^2, which a per-frame effective
-    // sigma cannot express (it would give sum_n (g_n sigma_D)^2).  Not built; refuse rather than return the other quantity.
-    if (dark_batch == 1 && batch > 1 && dark_std_dev && std_out_dev) return CT_ERR_UNSUPPORTED;
-    if (!std_mode_ok(std_mode, std_dev)) return CT_ERR_INVALID_ARGUMENT;
+    if (int rc = check_dark_frames(geom, batch, dark_batch, dark_std_dev && std_out_dev, std_mode, std_dev)) return rc;
     if (std_out_dev && !dark_std_dev) return CT_ERR_INVALID_ARGUMENT;
-    // a band that does not touch the global top / bottom needs its neighbours' rows; so does a one-row band's reflection
-    const bool top = geom->row_offset == 0, bottom = geom->row_offset + geom->h_tile == geom->h_global;
-    if ((!top || !bottom) && !halo_dev) return CT_ERR_INVALID_ARGUMENT;
-    if ((top || bottom) && geom->h_tile < 2 && !(top && bottom)) return CT_ERR_UNSUPPORTED;
+    if (int rc = check_dark_band(geom, halo_dev)) return rc;
     const int64_t plane = geom->h_tile * geom->width;
-    if (!stride_holds_image(geom)) return CT_ERR_INVALID_ARGUMENT;
     DarkArgs a{};
     a.stack = stack_dev;
     a.halo = halo_dev;
@@ -145,29 +131,16 @@ extern "C" int ct_dark_field_blur(const void *stack_dev, int32_t dtype, float ma
     a.width = (int32_t)geom->width;
     a.h_global = (int32_t)geom->h_global;
     a.row_offset = (int32_t)geom->row_offset;
-    a.std_mode = std_mode;
-    a.std_value = std_value;
-    a.threshold = threshold;
-    a.alpha = alpha;
-    // torchvision _get_gaussian_kernel1d(3, 1.0): pdf = exp(-0.5 x^2), x = -1, 0, 1; normalised in float32
-    const float side = expf(-0.5f), sum = (side + 1.0f) + side;
-    a.k0 = 1.0f / sum;
-    a.k1 = side / sum;
-    a.norm = NormConst{1.0f, 0.0f};
+    NormConst norm;
+    if (norm_for_dtype(dtype, max_code, &norm) != CT_OK) return CT_ERR_UNSUPPORTED;  // (the last refusal here)
+    fill_blur_args(a, norm, std_mode, std_value, threshold, alpha);
     const int64_t total = plane * geom->channels * batch;
     const int grid = (int)std::min<int64_t>((total + kBlock - 1) / kBlock, (int64_t)compute_units() * 16);
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (dtype) {
-        case CT_DTYPE_U8:
-            if (ct_norm_constants(max_code, &a.norm.hi, &a.norm.lo) != CT_OK) return CT_ERR_UNSUPPORTED;
-            hipLaunchKernelGGL(dark_blur_kernel<uint8_t>, dim3(grid), dim3(kBlock), 0, s, a);
-            break;
-        case CT_DTYPE_U16:
-            if (ct_norm_constants(max_code, &a.norm.hi, &a.norm.lo) != CT_OK) return CT_ERR_UNSUPPORTED;
-            hipLaunchKernelGGL(dark_blur_kernel<uint16_t>, dim3(grid), dim3(kBlock), 0, s, a);
-            break;
-        case CT_DTYPE_F32: hipLaunchKernelGGL(dark_blur_kernel<float>, dim3(grid), dim3(kBlock), 0, s, a); break;
-        default: return CT_ERR_UNSUPPORTED;
+        case CT_DTYPE_U8: hipLaunchKernelGGL(dark_blur_kernel<uint8_t>, dim3(grid), dim3(kBlock), 0, s, a); break;
+        case CT_DTYPE_U16: hipLaunchKernelGGL(dark_blur_kernel<uint16_t>, dim3(grid), dim3(kBlock), 0, s, a); break;
+        default: hipLaunchKernelGGL(dark_blur_kernel<float>, dim3(grid), dim3(kBlock), 0, s, a); break;
     }
     return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
 }

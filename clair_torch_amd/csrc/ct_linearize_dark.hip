@@ -6,9 +6,8 @@
 // true> of ct_linearize_ingest.hpp (linearize_sample with RANGED = false and its wave-uniform `tiny` fix-up), the step
 // ct_linearize.hip runs on float32 pixels with explicit uncertainties.
 //
-// The window walk and the blur are a second copy of those in md_run (ct_merge_dark.hip): the two must stay
-// expression-identical (and identical to dark_blur_kernel); tests/test_gpu_linearize_dark.py and test_gpu_merge_dark.py hold
-// each of them to the pair of launches bit for bit.
+// The window and the blur are those of md_run (ct_merge_dark.hip), from ct_dark_window.hpp; tests/test_gpu_linearize_dark.py
+// and test_gpu_merge_dark.py hold each kernel to the pair of launches bit for bit.
 //
 // Roofline: HBM.  Per sample sizeof(T) bytes of the frame (its neighbours in the 3 x 3 window are L1 / L2 hits: the rows
 // above and below belong to the wavefronts next door), 4 of the dark field and 4 of its std (+ 4 with explicit image
@@ -25,6 +24,7 @@
 // (li_store), else elements.  No atomics, no LDS tile; the frames and the dark fields are read only.  No row bands: the
 // generator that calls this has no tile=, so no halo is built here.
 #include <algorithm>
+#include "ct_dark_window.hpp"
 #include "ct_linearize_ingest.hpp"
 
 namespace ct {
@@ -39,7 +39,7 @@ struct LinDarkArgs {
     const float *dark_std[CT_LINEARIZE_DARK_MAX_FRAMES];
     int64_t image_stride;
     uint32_t plane;          // H * W
-    uint32_t width, height;
+    uint32_t width, h_tile;
     uint32_t channels, n_points;
     NormConst norm;
     int32_t std_mode;        // of the RAW image: how sigma enters sigma_eff
@@ -51,58 +51,17 @@ constexpr int kLdGroup = kLiGroup;  // columns per thread
 constexpr int kLdSlots = 4;         // groups per thread
 
 // xb and sigma_eff of columns w0 .. w0 + G - 1 of row h of plane c0 of the frame at `frame` (its dark field: dark, dark_std;
-// its explicit sigma: sigma or NULL).  md_run's load_raw and blur for one frame: dark_blur_kernel, expression for expression.
+// its explicit sigma: sigma or NULL): the window of ct_dark_window.hpp for one frame that is the whole image (no halo).
 template <typename T, int G>
 __device__ __forceinline__ void ld_blur(const LinDarkArgs &a, const T *frame, const float *sigma, const float *dark,
                                         const float *dark_std, uint32_t c0, uint32_t h, uint32_t w0, float *xb, float *sig)
 {
-    const uint32_t W = a.width, H = a.height;
-    const uint32_t q = c0 * a.plane + h * W + w0;  // first element inside the (C, H, W) frame
-    const T *img = frame + (int64_t)c0 * a.plane;
-    const T *mid = img + (int64_t)h * W;
-    const T *up = img + (int64_t)(h > 0 ? h - 1 : 1) * W;          // top: reflect -1 -> 1
-    const T *dn = img + (int64_t)(h + 1 < H ? h + 1 : H - 2) * W;  // bottom: reflect H -> H - 2
-    // column taps with reflect padding (index -1 -> 1, W -> W - 2)
-    const uint32_t cl = w0 > 0 ? w0 - 1 : 1, cr = w0 + G < W ? w0 + G : W - 2;
-    T vu[G + 2], vm[G + 2], vd[G + 2];
-    float d[G], ds[G], sg[G] = {};
-    auto load_row = [&](const T *row, T (&v)[G + 2]) {
-        v[0] = row[cl];
-        __builtin_memcpy(&v[1], row + w0, G * sizeof(T));  // any alignment: rows are only element-aligned in general
-        v[G + 1] = row[cr];
-    };
-    load_row(up, vu);
-    load_row(mid, vm);
-    load_row(dn, vd);
-    __builtin_memcpy(d, dark + q, G * sizeof(float));
-    __builtin_memcpy(ds, dark_std + q, G * sizeof(float));
+    const uint32_t q = c0 * a.plane + h * a.width + w0;  // first element inside the (C, H, W) frame
+    const DarkRows<T> rw = dark_rows<T, G, false>(a, frame + (int64_t)c0 * a.plane, c0, h, w0);
     const bool explicit_sigma = a.std_mode == CT_STD_EXPLICIT;
-    if (explicit_sigma) __builtin_memcpy(sg, sigma + q, G * sizeof(float));
-
-    float ru[G + 2], rm[G + 2], rd[G + 2];
-#pragma unroll
-    for (int j = 0; j < G + 2; ++j) {
-        ru[j] = to_pixel<T>(vu[j], a.norm);
-        rm[j] = to_pixel<T>(vm[j], a.norm);
-        rd[j] = to_pixel<T>(vd[j], a.norm);
-    }
-#pragma unroll
-    for (int e = 0; e < G; ++e) {
-        const float bu = (a.k1 * ru[e] + a.k0 * ru[e + 1]) + a.k1 * ru[e + 2];
-        const float bm = (a.k1 * rm[e] + a.k0 * rm[e + 1]) + a.k1 * rm[e + 2];
-        const float bd = (a.k1 * rd[e] + a.k0 * rd[e + 1]) + a.k1 * rd[e + 2];
-        const float x = rm[e + 1];
-        const float blurred = (a.k1 * bu + a.k0 * bm) + a.k1 * bd;
-        const float m = 1.0f / (1.0f + expf(-(d[e] - a.threshold) * a.alpha));  // torch.sigmoid
-        xb[e] = m * blurred + (1.0f - m) * x;
-        float s = 0.0f;
-        if (explicit_sigma) s = sg[e];
-        if (a.std_mode == CT_STD_CONSTANT) s = a.std_value;
-        if (a.std_mode == CT_STD_MULTIPLIER) s = a.std_value * x;  // the dataset derives sigma from the RAW image
-        const float dterm = (blurred - x) * (a.alpha * m * (1.0f - m));
-        const float dsv = dterm * ds[e];
-        sig[e] = sqrtf(s * s + dsv * dsv);
-    }
+    DarkRaw<T, G> raw{};
+    dark_load<T, G, true>(raw, rw, 0, 0, dark, dark_std, 0, explicit_sigma, sigma, q);
+    dark_blur<T, G, true>(a, raw, explicit_sigma, xb, sig);
 }
 
 // groups of kLdGroup columns in a row, the last one possibly short
@@ -122,7 +81,7 @@ __global__ __launch_bounds__(kBlock) void linearize_dark_kernel(const LinDarkArg
     const int64_t out0 = (int64_t)f * C * a.plane;  // the frame inside the dense outputs
     const uint32_t W = a.width;
     const uint32_t gpr = ld_groups_per_row(W);
-    const uint64_t n_slots = (uint64_t)gpr * a.height;
+    const uint64_t n_slots = (uint64_t)gpr * a.h_tile;
 #pragma unroll 1
     for (int k = 0; k < kLdSlots; ++k) {
         const uint64_t slot = ((uint64_t)blockIdx.x * kLdSlots + k) * kBlock + threadIdx.x;
@@ -155,7 +114,7 @@ template <typename T, int INTERP>
 static int ld_launch(const LinDarkArgs &a, int n_frames, hipStream_t s)
 {
     const size_t lds = lut_lds_bytes(INTERP, (int)a.channels, (int)a.n_points);
-    const uint64_t slots = (uint64_t)ld_groups_per_row(a.width) * a.height;
+    const uint64_t slots = (uint64_t)ld_groups_per_row(a.width) * a.h_tile;
     const uint64_t per_block = (uint64_t)kBlock * kLdSlots;
     const dim3 grid((uint32_t)((slots + per_block - 1) / per_block), (uint32_t)n_frames * a.channels);
     hipLaunchKernelGGL((linearize_dark_kernel<T, INTERP>), grid, dim3(kBlock), lds, s, a);
@@ -171,8 +130,6 @@ static int ld_dispatch(const LinDarkArgs &a, int interp, int n_frames, hipStream
 
 }  // namespace ct
 
-extern "C" int ct_norm_constants(float max_code, float *hi, float *lo);
-
 extern "C" int ct_linearize_dark(const void *frames_dev, int32_t dtype, float max_code, int64_t n_frames, const ct_geometry *geom,
                                  const float *std_dev, int32_t std_mode, float std_value, const float *const *dark_devs,
                                  const float *const *dark_std_devs, float threshold, float alpha, const ct_icrf *icrf,
@@ -184,18 +141,12 @@ extern "C" int ct_linearize_dark(const void *frames_dev, int32_t dtype, float ma
         return CT_ERR_INVALID_ARGUMENT;
     for (int64_t k = 0; k < n_frames; ++k)
         if (!dark_devs[k] || !dark_std_devs[k]) return CT_ERR_INVALID_ARGUMENT;
-    if (!shape_positive(geom) || geom->width < 2 || geom->h_global < 2 || !band_fits(geom)) return CT_ERR_INVALID_ARGUMENT;
-    if (geom->layout != CT_LAYOUT_NCHW) return CT_ERR_UNSUPPORTED;
-    if (!std_mode_ok(std_mode, std_dev)) return CT_ERR_INVALID_ARGUMENT;
+    if (int rc = check_dark_frames(geom, 1, 1, true, std_mode, std_dev)) return rc;
     // a row band would need the rows above and below it; the streamed generator has no tile=, so no halo is built here
     if (geom->row_offset != 0 || geom->h_tile != geom->h_global) return CT_ERR_UNSUPPORTED;
-    if (!stride_holds_image(geom)) return CT_ERR_INVALID_ARGUMENT;
-    NormConst norm{1.0f, 0.0f};
-    if (dtype == CT_DTYPE_U8 || dtype == CT_DTYPE_U16) {
-        if (ct_norm_constants(max_code, &norm.hi, &norm.lo) != CT_OK) return CT_ERR_UNSUPPORTED;
-    } else if (dtype != CT_DTYPE_F32) {
-        return CT_ERR_UNSUPPORTED;
-    }
+    if (int rc = check_dark_band(geom, nullptr)) return rc;  // (the whole image: what is left of it is the stride)
+    NormConst norm;
+    if (norm_for_dtype(dtype, max_code, &norm) != CT_OK) return CT_ERR_UNSUPPORTED;
     // ---- what ct_linearize_std refuses for (xb, sigma_eff): float32 pixels with explicit uncertainties ----
     if (!icrf || !icrf_ok(icrf)) return CT_ERR_INVALID_ARGUMENT;
     const int interp = icrf->interp;
@@ -220,18 +171,10 @@ extern "C" int ct_linearize_dark(const void *frames_dev, int32_t dtype, float ma
     a.image_stride = geom->image_stride;
     a.plane = (uint32_t)plane;
     a.width = (uint32_t)geom->width;
-    a.height = (uint32_t)geom->h_tile;
+    a.h_tile = (uint32_t)geom->h_tile;
     a.channels = (uint32_t)geom->channels;
     a.n_points = (uint32_t)n_points;
-    a.norm = norm;
-    a.std_mode = std_mode;
-    a.std_value = std_value;
-    a.threshold = threshold;
-    a.alpha = alpha;
-    // torchvision _get_gaussian_kernel1d(3, 1.0): pdf = exp(-0.5 x^2), x = -1, 0, 1; normalised in float32
-    const float side = expf(-0.5f), sum = (side + 1.0f) + side;
-    a.k0 = 1.0f / sum;
-    a.k1 = side / sum;
+    fill_blur_args(a, norm, std_mode, std_value, threshold, alpha);
     hipStream_t s = static_cast<hipStream_t>(stream);
     for (int64_t first = 0; first < n_frames; first += per_launch) {
         const int nf = (int)std::min<int64_t>(per_launch, n_frames - first);

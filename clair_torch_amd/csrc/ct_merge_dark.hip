@@ -17,6 +17,7 @@
 // group is aligned in memory (mi_store), else element by element.  No atomics, no LDS tile, the frames are read only.
 // Row bands: the rows above / below the band come from `halo` exactly as dark_blur_kernel takes them.
 #include <algorithm>
+#include "ct_dark_window.hpp"
 #include "ct_merge_ingest_kernel.hpp"
 
 namespace ct {
@@ -51,13 +52,6 @@ struct MergeDarkArgs {
 
 constexpr int kMdGroup = 4;  // columns per thread
 constexpr int kMdPF = 2;     // samples in flight ahead of the one being reduced, as mi_run
-
-// what one exposure contributes to the G elements of a thread, as loaded
-template <typename T, int G>
-struct MdRaw {
-    T up[G + 2], mid[G + 2], dn[G + 2];  // columns {left, w0 .. w0 + G - 1, right} of the rows h - 1, h, h + 1
-    float d[G], ds[G], sg[G];            // dark field, its std, the explicit sigma
-};
 
 // Columns w0 .. w0 + G - 1 of local row h of plane c0: the whole batch, state and outputs.  STD: CT_STD_EXPLICIT (a dark std:
 // sigma_eff is propagated) or CT_STD_NONE (none); the std mode of the raw image is a wave-uniform run-time branch.
@@ -94,89 +88,20 @@ __device__ __forceinline__ void md_run(const MergeDarkArgs &a, const char *lds, 
         }
     }
 
-    // the three rows of the window in frame 0 and what lies between two frames of each: the image, or the halo / the
-    // reflected row at the band's edges (dark_blur_kernel's row_blur)
-    const T *img = static_cast<const T *>(a.stack) + (int64_t)c0 * a.plane;
-    const T *halo = static_cast<const T *>(a.halo);
-    const int64_t halo_stride = (int64_t)C * 2 * W;
-    const T *mid = img + (int64_t)h * W;
-    const T *up, *dn;
-    int64_t up_stride = a.image_stride, dn_stride = a.image_stride;
-    if (h > 0) {
-        up = img + (int64_t)(h - 1) * W;
-    } else if (a.at_top) {
-        up = img + (int64_t)1 * W;  // global top: reflect -1 -> 1
-    } else {
-        up = halo + ((int64_t)c0 * 2 + 0) * W;
-        up_stride = halo_stride;
-    }
-    if (h + 1 < (uint32_t)a.h_tile) {
-        dn = img + (int64_t)(h + 1) * W;
-    } else if (a.at_bottom) {
-        dn = img + (int64_t)(a.h_tile - 2) * W;  // global bottom: reflect H -> H - 2
-    } else {
-        dn = halo + ((int64_t)c0 * 2 + 1) * W;
-        dn_stride = halo_stride;
-    }
-    // column taps with reflect padding (index -1 -> 1, W -> W - 2)
-    const uint32_t cl = w0 > 0 ? w0 - 1 : 1, cr = w0 + G < W ? w0 + G : W - 2;
-
-    auto load_row = [&](const T *row, T (&v)[G + 2]) {
-        v[0] = row[cl];
-        __builtin_memcpy(&v[1], row + w0, G * sizeof(T));  // any alignment: rows are only element-aligned in general
-        v[G + 1] = row[cr];
-    };
+    // the window of this group (ct_dark_window.hpp): its rows, frame n as loaded, and xb and sigma_eff of that
+    const DarkRows<T> rw = dark_rows<T, G, true>(a, static_cast<const T *>(a.stack) + (int64_t)c0 * a.plane, c0, h, w0);
     auto load_raw = [&](int64_t n) {
-        MdRaw<T, G> r{};
-        load_row(up + n * up_stride, r.up);
-        load_row(mid + n * a.image_stride, r.mid);
-        load_row(dn + n * dn_stride, r.dn);
-        const int64_t dq = n * a.dark_stride + q;
-        __builtin_memcpy(r.d, a.dark + dq, G * sizeof(float));
-        if constexpr (kHasStd) {
-            __builtin_memcpy(r.ds, a.dark_std + dq, G * sizeof(float));
-            if (explicit_sigma) __builtin_memcpy(r.sg, a.std_stack + n * a.image_stride + q, G * sizeof(float));
-        }
+        DarkRaw<T, G> r{};
+        dark_load<T, G, kHasStd>(r, rw, n, a.image_stride, a.dark, a.dark_std, a.dark_stride, explicit_sigma, a.std_stack, q);
         return r;
     };
-    // xb and sigma_eff of the G elements: dark_blur_kernel, expression for expression.  ld_blur of ct_linearize_dark.hip is a
-    // second copy of load_raw and this: the two must stay expression-identical
-    auto blur = [&](const MdRaw<T, G> &r, float (&xb)[G], float (&sig)[G]) {
-        float ru[G + 2], rm[G + 2], rd[G + 2];
-#pragma unroll
-        for (int j = 0; j < G + 2; ++j) {
-            ru[j] = to_pixel<T>(r.up[j], a.norm);
-            rm[j] = to_pixel<T>(r.mid[j], a.norm);
-            rd[j] = to_pixel<T>(r.dn[j], a.norm);
-        }
-#pragma unroll
-        for (int e = 0; e < G; ++e) {
-            const float bu = (a.k1 * ru[e] + a.k0 * ru[e + 1]) + a.k1 * ru[e + 2];
-            const float bm = (a.k1 * rm[e] + a.k0 * rm[e + 1]) + a.k1 * rm[e + 2];
-            const float bd = (a.k1 * rd[e] + a.k0 * rd[e + 1]) + a.k1 * rd[e + 2];
-            const float x = rm[e + 1];
-            const float blurred = (a.k1 * bu + a.k0 * bm) + a.k1 * bd;
-            const float d = r.d[e];
-            const float m = 1.0f / (1.0f + expf(-(d - a.threshold) * a.alpha));  // torch.sigmoid
-            xb[e] = m * blurred + (1.0f - m) * x;
-            sig[e] = 1.0f;
-            if constexpr (kHasStd) {
-                float sg = 0.0f;
-                if (explicit_sigma) sg = r.sg[e];
-                if (a.std_mode == CT_STD_CONSTANT) sg = a.std_value;
-                if (a.std_mode == CT_STD_MULTIPLIER) sg = a.std_value * x;  // the dataset derives sigma from the RAW image
-                const float dterm = (blurred - x) * (a.alpha * m * (1.0f - m));
-                const float ds = dterm * r.ds[e];
-                sig[e] = sqrtf(sg * sg + ds * ds);
-            }
-        }
-    };
+    auto blur = [&](const DarkRaw<T, G> &r, float (&xb)[G], float (&sig)[G]) { dark_blur<T, G, kHasStd>(a, r, explicit_sigma, xb, sig); };
 
     // ---- pivot: the middle exposure's sample on a first batch, else the running mean ----
     float p[G];
     if (first) {
         const int probe = B / 2;
-        const MdRaw<T, G> raw = load_raw(probe);
+        const DarkRaw<T, G> raw = load_raw(probe);
         const float itp = inv_t[probe];
         float xb[G], sig[G];
         blur(raw, xb, sig);
@@ -205,7 +130,7 @@ __device__ __forceinline__ void md_run(const MergeDarkArgs &a, const char *lds, 
         for (int k = 0; k < G; ++k) sum[k] = MiSums{0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
 
         // software pipeline, as mi_run's: kMdPF exposures in flight per thread ahead of the one being reduced
-        MdRaw<T, G> ring[kMdPF];
+        DarkRaw<T, G> ring[kMdPF];
 #pragma unroll
         for (int k = 0; k < kMdPF; ++k) ring[k] = load_raw(k < B ? k : B - 1);
 #pragma unroll kMdPF
@@ -215,8 +140,8 @@ __device__ __forceinline__ void md_run(const MergeDarkArgs &a, const char *lds, 
             //  sample at its point of use and the prefetch is gone)
             int64_t opaque_zero = 0;
             asm volatile("" : "+s"(opaque_zero));
-            const MdRaw<T, G> incoming = load_raw((int64_t)nn + opaque_zero);
-            const MdRaw<T, G> raw = ring[0];
+            const DarkRaw<T, G> incoming = load_raw((int64_t)nn + opaque_zero);
+            const DarkRaw<T, G> raw = ring[0];
 #pragma unroll
             for (int k = 0; k + 1 < kMdPF; ++k) ring[k] = ring[k + 1];
             ring[kMdPF - 1] = incoming;
@@ -347,8 +272,6 @@ static int md_dispatch(const MergeDarkArgs &a, int interp, int weight_mode, bool
 
 }  // namespace ct
 
-extern "C" int ct_norm_constants(float max_code, float *hi, float *lo);
-
 extern "C" int ct_hdr_merge_dark_batch(const void *stack_dev, int32_t dtype, float max_code, int32_t batch, const ct_geometry *geom,
                                        const void *halo_dev, const float *std_dev, int32_t std_mode, float std_value,
                                        const float *dark_dev, const float *dark_std_dev, int32_t dark_batch, float threshold,
@@ -357,24 +280,12 @@ extern "C" int ct_hdr_merge_dark_batch(const void *stack_dev, int32_t dtype, flo
                                        float *std_out_dev, uint32_t flags, void *stream)
 {
     using namespace ct;
-    // ---- what ct_dark_field_blur refuses, in its order (ct_darkfield.hip) ----
+    // ---- what ct_dark_field_blur refuses, in its order (ct_darkfield.hip); a dark std is always propagated here ----
     if (!stack_dev || !geom || !dark_dev || batch <= 0) return CT_ERR_INVALID_ARGUMENT;
-    if (!shape_positive(geom) || geom->width < 2 || geom->h_global < 2 || !band_fits(geom)) return CT_ERR_INVALID_ARGUMENT;
-    if (geom->layout != CT_LAYOUT_NCHW) return CT_ERR_UNSUPPORTED;
-    if (dark_batch != 1 && dark_batch != batch) return CT_ERR_INVALID_ARGUMENT;
-    // one SHARED dark field for several frames with its uncertainty is another quantity in the reference (see there)
-    if (dark_batch == 1 && batch > 1 && dark_std_dev) return CT_ERR_UNSUPPORTED;
-    if (!std_mode_ok(std_mode, std_dev)) return CT_ERR_INVALID_ARGUMENT;
-    const bool at_top = geom->row_offset == 0, at_bottom = geom->row_offset + geom->h_tile == geom->h_global;
-    if ((!at_top || !at_bottom) && !halo_dev) return CT_ERR_INVALID_ARGUMENT;
-    if ((at_top || at_bottom) && geom->h_tile < 2 && !(at_top && at_bottom)) return CT_ERR_UNSUPPORTED;
-    if (!stride_holds_image(geom)) return CT_ERR_INVALID_ARGUMENT;
-    NormConst norm{1.0f, 0.0f};
-    if (dtype == CT_DTYPE_U8 || dtype == CT_DTYPE_U16) {
-        if (ct_norm_constants(max_code, &norm.hi, &norm.lo) != CT_OK) return CT_ERR_UNSUPPORTED;
-    } else if (dtype != CT_DTYPE_F32) {
-        return CT_ERR_UNSUPPORTED;
-    }
+    if (int rc = check_dark_frames(geom, batch, dark_batch, dark_std_dev != nullptr, std_mode, std_dev)) return rc;
+    if (int rc = check_dark_band(geom, halo_dev)) return rc;
+    NormConst norm;
+    if (norm_for_dtype(dtype, max_code, &norm) != CT_OK) return CT_ERR_UNSUPPORTED;
     // ---- what ct_hdr_merge_batch refuses for (xb, sigma_eff): float32 pixels, explicit uncertainties with a dark std and
     //      none without, in the order of validate_merge (ct_merge.hip) ----
     const bool has_std = dark_std_dev != nullptr;
@@ -421,20 +332,12 @@ extern "C" int ct_hdr_merge_dark_batch(const void *stack_dev, int32_t dtype, flo
     a.base = (uint32_t)(geom->row_offset * geom->width);
     a.width = (int32_t)geom->width;
     a.h_tile = (int32_t)geom->h_tile;
-    a.at_top = at_top ? 1u : 0u;
-    a.at_bottom = at_bottom ? 1u : 0u;
+    a.at_top = geom->row_offset == 0 ? 1u : 0u;
+    a.at_bottom = geom->row_offset + geom->h_tile == geom->h_global ? 1u : 0u;
     a.batch = batch;
     a.channels = geom->channels;
     a.n_points = n_points;
-    a.norm = norm;
-    a.std_mode = std_mode;
-    a.std_value = std_value;
-    a.threshold = threshold;
-    a.alpha = alpha;
-    // torchvision _get_gaussian_kernel1d(3, 1.0): pdf = exp(-0.5 x^2), x = -1, 0, 1; normalised in float32
-    const float side = expf(-0.5f), sum = (side + 1.0f) + side;
-    a.k0 = 1.0f / sum;
-    a.k1 = side / sum;
+    fill_blur_args(a, norm, std_mode, std_value, threshold, alpha);
     a.weight_scale = 30.0f;  // gaussian_value_weights default scale, hdr_merge.py:95
     a.flags = flags;
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -3,12 +3,16 @@ pass.  Its specification is one sentence -- for every frame the outputs are bit 
 batch of one followed by ct_linearize_std on (xb, sigma_eff) -- so nearly everything here is torch.equal against that pair,
 through ops.linearize_dark_frames and through linearize_dataset_generator(fused_dark=True / False); the generator is also held
 against the eager restatement of the reference (oracle/eager_torch.py) at the tolerances of test_gpu_darkfield.py."""
-import numpy as np
+import functools
+
 import pytest
 import torch
 from torch.utils.data import DataLoader
 
+from _dark_cases import as_dtype as _as_dtype, scene
 from _util import assert_parity
+
+_scene = functools.partial(scene, period=8)     # 17 and 50 frames: the exposure times start over every 8
 
 pytestmark = pytest.mark.gpu
 
@@ -19,28 +23,6 @@ def dev():
     from clair_torch_amd import _native
     _native.load()
     return torch.device("cuda:0")
-
-
-def _scene(seed, n, c, h, w):
-    """tests/test_gpu_merge_dark.py's recipe: frames through a gamma curve, uncertainties, one dark field PER FRAME straddling
-    the 0.05 threshold (so a wrong pointer or stride shows) with its std, and a LUT whose rows differ."""
-    gen = torch.Generator().manual_seed(seed)
-    t = torch.tensor([0.002 * 2.0 ** (k % 8) for k in range(n)], dtype=torch.float64)
-    e = torch.rand((c, h, w), generator=gen, dtype=torch.float64) * (2.0 / float(torch.sqrt(t.min() * t.max())))
-    x = ((e.unsqueeze(0) * t.view(-1, 1, 1, 1)).clamp(0, 1) ** (1 / 2.2)).float()
-    sd = (0.002 + 0.03 * torch.rand(x.shape, generator=gen)).float()
-    dark = (0.1 * torch.rand((n, c, h, w), generator=gen)).float()
-    dark_std = (0.002 + 0.01 * torch.rand((n, c, h, w), generator=gen)).float()
-    lut = torch.stack([torch.linspace(0, 1, 256) ** p for p in (1.8, 2.2, 2.6)])[:c].contiguous()
-    return x, sd, t, dark, dark_std, lut
-
-
-def _as_dtype(x, dtype):
-    """(frames of that dtype, max_code)"""
-    if dtype == torch.float32:
-        return x, None
-    top = 65535 if dtype == torch.uint16 else 255
-    return torch.from_numpy(np.rint(x.numpy().astype(np.float64) * top).astype(np.uint16 if top == 65535 else np.uint8)), float(top)
 
 
 def _pair(frames, darks, dark_stds, lut, interp, *, std=None, **kw):
@@ -64,9 +46,12 @@ def _src(std_mode, sd):
 
 # (3,3,13,9): rows end inside a thread's group and the plane (117) is no multiple of it; (2,3,2,2): both reflections fold onto
 # one row and column; (1,1,5,6): a single frame and channel; (5,2,3,130): more than one wavefront per row, a 2-column tail;
-# (17,1,2,3): the 16-frame launch boundary
+# (17,1,2,3): the 16-frame launch boundary; (2,1,2,4): a row of exactly one full group, whose right tap is the reflected W - 2;
+# (1,2,3,8): full groups only, the last one at the right border; (2,1,3,5): one group and a one-element tail whose left tap lies
+# in the group
 @pytest.mark.parametrize("dtype", [torch.float32, torch.uint16, torch.uint8], ids=["f32", "u16", "u8"])
-@pytest.mark.parametrize("shape", [(3, 3, 13, 9), (2, 3, 2, 2), (1, 1, 5, 6), (5, 2, 3, 130), (17, 1, 2, 3)], ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("shape", [(3, 3, 13, 9), (2, 3, 2, 2), (1, 1, 5, 6), (5, 2, 3, 130), (17, 1, 2, 3), (2, 1, 2, 4), (1, 2, 3, 8), (2, 1, 3, 5)],
+                         ids=lambda s: "x".join(map(str, s)))
 def test_bit_equal_to_the_pair(dev, shape, dtype):
     from clair_torch_amd import ops
     n, c, h, w = shape

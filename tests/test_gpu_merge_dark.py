@@ -7,6 +7,7 @@ import pytest
 import torch
 from torch.utils.data import DataLoader
 
+from _dark_cases import as_dtype as _as_dtype, scene as _scene
 from _util import assert_parity
 
 pytestmark = pytest.mark.gpu
@@ -18,28 +19,6 @@ def dev():
     from clair_torch_amd import _native
     _native.load()
     return torch.device("cuda:0")
-
-
-def _scene(seed, n, c, h, w):
-    """A consistent exposure series through a gamma curve, uncertainties, one dark field PER FRAME straddling the 0.05
-    threshold (so a wrong frame stride shows) with its std, and a LUT whose rows differ."""
-    gen = torch.Generator().manual_seed(seed)
-    t = torch.tensor([0.002 * 2.0 ** k for k in range(n)], dtype=torch.float64)
-    e = torch.rand((c, h, w), generator=gen, dtype=torch.float64) * (2.0 / float(torch.sqrt(t[0] * t[-1])))
-    x = ((e.unsqueeze(0) * t.view(-1, 1, 1, 1)).clamp(0, 1) ** (1 / 2.2)).float()
-    sd = (0.002 + 0.03 * torch.rand(x.shape, generator=gen)).float()
-    dark = (0.1 * torch.rand((n, c, h, w), generator=gen)).float()
-    dark_std = (0.002 + 0.01 * torch.rand((n, c, h, w), generator=gen)).float()
-    lut = torch.stack([torch.linspace(0, 1, 256) ** p for p in (1.8, 2.2, 2.6)])[:c].contiguous()
-    return x, sd, t, dark, dark_std, lut
-
-
-def _as_dtype(x, dtype):
-    """(stack of that dtype, max_code)"""
-    if dtype == torch.float32:
-        return x, None
-    top = 65535 if dtype == torch.uint16 else 255
-    return torch.from_numpy(np.rint(x.numpy().astype(np.float64) * top).astype(np.uint16 if top == 65535 else np.uint8)), float(top)
 
 
 def _pair(stack, t, dark, dark_std, *, std=None, std_mode="none", std_value=0.0, max_code=None, tile=None, halo=None, **merge):
@@ -64,9 +43,13 @@ STDS = ["explicit", "constant", "multiplier"]
 
 
 # (4,3,13,9): rows end inside a thread's group and the plane (117) is no multiple of it; (3,3,2,2): both reflections fold
-# onto the same column and row; (1,1,5,6): B = 1, probe 0; (5,2,3,130): more than one wavefront per row band, a 2-column tail
+# onto the same column and row; (1,1,5,6): B = 1, probe 0; (5,2,3,130): more than one wavefront per row band, a 2-column tail;
+# (2,1,2,4): a row of exactly one full group, whose right tap is the reflected W - 2, B = 2 so the probe is exposure 1;
+# (2,2,3,8): full groups only, the last one at the right border; (2,1,3,5): one group and a one-element tail whose left tap lies
+# in the group
 @pytest.mark.parametrize("dtype", [torch.float32, torch.uint16, torch.uint8], ids=["f32", "u16", "u8"])
-@pytest.mark.parametrize("shape", [(4, 3, 13, 9), (3, 3, 2, 2), (1, 1, 5, 6), (5, 2, 3, 130)], ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("shape", [(4, 3, 13, 9), (3, 3, 2, 2), (1, 1, 5, 6), (5, 2, 3, 130), (2, 1, 2, 4), (2, 2, 3, 8), (2, 1, 3, 5)],
+                         ids=lambda s: "x".join(map(str, s)))
 def test_bit_equal_to_the_pair(dev, shape, dtype):
     from clair_torch_amd import ops
     n, c, h, w = shape
