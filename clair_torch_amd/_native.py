@@ -33,7 +33,8 @@ EXPORTS = ("ct_abi_version", "ct_error_string", "ct_hdr_merge_batch", "ct_hdr_me
            "ct_ingest_transform_data", "ct_linearize_ingest", "ct_hdr_merge_ingest_batch", "ct_video_stats_ingest_batch",
            "ct_hdr_merge_ingest_batches", "ct_ingest_extrema_frames_workspace", "ct_ingest_extrema_frames",
            "ct_linearize_ingest_data", "ct_pair_residual_ingest_fwd", "ct_pair_residual_ingest_bwd", "ct_linearize_ingest_strided",
-           "ct_video_stats_batches", "ct_video_stats_ingest_batches", "ct_hdr_merge_dark_batch", "ct_linearize_dark")
+           "ct_video_stats_batches", "ct_video_stats_ingest_batches", "ct_hdr_merge_dark_batch", "ct_linearize_dark",
+           "ct_hdr_merge_dark_batches")
 
 
 class Geometry(ctypes.Structure):
@@ -120,6 +121,9 @@ def load():
     lib.ct_hdr_merge_dark_batch.restype = i32
     lib.ct_hdr_merge_dark_batch.argtypes = [vp, i32, f32, i32, gp, vp, vp, i32, f32, vp, vp, i32, f32, f32, vp, ip, i32, vp, vp, vp,
                                             vp, vp, u32, vp]
+    lib.ct_hdr_merge_dark_batches.restype = i32
+    lib.ct_hdr_merge_dark_batches.argtypes = [vp, vp, i32, i32, f32, gp, vp, vp, i32, f32, vp, vp, vp, f32, f32, vp, ip, i32, vp, vp, vp,
+                                              vp, vp, u32, vp]
     lib.ct_linearize_dark.restype = i32
     lib.ct_linearize_dark.argtypes = [vp, i32, f32, i64, gp, vp, i32, f32, vp, vp, f32, f32, ip, vp, vp, vp]
     lib.ct_band_stats_workspace.restype = i64

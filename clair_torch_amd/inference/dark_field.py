@@ -7,7 +7,8 @@ second autograd.grad (hdr_merge.py:117-126, linearization.py:108-116).  Here one
 blurred batch and a per-sample uncertainty that carries both variance terms; the merge / linearize kernels then run
 unchanged on (float32 pixels, explicit uncertainty).  In compute_hdr_image a matched batch in a closed-form mode can
 instead take ct_hdr_merge_dark_batch, which forms both per sample in registers and merges them in the same pass
-(``DarkField.fuses_with_merge`` / ``merge``; bit-identical to the pair).  linearize_dataset_generator does the same for its
+(``DarkField.fuses_with_merge`` / ``merge``; bit-identical to the pair), and several consecutive such batches can share one
+launch (``merge_batches``, ct_hdr_merge_dark_batches; bit-identical to the launches it replaces).  linearize_dataset_generator does the same for its
 frames: where ``DarkField.fuses_with_linearize`` says so, the streamed pipeline hands each run of matched frames of a group to
 ct_linearize_dark (blur and ICRF in one pass, bit-identical to the pair) with the matched dark fields uploaded once and kept in
 a small device cache (``device_pair``).
@@ -160,6 +161,17 @@ class DarkField:
         halo = exchange_halo(images, tile, group)
         return ops.hdr_merge_dark_batch(images, exposures, dark, dark_std, std=std, std_mode=std_mode, std_value=std_value,
                                         max_code=max_code, tile=tile, halo=halo, **merge_args)
+
+    @staticmethod
+    def merge_batches(matched, images, exposures, max_code, stds, std_mode, std_value, tile=None, halos=None, **merge_args):
+        """Several consecutive matched batches through ct_hdr_merge_dark_batches: what ``merge`` on each of them in turn gives,
+        bit for bit, in one launch.  Lists, one entry per batch: ``matched`` (what ``match`` returned), ``images``,
+        ``exposures``, ``stds`` (or None) and ``halos`` -- the rows ``exchange_halo`` got for each batch when it was queued,
+        so that every rank issues its sends and receives in loader order (None for an untiled image).  ``merge_args``: lut,
+        interp, gaussian_weight, state, finalize, reference_order."""
+        return ops.hdr_merge_dark_batches(images, exposures, [m[0] for m in matched], [m[1] for m in matched], stds=stds,
+                                          std_mode=std_mode, std_value=std_value, max_code=max_code, tile=tile, halos=halos,
+                                          **merge_args)
 
     def linearize(self, index_batch, images, max_code, std, std_mode, std_value, lut, interp):
         xb, sig = self.apply(index_batch, images, max_code, std, std_mode, std_value)

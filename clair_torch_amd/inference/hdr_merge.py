@@ -15,12 +15,23 @@ from ..common.typecheck import expect
 from ..models.base import ICRFModelBase
 from ._staging import DeferredIngest, normalise_transform_list, refuse_tile_with_downscale, resolve_device, stage_images, std_arguments
 
+# The most the queued dark-field batches of one launch may hold on the device: frames, explicit stds, dark fields, dark stds and
+# halo rows.  Under 3 % of the device's memory, and about four batches of 4 frames of 3 x 4096 x 4096 uint16 with a dark field and
+# a dark std per frame (2 GB each: the dark fields are 8 B per element and frame).
+DARK_QUEUE_BYTES = 8 << 30
+
+
+def _dark_batch_bytes(images, std, matched, halo):
+    """What a queued dark-field batch holds on the device (dark field and dark std as the float32 the kernel reads)."""
+    held = sum(t.numel() * t.element_size() for t in (images, std, halo) if t is not None)
+    return held + sum(4 * t.numel() for t in matched if t is not None)
+
 
 def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFModelBase] = None,
                       weight_fn: Optional[Callable] = None, flat_field_dataset=None, gpu_transforms=None,
                       dark_field_dataset=None, tile: Optional[ops.TileGeometry] = None, group=None,
                       output_layout: str = "planar", reference_order: Optional[bool] = None, fused_ingest: bool = True,
-                      fused_dark: bool = True):
+                      fused_dark: bool = True, dark_batches_per_launch: int = 1):
     """Merge the exposure stack served by ``dataloader`` into an HDR image and its standard uncertainty.
 
     Returns ``(mean float64 (C,H,W), std float32 (C,H,W) | None)`` on ``device`` (squeezed like the reference).
@@ -53,7 +64,19 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
     ct_dark_field_blur, then the float32 merge.  The results are the same bit for bit.  On by default: the fused launch
     was faster than the pair at every measured shape, beyond the run-to-run spread (0.89-0.94 of its time for batches of 4,
     0.41-0.45 for batches of 32; profiles/merge_dark.md).
+    ``dark_batches_per_launch`` (extension, 1 .. 16): how many consecutive batches of that kind one launch takes.  1 = one launch
+    per matched batch, as above.  Above 1 such a batch is queued like the others -- staged images, its uncertainties, the
+    matched dark fields and, for a row band, the halo rows exchanged right then, so that every rank sends and receives in
+    loader order -- and the queue goes through ct_hdr_merge_dark_batches (one launch, the streaming state in registers between
+    the batches, bit for bit the launches it replaces) when the next batch is of another kind (unmatched, not fused, another
+    shape, dtype or uncertainty mode), when it holds ``dark_batches_per_launch`` batches, when the next batch would take it
+    above DARK_QUEUE_BYTES (8 GiB; a larger single batch runs alone), and at the end.  Measured on 32 exposures of 3x4096x4096:
+    0.67-0.74 of the time of one launch per batch for batches of 4 and 0.82-0.92 for batches of 8, every run faster than every
+    per-batch run (profiles/merge_dark_batches.md).  The default stays 1, one launch per matched batch as before this keyword
+    existed; pass 16 to queue.
     """
+    if type(dark_batches_per_launch) is not int or not 1 <= dark_batches_per_launch <= ops.MAX_MERGE_BATCHES:
+        raise ValueError(f"dark_batches_per_launch must be an int in 1 .. {ops.MAX_MERGE_BATCHES}, got {dark_batches_per_launch!r}")
     if output_layout not in ("planar", "input", "cv"):
         raise ValueError(f"unknown output_layout {output_layout!r} (planar, input, cv)")
     if output_layout == "input" and (flat_field_dataset is not None or dark_field_dataset is not None):
@@ -66,7 +89,7 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
     dev = resolve_device(device)
     dark = None
     if dark_field_dataset is not None:  # hdr_merge.py:76-92 (PARITY UNPINNED: the blur is torchvision's, restated)
-        from .dark_field import DarkField
+        from .dark_field import DarkField, exchange_halo
         dark = DarkField.from_dataset(dark_field_dataset, dataloader.dataset, dev)
     transforms = normalise_transform_list(gpu_transforms)
     refuse_tile_with_downscale(tile, transforms)
@@ -83,13 +106,24 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
     # ct_hdr_merge_batches call keeps the streaming state in registers across up to 16 batches instead of writing and
     # re-reading 32 B per element after every one of them (the reference's default is batch_size: 4).  The result is the
     # same bit for bit as merging batch by batch (per-batch detach of the state, hdr_merge.py:128, included).
-    queue, queue_key = [], None
+    queue, queue_key, queue_bytes = [], None, 0
 
     def flush(final):
-        nonlocal state, result, queue
+        nonlocal state, result, queue, queue_bytes
         if not queue:
             return
         k0 = queue[0]
+        if "matched" in k0:
+            # blur and merge of every queued dark-field batch in one launch (ct_hdr_merge_dark_batches)
+            if state is None and (not final or flat_field_dataset is not None):
+                state = ops.MergeState(tuple(k0["images"].shape[1:]), dev, with_variance=True)
+            result = dark.merge_batches([q["matched"] for q in queue], [q["images"] for q in queue], [q["exposure"] for q in queue],
+                                        k0["max_code"], None if k0["std"] is None else [q["std"] for q in queue], k0["std_mode"],
+                                        k0["std_value"], tile, None if k0["halo"] is None else [q["halo"] for q in queue],
+                                        lut=lut, interp=interp, gaussian_weight=weight_fn is not None, state=state,
+                                        finalize=final and flat_field_dataset is None, reference_order=reference_order)
+            queue, queue_bytes = [], 0
+            return
         if isinstance(k0["images"], DeferredIngest):
             # the chain and the merge of every queued batch in one launch (ct_hdr_merge_ingest_batches): the raw frames are
             # read once and the streaming state stays in registers between the batches, as on the code route
@@ -133,7 +167,22 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
             fused = False
         if dark is not None:
             matched = dark.match(index_batch, std, std_mode)
-            if matched is not None and fused_dark and dark.fuses_with_merge(images, layout, interp, reference_order):
+            fuses = matched is not None and fused_dark and dark.fuses_with_merge(images, layout, interp, reference_order)
+            if fuses and dark_batches_per_launch > 1:
+                # queued under a key of its own; the halo rows are exchanged now, in loader order on every rank
+                halo = exchange_halo(images, tile, group)
+                key = ("dark", images.dtype, tuple(images.shape[1:]), max_code, std_mode, std_value, std is None)
+                held = _dark_batch_bytes(images, std, matched, halo)
+                if queue and (key != queue_key or len(queue) == dark_batches_per_launch or queue_bytes + held > DARK_QUEUE_BYTES):
+                    flush(False)
+                queue_key = key
+                queue_bytes += held
+                queue.append(dict(images=images, exposure=meta_batch["exposure_time"], std=std, std_mode=std_mode, std_value=std_value,
+                                  max_code=max_code, matched=matched, halo=halo))
+                if last:
+                    flush(last)
+                continue
+            if fuses:
                 # blur and merge in one pass over the staged images (ct_hdr_merge_dark_batch), on the state the queued
                 # batches leave: they are merged first
                 flush(False)

@@ -728,7 +728,113 @@ def hdr_merge_dark_batch(stack: torch.Tensor, exposures: torch.Tensor, dark: tor
     return (mean_out, std_out) if finalize else None
 
 
-MAX_LINEARIZE_DARK_FRAMES = nv.LINEARIZE_DARK_MAX_FRAMES  # frames one ct_linearize_dark launch takes (longer stacks: several)
+def _exposure_list_on_device(exposures, sizes, device):
+    """``_exposure_list_to_device`` for lists that may live on the device already: those are concatenated there (no copy back
+    to the host, which would wait for the stream); host lists take the pinned staging copy."""
+    if not all(isinstance(e, torch.Tensor) and e.is_cuda for e in exposures):
+        return _exposure_list_to_device(exposures, sizes, device)
+    for e, n in zip(exposures, sizes):
+        if e.numel() != n:
+            raise ValueError(f"{e.numel()} exposure times for a batch of {n}")
+    return torch.cat([e.detach().to(device=device, dtype=torch.float64).reshape(-1) for e in exposures])
+
+
+def hdr_merge_dark_batches(stacks, exposures, darks, dark_stds, *, stds=None, std_mode: str = "none", std_value: float = 0.0,
+                           max_code: Optional[float] = None, lut: Optional[torch.Tensor] = None, interp: Optional[str] = "linear",
+                           gaussian_weight: bool = True, state: Optional[MergeState] = None, finalize: bool = True,
+                           first: Optional[bool] = None, tile: Optional[TileGeometry] = None, halos=None,
+                           mean_dtype: torch.dtype = torch.float64, reference_order: Optional[bool] = None,
+                           require_one_launch: bool = False, threshold: float = 0.05, alpha: float = 50.0):
+    """Several CONSECUTIVE dark-field batches of one merge in one call (ct_hdr_merge_dark_batches): the same result, bit for
+    bit, as ``hdr_merge_dark_batch`` on each of them in turn with ``state`` carried along -- but one launch walks them all with
+    the streaming state in registers in between (no state traffic between the batches).
+
+    ``stacks``: list of (B_k,C,H,W) device stacks of one dtype, image shape and device, each as ``hdr_merge_dark_batch`` takes
+    it; ``exposures``: list of (B_k) tensors (concatenated on the device when they are there already); ``darks``: list of
+    (1|B_k,C,H,W) dark fields; ``dark_stds``: list of their stds, or None for none at all; ``stds``: list of explicit std
+    tensors of the raw images or None; ``halos``: list of (B_k,C,2,W) halo rows of a row band or None.  At most
+    MAX_MERGE_BATCHES.  ``first``: None = the state decides (a fresh MergeState, or none, starts the merge); True / False
+    says so for a state filled elsewhere.  ``require_one_launch`` (tests): raise instead of falling back to one launch per
+    batch (more exposure times than the LDS holds beside the LUT).  Everything else as in ``hdr_merge_dark_batch``.
+    Returns (mean, std|None), planar (C,H,W), when ``finalize`` else None."""
+    k = len(stacks)
+    lists = (exposures, darks) + tuple(v for v in (dark_stds, stds, halos) if v is not None)
+    if k == 0 or any(len(v) != k for v in lists):
+        raise ValueError("stacks / exposures / darks / dark_stds / stds / halos must be non-empty lists of equal length")
+    if k > MAX_MERGE_BATCHES:
+        raise ValueError(f"at most {MAX_MERGE_BATCHES} batches per call")
+    if dark_stds is not None and any(t is None for t in dark_stds):
+        if any(t is not None for t in dark_stds):
+            raise ValueError("a dark std for every batch of one call, or for none")
+        dark_stds = None
+    if k == 1 and first is None:
+        return hdr_merge_dark_batch(stacks[0], exposures[0], darks[0], None if dark_stds is None else dark_stds[0], lut=lut,
+                                    interp=interp, gaussian_weight=gaussian_weight, std=None if stds is None else stds[0],
+                                    std_mode=std_mode, std_value=std_value, max_code=max_code, state=state, finalize=finalize,
+                                    tile=tile, halo=None if halos is None else halos[0], mean_dtype=mean_dtype,
+                                    reference_order=reference_order, threshold=threshold, alpha=alpha)
+    s0 = stacks[0]
+    for t in stacks:
+        _check_stack(t)
+        if t.dtype != s0.dtype or t.shape[1:] != s0.shape[1:] or t.device != s0.device:
+            raise ValueError("all batches of one call must share dtype, image shape and device")
+        if t.shape[0] < 1:
+            raise ValueError("empty batch")
+    _, c, h, w = s0.shape
+    dev = s0.device
+    if stds is not None:
+        std_mode = "explicit"
+        stds = [_explicit_std(sd, t) for sd, t in zip(stds, stacks)]
+    if std_mode not in _STD:
+        raise ValueError(f"unknown std_mode {std_mode}")
+    stacks = [t.contiguous() for t in stacks]
+    max_code = _default_max_code(s0, max_code)
+    checked = [_dark_arguments(t, darks[i], None if dark_stds is None else dark_stds[i], None if halos is None else halos[i])
+               for i, t in enumerate(stacks)]
+    darks, dark_stds, halos = ([v[j] for v in checked] for j in range(3))
+    if any(t is None for t in halos) and any(t is not None for t in halos):
+        raise ValueError("halo rows for every batch of one call, or for none")
+    has_std = dark_stds[0] is not None
+    sizes = [int(t.shape[0]) for t in stacks]
+    exposure_dev = _exposure_list_on_device(exposures, sizes, dev)
+    icrf, lut_keep = _icrf_struct(lut, interp, c)
+    geom = _geometry(stacks[0], tile)
+    flags, out_shape, mean_out, std_out = _merge_setup_for((c, h, w), dev, "planar", state, finalize, has_std, mean_dtype, reference_order,
+                                                           nv.MERGE_REQUIRE_ONE_LAUNCH if require_one_launch else 0, "call")
+
+    if first is not None:
+        flags = (flags | nv.MERGE_FIRST_BATCH) if first else (flags & ~nv.MERGE_FIRST_BATCH)
+
+    def pointers(tensors):
+        return (ctypes.c_void_p * k)(*[None if t is None else t.data_ptr() for t in tensors])
+
+    stack_arr, dark_arr, dark_std_arr, halo_arr = pointers(stacks), pointers(darks), pointers(dark_stds), pointers(halos)
+    std_arr = pointers(stds) if stds is not None else None
+    size_arr = (ctypes.c_int32 * k)(*sizes)
+    dark_size_arr = (ctypes.c_int32 * k)(*[int(t.shape[0]) for t in darks])
+
+    def call(st, fl):
+        with torch.cuda.device(dev):
+            return nv.load().ct_hdr_merge_dark_batches(
+                stack_arr, size_arr, k, _DTYPE[s0.dtype], float(max_code or 1.0), ctypes.byref(geom), halo_arr, std_arr, _STD[std_mode],
+                float(std_value), dark_arr, dark_std_arr, dark_size_arr, float(threshold), float(alpha), _ptr(exposure_dev),
+                ctypes.byref(icrf), nv.WEIGHT_GAUSS if gaussian_weight else nv.WEIGHT_NONE, *_state_ptrs(st), _ptr(mean_out),
+                _ptr(std_out), fl, _stream(dev))
+
+    # a whole merge in one launch needs no state arrays at all; only what cannot run as one launch walks the batches with
+    # the state in memory (nothing has been launched when the library says so)
+    rc = call(state, flags)
+    if rc == nv.ERR_UNSUPPORTED and state is None and not require_one_launch:
+        state = MergeState(out_shape, dev, has_std)
+        rc = call(state, flags)
+    nv.check(rc, "ct_hdr_merge_dark_batches")
+    del lut_keep
+    if state is not None:
+        state.batches += k
+    return (mean_out, std_out) if finalize else None
+
+
+MAX_LINEARIZE_DARK_FRAMES =nv.LINEARIZE_DARK_MAX_FRAMES  # frames one ct_linearize_dark launch takes (longer stacks: several)
 
 
 def _dark_per_frame(frames, darks, dark_stds):

@@ -68,7 +68,7 @@ extern "C" {
                                         float64 exp / divisions; ct_merge_exact.hip).  Default for LOOKUP and CATMULL with
                                         uncertainties, whose reference results are dominated by float32 cancellation */
 #define CT_MERGE_CLOSED_FORM 32u     /* keep the fast closed-form kernels for LOOKUP / CATMULL with uncertainties as well */
-#define CT_MERGE_REQUIRE_ONE_LAUNCH 128u /* ct_hdr_merge_batches, ct_hdr_merge_ingest_batches: CT_ERR_UNSUPPORTED instead of one launch per batch */
+#define CT_MERGE_REQUIRE_ONE_LAUNCH 128u /* ct_hdr_merge_batches, ct_hdr_merge_ingest_batches, ct_hdr_merge_dark_batches: CT_ERR_UNSUPPORTED instead of one launch per batch */
 #define CT_MERGE_STD_HINT 64u        /* ct_hdr_merge_kernel_name only: uncertainties are propagated */
 #define CT_MERGE_OUT_AS_INPUT 256u   /* extension: state and outputs in the MEMORY ORDER OF THE INPUT stack instead of planar
                                         (C, H, W): an interleaved (H, W, C) RGB / BGR stack then gives (H, W, C) outputs in the
@@ -354,7 +354,40 @@ int ct_hdr_merge_dark_batch(const void *stack_dev, int32_t dtype, float max_code
                             void *stream);
 
 /*
- * ct_linearize_dark -- that blur and the body of linearize_dataset_generator in ONE pass over F independent raw frames, each
+ * ct_hdr_merge_dark_batches -- n_batches consecutive dark-field batches of one merge in one call: exactly
+ * ct_hdr_merge_dark_batch applied to batch 0 .. n_batches - 1 in turn on the same state, bit for bit -- but where it can, ONE
+ * launch walks all of them with (mean, sum of weights, variance) in registers in between: the state arrays are read at most
+ * once (not at all with CT_MERGE_FIRST_BATCH) and written at most once, and only if a state was passed, where a launch per batch
+ * reads 16 B and writes 16 B per element and batch beside the samples and dark fields.
+ *   stack_devs, batch_sizes, dark_devs, dark_batches   HOST arrays of n_batches (1 .. 16) entries: batch b is batch_sizes[b]
+ *                frames at stack_devs[b] with dark_batches[b] (1 or batch_sizes[b]) dark fields at dark_devs[b], each as
+ *                ct_hdr_merge_dark_batch takes it; one dtype, max_code and geometry (image_stride included) for all of them
+ *   halo_devs    HOST array of n_batches device pointers, each the (B_b, C, 2, W) halo rows of that batch, or NULL as a whole;
+ *                its entries are all NULL or all non-NULL
+ *   std_devs     CT_STD_EXPLICIT: HOST array of n_batches device pointers, each laid out like its stack; else NULL as a whole
+ *   dark_std_devs  HOST array of n_batches device pointers, or NULL as a whole; its entries are all NULL or all non-NULL
+ *   exposure_dev the exposure times of all batches, concatenated (sum of batch_sizes doubles)
+ *   flags        as ct_hdr_merge_dark_batch; CT_MERGE_FIRST_BATCH applies to the first and CT_MERGE_FINALIZE to the last batch.
+ *                CT_MERGE_REQUIRE_ONE_LAUNCH: CT_ERR_UNSUPPORTED instead of one launch per batch.
+ * n_batches outside 1 .. 16 (or a missing array) is CT_ERR_INVALID_ARGUMENT; n_batches == 1 is ct_hdr_merge_dark_batch.  A
+ * mixture of NULL and non-NULL entries in dark_std_devs or in halo_devs is CT_ERR_INVALID_ARGUMENT.  Then every batch is judged
+ * as ct_hdr_merge_dark_batch judges it (its checks in its order, the same status codes, the first refusal wins; the flags are
+ * those of the whole call, so a state is needed unless both FIRST_BATCH and FINALIZE are set).  Every argument is validated
+ * before anything touches the device.  One launch needs the LUT with 8 B per exposure of ALL batches to fit 160 KiB of LDS;
+ * where only each batch alone fits, the batches are launched one by one on the state in memory -- not CT_ERR_TOO_LARGE --
+ * which then must be given: without state arrays, or with CT_MERGE_REQUIRE_ONE_LAUNCH, that is CT_ERR_UNSUPPORTED and nothing
+ * is launched.  Allocates nothing, synchronises nothing, reads nothing back, never writes the frames or the dark fields,
+ * touches nothing outside C*H_tile*W elements of the state and the outputs.
+ */
+int ct_hdr_merge_dark_batches(const void *const *stack_devs, const int32_t *batch_sizes, int32_t n_batches, int32_t dtype,
+                              float max_code, const ct_geometry *geom, const void *const *halo_devs, const float *const *std_devs,
+                              int32_t std_mode, float std_value, const float *const *dark_devs, const float *const *dark_std_devs,
+                              const int32_t *dark_batches, float threshold, float alpha, const double *exposure_dev,
+                              const ct_icrf *icrf, int32_t weight_mode, double *mean_state_dev, float *sumw_state_dev,
+                              float *var_state_dev, void *mean_out_dev, float *std_out_dev, uint32_t flags, void *stream);
+
+/*
+ * ct_linearize_dark --that blur and the body of linearize_dataset_generator in ONE pass over F independent raw frames, each
  * its own batch of one (linearization.py:42) with its own matched dark field: for every frame lin_out and std_out are bit for
  * bit those of ct_dark_field_blur on it (batch = 1, dark_batch = 1) into float32 xb and sigma_eff followed by
  * ct_linearize_std on (xb, CT_DTYPE_F32, std = sigma_eff, CT_STD_EXPLICIT) -- without the two stacks: sizeof(code) + 8 bytes
