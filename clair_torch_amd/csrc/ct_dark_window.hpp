@@ -3,7 +3,9 @@
 // rows lie, how they are loaded, and the conditional blur with its effective uncertainty.  The blur is dark_blur_kernel's
 // expressions (ct_darkfield.hip) in its operation order; that kernel keeps its own plain statement of them, and the GPU
 // tests hold both fused kernels to it bit for bit.  Templated on the argument block (norm, k0, k1, threshold, alpha, std_mode,
-// std_value), so every kernel keeps the layout of its own.
+// std_value), so every kernel keeps the layout of its own.  The blur itself works on floats (dark_blur_staged), so a kernel
+// that puts something between the load and the blur -- ct_linearize_dark_ingest.hip: a gpu_transforms chain -- runs the same
+// expressions.
 #pragma once
 #include "ct_device.hpp"
 
@@ -89,8 +91,38 @@ __device__ __forceinline__ void dark_load(DarkRaw<T, G> &r, const DarkRows<T> &r
     }
 }
 
-// xb and sigma_eff of the G elements: dark_blur_kernel, expression for expression.  The std mode of the raw image is a
-// wave-uniform run-time branch; without a dark std (HAS_STD false) nothing is propagated and sig is 1.
+// xb and sigma_eff of the G elements from the window as floats -- ru, rm, rd: the G + 2 pixel values of the rows h - 1, h,
+// h + 1; d, ds, sg: the dark field, its std and the explicit sigma of the G elements -- dark_blur_kernel, expression for
+// expression.  The std mode of the raw image is a wave-uniform run-time branch; without a dark std (HAS_STD false) nothing is
+// propagated and sig is 1.  Of the argument block only k0, k1, threshold, alpha, std_mode and std_value are read.
+template <int G, bool HAS_STD, typename Args>
+__device__ __forceinline__ void dark_blur_staged(const Args &a, const float *ru, const float *rm, const float *rd, const float *d,
+                                                 const float *ds, const float *sgx, bool explicit_sigma, float *xb, float *sig)
+{
+#pragma unroll
+    for (int e = 0; e < G; ++e) {
+        const float bu = (a.k1 * ru[e] + a.k0 * ru[e + 1]) + a.k1 * ru[e + 2];
+        const float bm = (a.k1 * rm[e] + a.k0 * rm[e + 1]) + a.k1 * rm[e + 2];
+        const float bd = (a.k1 * rd[e] + a.k0 * rd[e + 1]) + a.k1 * rd[e + 2];
+        const float x = rm[e + 1];
+        const float blurred = (a.k1 * bu + a.k0 * bm) + a.k1 * bd;
+        const float dv = d[e];
+        const float m = 1.0f / (1.0f + expf(-(dv - a.threshold) * a.alpha));  // torch.sigmoid
+        xb[e] = m * blurred + (1.0f - m) * x;
+        sig[e] = 1.0f;
+        if constexpr (HAS_STD) {
+            float sg = 0.0f;
+            if (explicit_sigma) sg = sgx[e];
+            if (a.std_mode == CT_STD_CONSTANT) sg = a.std_value;
+            if (a.std_mode == CT_STD_MULTIPLIER) sg = a.std_value * x;  // the dataset derives sigma from the RAW image
+            const float dterm = (blurred - x) * (a.alpha * m * (1.0f - m));
+            const float dsv = dterm * ds[e];
+            sig[e] = sqrtf(sg * sg + dsv * dsv);
+        }
+    }
+}
+
+// ... of the window as loaded: every element to its pixel value (to_pixel with a.norm), then the blur above
 template <typename T, int G, bool HAS_STD, typename Args>
 __device__ __forceinline__ void dark_blur(const Args &a, const DarkRaw<T, G> &r, bool explicit_sigma, float *xb, float *sig)
 {
@@ -101,27 +133,7 @@ __device__ __forceinline__ void dark_blur(const Args &a, const DarkRaw<T, G> &r,
         rm[j] = to_pixel<T>(r.mid[j], a.norm);
         rd[j] = to_pixel<T>(r.dn[j], a.norm);
     }
-#pragma unroll
-    for (int e = 0; e < G; ++e) {
-        const float bu = (a.k1 * ru[e] + a.k0 * ru[e + 1]) + a.k1 * ru[e + 2];
-        const float bm = (a.k1 * rm[e] + a.k0 * rm[e + 1]) + a.k1 * rm[e + 2];
-        const float bd = (a.k1 * rd[e] + a.k0 * rd[e + 1]) + a.k1 * rd[e + 2];
-        const float x = rm[e + 1];
-        const float blurred = (a.k1 * bu + a.k0 * bm) + a.k1 * bd;
-        const float d = r.d[e];
-        const float m = 1.0f / (1.0f + expf(-(d - a.threshold) * a.alpha));  // torch.sigmoid
-        xb[e] = m * blurred + (1.0f - m) * x;
-        sig[e] = 1.0f;
-        if constexpr (HAS_STD) {
-            float sg = 0.0f;
-            if (explicit_sigma) sg = r.sg[e];
-            if (a.std_mode == CT_STD_CONSTANT) sg = a.std_value;
-            if (a.std_mode == CT_STD_MULTIPLIER) sg = a.std_value * x;  // the dataset derives sigma from the RAW image
-            const float dterm = (blurred - x) * (a.alpha * m * (1.0f - m));
-            const float ds = dterm * r.ds[e];
-            sig[e] = sqrtf(sg * sg + ds * ds);
-        }
-    }
+    dark_blur_staged<G, HAS_STD>(a, ru, rm, rd, r.d, r.ds, r.sg, explicit_sigma, xb, sig);
 }
 
 }  // namespace ct

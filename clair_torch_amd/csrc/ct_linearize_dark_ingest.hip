@@ -1,0 +1,322 @@
+// ct_linearize_dark_ingest.hip -- a recognised gpu_transforms chain, the dark-field conditional blur and the ICRF linearization of
+// F independent RAW frames in ONE pass (gfx950).  For every frame the outputs are bit for bit those of ct_ingest_transform
+// (ct_ingest.hip) on it into a planar float32 stack x, ct_dark_field_blur (ct_darkfield.hip) on x as a batch of one with its
+// own matched dark field into xb and sigma_eff, and ct_linearize_std (ct_linearize.hip) on (xb, CT_DTYPE_F32, std = sigma_eff,
+// CT_STD_EXPLICIT): the same device functions run here on values that never leave the registers.  The 9 taps of a sample's
+// window go through ct::ingest_stages<false> (ct_ingest_stages.hpp) with the tap's PLANE channel, the blur is dark_blur_staged
+// (ct_dark_window.hpp: dark_blur_kernel's expressions in its order, on floats), the sample step is li_sample4<INTERP,
+// CT_STD_EXPLICIT, true> (ct_linearize_ingest.hpp).  float32 throughout, every operation rounded on its own
+// (-ffp-contract=off).  tests/test_gpu_linearize_dark_ingest.py holds the kernels to the three launches bit for bit.
+//
+// Roofline: HBM.  Per sample sizeof(T) bytes of the frame (window neighbours are L1 / L2 hits), 4 of the dark field and 4 of
+// its std (+ 4 with explicit image uncertainties), 8 written: 18 B per uint16 sample with derived uncertainties (22 explicit)
+// where the three launches move 2 + 4, then 4 + 8 + 8, then 8 + 8 = 42 (46), and the three float32 stacks of a group never
+// exist.  (Byte counts from the shapes; what was timed: profiles/linearize_dark_ingest.md.)
+//
+// Ownership.  At most CT_LINEARIZE_DARK_MAX_FRAMES frames per launch: their dark-field pointers travel in the argument block,
+// like the stage list; the stage loop is wave-uniform.
+// PLANAR (CT_LAYOUT_NCHW, any C): the walk of linearize_dark_kernel (ct_linearize_dark.hip).  A workgroup row (blockIdx.y) is
+//   one (frame, channel) plane, so the clamp pair is wave-uniform; a thread owns 4 consecutive columns of ONE image row,
+//   3 x (1 + 4 + 1) window loads; the end of a row whose width is no multiple of 4 goes one element after the other.
+// PACKED3 (CT_LAYOUT_NHWC / NHWC_BGR, raw (F, H, W, 3) frames): a workgroup row is one frame.  A thread owns 4 consecutive
+//   PIXELS of one image row with all 3 channels: on each of the three rows the 12 contiguous elements of its pixels and the
+//   3 of the pixel left and of the pixel right of them (or the reflected ones) -- neighbours of a sample lie 3 elements apart
+//   in a row and 3 * W apart between rows.  It regroups in registers and writes one packet per plane and output, so the frame
+//   is read once; memory channel cm feeds plane 2 - cm with BGR (a wave-uniform index, not a variant).  This is the only
+//   interleaved walk built: three stride-3 walks, one per plane, would read every frame three times through the caches and
+//   were neither built nor timed.
+// The dark field, its std and explicit image uncertainties are planar (C, H, W) float32 in plane (RGB) order whatever the
+// layout of the frames.  A workgroup walks kLdiSlots groups per thread, a workgroup apart, so one staging of the LUT
+// (stage_lut) serves kLdiSlots * 1024 samples per plane.  Outputs are one packet where the group is 16-byte aligned in
+// memory (li_store), else elements.  No atomics, no LDS tile; frames, dark fields and uncertainties are read only.  No row
+// bands (no halo is built here), no CT_INGEST_AFFINE_DATA stage, no LOOKUP (no gradient path: refused, no kernel).
+//
+// Resources (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage; scratch is 0 bytes for all 18 kernels),
+// VGPRs for LINEAR / CATMULL / no LUT:
+//   planar   uint8, uint16, float32: 73 / 73 / 71 each (6 to 7 wavefronts per SIMD)
+//   packed3  uint8 111 / 111 / 109, uint16 115 / 115 / 114 (4 wavefronts per SIMD), float32 148 / 148 / 147 (3)
+// Measured on 16 x 3 x 1080 x 1920 (profiles/linearize_dark_ingest.md): 0.55 to 0.63 of the time of the three launches, 2.8 to
+// 3.5 TB/s of the bytes counted above; the packed3 walk's occupancy is the first thing to look at for more.
+#include <algorithm>
+#include "ct_dark_window.hpp"
+#include "ct_linearize_ingest.hpp"
+
+namespace ct {
+
+struct LinDarkIngestArgs {
+    const void *frames;      // (F, C, H, W) or (F, H, W, 3) T, image_stride between frames
+    const float *std_in;     // explicit sigma of the raw image: planar (F, C, H, W) float32, dense, or NULL
+    const float *lut;
+    float *lin_out;          // (F, C, H, W) dense
+    float *std_out;
+    const float *dark[CT_LINEARIZE_DARK_MAX_FRAMES];      // (C, H, W) each, one per frame of this launch
+    const float *dark_std[CT_LINEARIZE_DARK_MAX_FRAMES];
+    int64_t image_stride;
+    uint32_t plane;          // H * W
+    uint32_t width, h_tile;
+    uint32_t channels, n_points;
+    uint32_t reversed;       // PACKED3: memory channel cm feeds plane 2 - cm (BGR)
+    uint32_t by_channel;     // some clamp holds different pairs for different channels; else every channel takes pair 0
+    NormConst norm;          // (fill_blur_args; the chain stands where the code normalisation would)
+    int32_t std_mode;        // of the image behind the chain: how sigma enters sigma_eff
+    float std_value, threshold, alpha;
+    float k0, k1;            // the two distinct taps of the normalised 1-D kernel: k0 (centre), k1 (sides)
+    uint32_t n_stages;
+    ct_ingest_stage stage[CT_INGEST_MAX_STAGES];
+};
+
+constexpr int kLdiGroup = kLiGroup;  // columns / pixels per thread
+constexpr int kLdiSlots = 4;         // groups per thread
+
+static inline __host__ __device__ uint32_t ldi_groups_per_row(uint32_t width) { return (width + kLdiGroup - 1) / kLdiGroup; }
+
+// PLANAR: xb and sigma_eff of columns w0 .. w0 + G - 1 of row h of plane c0 of the frame at `frame` (its dark field: dark,
+// dark_std; its explicit sigma: sigma or NULL, planar like the dark field)
+template <typename T, int G>
+__device__ __forceinline__ void ldi_planar(const LinDarkIngestArgs &a, const T *frame, const float *sigma, const float *dark,
+                                           const float *dark_std, uint32_t c0, uint32_t h, uint32_t w0, float *xb, float *sig)
+{
+    constexpr int N = G + 2;
+    const uint32_t q = c0 * a.plane + h * a.width + w0;  // first element inside the (C, H, W) frame
+    const DarkRows<T> rw = dark_rows<T, G, false>(a, frame + (int64_t)c0 * a.plane, c0, h, w0);
+    const bool explicit_sigma = a.std_mode == CT_STD_EXPLICIT;
+    DarkRaw<T, G> raw{};
+    dark_load<T, G, true>(raw, rw, 0, 0, dark, dark_std, 0, explicit_sigma, sigma, q);
+    float v[3 * N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        v[j] = (float)raw.up[j];
+        v[N + j] = (float)raw.mid[j];
+        v[2 * N + j] = (float)raw.dn[j];
+    }
+    ingest_stages<false>(v, a, a.by_channel ? c0 : 0u);
+    dark_blur_staged<G, true>(a, v, v + N, v + 2 * N, raw.d, raw.ds, raw.sg, explicit_sigma, xb, sig);
+}
+
+template <typename T, int INTERP>
+__global__ __launch_bounds__(kBlock) void linearize_dark_ingest_planar_kernel(const LinDarkIngestArgs a)
+{
+    extern __shared__ __align__(16) char lds[];
+    const int C = (int)a.channels, L = (int)a.n_points;
+    stage_lut<INTERP>(lds, a.lut, C, L);
+    __syncthreads();
+    const uint32_t f = blockIdx.y / a.channels, c0 = blockIdx.y - f * a.channels;  // frame of this launch, channel
+    const T *frame = static_cast<const T *>(a.frames) + (int64_t)f * a.image_stride;
+    const int64_t out0 = (int64_t)f * C * a.plane;  // the frame inside the dense planar arrays
+    const float *sigma = a.std_in ? a.std_in + out0 : nullptr;
+    const float *dark = a.dark[f], *dark_std = a.dark_std[f];
+    const uint32_t W = a.width;
+    const uint32_t gpr = ldi_groups_per_row(W);
+    const uint64_t n_slots = (uint64_t)gpr * a.h_tile;
+#pragma unroll 1
+    for (int k = 0; k < kLdiSlots; ++k) {
+        const uint64_t slot = ((uint64_t)blockIdx.x * kLdiSlots + k) * kBlock + threadIdx.x;
+        if (slot >= n_slots) break;
+        const uint32_t h = (uint32_t)(slot / gpr);
+        const uint32_t w0 = ((uint32_t)slot - h * gpr) * kLdiGroup;
+        float xb[kLdiGroup] = {0.0f, 0.0f, 0.0f, 0.0f}, sig[kLdiGroup] = {0.0f, 0.0f, 0.0f, 0.0f};
+        int n = kLdiGroup;
+        if (W - w0 >= (uint32_t)kLdiGroup) {
+            ldi_planar<T, kLdiGroup>(a, frame, sigma, dark, dark_std, c0, h, w0, xb, sig);
+        } else {
+            // the end of a row whose width is no multiple of the group (at most kLdiGroup - 1 elements): one lane, one element
+            // after the other, each with its own window
+            n = (int)(W - w0);
+#pragma unroll
+            for (int e = 0; e < kLdiGroup - 1; ++e)
+                if (e < n) ldi_planar<T, 1>(a, frame, sigma, dark, dark_std, c0, h, w0 + e, &xb[e], &sig[e]);
+        }
+        // the frame is batch element 0 of its own batch: the LINEAR / CATMULL row is the flat (C, H, W) index modulo C
+        const uint32_t q = c0 * a.plane + h * W + w0;
+        const int r = C == 3 ? (int)(q % 3u) : (int)(q % a.channels);
+        LinIngestPacket lo, so;
+        li_sample4<INTERP, CT_STD_EXPLICIT, true>(xb, sig, lds, L, C, (int)c0, r, 0.0f, lo, so);
+        li_store(a.lin_out + out0 + q, lo, n);
+        li_store(a.std_out + out0 + q, so, n);
+    }
+}
+
+// PACKED3: xb and sigma_eff of pixels w0 .. w0 + G - 1 of row h of the interleaved frame at `frame`, all 3 channels, into
+// elements E0 .. E0 + G - 1 of xb[cm] / sig[cm] (cm: the MEMORY channel; its plane is 2 - cm with a.reversed)
+template <typename T, int G, int E0>
+__device__ __forceinline__ void ldi_packed3(const LinDarkIngestArgs &a, const T *frame, const float *sigma, const float *dark,
+                                            const float *dark_std, uint32_t h, uint32_t w0, float (&xb)[3][kLdiGroup],
+                                            float (&sig)[3][kLdiGroup])
+{
+    constexpr int C = 3, N = G + 2;
+    const uint32_t W = a.width, H = a.h_tile;
+    // rows and column taps with reflect padding (index -1 -> 1, H -> H - 2, W -> W - 2)
+    const uint32_t hu = h > 0 ? h - 1 : 1, hd = h + 1 < H ? h + 1 : H - 2;
+    const uint32_t cl = w0 > 0 ? w0 - 1 : 1, cr = w0 + G < W ? w0 + G : W - 2;
+    T raw[3][N * C];  // rows h - 1, h, h + 1: pixels {left, w0 .. w0 + G - 1, right}, 3 elements each
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const T *row = frame + (int64_t)(k == 0 ? hu : (k == 1 ? h : hd)) * W * C;
+        __builtin_memcpy(&raw[k][0], row + (int64_t)cl * C, C * sizeof(T));  // any alignment: rows are only element-aligned
+        __builtin_memcpy(&raw[k][C], row + (int64_t)w0 * C, G * C * sizeof(T));
+        __builtin_memcpy(&raw[k][(G + 1) * C], row + (int64_t)cr * C, C * sizeof(T));
+    }
+    const bool explicit_sigma = a.std_mode == CT_STD_EXPLICIT;
+#pragma unroll
+    for (int cm = 0; cm < C; ++cm) {
+        const uint32_t c = a.reversed ? (uint32_t)(C - 1 - cm) : (uint32_t)cm;  // plane (wave-uniform)
+        const uint32_t q = c * a.plane + h * W + w0;                           // first element inside the planar (C, H, W) arrays
+        float v[3 * N];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int j = 0; j < N; ++j) v[k * N + j] = (float)raw[k][j * C + cm];
+        ingest_stages<false>(v, a, a.by_channel ? c : 0u);
+        float d[G], ds[G], sg[G];
+        __builtin_memcpy(d, dark + q, sizeof(d));
+        __builtin_memcpy(ds, dark_std + q, sizeof(ds));
+#pragma unroll
+        for (int e = 0; e < G; ++e) sg[e] = 0.0f;
+        if (explicit_sigma) __builtin_memcpy(sg, sigma + q, sizeof(sg));
+        dark_blur_staged<G, true>(a, v, v + N, v + 2 * N, d, ds, sg, explicit_sigma, &xb[cm][E0], &sig[cm][E0]);
+    }
+}
+
+template <typename T, int INTERP>
+__global__ __launch_bounds__(kBlock) void linearize_dark_ingest_packed3_kernel(const LinDarkIngestArgs a)
+{
+    extern __shared__ __align__(16) char lds[];
+    constexpr int C = 3;
+    const int L = (int)a.n_points;
+    stage_lut<INTERP>(lds, a.lut, C, L);
+    __syncthreads();
+    const uint32_t f = blockIdx.y;  // frame of this launch
+    const T *frame = static_cast<const T *>(a.frames) + (int64_t)f * a.image_stride;
+    const int64_t out0 = (int64_t)f * C * a.plane;
+    const float *sigma = a.std_in ? a.std_in + out0 : nullptr;
+    const float *dark = a.dark[f], *dark_std = a.dark_std[f];
+    const uint32_t W = a.width;
+    const uint32_t gpr = ldi_groups_per_row(W);
+    const uint64_t n_slots = (uint64_t)gpr * a.h_tile;
+#pragma unroll 1
+    for (int k = 0; k < kLdiSlots; ++k) {
+        const uint64_t slot = ((uint64_t)blockIdx.x * kLdiSlots + k) * kBlock + threadIdx.x;
+        if (slot >= n_slots) break;
+        const uint32_t h = (uint32_t)(slot / gpr);
+        const uint32_t w0 = ((uint32_t)slot - h * gpr) * kLdiGroup;
+        float xb[C][kLdiGroup] = {}, sig[C][kLdiGroup] = {};
+        int n = kLdiGroup;
+        if (W - w0 >= (uint32_t)kLdiGroup) {
+            ldi_packed3<T, kLdiGroup, 0>(a, frame, sigma, dark, dark_std, h, w0, xb, sig);
+        } else {
+            // the end of a row whose width is no multiple of the group (1 to 3 pixels): one pixel after the other
+            n = (int)(W - w0);
+            ldi_packed3<T, 1, 0>(a, frame, sigma, dark, dark_std, h, w0, xb, sig);
+            if (n > 1) ldi_packed3<T, 1, 1>(a, frame, sigma, dark, dark_std, h, w0 + 1, xb, sig);
+            if (n > 2) ldi_packed3<T, 1, 2>(a, frame, sigma, dark, dark_std, h, w0 + 2, xb, sig);
+        }
+#pragma unroll
+        for (int cm = 0; cm < C; ++cm) {
+            const uint32_t c = a.reversed ? (uint32_t)(C - 1 - cm) : (uint32_t)cm;
+            const uint32_t q = c * a.plane + h * W + w0;
+            LinIngestPacket lo, so;
+            li_sample4<INTERP, CT_STD_EXPLICIT, true>(xb[cm], sig[cm], lds, L, C, (int)c, (int)(q % 3u), 0.0f, lo, so);
+            li_store(a.lin_out + out0 + q, lo, n);
+            li_store(a.std_out + out0 + q, so, n);
+        }
+    }
+}
+
+template <typename T, int INTERP>
+static int ldi_launch(const LinDarkIngestArgs &a, bool packed, int n_frames, hipStream_t s)
+{
+    const size_t lds = lut_lds_bytes(INTERP, (int)a.channels, (int)a.n_points);
+    const uint64_t slots = (uint64_t)ldi_groups_per_row(a.width) * a.h_tile;
+    const uint64_t per_block = (uint64_t)kBlock * kLdiSlots;
+    const dim3 grid((uint32_t)((slots + per_block - 1) / per_block), (uint32_t)n_frames * (packed ? 1u : a.channels));
+    if (packed)
+        hipLaunchKernelGGL((linearize_dark_ingest_packed3_kernel<T, INTERP>), grid, dim3(kBlock), lds, s, a);
+    else
+        hipLaunchKernelGGL((linearize_dark_ingest_planar_kernel<T, INTERP>), grid, dim3(kBlock), lds, s, a);
+    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
+}
+
+template <typename T>
+static int ldi_dispatch(const LinDarkIngestArgs &a, bool packed, int interp, int n_frames, hipStream_t s)
+{
+    // (LOOKUP has no gradient path: refused by the entry point, no kernel)
+    return with_enum<CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp,
+                                                                          [&](auto I) { return ldi_launch<T, I>(a, packed, n_frames, s); });
+}
+
+}  // namespace ct
+
+extern "C" int ct_linearize_dark_ingest(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
+                                        const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,
+                                        float std_value, const float *const *dark_devs, const float *const *dark_std_devs,
+                                        float threshold, float alpha, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev,
+                                        void *stream)
+{
+    using namespace ct;
+    // ---- what ct_linearize_dark refuses first: pointers, the frame count, a dark field per frame ----
+    if (!frames_dev || !geom || !dark_devs || !dark_std_devs || !lin_out_dev || !std_out_dev || n_frames <= 0 || n_frames > 0x7fffffff)
+        return CT_ERR_INVALID_ARGUMENT;
+    for (int64_t k = 0; k < n_frames; ++k)
+        if (!dark_devs[k] || !dark_std_devs[k]) return CT_ERR_INVALID_ARGUMENT;
+    // ---- the dark geometry, of the planar image the chain yields (the layout of the raw frames is the stage list's matter) ----
+    ct_geometry planar = *geom;
+    planar.layout = CT_LAYOUT_NCHW;
+    if (int rc = check_dark_frames(&planar, 1, 1, true, std_mode, std_dev)) return rc;
+    if (geom->row_offset != 0 || geom->h_tile != geom->h_global) return CT_ERR_UNSUPPORTED;  // a row band: no halo is built here
+    if (int rc = check_dark_band(&planar, nullptr)) return rc;  // (the whole image: what is left of it is the stride)
+    // ---- the stack and the stage list: constant chains only ----
+    bool by_channel = false;
+    if (int rc = ingest_validate(dtype, geom->layout, n_frames, geom->channels, geom->h_tile * geom->width, stages, n_stages,
+                                 CT_INGEST_MAX_STAGES, 0, by_channel))
+        return rc;
+    // ---- the model: float32 pixels with explicit uncertainties, as ct_linearize_std sees (xb, sigma_eff) ----
+    if (!icrf || !icrf_ok(icrf)) return CT_ERR_INVALID_ARGUMENT;
+    const int interp = icrf->interp;
+    if (interp == CT_INTERP_LOOKUP) return CT_ERR_NO_GRADIENT_PATH;  // linearization.py:100-105
+    const int n_points = icrf_points(icrf);
+    if (lut_lds_bytes(interp, geom->channels, n_points) > kLdsBudget) return CT_ERR_TOO_LARGE;
+    if (!global_below_2_31(geom)) return CT_ERR_TOO_LARGE;
+    const bool packed = geom->layout != CT_LAYOUT_NCHW;
+    // frames per launch: what the argument block holds, and a grid's y extent (65535) in workgroup rows
+    const int64_t per_launch = std::min<int64_t>(CT_LINEARIZE_DARK_MAX_FRAMES, (int64_t)kLiMaxRows / (packed ? 1 : geom->channels));
+    if (per_launch < 1) return CT_ERR_TOO_LARGE;
+    if (!li_pointers_ok(frames_dev, dtype, std_dev, lin_out_dev, std_out_dev)) return CT_ERR_INVALID_ARGUMENT;
+    for (int64_t k = 0; k < n_frames; ++k)
+        if (!aligned(dark_devs[k], sizeof(float)) || !aligned(dark_std_devs[k], sizeof(float))) return CT_ERR_INVALID_ARGUMENT;
+
+    const int64_t plane = geom->h_tile * geom->width;
+    const size_t elem = dtype_bytes(dtype);
+    LinDarkIngestArgs a{};
+    a.lut = icrf->lut_dev;
+    a.image_stride = geom->image_stride;
+    a.plane = (uint32_t)plane;
+    a.width = (uint32_t)geom->width;
+    a.h_tile = (uint32_t)geom->h_tile;
+    a.channels = (uint32_t)geom->channels;
+    a.n_points = (uint32_t)n_points;
+    a.reversed = geom->layout == CT_LAYOUT_NHWC_BGR ? 1u : 0u;
+    a.by_channel = by_channel ? 1u : 0u;
+    a.n_stages = (uint32_t)n_stages;
+    for (int32_t k = 0; k < n_stages; ++k) a.stage[k] = stages[k];
+    fill_blur_args(a, NormConst{1.0f, 0.0f}, std_mode, std_value, threshold, alpha);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    for (int64_t first = 0; first < n_frames; first += per_launch) {
+        const int nf = (int)std::min<int64_t>(per_launch, n_frames - first);
+        a.frames = static_cast<const char *>(frames_dev) + first * geom->image_stride * (int64_t)elem;
+        a.std_in = std_mode == CT_STD_EXPLICIT ? std_dev + first * geom->channels * plane : nullptr;
+        a.lin_out = lin_out_dev + first * geom->channels * plane;
+        a.std_out = std_out_dev + first * geom->channels * plane;
+        for (int k = 0; k < nf; ++k) {
+            a.dark[k] = dark_devs[first + k];
+            a.dark_std[k] = dark_std_devs[first + k];
+        }
+        int rc;
+        switch (dtype) {
+            case CT_DTYPE_U8: rc = ldi_dispatch<uint8_t>(a, packed, interp, nf, s); break;
+            case CT_DTYPE_U16: rc = ldi_dispatch<uint16_t>(a, packed, interp, nf, s); break;
+            default: rc = ldi_dispatch<float>(a, packed, interp, nf, s); break;
+        }
+        if (rc != CT_OK) return rc;
+    }
+    return CT_OK;
+}

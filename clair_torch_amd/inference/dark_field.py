@@ -118,6 +118,22 @@ class DarkField:
         return plan.route == "torch" and plan.no_transforms and t.dtype == torch.float32
 
     @staticmethod
+    def fuses_with_linearize_ingest(probe, plan, interp) -> bool:
+        """The second route decision of linearize_dataset_generator with a dark-field dataset, asked for what
+        ``fuses_with_linearize`` declined (``fused_dark_ingest``): True = the streamed pipeline with ct_linearize_dark_ingest on
+        the matched frames (chain, blur and ICRF in one pass over the slot's raw frames).  ``probe`` and ``plan`` as above.
+        Fused are 4-D uint8 / uint16 / float32 frames on route "ingest" -- a black level, a target range, ``ClampAlongDims``,
+        raw (H,W,3) BGR frames behind a leading ``CvToTorch`` -- without a StridedDownscale, LINEAR / CATMULL.  A
+        data-dependent Normalize (route "ingest_data"), a StridedDownscale, LOOKUP and lists that run as torch ops stay frame
+        by frame."""
+        t = probe
+        if not isinstance(t, torch.Tensor) or t.ndim != 4 or interp not in ("linear", "catmull"):
+            return False
+        if plan.route != "ingest" or plan.step != 1:
+            return False
+        return t.dtype in (torch.uint8, torch.uint16, torch.float32) and plan.source_layout in ("nchw", "nhwc_bgr")
+
+    @staticmethod
     def cache_key(dark, dark_std):
         """What identifies the contents of a matched host pair: address, in-place version counter, shape and dtype of both
         (an in-place edit bumps ``_version``; the cache holds the host tensors, so an address is not re-used while its

@@ -42,7 +42,14 @@ stream (a device cache of 4 pairs) and each group is cut into maximal runs of ma
 on that range of the slot's raw frames: conditional blur and ICRF in one pass, bit for bit what ct_dark_field_blur followed
 by ct_linearize_std gives frame by frame -- and unmatched ones (ct_linearize_std).  An exception of the match (no dark std,
 no image uncertainties) is raised where the frame-by-frame route raises it: after the frames in front have been yielded.
-Everything else with a dark field, and ``fused_dark=False``, goes frame by frame as ever.
+What that decision declines goes to ``DarkField.fuses_with_linearize_ingest`` when ``fused_dark_ingest=True``: every list of
+route "ingest" without a StridedDownscale -- a black level, a target range, ``ClampAlongDims``, raw (H,W,3) BGR frames behind
+``CvToTorch`` -- on uint8 / uint16 / float32 frames (LINEAR / CATMULL) takes the same pipeline with the RAW frames in the slot
+(explicit uncertainty images planar): matched runs go to ct_linearize_dark_ingest -- chain, blur and ICRF in one pass, bit for
+bit what ct_ingest_transform, ct_dark_field_blur and ct_linearize_std give frame by frame; 18 B per uint16 sample (22 with
+explicit uncertainties) against 42 (46), from the shapes; measured in profiles/linearize_dark_ingest.md -- and unmatched ones
+to ct_linearize_ingest.  Everything else with a dark field (a data-dependent Normalize, a StridedDownscale, LOOKUP, torch
+lists), and ``fused_dark=False``, goes frame by frame as ever.
 
 ``output_layout="cv"`` (extension): every yielded pair is in the order the reference's ``save_image`` writes -- (H,W,C),
 a 3-channel frame reversed to BGR -- made by two ct_export_cv launches per group before the device-to-host copy, which
@@ -70,16 +77,34 @@ _SLOTS = 3                # ring slots = groups in flight (copy-in | compute | c
 # 1037 [715 .. 1041] frames/s fused against 456 [388 .. 461] frame by frame, 2.27x at the medians, the slowest fused run (89 ms)
 # ahead of the fastest frame-by-frame run (139 ms): True.
 FUSED_DARK_DEFAULT = True
+# linearize_dataset_generator(fused_dark_ingest=...).  The rule, set before measuring (profiles/linearize_dark_ingest.md): True
+# only if, end to end on 64 uint16 1080p frames from pinned memory, every fused run was faster than every frame-by-frame run in
+# BOTH comparisons -- raw (H,W,3) BGR frames behind [CvToTorch, CastTo, Normalize(65535, 0)] and a planar black-level list.
+# Measured: BGR 1042 [790 .. 1043] frames/s fused against 462 [246 .. 462] frame by frame, 2.26x at the medians, the slowest fused
+# run (81 ms) ahead of the fastest frame-by-frame run (139 ms); planar black level 1042 [1022 .. 1044] against 460 [313 .. 461],
+# 2.27x, 63 ms ahead of 139 ms: True.
+FUSED_DARK_INGEST_DEFAULT = True
 
 
 def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRFModelBase, flatfield_dataset=None,
                                 gpu_transforms=None, dark_field_dataset=None, output_layout: str = "planar",
-                                fused_dark: bool = FUSED_DARK_DEFAULT):
+                                fused_dark: bool = FUSED_DARK_DEFAULT, fused_dark_ingest: bool = FUSED_DARK_INGEST_DEFAULT):
     """``fused_dark`` (extension; only read with a ``dark_field_dataset``): True lets inputs that
     ``DarkField.fuses_with_linearize`` accepts take the streamed pipeline with ct_linearize_dark; False is the frame-by-frame
     route through ct_dark_field_blur and ct_linearize_std.  The yielded values are the same bit for bit.  The default and the
     measurement behind it: FUSED_DARK_DEFAULT above (True: 2.27x the frames/s of the frame-by-frame route on 64 uint16 1080p
-    frames, every fused run faster than every frame-by-frame run; profiles/linearize_dark.md)."""
+    frames, every fused run faster than every frame-by-frame run; profiles/linearize_dark.md).
+
+    ``fused_dark_ingest`` (extension; only read with a ``dark_field_dataset`` and ``fused_dark=True``): True lets inputs that
+    ``fuses_with_linearize`` declined and ``DarkField.fuses_with_linearize_ingest`` accepts -- every ``plan_staging`` route
+    "ingest" without a StridedDownscale: a black level, a target range, ``ClampAlongDims``, raw (H,W,3) BGR frames behind a
+    leading ``CvToTorch`` -- take the streamed pipeline with ct_linearize_dark_ingest on the slot's raw frames (chain, blur and
+    ICRF in one pass: 18 B per uint16 sample with derived uncertainties, 22 with explicit ones, where ct_ingest_transform,
+    ct_dark_field_blur and ct_linearize_std move 42 / 46; byte counts from the shapes); False is the frame-by-frame route
+    through those three.  The yielded values are the same bit for bit.  The default and the measurement behind it:
+    FUSED_DARK_INGEST_DEFAULT above (True: 2.26x the frames/s of the frame-by-frame route on 64 uint16 1080p raw BGR frames
+    and 2.27x on planar frames behind a black level, every fused run faster than every frame-by-frame run; the kernel alone
+    takes 0.55 to 0.63 of the time of the three launches; profiles/linearize_dark_ingest.md)."""
     if output_layout not in ("planar", "cv"):
         raise ValueError(f"unknown output_layout {output_layout!r} (planar, cv)")
     expect(dataloader, DataLoader, "dataloader")
@@ -112,6 +137,10 @@ def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRF
         # the dark field's own decision, on the first frame planned as _frame_by_frame plans it (dark images are planar)
         dark_plan = plan_staging(probe, transforms, planar=True)
         if dark.fuses_with_linearize(probe, dark_plan, interp):
+            yield from _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, dark_plan, output_layout == "cv", dark)
+            return
+        # ... and, for what that declined, the chain's: route "ingest" keeps the raw frames in the slot (ct_linearize_dark_ingest)
+        if fused_dark_ingest and dark.fuses_with_linearize_ingest(probe, dark_plan, interp):
             yield from _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, dark_plan, output_layout == "cv", dark)
             return
     if route != "pipelined":
@@ -292,7 +321,10 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
             break
         compute.wait_event(slot.copied_in)
         compute.wait_event(slot.copied_out)  # the slot's output buffers were last read by its previous copy-out
-        if fused:
+        if dark is not None:
+            lin, lin_std = _linearize_dark_runs(slot, k, pairs, with_std, lut, interp, std_mode, std_value, max_code,
+                                                (stages, layout) if fused else None)
+        elif fused:
             consts = None
             if data:  # two launches for the group's k sets of constants, into the slot's own buffers
                 consts = ops.ingest_extrema_frames(slot.frames[:k], plan.prefix, layout, plan.min_val, plan.max_val,
@@ -303,8 +335,6 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
                 lin, lin_std = ops.linearize_ingest_frames_strided(slot.frames[:k], step, stages, lut, interp, **args)
             else:
                 lin, lin_std = ops.linearize_ingest_frames(slot.frames[:k], stages, lut, interp, **args)
-        elif dark is not None:
-            lin, lin_std = _linearize_dark_runs(slot, k, pairs, with_std, lut, interp, std_mode, std_value, max_code)
         else:
             lin, lin_std = ops.linearize_frames(slot.frames[:k], lut, interp, std=slot.std[:k] if with_std else None,
                                                 std_mode=std_mode, std_value=std_value, max_code=max_code, want_std=True,
@@ -332,10 +362,12 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
         raise pending
 
 
-def _linearize_dark_runs(slot, k, pairs, with_std, lut, interp, std_mode, std_value, max_code):
-    """The first ``k`` planar frames of ``slot`` into its output buffers, cut into maximal runs of frames with a matched dark
+def _linearize_dark_runs(slot, k, pairs, with_std, lut, interp, std_mode, std_value, max_code, chain=None):
+    """The first ``k`` frames of ``slot`` into its output buffers, cut into maximal runs of frames with a matched dark
     field (``pairs[i]``: its device (dark, dark std); one ct_linearize_dark launch on that range of the raw frames) and
-    without one (None: MissingValMode.SKIP_BATCH leaves the frame uncorrected; one ct_linearize_std launch)."""
+    without one (None: MissingValMode.SKIP_BATCH leaves the frame uncorrected; one ct_linearize_std launch).  ``chain`` =
+    (stages, layout) of a route "ingest" plan: the slot holds the raw frames in that layout (explicit uncertainties planar),
+    matched runs go to ct_linearize_dark_ingest and unmatched ones to ct_linearize_ingest."""
     a = 0
     while a < k:
         b = a + 1
@@ -343,7 +375,14 @@ def _linearize_dark_runs(slot, k, pairs, with_std, lut, interp, std_mode, std_va
             b += 1
         args = dict(std=slot.std[a:b] if with_std else None, std_mode=std_mode, std_value=std_value, max_code=max_code,
                     out=(slot.lin_out[a:b], slot.std_out[a:b]))
-        if pairs[a] is None:
+        if chain is not None:
+            del args["max_code"]
+            if pairs[a] is None:
+                ops.linearize_ingest_frames(slot.frames[a:b], chain[0], lut, interp, want_std=True, layout=chain[1], **args)
+            else:
+                ops.linearize_dark_ingest_frames(slot.frames[a:b], chain[0], [p[0] for p in pairs[a:b]], [p[1] for p in pairs[a:b]],
+                                                 lut, interp, layout=chain[1], **args)
+        elif pairs[a] is None:
             ops.linearize_frames(slot.frames[a:b], lut, interp, want_std=True, **args)
         else:
             ops.linearize_dark_frames(slot.frames[a:b], [p[0] for p in pairs[a:b]], [p[1] for p in pairs[a:b]], lut, interp, **args)

@@ -1185,6 +1185,51 @@ def linearize_ingest_frames_strided(frames: torch.Tensor, step: int, stages, lut
     return _linearize_ingest(True, frames, step, stages, lut, interp, std, std_mode, std_value, want_std, tile, layout, out, consts)
 
 
+# ---- such a chain, the dark-field blur and the linearization in one pass ------------------------------------------------------
+def linearize_dark_ingest_frames(frames: torch.Tensor, stages, darks, dark_stds, lut: Optional[torch.Tensor],
+                                 interp: Optional[str] = "linear", *, std: Optional[torch.Tensor] = None, std_mode: str = "none",
+                                 std_value: float = 0.0, layout: str = "nchw", out=None, threshold: float = 0.05,
+                                 alpha: float = 50.0):
+    """ct_linearize_dark_ingest on raw frames -> (lin, std) float32, planar (F,C,H,W): for every frame k, bit for bit
+    ``x = ingest_transform(frames[k:k+1], stages, layout)``, ``xb, sig = dark_field_blur(x, darks[k], dark_stds[k], ...)`` and
+    ``linearize_frames(xb, lut, interp, std=sig)``, in one launch per MAX_LINEARIZE_DARK_FRAMES frames and without the three
+    float32 stacks in between.
+
+    ``frames``, ``stages``, ``layout``: as ``linearize_ingest_frames`` takes them (a contiguous uint8 / uint16 / float32 device
+    stack, (F,C,H,W) for "nchw" or (F,H,W,3) for "nhwc" / "nhwc_bgr"; constant stages only).  ``darks`` / ``dark_stds``: as
+    ``linearize_dark_frames`` takes them, planar (C,H,W) in the order of the result's planes.  ``std`` / ``std_mode`` /
+    ``std_value``: the uncertainty of the image BEHIND the chain as ``dark_field_blur`` takes it on ``x``; ``std`` is float32
+    and PLANAR (F,C,H,W) whatever the layout of the frames.  ``out`` = (lin, std): contiguous float32 (F,C,H,W) device
+    buffers to write into.  LOOKUP has no gradient path to the image (RuntimeError, as ``linearize_frames`` with
+    uncertainties)."""
+    _check_ingest_stack(frames, layout)
+    shape = ingest_shape(tuple(frames.shape), layout)
+    f, c, h, w = shape
+    dev = frames.device
+    if f < 1:
+        raise ValueError("no frames")
+    arr, n_stages = _ingest_stages(stages, c)
+    if std is not None:
+        std_mode, std = "explicit", _planar_std(std, shape, dev, "outputs")
+    if std_mode not in _STD:
+        raise ValueError(f"unknown std_mode {std_mode}")
+    # the dark fields are checked against the planar shape (of the stack only shape and device are read: a view without memory)
+    planar = frames if layout == "nchw" else frames.new_empty((1, 1, 1, 1)).expand(shape)
+    dark_list, dark_std_list = _dark_per_frame(planar, darks, dark_stds)
+    icrf, lut_keep = _icrf_struct(lut, interp, c)
+    geom = _ingest_geometry(shape, None, layout)
+    lin, std_out = _lin_std_out(out, shape, dev, True, lin_required=True)
+    dark_arr = (ctypes.c_void_p * f)(*[t.data_ptr() for t in dark_list])
+    dark_std_arr = (ctypes.c_void_p * f)(*[t.data_ptr() for t in dark_std_list])
+    with torch.cuda.device(dev):
+        rc = nv.load().ct_linearize_dark_ingest(_ptr(frames), _DTYPE[frames.dtype], f, ctypes.byref(geom), arr, n_stages, _ptr(std),
+                                                _STD[std_mode], float(std_value), dark_arr, dark_std_arr, float(threshold),
+                                                float(alpha), ctypes.byref(icrf), _ptr(lin), _ptr(std_out), _stream(dev))
+    nv.check(rc, "ct_linearize_dark_ingest")
+    del lut_keep, dark_list, dark_std_list
+    return lin, std_out
+
+
 # ---- such a chain and one batch of the HDR merge in one pass ---------------------------------------------------------------
 def hdr_merge_ingest_batch(frames: torch.Tensor, stages, exposures: torch.Tensor, *, lut: Optional[torch.Tensor] = None,
                            interp: Optional[str] = "linear", gaussian_weight: bool = True, std: Optional[torch.Tensor] = None,

@@ -583,6 +583,39 @@ int ct_linearize_ingest_strided(const void *frames_dev, int32_t dtype, int64_t n
                                 const float *consts_dev /* may be NULL */, void *stream);
 
 /*
+ * ct_linearize_dark_ingest -- ct_linearize_dark on RAW frames behind a recognised gpu_transforms chain (the stage list of
+ * ct_ingest_transform, declared above): for every frame lin_out and std_out are bit for bit those of
+ * ct_ingest_transform on it into a planar float32 image x, ct_dark_field_blur on x (batch = 1, dark_batch = 1) into xb and
+ * sigma_eff, and ct_linearize_std on (xb, CT_DTYPE_F32, std = sigma_eff, CT_STD_EXPLICIT) -- in one pass and without the three
+ * float32 stacks: sizeof(element) + 8 bytes read per sample (+ 4 with explicit image uncertainties) and 8 written, 18 (22) for
+ * uint16 where the three launches move 42 (46).
+ *   frames_dev   CT_DTYPE_U8 / U16 / F32; geom->layout CT_LAYOUT_NCHW (any C) or, with C == 3, CT_LAYOUT_NHWC / NHWC_BGR: raw
+ *                (F, H, W, 3) frames as ct_linearize_ingest reads them (BGR: memory channel cm feeds plane 2 - cm);
+ *                geom->image_stride elements between frames; the whole image (no row band)
+ *   stages       0 to CT_INGEST_MAX_STAGES of CT_INGEST_AFFINE / CT_INGEST_CLAMP; a CT_INGEST_AFFINE_DATA stage is
+ *                CT_ERR_INVALID_ARGUMENT.  Every tap of the 3 x 3 window goes through the chain with its PLANE channel
+ *   std_dev / std_mode / std_value   sigma of the image BEHIND the chain, as ct_dark_field_blur takes it on x (EXPLICIT: planar
+ *                (F, C, H, W) float32, dense, like the outputs whatever the layout of the frames; CT_STD_MULTIPLIER multiplies
+ *                x, not xb)
+ *   dark_devs, dark_std_devs   HOST arrays of n_frames device pointers as ct_linearize_dark takes them: planar (C, H, W)
+ *                float32 in plane (RGB) order
+ *   lin_out_dev, std_out_dev   planar (F, C, H, W) float32, dense; both required
+ * Status, in this order: what ct_linearize_dark refuses first (a missing pointer, n_frames <= 0, a NULL entry of either
+ * array); the dark geometry (width < 2 or h_global < 2, a bad std mode: CT_ERR_INVALID_ARGUMENT; a row band:
+ * CT_ERR_UNSUPPORTED; a short image_stride); the stack and the stage list as ct_linearize_ingest (an unknown dtype, layout or
+ * kind, more than CT_INGEST_MAX_STAGES: CT_ERR_INVALID_ARGUMENT; an interleaved layout with C != 3, per-channel clamp pairs
+ * with C > CT_INGEST_MAX_CHANNELS: CT_ERR_UNSUPPORTED); the model, CT_ERR_NO_GRADIENT_PATH for LOOKUP, CT_ERR_TOO_LARGE for a
+ * LUT beyond 160 KiB of LDS or 2^31 elements per frame; last, CT_ERR_INVALID_ARGUMENT for a pointer not aligned to its
+ * element.  Every argument is validated before anything touches the device.  Allocates nothing, synchronises nothing, reads
+ * nothing back, never writes the frames, the dark fields or the uncertainties.
+ */
+int ct_linearize_dark_ingest(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
+                             const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,
+                             float std_value, const float *const *dark_devs, const float *const *dark_std_devs,
+                             float threshold, float alpha, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev,
+                             void *stream);
+
+/*
  * ct_hdr_merge_ingest_batch -- such a chain and one batch of compute_hdr_image's loop body in ONE pass over B raw frames:
  * state and outputs are bit for bit those of ct_ingest_transform (with consts_dev: ct_ingest_transform_data) into a dense
  * planar float32 (B, C, H_tile, W) stack followed by ct_hdr_merge_batch on that stack with CT_DTYPE_F32, the same geometry
