@@ -34,7 +34,7 @@ EXPORTS = ("ct_abi_version", "ct_error_string", "ct_hdr_merge_batch", "ct_hdr_me
            "ct_hdr_merge_ingest_batches", "ct_ingest_extrema_frames_workspace", "ct_ingest_extrema_frames",
            "ct_linearize_ingest_data", "ct_pair_residual_ingest_fwd", "ct_pair_residual_ingest_bwd", "ct_linearize_ingest_strided",
            "ct_video_stats_batches", "ct_video_stats_ingest_batches", "ct_hdr_merge_dark_batch", "ct_linearize_dark",
-           "ct_hdr_merge_dark_batches", "ct_linearize_dark_ingest")
+           "ct_hdr_merge_dark_batches", "ct_linearize_dark_ingest", "ct_hdr_merge_dark_ingest_batches")
 
 
 class Geometry(ctypes.Structure):
@@ -124,6 +124,9 @@ def load():
     lib.ct_hdr_merge_dark_batches.restype = i32
     lib.ct_hdr_merge_dark_batches.argtypes = [vp, vp, i32, i32, f32, gp, vp, vp, i32, f32, vp, vp, vp, f32, f32, vp, ip, i32, vp, vp, vp,
                                               vp, vp, u32, vp]
+    lib.ct_hdr_merge_dark_ingest_batches.restype = i32
+    lib.ct_hdr_merge_dark_ingest_batches.argtypes = [vp, vp, i32, i32, gp, ctypes.POINTER(IngestStage), i32, vp, vp, vp, i32, f32, vp, vp, vp,
+                                                     f32, f32, vp, ip, i32, vp, vp, vp, vp, vp, u32, vp]
     lib.ct_linearize_dark.restype = i32
     lib.ct_linearize_dark.argtypes = [vp, i32, f32, i64, gp, vp, i32, f32, vp, vp, f32, f32, ip, vp, vp, vp]
     lib.ct_linearize_dark_ingest.restype = i32

@@ -298,4 +298,93 @@ static inline dim3 md_grid(const MergeDarkArgs &a)
     return dim3((uint32_t)((slots + kBlock - 1) / kBlock), (uint32_t)a.channels);
 }
 
+// ---- host: the checks and the argument block the dark-field merge entry points share -------------------------------------
+// What ct_hdr_merge_dark_batch and ct_hdr_merge_dark_batches have in common besides the frames and dark fields of a batch: one
+// dtype, one geometry, one set of modes, the state and the outputs.
+struct MergeDarkCall {
+    int32_t dtype;
+    float max_code;
+    const ct_geometry *geom;
+    int32_t std_mode;
+    float std_value, threshold, alpha;
+    const ct_icrf *icrf;
+    int32_t weight_mode;
+    double *mean_state;
+    float *sumw_state, *var_state;
+    void *mean_out;
+    float *std_out;
+    uint32_t flags;
+};
+
+// One batch as ct_hdr_merge_dark_batch judges it, every check in its order; nothing is read.  FIRST_BATCH / FINALIZE in
+// c.flags are those of the whole call.  norm: the constants of the dtype.
+static inline int md_validate(const MergeDarkCall &c, const void *stack_dev, int32_t batch, const void *halo_dev, const float *std_dev,
+                       const float *dark_dev, const float *dark_std_dev, int32_t dark_batch, const double *exposure_dev, NormConst &norm)
+{
+    const ct_geometry *geom = c.geom;
+    const ct_icrf *icrf = c.icrf;
+    const int32_t std_mode = c.std_mode, weight_mode = c.weight_mode;
+    const uint32_t flags = c.flags;
+    // ---- what ct_dark_field_blur refuses, in its order (ct_darkfield.hip); a dark std is always propagated here ----
+    if (!stack_dev || !geom || !dark_dev || batch <= 0) return CT_ERR_INVALID_ARGUMENT;
+    if (int rc = check_dark_frames(geom, batch, dark_batch, dark_std_dev != nullptr, std_mode, std_dev)) return rc;
+    if (int rc = check_dark_band(geom, halo_dev)) return rc;
+    if (norm_for_dtype(c.dtype, c.max_code, &norm) != CT_OK) return CT_ERR_UNSUPPORTED;
+    // ---- what ct_hdr_merge_batch refuses for (xb, sigma_eff): float32 pixels, explicit uncertainties with a dark std and
+    //      none without, in the order of validate_merge (ct_merge.hip) ----
+    const bool has_std = dark_std_dev != nullptr;
+    if (!icrf || !exposure_dev) return CT_ERR_INVALID_ARGUMENT;
+    if (!icrf_ok(icrf)) return CT_ERR_INVALID_ARGUMENT;
+    if (weight_mode != CT_WEIGHT_NONE && weight_mode != CT_WEIGHT_GAUSS) return CT_ERR_INVALID_ARGUMENT;
+    const int interp = icrf->interp;
+    // hdr_merge.py:107-113: autograd.grad raises when nothing connects the mean to the image
+    if (has_std && interp == CT_INTERP_LOOKUP && weight_mode == CT_WEIGHT_NONE) return CT_ERR_NO_GRADIENT_PATH;
+    const bool has_state = c.mean_state && c.sumw_state && (!has_std || c.var_state);
+    if (!has_state && !((flags & CT_MERGE_FIRST_BATCH) && (flags & CT_MERGE_FINALIZE))) return CT_ERR_INVALID_ARGUMENT;
+    if ((flags & CT_MERGE_FINALIZE) && (!c.mean_out || (has_std && !c.std_out))) return CT_ERR_INVALID_ARGUMENT;
+    if (!global_below_2_31(geom)) return CT_ERR_TOO_LARGE;
+    // ---- what this entry point does not have: the routes of ct_hdr_merge_batch besides the closed-form float32 kernel ----
+    if (flags & (CT_MERGE_F64_MOMENTS | CT_MERGE_REFERENCE_ORDER | CT_MERGE_OUT_AS_INPUT)) return CT_ERR_UNSUPPORTED;
+    if ((interp == CT_INTERP_CATMULL || interp == CT_INTERP_LOOKUP) && has_std && !(flags & CT_MERGE_CLOSED_FORM)) return CT_ERR_UNSUPPORTED;
+    if (mi_lds_bytes(interp, geom->channels, icrf_points(icrf), batch) > kLdsBudget) return CT_ERR_TOO_LARGE;
+    const size_t elem = dtype_bytes(c.dtype);
+    if (!aligned(stack_dev, elem) || !aligned(halo_dev, elem) || !aligned(std_dev, sizeof(float)) || !aligned(dark_dev, sizeof(float)) ||
+        !aligned(dark_std_dev, sizeof(float)) || !aligned(exposure_dev, sizeof(double)) || !aligned(c.mean_state, sizeof(double)) ||
+        !aligned(c.sumw_state, sizeof(float)) || !aligned(c.var_state, sizeof(float)) ||
+        !aligned(c.mean_out, (flags & CT_MERGE_MEAN_OUT_F32) ? sizeof(float) : sizeof(double)) || !aligned(c.std_out, sizeof(float)))
+        return CT_ERR_INVALID_ARGUMENT;
+    return CT_OK;
+}
+
+// the kernels' argument block of a validated call without what belongs to a batch (MULTI: `batch` exposures in all batches)
+static inline MergeDarkArgs md_fill_args(const MergeDarkCall &c, bool has_std, NormConst norm, const double *exposure_dev, int32_t batch)
+{
+    const ct_geometry *geom = c.geom;
+    const bool has_state = c.mean_state && c.sumw_state && (!has_std || c.var_state);
+    const int64_t plane = geom->h_tile * geom->width;
+    MergeDarkArgs a{};
+    a.exposure = exposure_dev;
+    a.lut = c.icrf->lut_dev;
+    a.mean_state = has_state ? c.mean_state : nullptr;
+    a.sumw_state = has_state ? c.sumw_state : nullptr;
+    a.var_state = has_state ? c.var_state : nullptr;
+    a.mean_out = c.mean_out;
+    a.std_out = c.std_out;
+    a.image_stride = geom->image_stride;
+    a.plane = (uint32_t)plane;
+    a.plane_global = (uint32_t)(geom->h_global * geom->width);
+    a.base = (uint32_t)(geom->row_offset * geom->width);
+    a.width = (int32_t)geom->width;
+    a.h_tile = (int32_t)geom->h_tile;
+    a.at_top = geom->row_offset == 0 ? 1u : 0u;
+    a.at_bottom = geom->row_offset + geom->h_tile == geom->h_global ? 1u : 0u;
+    a.batch = batch;
+    a.channels = geom->channels;
+    a.n_points = icrf_points(c.icrf);
+    fill_blur_args(a, norm, c.std_mode, c.std_value, c.threshold, c.alpha);
+    a.weight_scale = 30.0f;  // gaussian_value_weights default scale, hdr_merge.py:95
+    a.flags = c.flags;
+    return a;
+}
+
 }  // namespace ct

@@ -102,6 +102,26 @@ class DarkField:
         return not (reference_order is True or (interp in ("lookup", "catmull") and reference_order is None))
 
     @staticmethod
+    def fuses_with_merge_ingest(deferred, interp, reference_order, tile=None) -> bool:
+        """The route decision of a matched batch whose chain has not been executed (a ``DeferredIngest`` of routes "ingest" /
+        "ingest_data", ``compute_hdr_image(fused_dark_ingest=True)``): True = ct_hdr_merge_dark_ingest_batches (chain, blur and
+        merge in one pass over the raw frames), False = ``ops.ingest_transform`` into the float32 stack, then what
+        ``fuses_with_merge`` decides for that.  Fused are 4-D uint8 / uint16 / float32 frames, planar or -- without a row band
+        (``tile`` None or the whole image) -- interleaved (H,W,3), in a closed-form mode (``fuses_with_merge``'s rule: not
+        ``reference_order=True``, and LOOKUP / CATMULL only with ``reference_order=False``)."""
+        frames = getattr(deferred, "frames", None)
+        if not isinstance(frames, torch.Tensor) or frames.ndim != 4 or deferred.layout not in ("nchw", "nhwc", "nhwc_bgr"):
+            return False
+        if frames.dtype not in (torch.uint8, torch.uint16, torch.float32):
+            return False
+        if deferred.layout != "nchw":
+            if frames.shape[3] != 3:
+                return False
+            if tile is not None and (tile.row_offset != 0 or tile.h_global != frames.shape[1]):
+                return False
+        return not (reference_order is True or (interp in ("lookup", "catmull") and reference_order is None))
+
+    @staticmethod
     def fuses_with_linearize(images_or_probe, plan, interp) -> bool:
         """The route decision of linearize_dataset_generator with a dark-field dataset: True = the streamed pipeline with
         ct_linearize_dark on the matched frames (blur and ICRF in one pass over the slot's raw frames), False = frame by
@@ -188,6 +208,19 @@ class DarkField:
         return ops.hdr_merge_dark_batches(images, exposures, [m[0] for m in matched], [m[1] for m in matched], stds=stds,
                                           std_mode=std_mode, std_value=std_value, max_code=max_code, tile=tile, halos=halos,
                                           **merge_args)
+
+    @staticmethod
+    def merge_ingest_batches(matched, deferred, exposures, stds, std_mode, std_value, tile=None, halos=None, **merge_args):
+        """Several consecutive matched batches whose chain has not been executed through ct_hdr_merge_dark_ingest_batches: what
+        ``ops.ingest_transform`` and ``merge`` on each of them in turn give, bit for bit, in one launch over the raw frames.
+        Lists, one entry per batch: ``matched``, ``deferred`` (``DeferredIngest`` of one chain and layout), ``exposures``,
+        ``stds`` (or None) and ``halos`` -- the RAW rows ``exchange_halo`` got for each batch's frames when it was queued (None
+        for an untiled image).  ``merge_args``: lut, interp, gaussian_weight, state, finalize, reference_order."""
+        d0 = deferred[0]
+        consts = None if d0.consts is None else [d.consts for d in deferred]
+        return ops.hdr_merge_dark_ingest_batches([d.frames for d in deferred], d0.stages, exposures, [m[0] for m in matched],
+                                                 [m[1] for m in matched], consts=consts, stds=stds, std_mode=std_mode,
+                                                 std_value=std_value, tile=tile, halos=halos, layout=d0.layout, **merge_args)
 
     def linearize(self, index_batch, images, max_code, std, std_mode, std_value, lut, interp):
         xb, sig = self.apply(index_batch, images, max_code, std, std_mode, std_value)

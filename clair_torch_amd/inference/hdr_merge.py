@@ -20,6 +20,11 @@ from ._staging import DeferredIngest, normalise_transform_list, refuse_tile_with
 # a dark std per frame (2 GB each: the dark fields are 8 B per element and frame).
 DARK_QUEUE_BYTES = 8 << 30
 
+# compute_hdr_image(fused_dark_ingest=...).  The rule, set before measuring (profiles/merge_dark_ingest.md): True only if every
+# timed run of the fused launch is faster than every timed run of ops.ingest_transform + ops.hdr_merge_dark_batch(es) at every
+# measured shape -- the rule ``fused_dark`` was decided by.
+FUSED_DARK_INGEST_DEFAULT = False
+
 
 def _dark_batch_bytes(images, std, matched, halo):
     """What a queued dark-field batch holds on the device (dark field and dark std as the float32 the kernel reads)."""
@@ -31,7 +36,8 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
                       weight_fn: Optional[Callable] = None, flat_field_dataset=None, gpu_transforms=None,
                       dark_field_dataset=None, tile: Optional[ops.TileGeometry] = None, group=None,
                       output_layout: str = "planar", reference_order: Optional[bool] = None, fused_ingest: bool = True,
-                      fused_dark: bool = True, dark_batches_per_launch: int = 1):
+                      fused_dark: bool = True, dark_batches_per_launch: int = 1,
+                      fused_dark_ingest: bool = FUSED_DARK_INGEST_DEFAULT):
     """Merge the exposure stack served by ``dataloader`` into an HDR image and its standard uncertainty.
 
     Returns ``(mean float64 (C,H,W), std float32 (C,H,W) | None)`` on ``device`` (squeezed like the reference).
@@ -74,6 +80,20 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
     0.67-0.74 of the time of one launch per batch for batches of 4 and 0.82-0.92 for batches of 8, every run faster than every
     per-batch run (profiles/merge_dark_batches.md).  The default stays 1, one launch per matched batch as before this keyword
     existed; pass 16 to queue.
+    ``fused_dark_ingest`` (extension; only read with a ``dark_field_dataset`` and ``fused_dark=True``): a ``gpu_transforms`` list
+    on route "ingest" / "ingest_data" (a black level, a target range, ``ClampAlongDims``, raw (H,W,3) BGR frames behind
+    ``CvToTorch``, a data-dependent ``Normalize()``) in front of a dark-field dataset.  True = the chain is not executed when
+    the batch is staged; a batch that a dark field matched goes through ct_hdr_merge_dark_ingest_batches -- chain, blur and merge
+    in one pass over the RAW frames, no float32 copy of the batch; 10 B per uint16 sample with derived uncertainties against 18,
+    from the shapes -- when ``DarkField.fuses_with_merge_ingest`` accepts it (uint8 / uint16 / float32 frames, a closed-form
+    mode, interleaved frames only without a row band).  Such batches are queued under a key of their own (dtype, shape, layout,
+    chain, uncertainty mode, with or without constants) and flushed like the queue above: on a change of kind, at
+    ``dark_batches_per_launch`` batches (1: one batch per launch), at DARK_QUEUE_BYTES and at the end; for a row band the halo
+    rows are exchanged on the RAW frames when the batch is queued.  Unmatched batches take the ``fused_ingest`` queue
+    (ct_hdr_merge_ingest_batches; float32 frames and the reference-order modes get the float32 stack, as there), declined ones
+    are materialised with ct_ingest_transform and go on as without this keyword.  The results are the same bit for bit.
+    False = ct_ingest_transform when the batch is staged, as before this keyword existed.  Measured: see
+    profiles/merge_dark_ingest.md for the numbers and for the default, which follows the rule stated there.
     """
     if type(dark_batches_per_launch) is not int or not 1 <= dark_batches_per_launch <= ops.MAX_MERGE_BATCHES:
         raise ValueError(f"dark_batches_per_launch must be an int in 1 .. {ops.MAX_MERGE_BATCHES}, got {dark_batches_per_launch!r}")
@@ -113,6 +133,20 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
         if not queue:
             return
         k0 = queue[0]
+        if "matched" in k0 and isinstance(k0["images"], DeferredIngest):
+            # chain, blur and merge of every queued dark-field batch in one launch over the raw frames
+            # (ct_hdr_merge_dark_ingest_batches)
+            d = k0["images"]
+            if state is None and (not final or flat_field_dataset is not None):
+                state = ops.MergeState(ops.ingest_shape(tuple(d.frames.shape), d.layout)[1:], dev, with_variance=True)
+            result = dark.merge_ingest_batches([q["matched"] for q in queue], [q["images"] for q in queue],
+                                               [q["exposure"] for q in queue], None if k0["std"] is None else [q["std"] for q in queue],
+                                               k0["std_mode"], k0["std_value"], tile,
+                                               None if k0["halo"] is None else [q["halo"] for q in queue], lut=lut, interp=interp,
+                                               gaussian_weight=weight_fn is not None, state=state,
+                                               finalize=final and flat_field_dataset is None, reference_order=reference_order)
+            queue, queue_bytes = [], 0
+            return
         if "matched" in k0:
             # blur and merge of every queued dark-field batch in one launch (ct_hdr_merge_dark_batches)
             if state is None and (not final or flat_field_dataset is not None):
@@ -157,16 +191,39 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
         pending = next(batches, None)
         last = pending is None
         planar = std_batch is not None or dark is not None  # explicit std / dark images are planar
-        images, max_code, layout = stage_images(val_batch, dev, transforms, planar, defer_ingest=fused_ingest and dark is None)
+        defer = fused_ingest if dark is None else (fused_dark and fused_dark_ingest)
+        images, max_code, layout = stage_images(val_batch, dev, transforms, planar, defer_ingest=defer)
         std, std_mode, std_value = std_arguments(std_batch, dataloader.dataset, dev)
         fused = isinstance(images, DeferredIngest)
+        matched, asked = None, False
+        if fused and dark is not None:
+            matched, asked = dark.match(index_batch, std, std_mode), True
+            if matched is not None and dark.fuses_with_merge_ingest(images, interp, reference_order, tile):
+                # queued under a key of its own; the halo rows are exchanged now, on the RAW frames, in loader order on every rank
+                halo = exchange_halo(images.frames, tile, group) if images.layout == "nchw" else None
+                key = ("dark_ingest", images.frames.dtype, tuple(images.frames.shape[1:]), images.layout, images.stages, std_mode,
+                       std_value, std is None, images.consts is None)
+                held = _dark_batch_bytes(images.frames, std, matched, halo)
+                if queue and (key != queue_key or len(queue) == dark_batches_per_launch or queue_bytes + held > DARK_QUEUE_BYTES):
+                    flush(False)
+                queue_key = key
+                queue_bytes += held
+                queue.append(dict(images=images, exposure=meta_batch["exposure_time"], std=std, std_mode=std_mode, std_value=std_value,
+                                  max_code=None, matched=matched, halo=halo))
+                if last:
+                    flush(last)
+                continue
+            if matched is not None:  # declined: the float32 stack, then as without the keyword
+                images = ops.ingest_transform(images.frames, images.stages, layout=images.layout, consts=images.consts)
+                fused = False
         if fused and (images.frames.dtype == torch.float32 or reference_order is True or
                       (interp in ("lookup", "catmull") and std_mode != "none" and reference_order is None)):
             # float32 frames have no copy to save, and the reference-order kernel is not fused: they get the float32 stack
             images = ops.ingest_transform(images.frames, images.stages, layout=images.layout, consts=images.consts)
             fused = False
         if dark is not None:
-            matched = dark.match(index_batch, std, std_mode)
+            if not asked:
+                matched = dark.match(index_batch, std, std_mode)
             fuses = matched is not None and fused_dark and dark.fuses_with_merge(images, layout, interp, reference_order)
             if fuses and dark_batches_per_launch > 1:
                 # queued under a key of its own; the halo rows are exchanged now, in loader order on every rank

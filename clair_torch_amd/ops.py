@@ -1360,6 +1360,115 @@ def hdr_merge_ingest_batches(frames_list, stages, exposures_list, *, lut: Option
     return (mean_out, std_out) if finalize else None
 
 
+# ---- such a chain, the dark-field blur and several batches of the HDR merge in one pass ---------------------------------------
+def hdr_merge_dark_ingest_batches(frames_list, stages, exposures_list, darks, dark_stds, *, consts=None, stds=None,
+                                  std_mode: str = "none", std_value: float = 0.0, lut: Optional[torch.Tensor] = None,
+                                  interp: Optional[str] = "linear", gaussian_weight: bool = True,
+                                  state: Optional[MergeState] = None, finalize: bool = True, first: Optional[bool] = None,
+                                  tile: Optional[TileGeometry] = None, halos=None, layout: str = "nchw",
+                                  mean_dtype: torch.dtype = torch.float64, reference_order: Optional[bool] = None,
+                                  require_one_launch: bool = False, threshold: float = 0.05, alpha: float = 50.0):
+    """1 to MAX_MERGE_BATCHES CONSECUTIVE dark-field batches of one merge behind one chain in one call, on the RAW frames
+    (ct_hdr_merge_dark_ingest_batches): for every batch k, bit for bit, ``x = ingest_transform(frames_list[k], stages, layout,
+    consts=consts[k])`` followed by ``hdr_merge_dark_batch(x, exposures_list[k], darks[k], dark_stds[k], ...)`` on the same
+    ``state`` -- but one launch walks all batches with the streaming state in registers in between, and the float32 stack of
+    a batch never exists.  One batch is a list of one (the same kernel).
+
+    ``frames_list``: list of contiguous uint8 / uint16 / float32 device stacks of one dtype, image shape and device,
+    (B_k,C,H,W) for "nchw" or (B_k,H,W,3) for "nhwc" / "nhwc_bgr" (the order of the source: a folded CvToTorch).  ``stages``:
+    as ``ingest_transform`` takes them; with ``consts`` (list of the tensors ``ingest_extrema`` returned, one per batch) one
+    of them may be ("affine_data", mul, add).  ``darks`` / ``dark_stds``: lists of (1|B_k,C,H,W) dark fields and their stds
+    (``dark_stds`` None: no uncertainty is propagated), planar in the order of the result's planes.  ``stds`` / ``std_mode`` /
+    ``std_value``: the uncertainty of the image BEHIND the chain as ``dark_field_blur`` takes it on ``x``; explicit ones are
+    float32 and PLANAR (B_k,C,H,W) whatever the layout of the frames.  ``halos``: for a row band (``tile``; planar frames only)
+    the list of (B_k,C,2,W) RAW rows of the frames' dtype above / below the band.  ``first``: None = the state decides; True /
+    False says so for a state filled elsewhere.  ``require_one_launch`` (tests): raise (ValueError) instead of falling back to
+    one launch per batch (more exposure times than the LDS holds beside the LUT).  ``reference_order``, ``exposures_list``,
+    ``lut``, ``interp``, ``gaussian_weight``, ``state``, ``finalize``, ``mean_dtype``, ``threshold``, ``alpha``: as in
+    ``hdr_merge_dark_batches``.  Returns (mean, std|None), planar (C,H,W), when ``finalize`` else None."""
+    k = len(frames_list)
+    lists = (exposures_list, darks) + tuple(v for v in (dark_stds, stds, halos, consts) if v is not None)
+    if k == 0 or any(len(v) != k for v in lists):
+        raise ValueError("frames / exposures / darks / dark_stds / stds / halos / consts must be non-empty lists of equal length")
+    if k > MAX_MERGE_BATCHES:
+        raise ValueError(f"at most {MAX_MERGE_BATCHES} batches per call")
+    if dark_stds is not None and any(t is None for t in dark_stds):
+        if any(t is not None for t in dark_stds):
+            raise ValueError("a dark std for every batch of one call, or for none")
+        dark_stds = None
+    if consts is not None and any(t is None for t in consts):
+        if any(t is not None for t in consts):
+            raise ValueError("constants for every batch of one call, or for none")
+        consts = None
+    f0 = frames_list[0]
+    for t in frames_list:
+        _check_ingest_stack(t, layout)
+        if t.dtype != f0.dtype or t.shape[1:] != f0.shape[1:] or t.device != f0.device:
+            raise ValueError("all batches of one call must share dtype, image shape and device")
+        if t.shape[0] < 1:
+            raise ValueError("empty batch")
+    dev = f0.device
+    shapes = [ingest_shape(tuple(t.shape), layout) for t in frames_list]
+    _, c, h, w = shapes[0]
+    if layout != "nchw" and tile is not None and (tile.row_offset != 0 or tile.h_global != h):
+        raise ValueError("a row band (tile=) needs planar frames: no halo is built for interleaved ones")
+    arr, n_stages = _ingest_stages(stages, c, data=consts is not None)
+    if consts is not None:
+        for t in consts:
+            _check_consts(t, dev)
+    if stds is not None:
+        std_mode = "explicit"
+        stds = [_planar_std(sd, shape, dev, "state") for sd, shape in zip(stds, shapes)]
+    if std_mode not in _STD:
+        raise ValueError(f"unknown std_mode {std_mode}")
+    # the refusals the dark ops share, against the planar shape (of the stack only shape, dtype and device are read: a view
+    # without memory stands for interleaved frames)
+    planar = [t if layout == "nchw" else t.new_empty((1, 1, 1, 1)).expand(shape) for t, shape in zip(frames_list, shapes)]
+    checked = [_dark_arguments(t, darks[i], None if dark_stds is None else dark_stds[i], None if halos is None else halos[i])
+               for i, t in enumerate(planar)]
+    darks, dark_stds, halos = ([v[j] for v in checked] for j in range(3))
+    if any(t is None for t in halos) and any(t is not None for t in halos):
+        raise ValueError("halo rows for every batch of one call, or for none")
+    has_std = dark_stds[0] is not None
+    sizes = [int(s[0]) for s in shapes]
+    exposure_dev = _exposure_list_on_device(exposures_list, sizes, dev)
+    icrf, lut_keep = _icrf_struct(lut, interp, c)
+    geom = _ingest_geometry(shapes[0], tile, layout)
+    flags, out_shape, mean_out, std_out = _merge_setup_for((c, h, w), dev, "planar", state, finalize, has_std, mean_dtype, reference_order,
+                                                           nv.MERGE_REQUIRE_ONE_LAUNCH if require_one_launch else 0, "call")
+    if first is not None:
+        flags = (flags | nv.MERGE_FIRST_BATCH) if first else (flags & ~nv.MERGE_FIRST_BATCH)
+
+    def pointers(tensors):
+        return (ctypes.c_void_p * k)(*[None if t is None else t.data_ptr() for t in tensors])
+
+    frames_arr, dark_arr, dark_std_arr, halo_arr = pointers(frames_list), pointers(darks), pointers(dark_stds), pointers(halos)
+    std_arr = pointers(stds) if stds is not None else None
+    consts_arr = pointers(consts) if consts is not None else None
+    size_arr = (ctypes.c_int32 * k)(*sizes)
+    dark_size_arr = (ctypes.c_int32 * k)(*[int(t.shape[0]) for t in darks])
+
+    def call(st, fl):
+        with torch.cuda.device(dev):
+            return nv.load().ct_hdr_merge_dark_ingest_batches(
+                frames_arr, size_arr, k, _DTYPE[f0.dtype], ctypes.byref(geom), arr, n_stages, consts_arr, halo_arr, std_arr,
+                _STD[std_mode], float(std_value), dark_arr, dark_std_arr, dark_size_arr, float(threshold), float(alpha),
+                _ptr(exposure_dev), ctypes.byref(icrf), nv.WEIGHT_GAUSS if gaussian_weight else nv.WEIGHT_NONE, *_state_ptrs(st),
+                _ptr(mean_out), _ptr(std_out), fl, _stream(dev))
+
+    # a whole merge in one launch needs no state arrays at all; only what cannot run as one launch walks the batches with
+    # the state in memory (nothing has been launched when the library says so)
+    rc = call(state, flags)
+    if rc == nv.ERR_UNSUPPORTED and state is None and not require_one_launch and k > 1:
+        state = MergeState(out_shape, dev, has_std)
+        rc = call(state, flags)
+    nv.check(rc, "ct_hdr_merge_dark_ingest_batches")
+    del lut_keep
+    if state is not None:
+        state.batches += k
+    return (mean_out, std_out) if finalize else None
+
+
 # ---- a data-dependent Normalize (max_val / min_val None) in such a chain ------------------------------------------------
 ZERO_RANGE = "Normalization range is zero (min == max); cannot normalize."  # general_functions.py:378
 

@@ -39,6 +39,11 @@ and pair lists are passed as their component tensors / scalars.
                                   layout, h_global, row_offset, closed_form, consts?) -> (mean float64, std float32)   (such
                                   a chain and hdr_merge in one pass over the raw frames; with ``consts`` a stage of kind 2 is
                                   the data-dependent Normalize: kind, 0, 0, mul, add)
+    torch.ops.clair_hip.hdr_merge_dark_ingest_batches(frames[], stages, exposures[], darks[], dark_stds[], consts[], stds[],
+                                  lut?, interp, gaussian, std_mode, std_value, layout, closed_form) -> (mean float64,
+                                  std float32)   (such a chain, the dark-field blur and 1 to 16 consecutive batches of one
+                                  whole merge in one pass over the raw frames; lists hold one tensor per batch, the last
+                                  three may be empty)
 
 CPU tensors are refused by the kernels' front-end exactly as through ``ops`` (there is no CPU path).
 """
@@ -375,3 +380,27 @@ def _(frames, stages, exposures, lut, interp, gaussian, std, std_mode, std_value
     chw = ops.ingest_shape(tuple(frames.shape), layout)[1:]
     has_std = std is not None or std_mode != "none"
     return frames.new_empty(chw, dtype=torch.float64), frames.new_empty(chw if has_std else (0,), dtype=torch.float32)
+
+
+@torch.library.custom_op(f"{_LIB}::hdr_merge_dark_ingest_batches", mutates_args=())
+def hdr_merge_dark_ingest_batches(frames: Sequence[torch.Tensor], stages: Sequence[float], exposures: Sequence[torch.Tensor],
+                                  darks: Sequence[torch.Tensor], dark_stds: Sequence[torch.Tensor], consts: Sequence[torch.Tensor],
+                                  stds: Sequence[torch.Tensor], lut: Optional[torch.Tensor], interp: str, gaussian: bool,
+                                  std_mode: str, std_value: float, layout: str = "nchw",
+                                  closed_form: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ct_hdr_merge_dark_ingest_batches: per batch ingest_transform followed by the fused dark-field blur + merge, bit for bit,
+    in one pass over the raw frames (a whole merge: first and final).  One tensor per batch in every list; ``dark_stds``,
+    ``consts`` and ``stds`` may be empty (none); explicit stds are planar (B_k,C,H,W)."""
+    mean, sd = ops.hdr_merge_dark_ingest_batches(list(frames), _listed_ingest_stages(frames[0], stages, layout), list(exposures),
+                                                 list(darks), list(dark_stds) or None, consts=list(consts) or None,
+                                                 stds=list(stds) or None, std_mode=std_mode, std_value=std_value, lut=lut,
+                                                 interp=interp if lut is not None else None, gaussian_weight=gaussian,
+                                                 layout=layout, reference_order=False if closed_form else None)
+    return mean, (sd if sd is not None else mean.new_zeros(0, dtype=torch.float32))
+
+
+@hdr_merge_dark_ingest_batches.register_fake
+def _(frames, stages, exposures, darks, dark_stds, consts, stds, lut, interp, gaussian, std_mode, std_value, layout="nchw",
+      closed_form=False):
+    chw = ops.ingest_shape(tuple(frames[0].shape), layout)[1:]
+    return frames[0].new_empty(chw, dtype=torch.float64), frames[0].new_empty(chw if len(dark_stds) else (0,), dtype=torch.float32)

@@ -68,7 +68,7 @@ extern "C" {
                                         float64 exp / divisions; ct_merge_exact.hip).  Default for LOOKUP and CATMULL with
                                         uncertainties, whose reference results are dominated by float32 cancellation */
 #define CT_MERGE_CLOSED_FORM 32u     /* keep the fast closed-form kernels for LOOKUP / CATMULL with uncertainties as well */
-#define CT_MERGE_REQUIRE_ONE_LAUNCH 128u /* ct_hdr_merge_batches, ct_hdr_merge_ingest_batches, ct_hdr_merge_dark_batches: CT_ERR_UNSUPPORTED instead of one launch per batch */
+#define CT_MERGE_REQUIRE_ONE_LAUNCH 128u /* ct_hdr_merge_batches, ct_hdr_merge_ingest_batches, ct_hdr_merge_dark_batches: CT_ERR_UNSUPPORTED instead of one launch per batch (ct_hdr_merge_dark_ingest_batches: CT_ERR_TOO_LARGE) */
 #define CT_MERGE_STD_HINT 64u        /* ct_hdr_merge_kernel_name only: uncertainties are propagated */
 #define CT_MERGE_OUT_AS_INPUT 256u   /* extension: state and outputs in the MEMORY ORDER OF THE INPUT stack instead of planar
                                         (C, H, W): an interleaved (H, W, C) RGB / BGR stack then gives (H, W, C) outputs in the
@@ -681,6 +681,62 @@ int ct_hdr_merge_ingest_batches(const void *const *frames_devs, const int32_t *b
                                 const double *exposure_dev, const ct_icrf *icrf, int32_t weight_mode, double *mean_state_dev,
                                 float *sumw_state_dev, float *var_state_dev, void *mean_out_dev, float *std_out_dev,
                                 uint32_t flags, void *stream);
+
+/*
+ * ct_hdr_merge_dark_ingest_batches -- n_batches consecutive dark-field batches of one merge behind one chain in one call, on
+ * the RAW frames: for every batch the state and the outputs are bit for bit those of ct_ingest_transform (with constants:
+ * ct_ingest_transform_data) into a dense planar float32 (B_b, C, H_tile, W) stack followed by ct_hdr_merge_dark_batch on that
+ * stack with CT_DTYPE_F32, the same dark fields, uncertainties, halo, geometry (layout CT_LAYOUT_NCHW) and flags, batch 0 ..
+ * n_batches - 1 in turn on the same state -- without the float32 stack: sizeof(element) + 8 bytes read per sample (+ 4 with
+ * explicit image uncertainties), 10 for uint16 where the two launches move 18; with one shared dark field per batch about 2
+ * against about 10.  Where it can, ONE launch walks all batches with (mean, sum of weights, variance) in registers in between:
+ * the state arrays are read at most once (not at all with CT_MERGE_FIRST_BATCH) and written at most once.  n_batches == 1 is
+ * the same kernel with a list of one.
+ *   frames_devs, batch_sizes   HOST arrays of n_batches (1 .. 16) entries: batch b is batch_sizes[b] >= 1 raw frames at
+ *                frames_devs[b], CT_DTYPE_U8 / U16 / F32, aligned to their element; geom->layout CT_LAYOUT_NCHW (any C) or,
+ *                with C == 3, CT_LAYOUT_NHWC / NHWC_BGR: raw (B, H, W, 3) frames (BGR: memory channel cm feeds plane 2 - cm);
+ *                geom->image_stride elements between frames; one dtype, geometry and stage list for all batches
+ *   geom         a row band (h_tile < h_global) with CT_LAYOUT_NCHW only; CT_ERR_UNSUPPORTED on interleaved frames
+ *   stages       0 to CT_INGEST_MAX_STAGES of CT_INGEST_AFFINE / CT_INGEST_CLAMP and, with consts_devs, at most one
+ *                CT_INGEST_AFFINE_DATA.  Every tap of the 3 x 3 window goes through the chain with its PLANE channel.  No
+ *                StridedDownscale: the caller compacts first
+ *   consts_devs  HOST array of n_batches device pointers, each the 4 floats ct_ingest_extrema left for that batch (sub and div
+ *                are read when the kernel runs), or NULL as a whole; its entries are all NULL or all non-NULL
+ *   halo_devs    HOST array of n_batches device pointers, each the (B_b, C, 2, W) RAW rows of the frames' dtype just above and
+ *                below the band (they go through the chain like any other tap), or NULL as a whole; all NULL or all non-NULL
+ *   std_devs / std_mode / std_value   sigma of the image BEHIND the chain, as ct_dark_field_blur takes it on the float32 stack
+ *                (EXPLICIT: HOST array of n_batches device pointers, each planar (B_b, C, H_tile, W) float32, dense, whatever
+ *                the layout of the frames; else NULL as a whole; CT_STD_MULTIPLIER multiplies x behind the chain, not xb)
+ *   dark_devs, dark_std_devs, dark_batches   as ct_hdr_merge_dark_batches takes them: planar (1 | B_b, C, H_tile, W) float32 in
+ *                plane (RGB) order; shared and per-frame dark fields may alternate between the batches of one call;
+ *                dark_std_devs NULL as a whole, or all entries NULL: no uncertainty is propagated
+ *   exposure_dev the exposure times of all batches, concatenated (sum of batch_sizes doubles)
+ *   icrf, weight_mode, state, outputs   as ct_hdr_merge_dark_batch; state and outputs are planar (C, H_tile, W)
+ *   flags        CT_MERGE_FIRST_BATCH (of batch 0), CT_MERGE_FINALIZE (of the last batch), CT_MERGE_MEAN_OUT_F32,
+ *                CT_MERGE_CLOSED_FORM; CT_MERGE_REQUIRE_ONE_LAUNCH: CT_ERR_TOO_LARGE instead of one launch per batch
+ * Status, in this order: n_batches outside 1 .. 16 or a missing array / geometry: CT_ERR_INVALID_ARGUMENT; a mixture of NULL
+ * and non-NULL entries in dark_std_devs, halo_devs or consts_devs: CT_ERR_INVALID_ARGUMENT; the stage list as
+ * ct_ingest_transform judges it (an unknown dtype, layout or kind, more than CT_INGEST_MAX_STAGES, a CT_INGEST_AFFINE_DATA
+ * stage without consts_devs, more than one of them: CT_ERR_INVALID_ARGUMENT; an interleaved layout with C != 3, per-channel
+ * clamp pairs with C > CT_INGEST_MAX_CHANNELS: CT_ERR_UNSUPPORTED); a row band on interleaved frames: CT_ERR_UNSUPPORTED; then
+ * every batch as ct_hdr_merge_dark_batch judges the float32 stack (its checks in its order, the same status codes, the first
+ * refusal wins -- width < 2, h_global < 2, a one-row band at the image's edge, a band without its halo, CT_MERGE_REFERENCE_ORDER,
+ * LOOKUP / CATMULL with a dark std and no CT_MERGE_CLOSED_FORM, ... -- the flags being those of the whole call, so a state is
+ * needed unless both FIRST_BATCH and FINALIZE are set) and its constants' alignment.  One launch needs the LUT with 8 B per
+ * exposure of ALL batches to fit 160 KiB of LDS; where only each batch alone fits, the batches are launched one by one on the
+ * state in memory, which then must be given (CT_ERR_UNSUPPORTED without; CT_ERR_TOO_LARGE with CT_MERGE_REQUIRE_ONE_LAUNCH).
+ * Every argument is validated before anything touches the device.  Allocates nothing, synchronises nothing, reads nothing
+ * back, never writes the frames, the dark fields or the uncertainties, touches nothing outside C*H_tile*W elements of the
+ * state and the outputs.
+ */
+int ct_hdr_merge_dark_ingest_batches(const void *const *frames_devs, const int32_t *batch_sizes, int32_t n_batches, int32_t dtype,
+                                     const ct_geometry *geom, const ct_ingest_stage *stages, int32_t n_stages,
+                                     const float *const *consts_devs, const void *const *halo_devs, const float *const *std_devs,
+                                     int32_t std_mode, float std_value, const float *const *dark_devs,
+                                     const float *const *dark_std_devs, const int32_t *dark_batches, float threshold, float alpha,
+                                     const double *exposure_dev, const ct_icrf *icrf, int32_t weight_mode, double *mean_state_dev,
+                                     float *sumw_state_dev, float *var_state_dev, void *mean_out_dev, float *std_out_dev,
+                                     uint32_t flags, void *stream);
 
 /*
  * ct_video_stats_ingest_batch -- such a chain and one batch of compute_video_mean_and_std's loop body in ONE pass over B raw
