@@ -5,7 +5,7 @@ through all of it to get the variance; here each batch is ONE fused kernel launc
 device-resident state, and the closed form of that variance is evaluated in registers.  Streaming semantics are the
 reference's, including the batch-partition dependence of the variance (state detached per batch, hdr_merge.py:128).
 """
-from typing import Callable, Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 from torch.utils.data import DataLoader
@@ -24,6 +24,16 @@ DARK_QUEUE_BYTES = 8 << 30
 # timed run of the fused launch is faster than every timed run of ops.ingest_transform + ops.hdr_merge_dark_batch(es) at every
 # measured shape -- the rule ``fused_dark`` was decided by.
 FUSED_DARK_INGEST_DEFAULT = False
+
+
+class _QueueKind(NamedTuple):
+    """What the queued batches of compute_hdr_image have in common, and what tells one launch of them from the next."""
+    key: tuple                  # batches of one key go into one launch
+    cap: int                    # ... at most so many of them
+    held: int                   # ... of at most DARK_QUEUE_BYTES together: the bytes THIS batch holds on the device (0: not counted)
+    state_shape: tuple          # the MergeState their launch needs when it is not the whole merge
+    with_variance: bool
+    launch: Callable            # (first queued batch, **merge keywords) -> (mean, std) of a final launch | None
 
 
 def _dark_batch_bytes(images, std, matched, halo):
@@ -126,65 +136,64 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
     # ct_hdr_merge_batches call keeps the streaming state in registers across up to 16 batches instead of writing and
     # re-reading 32 B per element after every one of them (the reference's default is batch_size: 4).  The result is the
     # same bit for bit as merging batch by batch (per-batch detach of the state, hdr_merge.py:128, included).
-    queue, queue_key, queue_bytes = [], None, 0
+    # What is queued is of one kind (``_QueueKind``): the key its batches share, how many of them and how many bytes one launch
+    # takes, the MergeState they need and the function that launches them.
+    queue, queue_kind, queue_bytes = [], None, 0
+
+    def merge_args(state_shape, with_variance, final):
+        """The keywords every merge op takes; a launch that is not the whole merge gets the MergeState, made here once."""
+        nonlocal state
+        if state is None and (not final or flat_field_dataset is not None):
+            state = ops.MergeState(state_shape, dev, with_variance=with_variance)
+        return dict(lut=lut, interp=interp, gaussian_weight=weight_fn is not None, state=state,
+                    finalize=final and flat_field_dataset is None, reference_order=reference_order)
+
+    def column(name):
+        """What the queued batches hold under ``name``, one entry per batch; None where they hold none."""
+        return None if queue[0][name] is None else [q[name] for q in queue]
 
     def flush(final):
-        nonlocal state, result, queue, queue_bytes
-        if not queue:
-            return
-        k0 = queue[0]
-        if "matched" in k0 and isinstance(k0["images"], DeferredIngest):
-            # chain, blur and merge of every queued dark-field batch in one launch over the raw frames
-            # (ct_hdr_merge_dark_ingest_batches)
-            d = k0["images"]
-            if state is None and (not final or flat_field_dataset is not None):
-                state = ops.MergeState(ops.ingest_shape(tuple(d.frames.shape), d.layout)[1:], dev, with_variance=True)
-            result = dark.merge_ingest_batches([q["matched"] for q in queue], [q["images"] for q in queue],
-                                               [q["exposure"] for q in queue], None if k0["std"] is None else [q["std"] for q in queue],
-                                               k0["std_mode"], k0["std_value"], tile,
-                                               None if k0["halo"] is None else [q["halo"] for q in queue], lut=lut, interp=interp,
-                                               gaussian_weight=weight_fn is not None, state=state,
-                                               finalize=final and flat_field_dataset is None, reference_order=reference_order)
-            queue, queue_bytes = [], 0
-            return
-        if "matched" in k0:
-            # blur and merge of every queued dark-field batch in one launch (ct_hdr_merge_dark_batches)
-            if state is None and (not final or flat_field_dataset is not None):
-                state = ops.MergeState(tuple(k0["images"].shape[1:]), dev, with_variance=True)
-            result = dark.merge_batches([q["matched"] for q in queue], [q["images"] for q in queue], [q["exposure"] for q in queue],
-                                        k0["max_code"], None if k0["std"] is None else [q["std"] for q in queue], k0["std_mode"],
-                                        k0["std_value"], tile, None if k0["halo"] is None else [q["halo"] for q in queue],
-                                        lut=lut, interp=interp, gaussian_weight=weight_fn is not None, state=state,
-                                        finalize=final and flat_field_dataset is None, reference_order=reference_order)
-            queue, queue_bytes = [], 0
-            return
-        if isinstance(k0["images"], DeferredIngest):
-            # the chain and the merge of every queued batch in one launch (ct_hdr_merge_ingest_batches): the raw frames are
-            # read once and the streaming state stays in registers between the batches, as on the code route
-            d = k0["images"]
-            if state is None and (not final or flat_field_dataset is not None):
-                state = ops.MergeState(ops.ingest_shape(tuple(d.frames.shape), d.layout)[1:], dev, with_variance=k0["std_mode"] != "none")
-            stds = None if k0["std"] is None else [q["std"] for q in queue]
-            consts = None if d.consts is None else [q["images"].consts for q in queue]
-            result = ops.hdr_merge_ingest_batches([q["images"].frames for q in queue], d.stages, [q["exposure"] for q in queue],
-                                                  lut=lut, interp=interp, gaussian_weight=weight_fn is not None, stds=stds,
-                                                  std_mode=k0["std_mode"], std_value=k0["std_value"], state=state,
-                                                  finalize=final and flat_field_dataset is None, tile=tile, layout=d.layout,
-                                                  reference_order=reference_order, consts=consts)
-            queue = []
-            return
-        out_layout = "input" if (output_layout == "input" and k0["layout"] != "nchw") else "planar"
-        if state is None and (not final or flat_field_dataset is not None):
-            chw = tuple(k0["images"].shape[1:]) if (k0["layout"] == "nchw" or out_layout == "input") else \
-                (k0["images"].shape[3], k0["images"].shape[1], k0["images"].shape[2])
-            state = ops.MergeState(chw, dev, with_variance=k0["std_mode"] != "none")
-        stds = None if k0["std"] is None else [q["std"] for q in queue]
-        result = ops.hdr_merge_batches([q["images"] for q in queue], [q["exposure"] for q in queue], lut=lut, interp=interp,
-                                       gaussian_weight=weight_fn is not None, stds=stds, std_mode=k0["std_mode"],
-                                       std_value=k0["std_value"], max_code=k0["max_code"], state=state,
-                                       finalize=final and flat_field_dataset is None, tile=tile, layout=k0["layout"],
-                                       out_layout=out_layout, reference_order=reference_order)
-        queue = []
+        nonlocal result, queue_bytes
+        if queue:
+            result = queue_kind.launch(queue[0], **merge_args(queue_kind.state_shape, queue_kind.with_variance, final))
+            del queue[:]
+            queue_bytes = 0
+
+    def enqueue(kind, **batch):
+        """Flush what is queued if this batch is of another kind or would take the queue over its cap, queue it, and flush at
+        the end of the loader."""
+        nonlocal queue_kind, queue_bytes
+        if queue and (kind.key != queue_kind.key or len(queue) == kind.cap or queue_bytes + kind.held > DARK_QUEUE_BYTES):
+            flush(False)
+        queue_kind = kind
+        queue_bytes += kind.held
+        queue.append(batch)
+        if last:
+            flush(True)
+
+    def launch_dark_ingest(k0, **args):
+        # chain, blur and merge of every queued dark-field batch in one launch over the raw frames (ct_hdr_merge_dark_ingest_batches)
+        return dark.merge_ingest_batches(column("matched"), column("images"), column("exposure"), column("std"), k0["std_mode"],
+                                         k0["std_value"], tile, column("halo"), **args)
+
+    def launch_dark(k0, **args):
+        # blur and merge of every queued dark-field batch in one launch (ct_hdr_merge_dark_batches)
+        return dark.merge_batches(column("matched"), column("images"), column("exposure"), k0["max_code"], column("std"), k0["std_mode"],
+                                  k0["std_value"], tile, column("halo"), **args)
+
+    def launch_ingest(k0, **args):
+        # the chain and the merge of every queued batch in one launch (ct_hdr_merge_ingest_batches): the raw frames are read once
+        # and the streaming state stays in registers between the batches, as on the code route
+        d = k0["images"]
+        consts = None if d.consts is None else [q["images"].consts for q in queue]
+        return ops.hdr_merge_ingest_batches([q["images"].frames for q in queue], d.stages, column("exposure"), stds=column("std"),
+                                            std_mode=k0["std_mode"], std_value=k0["std_value"], tile=tile, layout=d.layout, consts=consts,
+                                            **args)
+
+    def launch_plain(k0, **args):
+        return ops.hdr_merge_batches(column("images"), column("exposure"), stds=column("std"), std_mode=k0["std_mode"],
+                                     std_value=k0["std_value"], max_code=k0["max_code"], tile=tile, layout=k0["layout"],
+                                     out_layout=k0["out_layout"], **args)
 
     while pending is not None:
         index_batch, val_batch, std_batch, meta_batch = pending
@@ -194,6 +203,7 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
         defer = fused_ingest if dark is None else (fused_dark and fused_dark_ingest)
         images, max_code, layout = stage_images(val_batch, dev, transforms, planar, defer_ingest=defer)
         std, std_mode, std_value = std_arguments(std_batch, dataloader.dataset, dev)
+        exposure = meta_batch["exposure_time"]
         fused = isinstance(images, DeferredIngest)
         matched, asked = None, False
         if fused and dark is not None:
@@ -203,15 +213,9 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
                 halo = exchange_halo(images.frames, tile, group) if images.layout == "nchw" else None
                 key = ("dark_ingest", images.frames.dtype, tuple(images.frames.shape[1:]), images.layout, images.stages, std_mode,
                        std_value, std is None, images.consts is None)
-                held = _dark_batch_bytes(images.frames, std, matched, halo)
-                if queue and (key != queue_key or len(queue) == dark_batches_per_launch or queue_bytes + held > DARK_QUEUE_BYTES):
-                    flush(False)
-                queue_key = key
-                queue_bytes += held
-                queue.append(dict(images=images, exposure=meta_batch["exposure_time"], std=std, std_mode=std_mode, std_value=std_value,
-                                  max_code=None, matched=matched, halo=halo))
-                if last:
-                    flush(last)
+                enqueue(_QueueKind(key, dark_batches_per_launch, _dark_batch_bytes(images.frames, std, matched, halo),
+                                   ops.ingest_shape(tuple(images.frames.shape), images.layout)[1:], True, launch_dark_ingest),
+                        images=images, exposure=exposure, std=std, std_mode=std_mode, std_value=std_value, matched=matched, halo=halo)
                 continue
             if matched is not None:  # declined: the float32 stack, then as without the keyword
                 images = ops.ingest_transform(images.frames, images.stages, layout=images.layout, consts=images.consts)
@@ -229,25 +233,17 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
                 # queued under a key of its own; the halo rows are exchanged now, in loader order on every rank
                 halo = exchange_halo(images, tile, group)
                 key = ("dark", images.dtype, tuple(images.shape[1:]), max_code, std_mode, std_value, std is None)
-                held = _dark_batch_bytes(images, std, matched, halo)
-                if queue and (key != queue_key or len(queue) == dark_batches_per_launch or queue_bytes + held > DARK_QUEUE_BYTES):
-                    flush(False)
-                queue_key = key
-                queue_bytes += held
-                queue.append(dict(images=images, exposure=meta_batch["exposure_time"], std=std, std_mode=std_mode, std_value=std_value,
-                                  max_code=max_code, matched=matched, halo=halo))
-                if last:
-                    flush(last)
+                enqueue(_QueueKind(key, dark_batches_per_launch, _dark_batch_bytes(images, std, matched, halo), tuple(images.shape[1:]), True,
+                                   launch_dark),
+                        images=images, exposure=exposure, std=std, std_mode=std_mode, std_value=std_value, max_code=max_code,
+                        matched=matched, halo=halo)
                 continue
             if fuses:
                 # blur and merge in one pass over the staged images (ct_hdr_merge_dark_batch), on the state the queued
                 # batches leave: they are merged first
                 flush(False)
-                if state is None and (not last or flat_field_dataset is not None):
-                    state = ops.MergeState(tuple(images.shape[1:]), dev, with_variance=True)
-                result = dark.merge(matched, images, meta_batch["exposure_time"], max_code, std, std_mode, std_value, tile, group,
-                                    lut=lut, interp=interp, gaussian_weight=weight_fn is not None, state=state,
-                                    finalize=last and flat_field_dataset is None, reference_order=reference_order)
+                result = dark.merge(matched, images, exposure, max_code, std, std_mode, std_value, tile, group,
+                                    **merge_args(tuple(images.shape[1:]), True, last))
                 continue
             if matched is not None:  # the blurred batch replaces the images; its uncertainty carries both variance terms
                 xb, sig = dark.apply(index_batch, images, max_code, std, std_mode, std_value, tile, group, matched=matched)
@@ -255,15 +251,17 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
         if fused:  # one dtype, shape, layout and chain per call; every batch with constants of its own, or none
             key = ("ingest", images.frames.dtype, tuple(images.frames.shape[1:]), images.layout, images.stages, std_mode, std_value,
                    std is None, images.consts is None)
+            enqueue(_QueueKind(key, ops.MAX_MERGE_BATCHES, 0, ops.ingest_shape(tuple(images.frames.shape), images.layout)[1:],
+                               std_mode != "none", launch_ingest),
+                    images=images, exposure=exposure, std=std, std_mode=std_mode, std_value=std_value)
         else:
             key = (images.dtype, tuple(images.shape[1:]), max_code, layout, std_mode, std_value, std is None)
-        if queue and (key != queue_key or len(queue) == ops.MAX_MERGE_BATCHES):
-            flush(False)
-        queue_key = key
-        queue.append(dict(images=images, exposure=meta_batch["exposure_time"], std=std, std_mode=std_mode, std_value=std_value,
-                          max_code=max_code, layout=layout))
-        if last:
-            flush(last)
+            out_layout = "input" if (output_layout == "input" and layout != "nchw") else "planar"
+            chw = tuple(images.shape[1:]) if (layout == "nchw" or out_layout == "input") else \
+                (images.shape[3], images.shape[1], images.shape[2])
+            enqueue(_QueueKind(key, ops.MAX_MERGE_BATCHES, 0, chw, std_mode != "none", launch_plain),
+                    images=images, exposure=exposure, std=std, std_mode=std_mode, std_value=std_value, max_code=max_code, layout=layout,
+                    out_layout=out_layout)
     if flat_field_dataset is not None:
         mean, std = _flat_field_epilogue(state, flat_field_dataset, dataloader.dataset, dev, tile, group)
     else:

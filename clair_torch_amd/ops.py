@@ -134,13 +134,23 @@ def _exposures_to_device(exposures: torch.Tensor, batch: int, device):
 
 
 def _exposure_list_to_device(exposures, sizes, device):
-    """The exposure times of several batches of ``sizes`` frames, one after the other, as float64 on ``device`` (staged
-    through pinned memory: see ``_exposures_to_device``)."""
+    """The exposure times of several batches of ``sizes`` frames, one after the other, as float64 on ``device``.  Lists that
+    live on the device already are concatenated there (no copy back to the host, which would wait for the stream); host lists
+    are staged through pinned memory (see ``_exposures_to_device``)."""
     for e, n in zip(exposures, sizes):
         if e.numel() != n:
             raise ValueError(f"{e.numel()} exposure times for a batch of {n}")
+    if all(e.is_cuda for e in exposures):
+        return torch.cat([e.detach().to(device=device, dtype=torch.float64).reshape(-1) for e in exposures])
     host_exp = torch.cat([e.detach().to("cpu", torch.float64).reshape(-1) for e in exposures])
     return host_exp.pin_memory().to(device, non_blocking=True) if device.type == "cuda" else host_exp
+
+
+def _pointers(tensors):
+    """The HOST array of the tensors' device pointers (NULL for a None among them); None for no list at all."""
+    if tensors is None:
+        return None
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
 
 
 def _lin_std_out(out, shape, device, want_std: bool, lin_required: bool):
@@ -213,14 +223,10 @@ class MergeState:
         self.batches = 0
 
 
-def _merge_setup(stack, layout, out_layout, state, finalize, has_std, mean_dtype, reference_order, flags, what):
-    """What hdr_merge_batch and hdr_merge_batches share: (flag word, out_shape, mean_out, std_out) after the MergeState checks."""
-    return _merge_setup_for(_out_shape(stack, layout, out_layout), stack.device, out_layout, state, finalize, has_std, mean_dtype,
-                            reference_order, flags, what)
-
-
-def _merge_setup_for(out_shape, device, out_layout, state, finalize, has_std, mean_dtype, reference_order, flags, what):
-    """``_merge_setup`` for a state / output shape and device given as such."""
+def _merge_setup(out_shape, device, out_layout, state, finalize, has_std, mean_dtype, reference_order, flags, what, first=None):
+    """What every hdr_merge_* front does last before its call: (flag word, mean_out, std_out) for a state / output shape
+    ``out_shape`` on ``device``, after the MergeState checks.  ``first``: None = the state decides about FIRST_BATCH (a fresh
+    MergeState, or none, starts the merge); True / False says so for a state filled elsewhere."""
     if state is None or state.batches == 0:
         flags |= nv.MERGE_FIRST_BATCH
     if finalize:
@@ -241,9 +247,76 @@ def _merge_setup_for(out_shape, device, out_layout, state, finalize, has_std, me
         raise ValueError("MergeState was created without a variance buffer")
     if state is not None and tuple(state.mean.shape) != out_shape:
         raise ValueError(f"MergeState has shape {tuple(state.mean.shape)}, this merge needs {out_shape}")
+    if first is not None:
+        flags = (flags | nv.MERGE_FIRST_BATCH) if first else (flags & ~nv.MERGE_FIRST_BATCH)
     mean_out = torch.empty(out_shape, dtype=mean_dtype, device=device) if finalize else None
     std_out = torch.empty(out_shape, dtype=torch.float32, device=device) if (finalize and has_std) else None
-    return flags, out_shape, mean_out, std_out
+    return flags, mean_out, std_out
+
+
+def _launch_merge(entry, dev, head, state, flags, batches, mean_out, std_out, *, retry_with_state=False, probe_one_launch=False,
+                  retry_one_batch=True):
+    """The tail of every hdr_merge_* front: the library's ``entry``(*head, state pointers, outputs, flag word, stream) on ``dev``,
+    its status checked, ``state.batches`` advanced by ``batches``; -> (mean_out, std_out) of a final call, else None.
+
+    ``retry_with_state``: a whole merge in one launch needs no state arrays at all, so a call without a MergeState goes
+    without; only when the library answers CT_ERR_UNSUPPORTED (what cannot run as one launch walks the batches with the state
+    in memory; nothing has been launched then) is a fresh one made and the call repeated -- unless the caller's flag word
+    requires one launch.  ``probe_one_launch``: the first try without a state carries MERGE_REQUIRE_ONE_LAUNCH, for an entry
+    point that answers a stateless walk with CT_ERR_INVALID_ARGUMENT.  ``retry_one_batch`` False: no second try for one batch."""
+    def attempt(st, fl):
+        with torch.cuda.device(dev):
+            return getattr(nv.load(), entry)(*head, *_state_ptrs(st), _ptr(mean_out), _ptr(std_out), fl, _stream(dev))
+
+    rc = attempt(state, flags | (nv.MERGE_REQUIRE_ONE_LAUNCH if probe_one_launch and state is None else 0))
+    if (rc == nv.ERR_UNSUPPORTED and retry_with_state and state is None and not flags & nv.MERGE_REQUIRE_ONE_LAUNCH
+            and (retry_one_batch or batches > 1)):
+        state = MergeState(tuple(mean_out.shape), dev, std_out is not None)      # (no state: the call is final and has outputs)
+        rc = attempt(state, flags)
+    nv.check(rc, entry)
+    if state is not None:
+        state.batches += batches
+    return None if mean_out is None else (mean_out, std_out)
+
+
+def _weight(gaussian_weight):
+    return nv.WEIGHT_GAUSS if gaussian_weight else nv.WEIGHT_NONE
+
+
+MAX_MERGE_BATCHES = 16  # batches one ct_hdr_merge_batches call takes (the kernel's argument block holds 16 pointers)
+
+
+def _all_or_none(values, what):
+    """A per-batch list that holds a tensor for every batch or for none: -> the list, None for one of Nones (mixed: refused)."""
+    if values is None or not any(t is None for t in values):
+        return values
+    if any(t is not None for t in values):
+        raise ValueError(f"{what} for every batch of one call, or for none")
+    return None
+
+
+def _check_batch_list(stacks, lists, names, check_stack, *, all_or_none=(), refuse_empty=True, one_batch_elsewhere=False):
+    """The batches of one hdr_merge_*_batches call: ``stacks`` and the ``lists`` beside it (None: not given) are non-empty and
+    equally long, at most MAX_MERGE_BATCHES; the lists ``all_or_none`` names by position in ``lists``, with the message's
+    subject, hold a tensor for every batch or for none; every stack passes ``check_stack``, shares dtype, image shape and device
+    with the first and (``refuse_empty``) holds a frame.  -> the ``all_or_none`` lists, None for one of Nones.
+    ``one_batch_elsewhere``: a single batch goes to the single-batch front, which checks the stack itself."""
+    k = len(stacks)
+    if k == 0 or any(v is not None and len(v) != k for v in lists):
+        raise ValueError(f"{names} must be non-empty lists of equal length")
+    if k > MAX_MERGE_BATCHES:
+        raise ValueError(f"at most {MAX_MERGE_BATCHES} batches per call")
+    settled = [_all_or_none(lists[i], what) for i, what in all_or_none]
+    if k == 1 and one_batch_elsewhere:
+        return settled
+    s0 = stacks[0]
+    for t in stacks:
+        check_stack(t)
+        if t.dtype != s0.dtype or t.shape[1:] != s0.shape[1:] or t.device != s0.device:
+            raise ValueError("all batches of one call must share dtype, image shape and device")
+        if refuse_empty and t.shape[0] < 1:
+            raise ValueError("empty batch")
+    return settled
 
 
 def hdr_merge_batch(stack: torch.Tensor, exposures: torch.Tensor, *, lut: Optional[torch.Tensor] = None,
@@ -284,23 +357,13 @@ def hdr_merge_batch(stack: torch.Tensor, exposures: torch.Tensor, *, lut: Option
         raise ValueError(f"unknown std_mode {std_mode}")
     max_code = _default_max_code(stack, max_code)
     exposure_dev = _exposures_to_device(exposures, b, dev)
-    icrf, lut_keep = _icrf_struct(lut, interp, c)
+    icrf, lut_keep = _icrf_struct(lut, interp, c)      # (lut_keep: what the struct points to, alive until the call is made)
     geom = _geometry(stack, tile, layout)
-    flags, _, mean_out, std_out = _merge_setup(stack, layout, out_layout, state, finalize, std_mode != "none", mean_dtype,
-                                               reference_order, nv.MERGE_F64_MOMENTS if force_f64_moments else 0, "batch")
-    with torch.cuda.device(dev):
-        rc = nv.load().ct_hdr_merge_batch(
-            _ptr(stack), _DTYPE[stack.dtype], float(max_code or 1.0), b, ctypes.byref(geom), _ptr(std), _STD[std_mode],
-            float(std_value), _ptr(exposure_dev), ctypes.byref(icrf), nv.WEIGHT_GAUSS if gaussian_weight else nv.WEIGHT_NONE,
-            *_state_ptrs(state), _ptr(mean_out), _ptr(std_out), flags, _stream(dev))
-    nv.check(rc, "ct_hdr_merge_batch")
-    del lut_keep
-    if state is not None:
-        state.batches += 1
-    return (mean_out, std_out) if finalize else None
-
-
-MAX_MERGE_BATCHES = 16  # batches one ct_hdr_merge_batches call takes (the kernel's argument block holds 16 pointers)
+    flags, mean_out, std_out = _merge_setup(_out_shape(stack, layout, out_layout), dev, out_layout, state, finalize, std_mode != "none",
+                                            mean_dtype, reference_order, nv.MERGE_F64_MOMENTS if force_f64_moments else 0, "batch")
+    head = (_ptr(stack), _DTYPE[stack.dtype], float(max_code or 1.0), b, ctypes.byref(geom), _ptr(std), _STD[std_mode], float(std_value),
+            _ptr(exposure_dev), ctypes.byref(icrf), _weight(gaussian_weight))
+    return _launch_merge("ct_hdr_merge_batch", dev, head, state, flags, 1, mean_out, std_out)
 
 
 def hdr_merge_batches(stacks, exposures, *, lut: Optional[torch.Tensor] = None, interp: Optional[str] = "linear",
@@ -316,20 +379,14 @@ def hdr_merge_batches(stacks, exposures, *, lut: Optional[torch.Tensor] = None, 
     ``exposures``: list of (B_k) tensors; ``stds``: list of explicit std tensors or None.  At most MAX_MERGE_BATCHES.
     ``require_one_launch`` (tests): raise instead of falling back to one launch per batch.  ``out_layout``: as in hdr_merge_batch.
     Returns (mean, std|None) when ``finalize`` else None."""
+    # (an empty batch among several is left to the library, which skips it)
+    _check_batch_list(stacks, (exposures, stds), "stacks / exposures / stds", _check_stack, refuse_empty=False, one_batch_elsewhere=True)
     k = len(stacks)
-    if k == 0 or k != len(exposures) or (stds is not None and len(stds) != k):
-        raise ValueError("stacks / exposures / stds must be non-empty lists of equal length")
-    if k > MAX_MERGE_BATCHES:
-        raise ValueError(f"at most {MAX_MERGE_BATCHES} batches per call")
     if k == 1:
         return hdr_merge_batch(stacks[0], exposures[0], lut=lut, interp=interp, gaussian_weight=gaussian_weight,
                                std=None if stds is None else stds[0], std_mode=std_mode, std_value=std_value, max_code=max_code,
                                state=state, finalize=finalize, tile=tile, mean_dtype=mean_dtype, layout=layout,
                                reference_order=reference_order, out_layout=out_layout)
-    for t in stacks:
-        _check_stack(t)
-        if t.dtype != stacks[0].dtype or t.shape[1:] != stacks[0].shape[1:] or t.device != stacks[0].device:
-            raise ValueError("all batches of one call must share dtype, image shape and device")
     dev = stacks[0].device
     c, h, w = _chw(stacks[0], layout)
     if stds is not None:
@@ -344,24 +401,16 @@ def hdr_merge_batches(stacks, exposures, *, lut: Optional[torch.Tensor] = None, 
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _geometry(stacks[0], tile, layout)
     has_std = std_mode != "none"
-    flags, out_shape, mean_out, std_out = _merge_setup(stacks[0], layout, out_layout, state, finalize, has_std, mean_dtype,
-                                                       reference_order, nv.MERGE_REQUIRE_ONE_LAUNCH if require_one_launch else 0,
-                                                       "call")
+    out_shape = _out_shape(stacks[0], layout, out_layout)
+    flags, mean_out, std_out = _merge_setup(out_shape, dev, out_layout, state, finalize, has_std, mean_dtype, reference_order,
+                                            nv.MERGE_REQUIRE_ONE_LAUNCH if require_one_launch else 0, "call")
     if state is None:
-        # several batches: whatever cannot run as one launch walks them with the state in memory
+        # several batches: whatever cannot run as one launch walks them with the state in memory.  This front makes the state up
+        # front and never retries; the others try without one first (``_launch_merge``)
         state = MergeState(out_shape, dev, has_std)
-    ptr_arr = (ctypes.c_void_p * k)(*[t.data_ptr() for t in stacks])
-    std_arr = (ctypes.c_void_p * k)(*[sd.data_ptr() for sd in stds]) if stds is not None else None
-    size_arr = (ctypes.c_int32 * k)(*sizes)
-    with torch.cuda.device(dev):
-        rc = nv.load().ct_hdr_merge_batches(
-            ptr_arr, std_arr, size_arr, k, _DTYPE[stacks[0].dtype], float(max_code or 1.0), ctypes.byref(geom), _STD[std_mode],
-            float(std_value), _ptr(exposure_dev), ctypes.byref(icrf), nv.WEIGHT_GAUSS if gaussian_weight else nv.WEIGHT_NONE,
-            *_state_ptrs(state), _ptr(mean_out), _ptr(std_out), flags, _stream(dev))
-    nv.check(rc, "ct_hdr_merge_batches")
-    del lut_keep
-    state.batches += k
-    return (mean_out, std_out) if finalize else None
+    head = (_pointers(stacks), _pointers(stds), (ctypes.c_int32 * k)(*sizes), k, _DTYPE[stacks[0].dtype], float(max_code or 1.0),
+            ctypes.byref(geom), _STD[std_mode], float(std_value), _ptr(exposure_dev), ctypes.byref(icrf), _weight(gaussian_weight))
+    return _launch_merge("ct_hdr_merge_batches", dev, head, state, flags, k, mean_out, std_out)
 
 
 def linearize_frames(frames: torch.Tensor, lut: torch.Tensor, interp: str = "linear", *,
@@ -713,30 +762,23 @@ def hdr_merge_dark_batch(stack: torch.Tensor, exposures: torch.Tensor, dark: tor
     exposure_dev = _exposures_to_device(exposures, b, dev)
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _geometry(stack, tile)
-    flags, _, mean_out, std_out = _merge_setup_for((c, h, w), dev, "planar", state, finalize, dark_std is not None, mean_dtype,
-                                                   reference_order, 0, "batch")
-    with torch.cuda.device(dev):
-        rc = nv.load().ct_hdr_merge_dark_batch(
-            _ptr(stack), _DTYPE[stack.dtype], float(max_code or 1.0), b, ctypes.byref(geom), _ptr(halo), _ptr(std), _STD[std_mode],
+    flags, mean_out, std_out = _merge_setup((c, h, w), dev, "planar", state, finalize, dark_std is not None, mean_dtype, reference_order,
+                                            0, "batch")
+    head = (_ptr(stack), _DTYPE[stack.dtype], float(max_code or 1.0), b, ctypes.byref(geom), _ptr(halo), _ptr(std), _STD[std_mode],
             float(std_value), _ptr(dark), _ptr(dark_std), dark.shape[0], float(threshold), float(alpha), _ptr(exposure_dev),
-            ctypes.byref(icrf), nv.WEIGHT_GAUSS if gaussian_weight else nv.WEIGHT_NONE, *_state_ptrs(state), _ptr(mean_out),
-            _ptr(std_out), flags, _stream(dev))
-    nv.check(rc, "ct_hdr_merge_dark_batch")
-    del lut_keep
-    if state is not None:
-        state.batches += 1
-    return (mean_out, std_out) if finalize else None
+            ctypes.byref(icrf), _weight(gaussian_weight))
+    return _launch_merge("ct_hdr_merge_dark_batch", dev, head, state, flags, 1, mean_out, std_out)
 
 
-def _exposure_list_on_device(exposures, sizes, device):
-    """``_exposure_list_to_device`` for lists that may live on the device already: those are concatenated there (no copy back
-    to the host, which would wait for the stream); host lists take the pinned staging copy."""
-    if not all(isinstance(e, torch.Tensor) and e.is_cuda for e in exposures):
-        return _exposure_list_to_device(exposures, sizes, device)
-    for e, n in zip(exposures, sizes):
-        if e.numel() != n:
-            raise ValueError(f"{e.numel()} exposure times for a batch of {n}")
-    return torch.cat([e.detach().to(device=device, dtype=torch.float64).reshape(-1) for e in exposures])
+def _dark_argument_lists(stacks, darks, dark_stds, halos):
+    """``_dark_arguments`` of every batch of a list front (``dark_stds`` / ``halos`` None: none at all): lists of the dark
+    fields, their stds and the halo rows as the kernels read them, None standing for what a batch lacks; halo rows are given
+    for every batch or for none."""
+    checked = [_dark_arguments(t, darks[i], None if dark_stds is None else dark_stds[i], None if halos is None else halos[i])
+               for i, t in enumerate(stacks)]
+    darks, dark_stds, halos = ([v[j] for v in checked] for j in range(3))
+    _all_or_none(halos, "halo rows")
+    return darks, dark_stds, halos
 
 
 def hdr_merge_dark_batches(stacks, exposures, darks, dark_stds, *, stds=None, std_mode: str = "none", std_value: float = 0.0,
@@ -757,16 +799,9 @@ def hdr_merge_dark_batches(stacks, exposures, darks, dark_stds, *, stds=None, st
     says so for a state filled elsewhere.  ``require_one_launch`` (tests): raise instead of falling back to one launch per
     batch (more exposure times than the LDS holds beside the LUT).  Everything else as in ``hdr_merge_dark_batch``.
     Returns (mean, std|None), planar (C,H,W), when ``finalize`` else None."""
+    dark_stds, = _check_batch_list(stacks, (exposures, darks, dark_stds, stds, halos), "stacks / exposures / darks / dark_stds / stds / halos",
+                                   _check_stack, all_or_none=[(2, "a dark std")], one_batch_elsewhere=first is None)
     k = len(stacks)
-    lists = (exposures, darks) + tuple(v for v in (dark_stds, stds, halos) if v is not None)
-    if k == 0 or any(len(v) != k for v in lists):
-        raise ValueError("stacks / exposures / darks / dark_stds / stds / halos must be non-empty lists of equal length")
-    if k > MAX_MERGE_BATCHES:
-        raise ValueError(f"at most {MAX_MERGE_BATCHES} batches per call")
-    if dark_stds is not None and any(t is None for t in dark_stds):
-        if any(t is not None for t in dark_stds):
-            raise ValueError("a dark std for every batch of one call, or for none")
-        dark_stds = None
     if k == 1 and first is None:
         return hdr_merge_dark_batch(stacks[0], exposures[0], darks[0], None if dark_stds is None else dark_stds[0], lut=lut,
                                     interp=interp, gaussian_weight=gaussian_weight, std=None if stds is None else stds[0],
@@ -774,12 +809,6 @@ def hdr_merge_dark_batches(stacks, exposures, darks, dark_stds, *, stds=None, st
                                     tile=tile, halo=None if halos is None else halos[0], mean_dtype=mean_dtype,
                                     reference_order=reference_order, threshold=threshold, alpha=alpha)
     s0 = stacks[0]
-    for t in stacks:
-        _check_stack(t)
-        if t.dtype != s0.dtype or t.shape[1:] != s0.shape[1:] or t.device != s0.device:
-            raise ValueError("all batches of one call must share dtype, image shape and device")
-        if t.shape[0] < 1:
-            raise ValueError("empty batch")
     _, c, h, w = s0.shape
     dev = s0.device
     if stds is not None:
@@ -789,49 +818,20 @@ def hdr_merge_dark_batches(stacks, exposures, darks, dark_stds, *, stds=None, st
         raise ValueError(f"unknown std_mode {std_mode}")
     stacks = [t.contiguous() for t in stacks]
     max_code = _default_max_code(s0, max_code)
-    checked = [_dark_arguments(t, darks[i], None if dark_stds is None else dark_stds[i], None if halos is None else halos[i])
-               for i, t in enumerate(stacks)]
-    darks, dark_stds, halos = ([v[j] for v in checked] for j in range(3))
-    if any(t is None for t in halos) and any(t is not None for t in halos):
-        raise ValueError("halo rows for every batch of one call, or for none")
-    has_std = dark_stds[0] is not None
+    darks, dark_stds, halos = _dark_argument_lists(stacks, darks, dark_stds, halos)
     sizes = [int(t.shape[0]) for t in stacks]
-    exposure_dev = _exposure_list_on_device(exposures, sizes, dev)
+    exposure_dev = _exposure_list_to_device(exposures, sizes, dev)
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _geometry(stacks[0], tile)
-    flags, out_shape, mean_out, std_out = _merge_setup_for((c, h, w), dev, "planar", state, finalize, has_std, mean_dtype, reference_order,
-                                                           nv.MERGE_REQUIRE_ONE_LAUNCH if require_one_launch else 0, "call")
-
-    if first is not None:
-        flags = (flags | nv.MERGE_FIRST_BATCH) if first else (flags & ~nv.MERGE_FIRST_BATCH)
-
-    def pointers(tensors):
-        return (ctypes.c_void_p * k)(*[None if t is None else t.data_ptr() for t in tensors])
-
-    stack_arr, dark_arr, dark_std_arr, halo_arr = pointers(stacks), pointers(darks), pointers(dark_stds), pointers(halos)
-    std_arr = pointers(stds) if stds is not None else None
-    size_arr = (ctypes.c_int32 * k)(*sizes)
-    dark_size_arr = (ctypes.c_int32 * k)(*[int(t.shape[0]) for t in darks])
-
-    def call(st, fl):
-        with torch.cuda.device(dev):
-            return nv.load().ct_hdr_merge_dark_batches(
-                stack_arr, size_arr, k, _DTYPE[s0.dtype], float(max_code or 1.0), ctypes.byref(geom), halo_arr, std_arr, _STD[std_mode],
-                float(std_value), dark_arr, dark_std_arr, dark_size_arr, float(threshold), float(alpha), _ptr(exposure_dev),
-                ctypes.byref(icrf), nv.WEIGHT_GAUSS if gaussian_weight else nv.WEIGHT_NONE, *_state_ptrs(st), _ptr(mean_out),
-                _ptr(std_out), fl, _stream(dev))
-
-    # a whole merge in one launch needs no state arrays at all; only what cannot run as one launch walks the batches with
-    # the state in memory (nothing has been launched when the library says so)
-    rc = call(state, flags)
-    if rc == nv.ERR_UNSUPPORTED and state is None and not require_one_launch:
-        state = MergeState(out_shape, dev, has_std)
-        rc = call(state, flags)
-    nv.check(rc, "ct_hdr_merge_dark_batches")
-    del lut_keep
-    if state is not None:
-        state.batches += k
-    return (mean_out, std_out) if finalize else None
+    flags, mean_out, std_out = _merge_setup((c, h, w), dev, "planar", state, finalize, dark_stds[0] is not None, mean_dtype, reference_order,
+                                            nv.MERGE_REQUIRE_ONE_LAUNCH if require_one_launch else 0, "call", first)
+    head = (_pointers(stacks), (ctypes.c_int32 * k)(*sizes), k, _DTYPE[s0.dtype], float(max_code or 1.0), ctypes.byref(geom),
+            _pointers(halos), _pointers(stds), _STD[std_mode], float(std_value), _pointers(darks), _pointers(dark_stds),
+            (ctypes.c_int32 * k)(*[int(t.shape[0]) for t in darks]), float(threshold), float(alpha), _ptr(exposure_dev),
+            ctypes.byref(icrf), _weight(gaussian_weight))
+    # (probe_one_launch would be the same here: ct_hdr_merge_dark_batches answers a walk without state arrays and one refused by
+    # MERGE_REQUIRE_ONE_LAUNCH alike, with CT_ERR_UNSUPPORTED)
+    return _launch_merge("ct_hdr_merge_dark_batches", dev, head, state, flags, k, mean_out, std_out, retry_with_state=True)
 
 
 MAX_LINEARIZE_DARK_FRAMES =nv.LINEARIZE_DARK_MAX_FRAMES  # frames one ct_linearize_dark launch takes (longer stacks: several)
@@ -1266,18 +1266,11 @@ def hdr_merge_ingest_batch(frames: torch.Tensor, stages, exposures: torch.Tensor
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _ingest_geometry(shape, tile, layout)
     # (state and outputs are planar whatever the order of the source)
-    flags, _, mean_out, std_out = _merge_setup_for((c, h, w), dev, "planar", state, finalize, std_mode != "none", mean_dtype,
-                                                   reference_order, 0, "batch")
-    with torch.cuda.device(dev):
-        rc = nv.load().ct_hdr_merge_ingest_batch(
-            _ptr(frames), _DTYPE[frames.dtype], b, ctypes.byref(geom), arr, n_stages, _ptr(consts), _ptr(std), _STD[std_mode],
-            float(std_value), _ptr(exposure_dev), ctypes.byref(icrf), nv.WEIGHT_GAUSS if gaussian_weight else nv.WEIGHT_NONE,
-            *_state_ptrs(state), _ptr(mean_out), _ptr(std_out), flags, _stream(dev))
-    nv.check(rc, "ct_hdr_merge_ingest_batch")
-    del lut_keep
-    if state is not None:
-        state.batches += 1
-    return (mean_out, std_out) if finalize else None
+    flags, mean_out, std_out = _merge_setup((c, h, w), dev, "planar", state, finalize, std_mode != "none", mean_dtype, reference_order,
+                                            0, "batch")
+    head = (_ptr(frames), _DTYPE[frames.dtype], b, ctypes.byref(geom), arr, n_stages, _ptr(consts), _ptr(std), _STD[std_mode],
+            float(std_value), _ptr(exposure_dev), ctypes.byref(icrf), _weight(gaussian_weight))
+    return _launch_merge("ct_hdr_merge_ingest_batch", dev, head, state, flags, 1, mean_out, std_out)
 
 
 def hdr_merge_ingest_batches(frames_list, stages, exposures_list, *, lut: Optional[torch.Tensor] = None,
@@ -1296,24 +1289,18 @@ def hdr_merge_ingest_batches(frames_list, stages, exposures_list, *, lut: Option
     ``require_one_launch`` (tests): raise instead of falling back to one launch per batch (batches with and without
     constants mixed; more exposure times than the LDS holds).  Everything else as in ``hdr_merge_ingest_batch``.
     Returns (mean, std|None), planar (C,H,W), when ``finalize`` else None."""
+    def check_stack(t):
+        _check_ingest_stack(t, layout, codes_only="hdr_merge_ingest_batches takes uint8 / uint16 codes (float32 pixels: "
+                                                  "ingest_transform + hdr_merge_batches)")
+
+    _check_batch_list(frames_list, (exposures_list, stds, consts), "frames / exposures / stds / consts", check_stack, one_batch_elsewhere=True)
     k = len(frames_list)
-    if k == 0 or k != len(exposures_list) or (stds is not None and len(stds) != k) or (consts is not None and len(consts) != k):
-        raise ValueError("frames / exposures / stds / consts must be non-empty lists of equal length")
-    if k > MAX_MERGE_BATCHES:
-        raise ValueError(f"at most {MAX_MERGE_BATCHES} batches per call")
     if k == 1:
         return hdr_merge_ingest_batch(frames_list[0], stages, exposures_list[0], lut=lut, interp=interp,
                                       gaussian_weight=gaussian_weight, std=None if stds is None else stds[0], std_mode=std_mode,
                                       std_value=std_value, state=state, finalize=finalize, tile=tile, mean_dtype=mean_dtype,
                                       layout=layout, reference_order=reference_order, consts=None if consts is None else consts[0])
     f0 = frames_list[0]
-    for t in frames_list:
-        _check_ingest_stack(t, layout, codes_only="hdr_merge_ingest_batches takes uint8 / uint16 codes (float32 pixels: "
-                                                  "ingest_transform + hdr_merge_batches)")
-        if t.dtype != f0.dtype or t.shape[1:] != f0.shape[1:] or t.device != f0.device:
-            raise ValueError("all batches of one call must share dtype, image shape and device")
-        if t.shape[0] < 1:
-            raise ValueError("empty batch")
     dev = f0.device
     shape0 = ingest_shape(tuple(f0.shape), layout)
     _, c, h, w = shape0
@@ -1332,32 +1319,13 @@ def hdr_merge_ingest_batches(frames_list, stages, exposures_list, *, lut: Option
     exposure_dev = _exposure_list_to_device(exposures_list, sizes, dev)
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _ingest_geometry(shape0, tile, layout)
-    has_std = std_mode != "none"
-    flags, out_shape, mean_out, std_out = _merge_setup_for((c, h, w), dev, "planar", state, finalize, has_std, mean_dtype, reference_order,
-                                                           nv.MERGE_REQUIRE_ONE_LAUNCH if require_one_launch else 0, "call")
-    ptr_arr = (ctypes.c_void_p * k)(*[t.data_ptr() for t in frames_list])
-    size_arr = (ctypes.c_int32 * k)(*sizes)
-    std_arr = (ctypes.c_void_p * k)(*[sd.data_ptr() for sd in stds]) if stds is not None else None
-    consts_arr = (ctypes.c_void_p * k)(*[None if t is None else t.data_ptr() for t in consts]) if consts is not None else None
-
-    def call(st, fl):
-        with torch.cuda.device(dev):
-            return nv.load().ct_hdr_merge_ingest_batches(
-                ptr_arr, size_arr, k, _DTYPE[f0.dtype], ctypes.byref(geom), arr, n_stages, consts_arr, std_arr, _STD[std_mode],
-                float(std_value), _ptr(exposure_dev), ctypes.byref(icrf), nv.WEIGHT_GAUSS if gaussian_weight else nv.WEIGHT_NONE,
-                *_state_ptrs(st), _ptr(mean_out), _ptr(std_out), fl, _stream(dev))
-
-    # a whole merge in one launch needs no state arrays at all; only what cannot run as one launch walks the batches with
-    # the state in memory (nothing has been launched when the library says so)
-    rc = call(state, flags | (nv.MERGE_REQUIRE_ONE_LAUNCH if state is None else 0))
-    if rc == nv.ERR_UNSUPPORTED and state is None and not require_one_launch:
-        state = MergeState(out_shape, dev, has_std)
-        rc = call(state, flags)
-    nv.check(rc, "ct_hdr_merge_ingest_batches")
-    del lut_keep
-    if state is not None:
-        state.batches += k
-    return (mean_out, std_out) if finalize else None
+    flags, mean_out, std_out = _merge_setup((c, h, w), dev, "planar", state, finalize, std_mode != "none", mean_dtype, reference_order,
+                                            nv.MERGE_REQUIRE_ONE_LAUNCH if require_one_launch else 0, "call")
+    head = (_pointers(frames_list), (ctypes.c_int32 * k)(*sizes), k, _DTYPE[f0.dtype], ctypes.byref(geom), arr, n_stages, _pointers(consts),
+            _pointers(stds), _STD[std_mode], float(std_value), _ptr(exposure_dev), ctypes.byref(icrf), _weight(gaussian_weight))
+    # (probe_one_launch: without it ct_hdr_merge_ingest_batches answers a walk without state arrays with CT_ERR_INVALID_ARGUMENT)
+    return _launch_merge("ct_hdr_merge_ingest_batches", dev, head, state, flags, k, mean_out, std_out, retry_with_state=True,
+                         probe_one_launch=True)
 
 
 # ---- such a chain, the dark-field blur and several batches of the HDR merge in one pass ---------------------------------------
@@ -1386,27 +1354,11 @@ def hdr_merge_dark_ingest_batches(frames_list, stages, exposures_list, darks, da
     one launch per batch (more exposure times than the LDS holds beside the LUT).  ``reference_order``, ``exposures_list``,
     ``lut``, ``interp``, ``gaussian_weight``, ``state``, ``finalize``, ``mean_dtype``, ``threshold``, ``alpha``: as in
     ``hdr_merge_dark_batches``.  Returns (mean, std|None), planar (C,H,W), when ``finalize`` else None."""
+    dark_stds, consts = _check_batch_list(frames_list, (exposures_list, darks, dark_stds, stds, halos, consts),
+                                          "frames / exposures / darks / dark_stds / stds / halos / consts",
+                                          lambda t: _check_ingest_stack(t, layout), all_or_none=[(2, "a dark std"), (5, "constants")])
     k = len(frames_list)
-    lists = (exposures_list, darks) + tuple(v for v in (dark_stds, stds, halos, consts) if v is not None)
-    if k == 0 or any(len(v) != k for v in lists):
-        raise ValueError("frames / exposures / darks / dark_stds / stds / halos / consts must be non-empty lists of equal length")
-    if k > MAX_MERGE_BATCHES:
-        raise ValueError(f"at most {MAX_MERGE_BATCHES} batches per call")
-    if dark_stds is not None and any(t is None for t in dark_stds):
-        if any(t is not None for t in dark_stds):
-            raise ValueError("a dark std for every batch of one call, or for none")
-        dark_stds = None
-    if consts is not None and any(t is None for t in consts):
-        if any(t is not None for t in consts):
-            raise ValueError("constants for every batch of one call, or for none")
-        consts = None
     f0 = frames_list[0]
-    for t in frames_list:
-        _check_ingest_stack(t, layout)
-        if t.dtype != f0.dtype or t.shape[1:] != f0.shape[1:] or t.device != f0.device:
-            raise ValueError("all batches of one call must share dtype, image shape and device")
-        if t.shape[0] < 1:
-            raise ValueError("empty batch")
     dev = f0.device
     shapes = [ingest_shape(tuple(t.shape), layout) for t in frames_list]
     _, c, h, w = shapes[0]
@@ -1424,49 +1376,22 @@ def hdr_merge_dark_ingest_batches(frames_list, stages, exposures_list, darks, da
     # the refusals the dark ops share, against the planar shape (of the stack only shape, dtype and device are read: a view
     # without memory stands for interleaved frames)
     planar = [t if layout == "nchw" else t.new_empty((1, 1, 1, 1)).expand(shape) for t, shape in zip(frames_list, shapes)]
-    checked = [_dark_arguments(t, darks[i], None if dark_stds is None else dark_stds[i], None if halos is None else halos[i])
-               for i, t in enumerate(planar)]
-    darks, dark_stds, halos = ([v[j] for v in checked] for j in range(3))
-    if any(t is None for t in halos) and any(t is not None for t in halos):
-        raise ValueError("halo rows for every batch of one call, or for none")
-    has_std = dark_stds[0] is not None
+    darks, dark_stds, halos = _dark_argument_lists(planar, darks, dark_stds, halos)
     sizes = [int(s[0]) for s in shapes]
-    exposure_dev = _exposure_list_on_device(exposures_list, sizes, dev)
+    exposure_dev = _exposure_list_to_device(exposures_list, sizes, dev)
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _ingest_geometry(shapes[0], tile, layout)
-    flags, out_shape, mean_out, std_out = _merge_setup_for((c, h, w), dev, "planar", state, finalize, has_std, mean_dtype, reference_order,
-                                                           nv.MERGE_REQUIRE_ONE_LAUNCH if require_one_launch else 0, "call")
-    if first is not None:
-        flags = (flags | nv.MERGE_FIRST_BATCH) if first else (flags & ~nv.MERGE_FIRST_BATCH)
-
-    def pointers(tensors):
-        return (ctypes.c_void_p * k)(*[None if t is None else t.data_ptr() for t in tensors])
-
-    frames_arr, dark_arr, dark_std_arr, halo_arr = pointers(frames_list), pointers(darks), pointers(dark_stds), pointers(halos)
-    std_arr = pointers(stds) if stds is not None else None
-    consts_arr = pointers(consts) if consts is not None else None
-    size_arr = (ctypes.c_int32 * k)(*sizes)
-    dark_size_arr = (ctypes.c_int32 * k)(*[int(t.shape[0]) for t in darks])
-
-    def call(st, fl):
-        with torch.cuda.device(dev):
-            return nv.load().ct_hdr_merge_dark_ingest_batches(
-                frames_arr, size_arr, k, _DTYPE[f0.dtype], ctypes.byref(geom), arr, n_stages, consts_arr, halo_arr, std_arr,
-                _STD[std_mode], float(std_value), dark_arr, dark_std_arr, dark_size_arr, float(threshold), float(alpha),
-                _ptr(exposure_dev), ctypes.byref(icrf), nv.WEIGHT_GAUSS if gaussian_weight else nv.WEIGHT_NONE, *_state_ptrs(st),
-                _ptr(mean_out), _ptr(std_out), fl, _stream(dev))
-
-    # a whole merge in one launch needs no state arrays at all; only what cannot run as one launch walks the batches with
-    # the state in memory (nothing has been launched when the library says so)
-    rc = call(state, flags)
-    if rc == nv.ERR_UNSUPPORTED and state is None and not require_one_launch and k > 1:
-        state = MergeState(out_shape, dev, has_std)
-        rc = call(state, flags)
-    nv.check(rc, "ct_hdr_merge_dark_ingest_batches")
-    del lut_keep
-    if state is not None:
-        state.batches += k
-    return (mean_out, std_out) if finalize else None
+    flags, mean_out, std_out = _merge_setup((c, h, w), dev, "planar", state, finalize, dark_stds[0] is not None, mean_dtype, reference_order,
+                                            nv.MERGE_REQUIRE_ONE_LAUNCH if require_one_launch else 0, "call", first)
+    head = (_pointers(frames_list), (ctypes.c_int32 * k)(*sizes), k, _DTYPE[f0.dtype], ctypes.byref(geom), arr, n_stages, _pointers(consts),
+            _pointers(halos), _pointers(stds), _STD[std_mode], float(std_value), _pointers(darks), _pointers(dark_stds),
+            (ctypes.c_int32 * k)(*[int(t.shape[0]) for t in darks]), float(threshold), float(alpha), _ptr(exposure_dev),
+            ctypes.byref(icrf), _weight(gaussian_weight))
+    # (probe_one_launch would differ here: with MERGE_REQUIRE_ONE_LAUNCH this entry point answers CT_ERR_TOO_LARGE.  retry_one_batch
+    # True would only cost a state and a second call: one batch always runs as one launch, so CT_ERR_UNSUPPORTED for it is a
+    # refusal of the route, which a state does not lift)
+    return _launch_merge("ct_hdr_merge_dark_ingest_batches", dev, head, state, flags, k, mean_out, std_out, retry_with_state=True,
+                         retry_one_batch=False)
 
 
 # ---- a data-dependent Normalize (max_val / min_val None) in such a chain ------------------------------------------------
@@ -1606,11 +1531,8 @@ def _same_batches(frames_list):
 
 def _batch_arrays(frames_list, consts=None):
     """The HOST arrays of a ``*_batches`` entry point: frame pointers, batch sizes, and the constants' pointers or None."""
-    k = len(frames_list)
-    ptr_arr = (ctypes.c_void_p * k)(*[t.data_ptr() for t in frames_list])
-    size_arr = (ctypes.c_int32 * k)(*[int(t.shape[0]) for t in frames_list])
-    consts_arr = None if consts is None else (ctypes.c_void_p * k)(*[None if t is None else t.data_ptr() for t in consts])
-    return ptr_arr, size_arr, consts_arr
+    size_arr = (ctypes.c_int32 * len(frames_list))(*[int(t.shape[0]) for t in frames_list])
+    return _pointers(frames_list), size_arr, _pointers(consts)
 
 
 def _video_stats(frames_list, mean_state, m2_state, frames_before, lut, interp, max_code, tile, layout, flags=None):

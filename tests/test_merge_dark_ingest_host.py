@@ -290,3 +290,160 @@ def test_compute_hdr_image_has_the_keyword():
     from clair_torch_amd.inference import compute_hdr_image, hdr_merge
     p = inspect.signature(compute_hdr_image).parameters
     assert p["fused_dark_ingest"].default is hdr_merge.FUSED_DARK_INGEST_DEFAULT and type(hdr_merge.FUSED_DARK_INGEST_DEFAULT) is bool
+
+
+# ---- the same routing with the keywords of every call, the MergeState and the halo exchange in one record ---------------------------
+# Recorded from compute_hdr_image before its four queues became one; the literals below are the contract.
+MERGE_OPS = {"hdr_merge_dark_ingest_batches": "dark_ingest", "hdr_merge_ingest_batches": "ingest", "hdr_merge_dark_batch": "dark",
+             "hdr_merge_dark_batches": "dark_batches", "hdr_merge_batches": "plain"}
+
+
+@pytest.fixture()
+def events(routed, monkeypatch):
+    """``routed`` with a second recorder around each replacement: -> run(n_frames, matched, **keywords) = the events in order,
+    ("state", shape, with_variance) for a MergeState made, ("halo", frames) for an exchange, ("ingest_transform" | "blur", frames),
+    and (op, batch sizes, which MergeState it got (0 = the first one made) | None, finalize, std_mode, tile, layout) for a merge.
+    ``matched``: the frames a dark field matches, None = no dark-field dataset at all."""
+    from clair_torch_amd import ops
+    from clair_torch_amd.common.enums import InterpMode, MissingStdMode
+    from clair_torch_amd.common.transforms import CastTo, Normalize
+    from clair_torch_amd.datasets import ArtefactStack, StackDataset, custom_collate
+    from clair_torch_amd.inference import dark_field, hdr_merge
+    from clair_torch_amd.models import ICRFModelDirect
+    from clair_torch_amd.training.losses import gaussian_value_weights
+    from torch.utils.data import DataLoader
+    log, states = [], []
+
+    def merge_op(name, inner):
+        def op(*args, **kw):
+            sizes = [int(args[0].shape[0])] if name == "dark" else [int(f.shape[0]) for f in args[0]]
+            tile = kw.get("tile")
+            log.append((name, sizes, None if kw["state"] is None else [id(s) for s in states].index(id(kw["state"])), kw["finalize"],
+                        kw["std_mode"], None if tile is None else (tile.h_global, tile.row_offset), kw.get("layout")))
+            return inner(*args, **kw)
+        return op
+
+    for attr, name in MERGE_OPS.items():
+        monkeypatch.setattr(ops, attr, merge_op(name, getattr(ops, attr)))
+    make_state = ops.MergeState
+
+    def merge_state(shape, dev, with_variance):
+        states.append(make_state(shape, dev, with_variance))
+        log.append(("state", tuple(shape), with_variance))
+        return states[-1]
+
+    monkeypatch.setattr(ops, "MergeState", merge_state)
+
+    def counted(name, inner):
+        def op(images, *args, **kw):
+            log.append((name, int(images.shape[0])))
+            return inner(images, *args, **kw)
+        return op
+
+    monkeypatch.setattr(ops, "ingest_transform", counted("ingest_transform", ops.ingest_transform))
+    monkeypatch.setattr(ops, "dark_field_blur", counted("blur", ops.dark_field_blur))
+    monkeypatch.setattr(dark_field, "exchange_halo", counted("halo", dark_field.exchange_halo))
+    flat = (torch.zeros((3, 4, 6), dtype=torch.float64), torch.zeros((3, 4, 6)))
+    monkeypatch.setattr(hdr_merge, "_flat_field_epilogue", lambda state, *a: flat)
+    art = ArtefactStack(torch.zeros((3, 4, 6)), torch.zeros((3, 4, 6)))
+    model = ICRFModelDirect(icrf=torch.stack([torch.linspace(0, 1, 16)] * 3), interpolation_mode=InterpMode.LINEAR)
+
+    def run(n_frames=12, matched=None, existing=None, **kw):
+        del log[:], states[:]
+        if existing is not None:            # one of the runs of the three tests above, through ``routed.run`` itself
+            routed.run(*existing, **kw)
+            return list(log)
+        ds = StackDataset(torch.zeros((n_frames, 3, 4, 6), dtype=torch.uint16), [0.001 * 2 ** (k % 12) for k in range(n_frames)],
+                          missing_std_mode=MissingStdMode.MULTIPLIER, missing_std_value=0.05, materialize_std=False)
+        if matched is not None:
+            kw["dark_field_dataset"] = _Some(art, [ds.files[i] for i in matched])
+        loader = DataLoader(ds, batch_size=2, shuffle=False, collate_fn=custom_collate)
+        hdr_merge.compute_hdr_image(loader, "cpu", model, weight_fn=gaussian_value_weights,
+                                    gpu_transforms=[CastTo("float32"), Normalize(65535, 64)], **kw)
+        return list(log)
+
+    return SimpleNamespace(run=run, flat=art)
+
+
+H, T, B, ST = ("halo", 2), ("ingest_transform", 2), ("blur", 2), ("state", (3, 4, 6), True)
+SOME = [2, 3, 4, 5, 10, 11]
+
+
+def _m(name, batches, state, finalize, tile=None, std_mode="multiplier"):
+    """The event of a merge op on ``batches`` batches of 2 frames; the dark ops on staged images take no layout."""
+    return (name, [2] * batches, state, finalize, std_mode, tile, None if name in ("dark", "dark_batches") else "nchw")
+
+
+def test_routing_without_a_dark_field_dataset(events):
+    run = events.run
+    assert run(fused_ingest=True) == [_m("ingest", 6, None, True)]
+    assert run(fused_ingest=False) == [T] * 6 + [_m("plain", 6, None, True)]
+    # 18 batches: MAX_MERGE_BATCHES per call, on a MergeState made before the first launch
+    assert run(36, fused_ingest=True) == [ST, _m("ingest", 16, 0, False), _m("ingest", 2, 0, True)]
+    assert run(36, fused_ingest=False) == [T] * 17 + [ST, _m("plain", 16, 0, False), T, _m("plain", 2, 0, True)]
+
+
+def test_routing_with_a_flat_field_dataset(events):
+    """No call finalizes, one MergeState is made before the first launch and every call gets it."""
+    run, flat = events.run, events.flat
+    assert run(fused_ingest=True, flat_field_dataset=flat) == [ST, _m("ingest", 6, 0, False)]
+    assert run(36, fused_ingest=False, flat_field_dataset=flat) == [T] * 17 + [ST, _m("plain", 16, 0, False), T, _m("plain", 2, 0, False)]
+    assert run(matched=range(12), fused_dark_ingest=True, dark_batches_per_launch=4, flat_field_dataset=flat) == \
+        [H] * 5 + [ST, _m("dark_ingest", 4, 0, False), H, _m("dark_ingest", 2, 0, False)]
+    assert run(matched=range(12), fused_dark_ingest=False, dark_batches_per_launch=4, flat_field_dataset=flat) == \
+        [T, H] * 5 + [ST, _m("dark_batches", 4, 0, False), T, H, _m("dark_batches", 2, 0, False)]
+    assert run(matched=SOME, fused_dark_ingest=False, flat_field_dataset=flat) == \
+        [T, T, ST, _m("plain", 1, 0, False), H, _m("dark", 1, 0, False), T, H, _m("dark", 1, 0, False), T, T, T,
+         _m("plain", 2, 0, False), H, _m("dark", 1, 0, False)]
+
+
+def test_routing_of_a_row_band(events):
+    """Planar frames: the halo rows of a queued batch are exchanged when it is queued, in loader order, before the launch that
+    consumes them; the single-batch dark path exchanges after the flush of what was queued before it."""
+    from clair_torch_amd import ops
+    run, band = events.run, (12, 4)
+    tile = ops.TileGeometry(h_global=12, row_offset=4)
+    assert run(matched=range(12), fused_dark_ingest=True, dark_batches_per_launch=4, tile=tile) == \
+        [H] * 5 + [ST, _m("dark_ingest", 4, 0, False, band), H, _m("dark_ingest", 2, 0, True, band)]
+    assert run(matched=range(12), fused_dark_ingest=False, dark_batches_per_launch=4, tile=tile) == \
+        [T, H] * 5 + [ST, _m("dark_batches", 4, 0, False, band), T, H, _m("dark_batches", 2, 0, True, band)]
+    assert run(matched=SOME, fused_dark_ingest=False, tile=tile) == \
+        [T, T, ST, _m("plain", 1, 0, False, band), H, _m("dark", 1, 0, False, band), T, H, _m("dark", 1, 0, False, band), T, T, T,
+         _m("plain", 2, 0, False, band), H, _m("dark", 1, 0, True, band)]
+    assert run(matched=SOME, fused_dark_ingest=True, dark_batches_per_launch=16, tile=tile) == \
+        [H, ST, _m("ingest", 1, 0, False, band), H, _m("dark_ingest", 2, 0, False, band), H, _m("ingest", 2, 0, False, band),
+         _m("dark_ingest", 1, 0, True, band)]
+
+
+def test_keywords_of_the_routed_calls(events):
+    """The runs of the three routing tests above, with state=, finalize=, std_mode=, tile= and layout= of every call."""
+    run = events.run
+    assert run(existing=(), fused_dark_ingest=True, dark_batches_per_launch=4) == \
+        [H] * 5 + [ST, _m("dark_ingest", 4, 0, False), H, _m("dark_ingest", 2, 0, True)]
+    assert run(existing=(), fused_dark_ingest=True, dark_batches_per_launch=1) == \
+        [H, H, ST, _m("dark_ingest", 1, 0, False)] + [H, _m("dark_ingest", 1, 0, False)] * 4 + [_m("dark_ingest", 1, 0, True)]
+    assert run(existing=(), fused_dark_ingest=True, dark_batches_per_launch=16) == [H] * 6 + [_m("dark_ingest", 6, None, True)]
+    assert run(existing=(SOME,), fused_dark_ingest=True, dark_batches_per_launch=16) == \
+        [H, ST, _m("ingest", 1, 0, False), H, _m("dark_ingest", 2, 0, False), H, _m("ingest", 2, 0, False), _m("dark_ingest", 1, 0, True)]
+    declined = [T, H, B] * 6 + [_m("plain", 6, None, True, std_mode="explicit")]
+    assert run(existing=(), fused_dark_ingest=True, reference_order=True) == declined
+    assert run(existing=(), fused_dark_ingest=False, reference_order=True) == declined
+    assert run(existing=(), fused_dark_ingest=True, fused_dark=False) == declined
+    assert run(existing=(), fused_dark_ingest=False) == \
+        [T, ST, H, _m("dark", 1, 0, False)] + [T, H, _m("dark", 1, 0, False)] * 4 + [T, H, _m("dark", 1, 0, True)]
+    assert run(existing=(), fused_dark_ingest=False, dark_batches_per_launch=3) == \
+        [T, H] * 4 + [ST, _m("dark_batches", 3, 0, False)] + [T, H] * 2 + [_m("dark_batches", 3, 0, True)]
+
+
+def test_keywords_under_the_byte_cap(events, routed, monkeypatch):
+    one = 2 * 3 * 4 * 6 * 2 + 2 * (2 * 3 * 4 * 6 * 4)      # as in test_routing_byte_cap
+    monkeypatch.setattr(routed.hdr_merge, "DARK_QUEUE_BYTES", 2 * one - 1)
+    assert events.run(existing=(), fused_dark_ingest=True, dark_batches_per_launch=16) == \
+        [H, H, ST, _m("dark_ingest", 1, 0, False)] + [H, _m("dark_ingest", 1, 0, False)] * 4 + [_m("dark_ingest", 1, 0, True)]
+    monkeypatch.setattr(routed.hdr_merge, "DARK_QUEUE_BYTES", 3 * one)
+    assert events.run(existing=(), fused_dark_ingest=True, dark_batches_per_launch=16) == \
+        [H] * 4 + [ST, _m("dark_ingest", 3, 0, False), H, H, _m("dark_ingest", 3, 0, True)]
+    # the staged-image queue counts the same bytes (float32 images: twice the frames' share)
+    monkeypatch.setattr(routed.hdr_merge, "DARK_QUEUE_BYTES", 3 * (one + 2 * 3 * 4 * 6 * 2))
+    assert events.run(existing=(), fused_dark_ingest=False, dark_batches_per_launch=16) == \
+        [T, H] * 4 + [ST, _m("dark_batches", 3, 0, False)] + [T, H] * 2 + [_m("dark_batches", 3, 0, True)]
