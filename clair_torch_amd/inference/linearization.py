@@ -129,31 +129,34 @@ def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRF
     first = next(items, None)
     if first is None:
         return
-    probe = first[1]
-    # explicit uncertainty images are planar; a StridedDownscale is ct_linearize_ingest_strided's to apply (step_in_kernel)
-    plan = plan_staging(probe, transforms, planar=first[2] is not None, step_in_kernel=True)
-    route = pipeline_route(probe, plan, dark is not None)
-    if dark is not None and fused_dark:
-        # the dark field's own decision, on the first frame planned as _frame_by_frame plans it (dark images are planar)
-        dark_plan = plan_staging(probe, transforms, planar=True)
-        if dark.fuses_with_linearize(probe, dark_plan, interp):
-            yield from _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, dark_plan, output_layout == "cv", dark)
-            return
-        # ... and, for what that declined, the chain's: route "ingest" keeps the raw frames in the slot (ct_linearize_dark_ingest)
-        if fused_dark_ingest and dark.fuses_with_linearize_ingest(probe, dark_plan, interp):
-            yield from _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, dark_plan, output_layout == "cv", dark)
-            return
-    if route != "pipelined":
-        # the second, separate decision: a data-dependent Normalize with per-frame constants.  The probe is a host tensor;
-        # the list is planned as stage_images plans it for the batch on the device (route "ingest_data" exists only there)
-        staged = plan_staging(probe, transforms, planar=first[2] is not None, on_device=dev.type == "cuda", step_in_kernel=True)
-        route = pipeline_data_route(probe, staged, dark is not None)
-        plan = staged if route == "pipelined" else plan
-    if route != "pipelined":
+    plan = _pipeline_plan(first[1], first[2] is not None, transforms, dev, interp, dark, fused_dark, fused_dark_ingest)
+    if plan is None:
         yield from _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat, flat_std, dark,
                                    output_layout == "cv")
-        return
-    yield from _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan, output_layout == "cv")
+    else:  # (a dark field only ever comes with the plan its own decisions accepted)
+        yield from _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan, output_layout == "cv", dark)
+
+
+def _pipeline_plan(probe, with_std, transforms, dev, interp, dark, fused_dark, fused_dark_ingest):
+    """The plan the streamed pipeline runs with for a run whose first value batch is ``probe`` (``with_std``: it comes with an
+    explicit uncertainty image), or None for the frame-by-frame route.  Every decision is asked here, each on the plan made
+    for it."""
+    # explicit uncertainty images are planar; a StridedDownscale is ct_linearize_ingest_strided's to apply (step_in_kernel)
+    plan = plan_staging(probe, transforms, planar=with_std, step_in_kernel=True)
+    route = pipeline_route(probe, plan, dark is not None)
+    if dark is not None and fused_dark:
+        # the dark field's own decision, on the first frame planned as _frame_by_frame plans it (dark images are planar) ... and,
+        # for what that declined, the chain's: route "ingest" keeps the raw frames in the slot (ct_linearize_dark_ingest)
+        dark_plan = plan_staging(probe, transforms, planar=True)
+        if dark.fuses_with_linearize(probe, dark_plan, interp) or (
+                fused_dark_ingest and dark.fuses_with_linearize_ingest(probe, dark_plan, interp)):
+            return dark_plan
+    if route == "pipelined":
+        return plan
+    # the second, separate decision: a data-dependent Normalize with per-frame constants.  The probe is a host tensor;
+    # the list is planned as stage_images plans it for the batch on the device (route "ingest_data" exists only there)
+    staged = plan_staging(probe, transforms, planar=with_std, on_device=dev.type == "cuda", step_in_kernel=True)
+    return staged if pipeline_data_route(probe, staged, dark is not None) == "pipelined" else None
 
 
 def pipeline_route(probe: torch.Tensor, plan, has_dark: bool) -> str:
@@ -324,21 +327,13 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
         if dark is not None:
             lin, lin_std = _linearize_dark_runs(slot, k, pairs, with_std, lut, interp, std_mode, std_value, max_code,
                                                 (stages, layout) if fused else None)
-        elif fused:
+        else:
             consts = None
             if data:  # two launches for the group's k sets of constants, into the slot's own buffers
                 consts = ops.ingest_extrema_frames(slot.frames[:k], plan.prefix, layout, plan.min_val, plan.max_val,
                                                    out=slot.consts[:k], workspace=slot.workspace)
-            args = dict(std=slot.std[:k] if with_std else None, std_mode=std_mode, std_value=std_value, want_std=True,
-                        layout=layout, out=(slot.lin_out[:k], slot.std_out[:k]), consts=consts)
-            if step > 1:
-                lin, lin_std = ops.linearize_ingest_frames_strided(slot.frames[:k], step, stages, lut, interp, **args)
-            else:
-                lin, lin_std = ops.linearize_ingest_frames(slot.frames[:k], stages, lut, interp, **args)
-        else:
-            lin, lin_std = ops.linearize_frames(slot.frames[:k], lut, interp, std=slot.std[:k] if with_std else None,
-                                                std_mode=std_mode, std_value=std_value, max_code=max_code, want_std=True,
-                                                layout=layout, out=(slot.lin_out[:k], slot.std_out[:k]))
+            lin, lin_std = _linearize_run(slot, 0, k, with_std, lut, interp, std_mode, std_value, max_code,
+                                          stages if fused else None, layout, step, consts)
         if flat is not None:  # linearization.py:118-130
             ops.flatfield_correct(lin, lin_std, flat, flat_std, input_is_variance=False, through_mean=False)
         if cv:
@@ -362,29 +357,48 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
         raise pending
 
 
+def _linearize_run(slot, a, b, with_std, lut, interp, std_mode, std_value, max_code, stages=None, layout="nchw", step=1,
+                   consts=None, pairs=None):
+    """Frames [a:b] of ``slot`` into the same range of its output buffers, in ONE launch of the kernel they belong to.
+    ``stages``: the chain of a plan whose slot holds the RAW frames in ``layout`` (explicit uncertainties planar), None for
+    frames ct_linearize_std reads as they are; ``step``: a StridedDownscale the kernel applies; ``consts``: the per-frame
+    constants of a data-dependent Normalize; ``pairs``: the device (dark, dark std) matched to each frame of the run, None for a
+    run without dark fields.
+
+        pairs   stages  step    front
+        None    None    1       linearize_frames                 (ct_linearize_std)
+        None    given   1       linearize_ingest_frames          (ct_linearize_ingest / _data with ``consts``)
+        None    given   > 1     linearize_ingest_frames_strided  (ct_linearize_ingest_strided)
+        given   None    1       linearize_dark_frames            (ct_linearize_dark)
+        given   given   1       linearize_dark_ingest_frames     (ct_linearize_dark_ingest)"""
+    frames = slot.frames[a:b]
+    args = dict(std=slot.std[a:b] if with_std else None, std_mode=std_mode, std_value=std_value,
+                out=(slot.lin_out[a:b], slot.std_out[a:b]))
+    if pairs is not None:
+        darks, dark_stds = [p[0] for p in pairs], [p[1] for p in pairs]
+        if stages is None:
+            return ops.linearize_dark_frames(frames, darks, dark_stds, lut, interp, max_code=max_code, **args)
+        return ops.linearize_dark_ingest_frames(frames, stages, darks, dark_stds, lut, interp, layout=layout, **args)
+    args.update(want_std=True, layout=layout)
+    if stages is None:
+        return ops.linearize_frames(frames, lut, interp, max_code=max_code, **args)
+    if step > 1:
+        return ops.linearize_ingest_frames_strided(frames, step, stages, lut, interp, consts=consts, **args)
+    return ops.linearize_ingest_frames(frames, stages, lut, interp, consts=consts, **args)
+
+
 def _linearize_dark_runs(slot, k, pairs, with_std, lut, interp, std_mode, std_value, max_code, chain=None):
     """The first ``k`` frames of ``slot`` into its output buffers, cut into maximal runs of frames with a matched dark
-    field (``pairs[i]``: its device (dark, dark std); one ct_linearize_dark launch on that range of the raw frames) and
-    without one (None: MissingValMode.SKIP_BATCH leaves the frame uncorrected; one ct_linearize_std launch).  ``chain`` =
-    (stages, layout) of a route "ingest" plan: the slot holds the raw frames in that layout (explicit uncertainties planar),
-    matched runs go to ct_linearize_dark_ingest and unmatched ones to ct_linearize_ingest."""
+    field (``pairs[i]``: its device (dark, dark std)) and without one (None: MissingValMode.SKIP_BATCH leaves the frame
+    uncorrected), one ``_linearize_run`` each.  ``chain`` = (stages, layout) of a route "ingest" plan: the slot holds the raw
+    frames in that layout."""
+    stages, layout = chain if chain is not None else (None, "nchw")
     a = 0
     while a < k:
         b = a + 1
         while b < k and (pairs[b] is None) == (pairs[a] is None):
             b += 1
-        args = dict(std=slot.std[a:b] if with_std else None, std_mode=std_mode, std_value=std_value, max_code=max_code,
-                    out=(slot.lin_out[a:b], slot.std_out[a:b]))
-        if chain is not None:
-            del args["max_code"]
-            if pairs[a] is None:
-                ops.linearize_ingest_frames(slot.frames[a:b], chain[0], lut, interp, want_std=True, layout=chain[1], **args)
-            else:
-                ops.linearize_dark_ingest_frames(slot.frames[a:b], chain[0], [p[0] for p in pairs[a:b]], [p[1] for p in pairs[a:b]],
-                                                 lut, interp, layout=chain[1], **args)
-        elif pairs[a] is None:
-            ops.linearize_frames(slot.frames[a:b], lut, interp, want_std=True, **args)
-        else:
-            ops.linearize_dark_frames(slot.frames[a:b], [p[0] for p in pairs[a:b]], [p[1] for p in pairs[a:b]], lut, interp, **args)
+        _linearize_run(slot, a, b, with_std, lut, interp, std_mode, std_value, max_code, stages, layout,
+                       pairs=None if pairs[a] is None else pairs[a:b])
         a = b
     return slot.lin_out[:k], slot.std_out[:k]

@@ -194,7 +194,31 @@ def _checked_out(out, shape, dtype, device, dtype_name=None):
     return out
 
 
+def _call(entry, dev, *args):
+    """The tail of every front beside the HDR merge: the library's ``entry``(*args, stream) on ``dev``, its status checked."""
+    with torch.cuda.device(dev):
+        rc = getattr(nv.load(), entry)(*args, _stream(dev))
+    nv.check(rc, entry)
+
+
+def _std_arguments(std, std_mode, normalise, refuse_unknown: bool = True):
+    """(std, std_mode) of a front that takes explicit uncertainties: a given ``std`` means mode "explicit" and goes through
+    ``normalise`` (``_explicit_std`` / ``_planar_std`` with the front's own wording).  ``refuse_unknown`` False is what
+    linearize_frames, dark_field_blur and the two plain pair fronts have always done: they leave an unknown mode to the lookup
+    in ``_STD`` (KeyError), where every other front raises ValueError here.  Callers may rely on either, so the difference is
+    kept, not unified (tests/test_fronts_host.py, tests/test_ops_refusals_host.py)."""
+    if std is not None:
+        std_mode, std = "explicit", normalise(std)
+    if refuse_unknown and std_mode not in _STD:
+        raise ValueError(f"unknown std_mode {std_mode}")
+    return std, std_mode
+
+
 def _icrf_struct(lut: Optional[torch.Tensor], interp, channels):
+    """(the ct_icrf of ``lut``, the float32 table it points to).  The table is a local of the calling front and so lives until
+    that front returns, behind the call that reads it.  The rule for every pointer a front hands to ``_call``: a tensor the
+    front or one of its helpers made (a contiguous or float32 copy above all) stays in a local of a frame that is still
+    running when the call is made -- a helper that builds the arguments returns such tensors with them."""
     if lut is None:
         return nv.Icrf(lut_dev=None, n_points=0, interp=nv.INTERP_NONE), None
     _require_device(lut, "lut")
@@ -389,11 +413,8 @@ def hdr_merge_batches(stacks, exposures, *, lut: Optional[torch.Tensor] = None, 
                                reference_order=reference_order, out_layout=out_layout)
     dev = stacks[0].device
     c, h, w = _chw(stacks[0], layout)
-    if stds is not None:
-        std_mode = "explicit"
-        stds = [_explicit_std(sd.to(dev), t, shapes=True) for sd, t in zip(stds, stacks)]
-    if std_mode not in _STD:
-        raise ValueError(f"unknown std_mode {std_mode}")
+    stds, std_mode = _std_arguments(stds, std_mode,
+                                    lambda sds: [_explicit_std(sd.to(dev), t, shapes=True) for sd, t in zip(sds, stacks)])
     stacks = [t.contiguous() for t in stacks]
     max_code = _default_max_code(stacks[0], max_code)
     sizes = [int(t.shape[0]) for t in stacks]
@@ -425,19 +446,14 @@ def linearize_frames(frames: torch.Tensor, lut: torch.Tensor, interp: str = "lin
     f = frames.shape[0]
     c, h, w = _chw(frames, layout)
     dev = frames.device
-    if std is not None:
-        std_mode, std = "explicit", _explicit_std(std, frames, "frames")
+    std, std_mode = _std_arguments(std, std_mode, lambda sd: _explicit_std(sd, frames, "frames"), refuse_unknown=False)
     max_code = _default_max_code(frames, max_code)
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     frames = frames.contiguous()
     geom = _geometry(frames, tile, layout)
     lin, std_out = _lin_std_out(out, (f, c, h, w), dev, want_std, lin_required=False)
-    with torch.cuda.device(dev):
-        rc = nv.load().ct_linearize_std(_ptr(frames), _DTYPE[frames.dtype], float(max_code or 1.0), f, ctypes.byref(geom),
-                                        _ptr(std), _STD[std_mode], float(std_value), ctypes.byref(icrf), _ptr(lin),
-                                        _ptr(std_out), _stream(dev))
-    nv.check(rc, "ct_linearize_std")
-    del lut_keep
+    _call("ct_linearize_std", dev, _ptr(frames), _DTYPE[frames.dtype], float(max_code or 1.0), f, ctypes.byref(geom), _ptr(std),
+          _STD[std_mode], float(std_value), ctypes.byref(icrf), _ptr(lin), _ptr(std_out))
     return lin, std_out
 
 
@@ -450,11 +466,7 @@ def icrf_forward(x: torch.Tensor, lut: torch.Tensor, interp: str, tile: Optional
     icrf, lut_keep = _icrf_struct(lut, interp, x.shape[1])
     geom = _geometry(x, tile)
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        rc = nv.load().ct_linearize_fwd(_ptr(x), x.shape[0], ctypes.byref(geom), ctypes.byref(icrf), _ptr(out),
-                                        _stream(x.device))
-    nv.check(rc, "ct_linearize_fwd")
-    del lut_keep
+    _call("ct_linearize_fwd", x.device, _ptr(x), x.shape[0], ctypes.byref(geom), ctypes.byref(icrf), _ptr(out))
     return out
 
 
@@ -468,11 +480,8 @@ def icrf_backward(x: torch.Tensor, grad_out: torch.Tensor, lut: torch.Tensor, in
     geom = _geometry(x, tile)
     gx = torch.empty_like(x) if need_x else None
     gl = torch.zeros((x.shape[1], lut.shape[1]), dtype=torch.float32, device=x.device) if need_lut else None
-    with torch.cuda.device(x.device):
-        rc = nv.load().ct_linearize_bwd(_ptr(x), _ptr(grad_out), x.shape[0], ctypes.byref(geom), ctypes.byref(icrf),
-                                        _ptr(gx), _ptr(gl), _stream(x.device))
-    nv.check(rc, "ct_linearize_bwd")
-    del lut_keep
+    _call("ct_linearize_bwd", x.device, _ptr(x), _ptr(grad_out), x.shape[0], ctypes.byref(geom), ctypes.byref(icrf), _ptr(gx),
+          _ptr(gl))
     return gx, gl
 
 
@@ -481,6 +490,40 @@ def _pair_params(lower, upper, use_relative, use_unc_weight, std_mode, std_value
     return nv.PairParams(lower=float(lower), upper=float(upper), weight_scale=float(weight_scale),
                          use_relative=int(bool(use_relative)), use_uncertainty_weighting=int(bool(use_unc_weight)),
                          std_mode=_STD[std_mode], std_value=float(std_value), pair_band=int(pair_band))
+
+
+def _pair_sums(entry, dev, head, pairs, channels, prm, level, center):
+    """The forward half of the four pair fronts: ``entry``(*head, pair list, parameters, level, center, sums) -> the (P, C, 5)
+    float64 sums; ``head``: the entry point's arguments up to the ICRF.  Without pairs nothing is launched."""
+    sums = torch.zeros((pairs.n_pairs, channels, 5), dtype=torch.float64, device=dev)
+    if center is not None:
+        center = center.to(device=dev, dtype=torch.float64).contiguous()
+        if center.shape != (pairs.n_pairs, channels):
+            raise ValueError(f"center must be (P={pairs.n_pairs}, C={channels})")
+    if pairs.n_pairs:
+        _call(entry, dev, *head, _ptr(pairs.i), _ptr(pairs.j), _ptr(pairs.ratio), pairs.n_pairs, ctypes.byref(prm), int(level),
+              _ptr(center), _ptr(sums))
+    return sums
+
+
+def _pair_lut_grad(entry, dev, head, pairs, channels, prm, weighted, coef, smean, n_points):
+    """The backward half: ``entry``(*head, partner lists, parameters, coef, smean, grad, workspace) -> the (C, L) float64 LUT
+    gradient; ``weighted``: the uncertainties weigh the pairs, which needs the forward's spatial means ``smean``."""
+    if weighted:
+        if smean is None:
+            raise ValueError("the uncertainty-weighted backward needs the forward's spatial means")
+        smean = smean.to(device=dev, dtype=torch.float64).contiguous()
+    else:
+        smean = None
+    coef = coef.to(device=dev, dtype=torch.float64).contiguous()
+    if coef.shape != (pairs.n_pairs, channels):
+        raise ValueError(f"coef must be (P={pairs.n_pairs}, C={channels}), got {tuple(coef.shape)}")
+    grad = torch.zeros((channels, n_points), dtype=torch.float64, device=dev)
+    if pairs.n_pairs:
+        ws = pairs.workspace(channels)
+        _call(entry, dev, *head, _ptr(pairs.ratio), pairs.n_pairs, _ptr(pairs.part_off), _ptr(pairs.part_sample),
+              _ptr(pairs.part_pair), ctypes.byref(prm), _ptr(coef), _ptr(smean), _ptr(grad), _ptr(ws), ws.numel())
+    return grad
 
 
 class PairList:
@@ -535,27 +578,15 @@ def pair_residual_sums(stack: torch.Tensor, pairs: PairList, *, lut: Optional[to
     dev = stack.device
     if n != pairs.n_images:
         raise ValueError(f"pair list was built for {pairs.n_images} images, stack has {n}")
+    std, std_mode = _std_arguments(std, std_mode, lambda sd: _explicit_std(sd, stack), refuse_unknown=False)
     if std is not None:
-        std_mode, std = "explicit", _explicit_std(std, stack)
         stack = stack.contiguous()
     max_code = _default_max_code(stack, max_code)
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _geometry(stack, tile, layout)
     prm = _pair_params(lower, upper, use_relative, use_unc_weight, std_mode, std_value)
-    sums = torch.zeros((pairs.n_pairs, c, 5), dtype=torch.float64, device=dev)
-    if center is not None:
-        center = center.to(device=dev, dtype=torch.float64).contiguous()
-        if center.shape != (pairs.n_pairs, c):
-            raise ValueError(f"center must be (P={pairs.n_pairs}, C={c})")
-    if pairs.n_pairs:
-        with torch.cuda.device(dev):
-            rc = nv.load().ct_pair_residual_fwd(_ptr(stack), _DTYPE[stack.dtype], float(max_code or 1.0), n,
-                                                ctypes.byref(geom), _ptr(std), ctypes.byref(icrf), _ptr(pairs.i),
-                                                _ptr(pairs.j), _ptr(pairs.ratio), pairs.n_pairs, ctypes.byref(prm),
-                                                int(level), _ptr(center), _ptr(sums), _stream(dev))
-        nv.check(rc, "ct_pair_residual_fwd")
-    del lut_keep
-    return sums
+    head = (_ptr(stack), _DTYPE[stack.dtype], float(max_code or 1.0), n, ctypes.byref(geom), _ptr(std), ctypes.byref(icrf))
+    return _pair_sums("ct_pair_residual_fwd", dev, head, pairs, c, prm, level, center)
 
 
 def pair_residual_lut_grad(stack: torch.Tensor, pairs: PairList, coef: torch.Tensor, *, lut: torch.Tensor, interp: str,
@@ -571,8 +602,9 @@ def pair_residual_lut_grad(stack: torch.Tensor, pairs: PairList, coef: torch.Ten
     n = stack.shape[0]
     c, _, _ = _chw(stack, layout)
     dev = stack.device
+    # (the kernel reads explicit uncertainties at the stack's indices: same shape)
+    std, std_mode = _std_arguments(std, std_mode, lambda sd: _explicit_std(sd, stack), refuse_unknown=False)
     if std is not None:
-        std_mode, std = "explicit", _explicit_std(std, stack)  # the kernel reads it at the stack's indices: same shape
         stack = stack.contiguous()
     if not use_unc_weight:
         std, std_mode = None, "none"
@@ -581,27 +613,8 @@ def pair_residual_lut_grad(stack: torch.Tensor, pairs: PairList, coef: torch.Ten
     geom = _geometry(stack, tile, layout)
     prm = _pair_params(lower, upper, use_relative, use_unc_weight, std_mode, std_value,
                        pair_band=pairs.band if lane_kernel else 0)
-    if std_mode != "none":
-        if smean is None:
-            raise ValueError("the uncertainty-weighted backward needs the forward's spatial means")
-        smean = smean.to(device=dev, dtype=torch.float64).contiguous()
-    else:
-        smean = None
-    coef = coef.to(device=dev, dtype=torch.float64).contiguous()
-    if coef.shape != (pairs.n_pairs, c):
-        raise ValueError(f"coef must be (P={pairs.n_pairs}, C={c}), got {tuple(coef.shape)}")
-    grad = torch.zeros((c, lut.shape[1]), dtype=torch.float64, device=dev)
-    if pairs.n_pairs:
-        ws = pairs.workspace(c)
-        with torch.cuda.device(dev):
-            rc = nv.load().ct_pair_residual_bwd(_ptr(stack), _DTYPE[stack.dtype], float(max_code or 1.0), n,
-                                                ctypes.byref(geom), _ptr(std), ctypes.byref(icrf), _ptr(pairs.ratio),
-                                                pairs.n_pairs, _ptr(pairs.part_off), _ptr(pairs.part_sample),
-                                                _ptr(pairs.part_pair), ctypes.byref(prm), _ptr(coef), _ptr(smean),
-                                                _ptr(grad), _ptr(ws), ws.numel(), _stream(dev))
-        nv.check(rc, "ct_pair_residual_bwd")
-    del lut_keep
-    return grad
+    head = (_ptr(stack), _DTYPE[stack.dtype], float(max_code or 1.0), n, ctypes.byref(geom), _ptr(std), ctypes.byref(icrf))
+    return _pair_lut_grad("ct_pair_residual_bwd", dev, head, pairs, c, prm, std_mode != "none", coef, smean, lut.shape[1])
 
 
 # ---- per-band statistics (BASELINE configuration C5) -------------------------------------------------------------
@@ -619,13 +632,10 @@ def band_stats(mean: torch.Tensor, std: Optional[torch.Tensor] = None) -> torch.
         if std.dtype != torch.float32 or std.shape != mean.shape:
             raise ValueError("std must be float32 with the mean's shape")
         std = std.contiguous()
-    lib = nv.load()
-    ws_bytes = int(lib.ct_band_stats_workspace(c))
+    ws_bytes = int(nv.load().ct_band_stats_workspace(c))
     ws = torch.empty((ws_bytes // 8,), dtype=torch.float64, device=mean.device)
     out = torch.empty((6, c), dtype=torch.float64, device=mean.device)
-    with torch.cuda.device(mean.device):
-        rc = lib.ct_band_stats(_ptr(mean), _ptr(std), c, plane, _ptr(ws), ws_bytes, _ptr(out), _stream(mean.device))
-    nv.check(rc, "ct_band_stats")
+    _call("ct_band_stats", mean.device, _ptr(mean), _ptr(std), c, plane, _ptr(ws), ws_bytes, _ptr(out))
     return out
 
 
@@ -661,19 +671,14 @@ def flatfield_correct(value: torch.Tensor, var_or_std: Optional[torch.Tensor], f
             flat_std = flat_std[0]
     dev = value.device
     sums = torch.zeros((c, 2), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        rc = nv.load().ct_flatfield_sums(_ptr(value) if through_mean else None, int(is_f64), _ptr(flat),
-                                         c, plane, _ptr(sums), _stream(dev))
-    nv.check(rc, "ct_flatfield_sums")
+    _call("ct_flatfield_sums", dev, _ptr(value) if through_mean else None, int(is_f64), _ptr(flat), c, plane, _ptr(sums))
     if reduce is not None:
         reduce(sums)
     n_px = float(global_pixels if global_pixels is not None else plane)
     flat_mean = (sums[:, 0] / n_px).to(torch.float32).contiguous()
     through = (sums[:, 1] / n_px).contiguous() if through_mean else None
-    with torch.cuda.device(dev):
-        rc = nv.load().ct_flatfield_apply(_ptr(value), int(is_f64), frames, _ptr(var_or_std), int(input_is_variance),
-                                          _ptr(flat), _ptr(flat_std), _ptr(flat_mean), _ptr(through), c, plane, _stream(dev))
-    nv.check(rc, "ct_flatfield_apply")
+    _call("ct_flatfield_apply", dev, _ptr(value), int(is_f64), frames, _ptr(var_or_std), int(input_is_variance), _ptr(flat),
+          _ptr(flat_std), _ptr(flat_mean), _ptr(through), c, plane)
     return value, var_or_std
 
 
@@ -711,20 +716,16 @@ def dark_field_blur(stack: torch.Tensor, dark: torch.Tensor, dark_std: Optional[
     _check_stack(stack)
     b, c, h, w = stack.shape
     dev = stack.device
-    if std is not None:
-        std_mode, std = "explicit", _explicit_std(std, stack)
+    std, std_mode = _std_arguments(std, std_mode, lambda sd: _explicit_std(sd, stack), refuse_unknown=False)
     stack = stack.contiguous()
     max_code = _default_max_code(stack, max_code)
     dark, dark_std, halo = _dark_arguments(stack, dark, dark_std, halo)
     geom = _geometry(stack, tile)
     xb = torch.empty((b, c, h, w), dtype=torch.float32, device=dev)
     sig = torch.empty_like(xb) if dark_std is not None else None
-    with torch.cuda.device(dev):
-        rc = nv.load().ct_dark_field_blur(_ptr(stack), _DTYPE[stack.dtype], float(max_code or 1.0), b, ctypes.byref(geom),
-                                          _ptr(halo), _ptr(std), _STD[std_mode], float(std_value), _ptr(dark),
-                                          _ptr(dark_std), dark.shape[0], float(threshold), float(alpha), _ptr(xb), _ptr(sig),
-                                          _stream(dev))
-    nv.check(rc, "ct_dark_field_blur")
+    _call("ct_dark_field_blur", dev, _ptr(stack), _DTYPE[stack.dtype], float(max_code or 1.0), b, ctypes.byref(geom), _ptr(halo),
+          _ptr(std), _STD[std_mode], float(std_value), _ptr(dark), _ptr(dark_std), dark.shape[0], float(threshold), float(alpha),
+          _ptr(xb), _ptr(sig))
     return xb, sig
 
 
@@ -752,10 +753,7 @@ def hdr_merge_dark_batch(stack: torch.Tensor, exposures: torch.Tensor, dark: tor
     dev = stack.device
     if b < 1:
         raise ValueError("empty batch")
-    if std is not None:
-        std_mode, std = "explicit", _explicit_std(std, stack)
-    if std_mode not in _STD:
-        raise ValueError(f"unknown std_mode {std_mode}")
+    std, std_mode = _std_arguments(std, std_mode, lambda sd: _explicit_std(sd, stack))
     stack = stack.contiguous()
     max_code = _default_max_code(stack, max_code)
     dark, dark_std, halo = _dark_arguments(stack, dark, dark_std, halo)
@@ -811,11 +809,7 @@ def hdr_merge_dark_batches(stacks, exposures, darks, dark_stds, *, stds=None, st
     s0 = stacks[0]
     _, c, h, w = s0.shape
     dev = s0.device
-    if stds is not None:
-        std_mode = "explicit"
-        stds = [_explicit_std(sd, t) for sd, t in zip(stds, stacks)]
-    if std_mode not in _STD:
-        raise ValueError(f"unknown std_mode {std_mode}")
+    stds, std_mode = _std_arguments(stds, std_mode, lambda sds: [_explicit_std(sd, t) for sd, t in zip(sds, stacks)])
     stacks = [t.contiguous() for t in stacks]
     max_code = _default_max_code(s0, max_code)
     darks, dark_stds, halos = _dark_argument_lists(stacks, darks, dark_stds, halos)
@@ -866,6 +860,19 @@ def _dark_per_frame(frames, darks, dark_stds):
     return out
 
 
+def _linearize_dark(entry, planar, head, geom, middle, darks, dark_stds, threshold, alpha, lut, interp, out):
+    """What linearize_dark_frames and linearize_dark_ingest_frames share behind their own checks: the per-frame dark fields, the
+    ICRF, the (lin, std) outputs and ``entry``(*head, geometry, *middle, dark pointers, threshold, alpha, ICRF, outputs).
+    ``planar``: the frames, or a view without memory that has their planar shape (F,C,H,W) and device."""
+    shape, dev = tuple(planar.shape), planar.device
+    dark_list, dark_std_list = _dark_per_frame(planar, darks, dark_stds)
+    icrf, lut_keep = _icrf_struct(lut, interp, shape[1])
+    lin, std_out = _lin_std_out(out, shape, dev, True, lin_required=True)
+    _call(entry, dev, *head, ctypes.byref(geom), *middle, _pointers(dark_list), _pointers(dark_std_list), float(threshold),
+          float(alpha), ctypes.byref(icrf), _ptr(lin), _ptr(std_out))
+    return lin, std_out
+
+
 def linearize_dark_frames(frames: torch.Tensor, darks, dark_stds, lut: Optional[torch.Tensor], interp: Optional[str] = "linear", *,
                           std: Optional[torch.Tensor] = None, std_mode: str = "none", std_value: float = 0.0,
                           max_code: Optional[float] = None, threshold: float = 0.05, alpha: float = 50.0, out=None):
@@ -882,30 +889,17 @@ def linearize_dark_frames(frames: torch.Tensor, darks, dark_stds, lut: Optional[
     with uncertainties)."""
     _check_stack(frames, "frames")
     f, c, h, w = frames.shape
-    dev = frames.device
     if f < 1:
         raise ValueError("no frames")
-    if std is not None:
-        # (explicit uncertainties are dense: so are the frames then, the kernel strides both alike)
-        std_mode, std, frames = "explicit", _explicit_std(std, frames, "frames"), frames.contiguous()
-    if std_mode not in _STD:
-        raise ValueError(f"unknown std_mode {std_mode}")
+    std, std_mode = _std_arguments(std, std_mode, lambda sd: _explicit_std(sd, frames, "frames"))
+    if std is not None:  # (explicit uncertainties are dense: so are the frames then, the kernel strides both alike)
+        frames = frames.contiguous()
     max_code = _default_max_code(frames, max_code)
-    dark_list, dark_std_list = _dark_per_frame(frames, darks, dark_stds)
-    icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _geometry(frames, None)
     if f == 1:  # (the stride of a single frame means nothing)
         geom.image_stride = c * h * w
-    lin, std_out = _lin_std_out(out, (f, c, h, w), dev, True, lin_required=True)
-    dark_arr = (ctypes.c_void_p * f)(*[t.data_ptr() for t in dark_list])
-    dark_std_arr = (ctypes.c_void_p * f)(*[t.data_ptr() for t in dark_std_list])
-    with torch.cuda.device(dev):
-        rc = nv.load().ct_linearize_dark(_ptr(frames), _DTYPE[frames.dtype], float(max_code or 1.0), f, ctypes.byref(geom), _ptr(std),
-                                         _STD[std_mode], float(std_value), dark_arr, dark_std_arr, float(threshold), float(alpha),
-                                         ctypes.byref(icrf), _ptr(lin), _ptr(std_out), _stream(dev))
-    nv.check(rc, "ct_linearize_dark")
-    del lut_keep, dark_list, dark_std_list
-    return lin, std_out
+    return _linearize_dark("ct_linearize_dark", frames, (_ptr(frames), _DTYPE[frames.dtype], float(max_code or 1.0), f), geom,
+                           (_ptr(std), _STD[std_mode], float(std_value)), darks, dark_stds, threshold, alpha, lut, interp, out)
 
 
 # ---- strided downscale of raw codes (StridedDownscale folded in front of the code-domain kernels) -----------------
@@ -941,10 +935,7 @@ def strided_downscale(stack: torch.Tensor, step: int, layout: str = "nchw", out:
         planes, h, w, pixel_elems = stack.shape[0] * stack.shape[1], stack.shape[2], stack.shape[3], 1
     else:
         planes, h, w, pixel_elems = stack.shape[0], stack.shape[1], stack.shape[2], stack.shape[3]
-    with torch.cuda.device(stack.device):
-        rc = nv.load().ct_strided_downscale(_ptr(stack), _ptr(out), stack.element_size(), planes, h, w, pixel_elems, step,
-                                            _stream(stack.device))
-    nv.check(rc, "ct_strided_downscale")
+    _call("ct_strided_downscale", stack.device, _ptr(stack), _ptr(out), stack.element_size(), planes, h, w, pixel_elems, step)
     return out
 
 
@@ -987,10 +978,8 @@ def export_cv(x: torch.Tensor, dtype: Optional[torch.dtype] = None, out: Optiona
     else:
         channels, plane = x.shape[-3], x.shape[-2] * x.shape[-1]
         images = x.shape[0] if x.ndim == 4 else 1
-    with torch.cuda.device(x.device):
-        rc = nv.load().ct_export_cv(_ptr(x), int(x.dtype == torch.float64), _ptr(out), int(dtype == torch.float64), images,
-                                    channels, plane, int(channels == 3), _stream(x.device))
-    nv.check(rc, "ct_export_cv")
+    _call("ct_export_cv", x.device, _ptr(x), int(x.dtype == torch.float64), _ptr(out), int(dtype == torch.float64), images,
+          channels, plane, int(channels == 3))
     return out
 
 
@@ -1101,15 +1090,11 @@ def ingest_transform(stack: torch.Tensor, stages, layout: str = "nchw", out: Opt
     out = _checked_out(out, shape, torch.float32, stack.device, "float32")
     if out.numel() == 0:
         return out
-    with torch.cuda.device(stack.device):
-        if consts is None:
-            rc = nv.load().ct_ingest_transform(_ptr(stack), _DTYPE[stack.dtype], _LAYOUT[layout], shape[0], shape[1],
-                                               shape[2] * shape[3], arr, n_stages, _ptr(out), _stream(stack.device))
-        else:
-            rc = nv.load().ct_ingest_transform_data(_ptr(stack), _DTYPE[stack.dtype], _LAYOUT[layout], shape[0], shape[1],
-                                                    shape[2] * shape[3], arr, n_stages, _ptr(out), _ptr(consts),
-                                                    _stream(stack.device))
-    nv.check(rc, "ct_ingest_transform" if consts is None else "ct_ingest_transform_data")
+    args = (_ptr(stack), _DTYPE[stack.dtype], _LAYOUT[layout], shape[0], shape[1], shape[2] * shape[3], arr, n_stages, _ptr(out))
+    if consts is None:
+        _call("ct_ingest_transform", stack.device, *args)
+    else:
+        _call("ct_ingest_transform_data", stack.device, *args, _ptr(consts))
     return out
 
 
@@ -1126,10 +1111,7 @@ def _linearize_ingest(strided, frames, step, stages, lut, interp, std, std_mode,
     arr, n_stages = _ingest_stages(stages, c, data=consts is not None)
     if consts is not None:
         _check_frame_consts(consts, f, dev)
-    if std is not None:
-        std_mode, std = "explicit", _planar_std(std, shape, dev, "outputs")
-    if std_mode not in _STD:
-        raise ValueError(f"unknown std_mode {std_mode}")
+    std, std_mode = _std_arguments(std, std_mode, lambda sd: _planar_std(sd, shape, dev, "outputs"))
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _ingest_geometry(src_shape, tile, layout)
     lin, std_out = _lin_std_out(out, shape, dev, want_std, lin_required=True)
@@ -1137,16 +1119,12 @@ def _linearize_ingest(strided, frames, step, stages, lut, interp, std, std_mode,
         return lin, std_out
     head = (_ptr(frames), _DTYPE[frames.dtype], f, ctypes.byref(geom))
     tail = (arr, n_stages, _ptr(std), _STD[std_mode], float(std_value), ctypes.byref(icrf), _ptr(lin), _ptr(std_out))
-    with torch.cuda.device(dev):
-        if strided:
-            name, rc = "ct_linearize_ingest_strided", nv.load().ct_linearize_ingest_strided(*head, min(step, 0x7fffffff), *tail,
-                                                                                           _ptr(consts), _stream(dev))
-        elif consts is None:
-            name, rc = "ct_linearize_ingest", nv.load().ct_linearize_ingest(*head, *tail, _stream(dev))
-        else:
-            name, rc = "ct_linearize_ingest_data", nv.load().ct_linearize_ingest_data(*head, *tail, _ptr(consts), _stream(dev))
-    nv.check(rc, name)
-    del lut_keep
+    if strided:
+        _call("ct_linearize_ingest_strided", dev, *head, min(step, 0x7fffffff), *tail, _ptr(consts))
+    elif consts is None:
+        _call("ct_linearize_ingest", dev, *head, *tail)
+    else:
+        _call("ct_linearize_ingest_data", dev, *head, *tail, _ptr(consts))
     return lin, std_out
 
 
@@ -1204,30 +1182,17 @@ def linearize_dark_ingest_frames(frames: torch.Tensor, stages, darks, dark_stds,
     uncertainties)."""
     _check_ingest_stack(frames, layout)
     shape = ingest_shape(tuple(frames.shape), layout)
-    f, c, h, w = shape
+    f, c = shape[:2]
     dev = frames.device
     if f < 1:
         raise ValueError("no frames")
     arr, n_stages = _ingest_stages(stages, c)
-    if std is not None:
-        std_mode, std = "explicit", _planar_std(std, shape, dev, "outputs")
-    if std_mode not in _STD:
-        raise ValueError(f"unknown std_mode {std_mode}")
+    std, std_mode = _std_arguments(std, std_mode, lambda sd: _planar_std(sd, shape, dev, "outputs"))
     # the dark fields are checked against the planar shape (of the stack only shape and device are read: a view without memory)
     planar = frames if layout == "nchw" else frames.new_empty((1, 1, 1, 1)).expand(shape)
-    dark_list, dark_std_list = _dark_per_frame(planar, darks, dark_stds)
-    icrf, lut_keep = _icrf_struct(lut, interp, c)
-    geom = _ingest_geometry(shape, None, layout)
-    lin, std_out = _lin_std_out(out, shape, dev, True, lin_required=True)
-    dark_arr = (ctypes.c_void_p * f)(*[t.data_ptr() for t in dark_list])
-    dark_std_arr = (ctypes.c_void_p * f)(*[t.data_ptr() for t in dark_std_list])
-    with torch.cuda.device(dev):
-        rc = nv.load().ct_linearize_dark_ingest(_ptr(frames), _DTYPE[frames.dtype], f, ctypes.byref(geom), arr, n_stages, _ptr(std),
-                                                _STD[std_mode], float(std_value), dark_arr, dark_std_arr, float(threshold),
-                                                float(alpha), ctypes.byref(icrf), _ptr(lin), _ptr(std_out), _stream(dev))
-    nv.check(rc, "ct_linearize_dark_ingest")
-    del lut_keep, dark_list, dark_std_list
-    return lin, std_out
+    return _linearize_dark("ct_linearize_dark_ingest", planar, (_ptr(frames), _DTYPE[frames.dtype], f),
+                           _ingest_geometry(shape, None, layout), (arr, n_stages, _ptr(std), _STD[std_mode], float(std_value)),
+                           darks, dark_stds, threshold, alpha, lut, interp, out)
 
 
 # ---- such a chain and one batch of the HDR merge in one pass ---------------------------------------------------------------
@@ -1258,10 +1223,7 @@ def hdr_merge_ingest_batch(frames: torch.Tensor, stages, exposures: torch.Tensor
     arr, n_stages = _ingest_stages(stages, c, data=consts is not None)
     if consts is not None:
         _check_consts(consts, dev)
-    if std is not None:
-        std_mode, std = "explicit", _planar_std(std, shape, dev, "state")
-    if std_mode not in _STD:
-        raise ValueError(f"unknown std_mode {std_mode}")
+    std, std_mode = _std_arguments(std, std_mode, lambda sd: _planar_std(sd, shape, dev, "state"))
     exposure_dev = _exposures_to_device(exposures, b, dev)
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _ingest_geometry(shape, tile, layout)
@@ -1310,11 +1272,8 @@ def hdr_merge_ingest_batches(frames_list, stages, exposures_list, *, lut: Option
         for t in consts:
             if t is not None:
                 _check_consts(t, dev)
-    if stds is not None:
-        std_mode = "explicit"
-        stds = [_planar_std(sd, ingest_shape(tuple(t.shape), layout), dev, "state") for sd, t in zip(stds, frames_list)]
-    if std_mode not in _STD:
-        raise ValueError(f"unknown std_mode {std_mode}")
+    stds, std_mode = _std_arguments(stds, std_mode, lambda sds: [_planar_std(sd, ingest_shape(tuple(t.shape), layout), dev, "state")
+                                                                 for sd, t in zip(sds, frames_list)])
     sizes = [int(t.shape[0]) for t in frames_list]
     exposure_dev = _exposure_list_to_device(exposures_list, sizes, dev)
     icrf, lut_keep = _icrf_struct(lut, interp, c)
@@ -1368,11 +1327,8 @@ def hdr_merge_dark_ingest_batches(frames_list, stages, exposures_list, darks, da
     if consts is not None:
         for t in consts:
             _check_consts(t, dev)
-    if stds is not None:
-        std_mode = "explicit"
-        stds = [_planar_std(sd, shape, dev, "state") for sd, shape in zip(stds, shapes)]
-    if std_mode not in _STD:
-        raise ValueError(f"unknown std_mode {std_mode}")
+    stds, std_mode = _std_arguments(stds, std_mode,
+                                    lambda sds: [_planar_std(sd, shape, dev, "state") for sd, shape in zip(sds, shapes)])
     # the refusals the dark ops share, against the planar shape (of the stack only shape, dtype and device are read: a view
     # without memory stands for interleaved frames)
     planar = [t if layout == "nchw" else t.new_empty((1, 1, 1, 1)).expand(shape) for t, shape in zip(frames_list, shapes)]
@@ -1400,7 +1356,7 @@ ZERO_RANGE = "Normalization range is zero (min == max); cannot normalize."  # ge
 
 def _extrema_call(front, stack, prefix_stages, layout, min_val, max_val):
     """What ``ingest_extrema`` and ``ingest_extrema_frames`` (``front``: which of them, for the message) check and build
-    alike: the planar shape and the arguments of the entry points from ``prefix`` to ``fixed_max``."""
+    alike: the planar shape and the arguments of the entry points up to ``fixed_max``."""
     _check_ingest_stack(stack, layout)
     if min_val is not None and max_val is not None:
         raise ValueError("min_val and max_val are both given: nothing depends on the data (use ingest_transform)")
@@ -1411,7 +1367,8 @@ def _extrema_call(front, stack, prefix_stages, layout, min_val, max_val):
     fixed_max = 0.0 if max_val is None else _number(max_val, "max_val")
     if stack.numel() == 0:
         raise RuntimeError(f"{front}: the stack is empty (the extrema of an empty tensor are undefined)")
-    return shape, (arr, n_prefix, from_data, fixed_min, fixed_max)
+    return shape, (_ptr(stack), _DTYPE[stack.dtype], _LAYOUT[layout], shape[0], shape[1], shape[2] * shape[3], arr, n_prefix,
+                   from_data, fixed_min, fixed_max)
 
 
 def ingest_extrema(stack: torch.Tensor, prefix_stages=(), layout: str = "nchw", min_val=None, max_val=None):
@@ -1422,15 +1379,11 @@ def ingest_extrema(stack: torch.Tensor, prefix_stages=(), layout: str = "nchw", 
     one must be None), a number fixes it: sub = min, div = fl32(max - min) in float32, as torch forms them.  One
     streaming pass plus a fold, no synchronisation: ``div == 0``, where the reference raises, is for the caller to
     check (``ingest_transform_data``).  An empty stack raises, as torch's ``x.min()`` does."""
-    shape, args = _extrema_call("ingest_extrema", stack, prefix_stages, layout, min_val, max_val)
-    lib = nv.load()
-    ws_bytes = int(lib.ct_ingest_extrema_workspace())
+    _, args = _extrema_call("ingest_extrema", stack, prefix_stages, layout, min_val, max_val)
+    ws_bytes = int(nv.load().ct_ingest_extrema_workspace())
     ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=stack.device)
     consts = torch.empty((4,), dtype=torch.float32, device=stack.device)
-    with torch.cuda.device(stack.device):
-        rc = lib.ct_ingest_extrema(_ptr(stack), _DTYPE[stack.dtype], _LAYOUT[layout], shape[0], shape[1], shape[2] * shape[3],
-                                   *args, _ptr(ws), ws_bytes, _ptr(consts), _stream(stack.device))
-    nv.check(rc, "ct_ingest_extrema")
+    _call("ct_ingest_extrema", stack.device, *args, _ptr(ws), ws_bytes, _ptr(consts))
     return consts
 
 
@@ -1454,8 +1407,7 @@ def ingest_extrema_frames(frames: torch.Tensor, prefix_stages=(), layout: str = 
     without them both are allocated here.  An empty stack raises, as torch's ``x.min()`` does."""
     shape, args = _extrema_call("ingest_extrema_frames", frames, prefix_stages, layout, min_val, max_val)
     dev = frames.device
-    lib = nv.load()
-    ws_bytes = int(lib.ct_ingest_extrema_frames_workspace(shape[0]))
+    ws_bytes = int(nv.load().ct_ingest_extrema_frames_workspace(shape[0]))
     if ws_bytes == 0:
         raise ValueError(f"ingest_extrema_frames: {shape[0]} frames are more than one call takes (65535)")
     if workspace is None:
@@ -1469,11 +1421,7 @@ def ingest_extrema_frames(frames: torch.Tensor, prefix_stages=(), layout: str = 
         out = torch.empty((shape[0], 4), dtype=torch.float32, device=dev)
     else:
         _check_frame_consts(out, shape[0], dev)
-    with torch.cuda.device(dev):
-        rc = lib.ct_ingest_extrema_frames(_ptr(frames), _DTYPE[frames.dtype], _LAYOUT[layout], shape[0], shape[1],
-                                          shape[2] * shape[3], *args, _ptr(workspace), workspace.numel() * 4, _ptr(out),
-                                          _stream(dev))
-    nv.check(rc, "ct_ingest_extrema_frames")
+    _call("ct_ingest_extrema_frames", dev, *args, _ptr(workspace), workspace.numel() * 4, _ptr(out))
     return out
 
 
@@ -1548,20 +1496,14 @@ def _video_stats(frames_list, mean_state, m2_state, frames_before, lut, interp, 
     _check_stats_state(mean_state, m2_state, (c, h, w))
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _geometry(frames_list[0], tile, layout)
-    lib = nv.load()
-    with torch.cuda.device(dev):
-        if flags is None:
-            rc = lib.ct_video_stats_batch(_ptr(frames_list[0]), _DTYPE[f0.dtype], float(max_code or 1.0), f0.shape[0],
-                                          ctypes.byref(geom), ctypes.byref(icrf), float(frames_before),
-                                          _ptr(mean_state), _ptr(m2_state), _stream(dev))
-        else:
-            geom.image_stride = c * h * w  # contiguous batches: one stride for all (that of a 1-frame batch is arbitrary)
-            ptr_arr, size_arr, _ = _batch_arrays(frames_list)
-            rc = lib.ct_video_stats_batches(ptr_arr, size_arr, len(frames_list), _DTYPE[f0.dtype], float(max_code or 1.0),
-                                            ctypes.byref(geom), ctypes.byref(icrf), float(frames_before), _ptr(mean_state),
-                                            _ptr(m2_state), flags, _stream(dev))
-    nv.check(rc, "ct_video_stats_batch" if flags is None else "ct_video_stats_batches")
-    del lut_keep
+    tail = (ctypes.byref(geom), ctypes.byref(icrf), float(frames_before), _ptr(mean_state), _ptr(m2_state))
+    if flags is None:
+        _call("ct_video_stats_batch", dev, _ptr(frames_list[0]), _DTYPE[f0.dtype], float(max_code or 1.0), f0.shape[0], *tail)
+    else:
+        geom.image_stride = c * h * w  # contiguous batches: one stride for all (that of a 1-frame batch is arbitrary)
+        ptr_arr, size_arr, _ = _batch_arrays(frames_list)
+        _call("ct_video_stats_batches", dev, ptr_arr, size_arr, len(frames_list), _DTYPE[f0.dtype], float(max_code or 1.0), *tail,
+              flags)
 
 
 def video_stats_batch(frames: torch.Tensor, mean_state: torch.Tensor, m2_state: torch.Tensor, frames_before: int, *,
@@ -1608,19 +1550,14 @@ def _video_stats_ingest(front, frames_list, stages, mean_state, m2_state, frames
     _check_stats_state(mean_state, m2_state, (c, h, w), dev)
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _ingest_geometry(shape, tile, layout)
-    lib = nv.load()
-    with torch.cuda.device(dev):
-        if flags is None:
-            rc = lib.ct_video_stats_ingest_batch(_ptr(f0), _DTYPE[f0.dtype], shape[0], ctypes.byref(geom), arr, n_stages,
-                                                 _ptr(consts[0]) if consts is not None else None, ctypes.byref(icrf),
-                                                 float(frames_before), _ptr(mean_state), _ptr(m2_state), _stream(dev))
-        else:
-            ptr_arr, size_arr, consts_arr = _batch_arrays(frames_list, consts)
-            rc = lib.ct_video_stats_ingest_batches(ptr_arr, size_arr, len(frames_list), _DTYPE[f0.dtype], ctypes.byref(geom), arr,
-                                                   n_stages, consts_arr, ctypes.byref(icrf), float(frames_before),
-                                                   _ptr(mean_state), _ptr(m2_state), flags, _stream(dev))
-    nv.check(rc, "ct_video_stats_ingest_batch" if flags is None else "ct_video_stats_ingest_batches")
-    del lut_keep
+    tail = (ctypes.byref(icrf), float(frames_before), _ptr(mean_state), _ptr(m2_state))
+    if flags is None:
+        _call("ct_video_stats_ingest_batch", dev, _ptr(f0), _DTYPE[f0.dtype], shape[0], ctypes.byref(geom), arr, n_stages,
+              _ptr(consts[0]) if consts is not None else None, *tail)
+    else:
+        ptr_arr, size_arr, consts_arr = _batch_arrays(frames_list, consts)
+        _call("ct_video_stats_ingest_batches", dev, ptr_arr, size_arr, len(frames_list), _DTYPE[f0.dtype], ctypes.byref(geom), arr,
+              n_stages, consts_arr, *tail, flags)
 
 
 def video_stats_ingest_batch(frames: torch.Tensor, stages, mean_state: torch.Tensor, m2_state: torch.Tensor, frames_before: int, *,
@@ -1663,7 +1600,9 @@ _PAIR_INGEST_CODES = ("pair_residual_ingest takes uint8 / uint16 codes (float32 
 
 
 def _pair_ingest_setup(frames, stages, pairs, consts, layout, std, std_mode, lut, interp, tile):
-    """What the two pair ingest fronts share: the checks of ``video_stats_ingest_batch`` and the structs of the call."""
+    """What the two pair ingest fronts share: the checks of ``video_stats_ingest_batch`` -> (channels, std_mode, the entry
+    points' arguments up to the ICRF, the tensors made here that those arguments point to).  The front keeps that last tuple
+    in a local until it returns: the std as the kernel reads it may be a copy (``_planar_std``), like the ICRF's table."""
     _check_ingest_stack(frames, layout, codes_only=_PAIR_INGEST_CODES)
     shape = ingest_shape(tuple(frames.shape), layout)
     n, c = shape[0], shape[1]
@@ -1673,12 +1612,11 @@ def _pair_ingest_setup(frames, stages, pairs, consts, layout, std, std_mode, lut
     arr, n_stages = _ingest_stages(stages, c, data=consts is not None)
     if consts is not None:
         _check_consts(consts, dev)
-    if std is not None:
-        std_mode, std = "explicit", _planar_std(std, shape, dev, "ingested stack")
-    if std_mode not in _STD:
-        raise ValueError(f"unknown std_mode {std_mode}")
+    std, std_mode = _std_arguments(std, std_mode, lambda sd: _planar_std(sd, shape, dev, "ingested stack"))
     icrf, lut_keep = _icrf_struct(lut, interp, c)
-    return shape, arr, n_stages, std, std_mode, icrf, lut_keep, _ingest_geometry(shape, tile, layout)
+    geom = _ingest_geometry(shape, tile, layout)
+    head = (_ptr(frames), _DTYPE[frames.dtype], arr, n_stages, _ptr(consts), n, ctypes.byref(geom), _ptr(std), ctypes.byref(icrf))
+    return c, std_mode, head, (std, lut_keep)
 
 
 def pair_residual_ingest_sums(frames: torch.Tensor, stages, pairs: PairList, *, lut: Optional[torch.Tensor], interp: Optional[str],
@@ -1694,25 +1632,9 @@ def pair_residual_ingest_sums(frames: torch.Tensor, stages, pairs: PairList, *, 
     order of the source: a folded CvToTorch).  ``stages``: as ``ingest_transform`` takes them; with ``consts`` (the tensor
     ``ingest_extrema`` returned) one of them may be ("affine_data", mul, add).  ``std``: explicit uncertainties, float32 and
     PLANAR (N,C,H,W) whatever the layout of the frames.  Everything else as in ``pair_residual_sums``."""
-    shape, arr, n_stages, std, std_mode, icrf, lut_keep, geom = _pair_ingest_setup(frames, stages, pairs, consts, layout, std,
-                                                                                  std_mode, lut, interp, tile)
-    n, c = shape[0], shape[1]
-    dev = frames.device
+    c, std_mode, head, keep = _pair_ingest_setup(frames, stages, pairs, consts, layout, std, std_mode, lut, interp, tile)
     prm = _pair_params(lower, upper, use_relative, use_unc_weight, std_mode, std_value)
-    sums = torch.zeros((pairs.n_pairs, c, 5), dtype=torch.float64, device=dev)
-    if center is not None:
-        center = center.to(device=dev, dtype=torch.float64).contiguous()
-        if center.shape != (pairs.n_pairs, c):
-            raise ValueError(f"center must be (P={pairs.n_pairs}, C={c})")
-    if pairs.n_pairs:
-        with torch.cuda.device(dev):
-            rc = nv.load().ct_pair_residual_ingest_fwd(_ptr(frames), _DTYPE[frames.dtype], arr, n_stages, _ptr(consts), n,
-                                                       ctypes.byref(geom), _ptr(std), ctypes.byref(icrf), _ptr(pairs.i),
-                                                       _ptr(pairs.j), _ptr(pairs.ratio), pairs.n_pairs, ctypes.byref(prm),
-                                                       int(level), _ptr(center), _ptr(sums), _stream(dev))
-        nv.check(rc, "ct_pair_residual_ingest_fwd")
-    del lut_keep
-    return sums
+    return _pair_sums("ct_pair_residual_ingest_fwd", frames.device, head, pairs, c, prm, level, center)
 
 
 def pair_residual_ingest_lut_grad(frames: torch.Tensor, stages, pairs: PairList, coef: torch.Tensor, *, lut: torch.Tensor,
@@ -1726,30 +1648,8 @@ def pair_residual_ingest_lut_grad(frames: torch.Tensor, stages, pairs: PairList,
     ``consts`` and ``std`` as in ``pair_residual_ingest_sums``, everything else as in ``pair_residual_lut_grad``."""
     if not use_unc_weight:
         std, std_mode = None, "none"
-    shape, arr, n_stages, std, std_mode, icrf, lut_keep, geom = _pair_ingest_setup(frames, stages, pairs, consts, layout, std,
-                                                                                  std_mode, lut, interp, tile)
-    n, c = shape[0], shape[1]
-    dev = frames.device
+    c, std_mode, head, keep = _pair_ingest_setup(frames, stages, pairs, consts, layout, std, std_mode, lut, interp, tile)
     prm = _pair_params(lower, upper, use_relative, use_unc_weight, std_mode, std_value,
                        pair_band=pairs.band if lane_kernel else 0)
-    if std_mode != "none":
-        if smean is None:
-            raise ValueError("the uncertainty-weighted backward needs the forward's spatial means")
-        smean = smean.to(device=dev, dtype=torch.float64).contiguous()
-    else:
-        smean = None
-    coef = coef.to(device=dev, dtype=torch.float64).contiguous()
-    if coef.shape != (pairs.n_pairs, c):
-        raise ValueError(f"coef must be (P={pairs.n_pairs}, C={c}), got {tuple(coef.shape)}")
-    grad = torch.zeros((c, lut.shape[1]), dtype=torch.float64, device=dev)
-    if pairs.n_pairs:
-        ws = pairs.workspace(c)
-        with torch.cuda.device(dev):
-            rc = nv.load().ct_pair_residual_ingest_bwd(_ptr(frames), _DTYPE[frames.dtype], arr, n_stages, _ptr(consts), n,
-                                                       ctypes.byref(geom), _ptr(std), ctypes.byref(icrf), _ptr(pairs.ratio),
-                                                       pairs.n_pairs, _ptr(pairs.part_off), _ptr(pairs.part_sample),
-                                                       _ptr(pairs.part_pair), ctypes.byref(prm), _ptr(coef), _ptr(smean),
-                                                       _ptr(grad), _ptr(ws), ws.numel(), _stream(dev))
-        nv.check(rc, "ct_pair_residual_ingest_bwd")
-    del lut_keep
-    return grad
+    return _pair_lut_grad("ct_pair_residual_ingest_bwd", frames.device, head, pairs, c, prm, std_mode != "none", coef, smean,
+                          lut.shape[1])
