@@ -784,14 +784,12 @@ extern "C" int ct_hdr_merge_batches(const void *const *stack_devs, const float *
     }
     if (flags & CT_MERGE_REQUIRE_ONE_LAUNCH) return CT_ERR_UNSUPPORTED;  // (tests: make the route explicit)
     if (n_batches > 1 && !c.has_state()) return CT_ERR_INVALID_ARGUMENT;
-    const bool first = flags & CT_MERGE_FIRST_BATCH, finalize = flags & CT_MERGE_FINALIZE;
     int64_t n0 = 0;
     for (int b = 0; b < n_batches; ++b) {
-        const uint32_t f = (flags & ~(CT_MERGE_FIRST_BATCH | CT_MERGE_FINALIZE)) | ((first && b == 0) ? CT_MERGE_FIRST_BATCH : 0u) |
-                           ((finalize && b == n_batches - 1) ? CT_MERGE_FINALIZE : 0u);
         const int rc = ct_hdr_merge_batch(stack_devs[b], dtype, max_code, batch_sizes[b], geom, std_devs ? std_devs[b] : nullptr,
                                           std_mode, std_value, exposure_dev + n0, icrf, weight_mode, mean_state_dev,
-                                          sumw_state_dev, var_state_dev, mean_out_dev, std_out_dev, f, stream);
+                                          sumw_state_dev, var_state_dev, mean_out_dev, std_out_dev,
+                                          merge_batch_flags(flags, b == 0, b == n_batches - 1), stream);
         if (rc != CT_OK) return rc;
         n0 += batch_sizes[b];
     }

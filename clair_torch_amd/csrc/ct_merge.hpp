@@ -1,4 +1,6 @@
-// ct_merge.hpp -- argument block and packet type shared by the merge kernels (ct_merge.hip, ct_merge_exact.hip).
+// ct_merge.hpp -- argument block and packet type shared by the merge kernels (ct_merge.hip, ct_merge_exact.hip) and, host side,
+// what every merge entry point shares: the mode dispatch (with_merge_modes) and the FIRST_BATCH / FINALIZE split of a batch
+// list that is walked one launch per batch (merge_batch_flags).
 #pragma once
 #include "ct_args.hpp"
 
@@ -33,6 +35,31 @@ struct MergeArgs {
         return (flags & CT_MERGE_OUT_AS_INPUT) ? m : tile.planar_index(m);
     }
 };
+
+// ---- host ----------------------------------------------------------------------------------------------------------------
+// f(INTERP, WEIGHT, STD) with the three run-time modes of a merge as compile-time constants; CT_ERR_INVALID_ARGUMENT for a
+// value that is none.  STDS: the uncertainty modes the kernel family is built for, all four where none are given (the
+// dark-field families see sigma_eff or nothing: <CT_STD_NONE, CT_STD_EXPLICIT>).
+template <int... STDS, typename F>
+static int with_merge_modes(int interp, int weight_mode, int std_mode, F &&f)
+{
+    return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
+        return with_enum<CT_WEIGHT_NONE, CT_WEIGHT_GAUSS>(weight_mode, [&](auto W) {
+            if constexpr (sizeof...(STDS) == 0)
+                return with_enum<CT_STD_NONE, CT_STD_CONSTANT, CT_STD_MULTIPLIER, CT_STD_EXPLICIT>(std_mode, [&](auto S) { return f(I, W, S); });
+            else
+                return with_enum<STDS...>(std_mode, [&](auto S) { return f(I, W, S); });
+        });
+    });
+}
+
+// The flags of one batch of a list that is walked one launch per batch: FIRST_BATCH is the first one's and FINALIZE the last
+// one's, where the call has them; CT_MERGE_REQUIRE_ONE_LAUNCH is the list's matter.
+static inline uint32_t merge_batch_flags(uint32_t flags, bool is_first, bool is_last)
+{
+    const uint32_t own = (is_first ? CT_MERGE_FIRST_BATCH : 0u) | (is_last ? CT_MERGE_FINALIZE : 0u);
+    return (flags & ~(CT_MERGE_FIRST_BATCH | CT_MERGE_FINALIZE | CT_MERGE_REQUIRE_ONE_LAUNCH)) | (flags & own);
+}
 
 constexpr float kPivotCondLimit = 8.0f;  // sum |terms| / result above which a wavefront repeats the batch about the mean
 

@@ -16,7 +16,6 @@
 // multiple of 4 goes through the same code one element after the other.  State and outputs move as packets where the
 // group is aligned in memory (mi_store), else element by element.  No atomics, no LDS tile, the frames are read only.
 // Row bands: the rows above / below the band come from `halo` exactly as dark_blur_kernel takes them.
-#include <algorithm>
 #include "ct_merge_dark_kernel.hpp"
 
 namespace ct {
@@ -42,7 +41,7 @@ __global__ __launch_bounds__(kBlock) void merge_dark_kernel(const MergeDarkArgs 
     __syncthreads();
 
     const uint32_t W = (uint32_t)a.width;
-    const uint32_t gpr = md_groups_per_row(W);
+    const uint32_t gpr = groups_per_row<kMdGroup>(W);
     const uint64_t slot = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (slot >= (uint64_t)gpr * (uint32_t)a.h_tile) return;
     const uint32_t h = (uint32_t)(slot / gpr);
@@ -58,30 +57,16 @@ __global__ __launch_bounds__(kBlock) void merge_dark_kernel(const MergeDarkArgs 
     for (uint32_t w = w0; w < W; ++w) md_run<T, 1, INTERP, WEIGHT, STD, false>(a, nullptr, lds, inv_t, cq, c0, h, w);
 }
 
-template <typename T, int INTERP, int WEIGHT, int STD>
-static int md_launch(const MergeDarkArgs &a, hipStream_t s)
+// the launch of one batch, dispatched on dtype / interpolation / weight / dark std (has_std: CT_STD_EXPLICIT, else none)
+static int merge_dark_single(const MergeDarkArgs &a, int dtype, int interp, int weight_mode, bool has_std, hipStream_t s)
 {
-    if constexpr (INTERP == CT_INTERP_LOOKUP && WEIGHT == CT_WEIGHT_NONE && STD != CT_STD_NONE) {
-        return CT_ERR_NO_GRADIENT_PATH;  // (refused by the entry point before it gets here)
-    } else {
-        const size_t lds = mi_lds_bytes(INTERP, a.channels, a.n_points, a.batch);
-        hipLaunchKernelGGL((merge_dark_kernel<T, INTERP, WEIGHT, STD>), md_grid(a), dim3(kBlock), lds, s, a);
-        return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
-    }
-}
-
-template <typename T>
-static int md_dispatch(const MergeDarkArgs &a, int interp, int weight_mode, bool has_std, hipStream_t s)
-{
-    return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
-        return with_enum<CT_WEIGHT_NONE, CT_WEIGHT_GAUSS>(weight_mode, [&](auto W) {
-            return has_std ? md_launch<T, I, W, CT_STD_EXPLICIT>(a, s) : md_launch<T, I, W, CT_STD_NONE>(a, s);
+    return with_pixel_dtype(dtype, [&](auto t) {
+        return with_dark_merge_modes(interp, weight_mode, has_std, [&](auto I, auto W, auto S) {
+            return merge_fused_launch(merge_dark_kernel<decltype(t), I, W, S>, md_grid<kMdGroup>(a, (uint32_t)a.channels), I, a.channels, a.n_points,
+                                      a.batch, s, a);
         });
     });
 }
-
-// (MergeDarkCall, md_validate and md_fill_args -- what the entry points below and ct_hdr_merge_dark_ingest_batches check and fill
-//  alike -- are host code of ct_merge_dark_kernel.hpp)
 
 }  // namespace ct
 
@@ -106,12 +91,7 @@ extern "C" int ct_hdr_merge_dark_batch(const void *stack_dev, int32_t dtype, flo
     a.dark = dark_dev;
     a.dark_std = dark_std_dev;
     a.dark_stride = dark_batch == 1 ? 0 : (int64_t)a.plane * geom->channels;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case CT_DTYPE_U8: return md_dispatch<uint8_t>(a, icrf->interp, weight_mode, has_std, s);
-        case CT_DTYPE_U16: return md_dispatch<uint16_t>(a, icrf->interp, weight_mode, has_std, s);
-        default: return md_dispatch<float>(a, icrf->interp, weight_mode, has_std, s);
-    }
+    return merge_dark_single(a, dtype, icrf->interp, weight_mode, has_std, static_cast<hipStream_t>(stream));
 }
 
 // Several consecutive dark-field batches of one merge: ONE launch of the MULTI kernels (ct_merge_dark_multi.hip) where the
@@ -126,64 +106,48 @@ extern "C" int ct_hdr_merge_dark_batches(const void *const *stack_devs, const in
                                          void *mean_out_dev, float *std_out_dev, uint32_t flags, void *stream)
 {
     using namespace ct;
-    if (n_batches < 1 || n_batches > kMaxDarkBatches || !stack_devs || !batch_sizes || !dark_devs || !dark_batches) return CT_ERR_INVALID_ARGUMENT;
+    if (!batch_list_ok(n_batches, batch_sizes, stack_devs, dark_devs, dark_batches)) return CT_ERR_INVALID_ARGUMENT;
     const uint32_t single_flags = flags & ~CT_MERGE_REQUIRE_ONE_LAUNCH;
     const int n = n_batches;
-    auto halo_of = [&](int b) { return halo_devs ? halo_devs[b] : nullptr; };
-    auto std_of = [&](int b) { return std_devs ? std_devs[b] : nullptr; };
-    auto dark_std_of = [&](int b) { return dark_std_devs ? dark_std_devs[b] : nullptr; };
-    if (n == 1)
-        return ct_hdr_merge_dark_batch(stack_devs[0], dtype, max_code, batch_sizes[0], geom, halo_of(0), std_of(0), std_mode, std_value,
-                                       dark_devs[0], dark_std_of(0), dark_batches[0], threshold, alpha, exposure_dev, icrf, weight_mode,
-                                       mean_state_dev, sumw_state_dev, var_state_dev, mean_out_dev, std_out_dev, single_flags, stream);
+    auto single = [&](int b, uint32_t f, int64_t offset) {
+        return ct_hdr_merge_dark_batch(stack_devs[b], dtype, max_code, batch_sizes[b], geom, batch_item(halo_devs, b), batch_item(std_devs, b),
+                                       std_mode, std_value, dark_devs[b], batch_item(dark_std_devs, b), dark_batches[b], threshold, alpha,
+                                       exposure_dev + offset, icrf, weight_mode, mean_state_dev, sumw_state_dev, var_state_dev, mean_out_dev,
+                                       std_out_dev, f, stream);
+    };
+    if (n == 1) return single(0, single_flags, 0);
     // a dark std for every batch or for none (the kernels propagate an uncertainty or do not), and likewise the halo rows
-    for (int b = 1; b < n; ++b)
-        if ((dark_std_of(b) != nullptr) != (dark_std_of(0) != nullptr) || (halo_of(b) != nullptr) != (halo_of(0) != nullptr))
-            return CT_ERR_INVALID_ARGUMENT;
-    // every batch as the single-batch entry point would judge it (FIRST_BATCH / FINALIZE: of the whole call, so that a state
-    // is needed unless the call is a whole merge); nothing has touched the device when one of them is refused
+    if (!all_or_none(dark_std_devs, n) || !all_or_none(halo_devs, n)) return CT_ERR_INVALID_ARGUMENT;
     const MergeDarkCall c{dtype, max_code, geom, std_mode, std_value, threshold, alpha, icrf, weight_mode, mean_state_dev,
                           sumw_state_dev, var_state_dev, mean_out_dev, std_out_dev, single_flags};
+    const bool has_std = batch_item(dark_std_devs, 0) != nullptr;
+    // an empty batch is refused like any other fault of a batch; what cannot be walked batch by batch is not built
+    constexpr MergeBatchPolicy kPolicy{/*skip_empty*/ false, /*no_state*/ CT_ERR_UNSUPPORTED, /*require_one_launch*/ CT_ERR_UNSUPPORTED};
     NormConst norm;
-    int64_t offset[kMaxDarkBatches] = {}, total = 0;
-    for (int b = 0; b < n; ++b) {
-        offset[b] = total;
-        if (const int rc = md_validate(c, stack_devs[b], batch_sizes[b], halo_of(b), std_of(b), dark_devs[b], dark_std_of(b), dark_batches[b],
-                                       exposure_dev ? exposure_dev + total : nullptr, norm);
-            rc != CT_OK)
-            return rc;
-        total += batch_sizes[b];
-    }
-    const bool has_std = dark_std_of(0) != nullptr;
-    const bool has_state = mean_state_dev && sumw_state_dev && (!has_std || var_state_dev);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (mi_lds_bytes(icrf->interp, geom->channels, icrf_points(icrf), total) <= kLdsBudget) {
-        const MergeDarkArgs a = md_fill_args(c, has_std, norm, exposure_dev, (int32_t)total);
-        MergeDarkBatches mb = {};
-        for (int b = 0; b < n; ++b) {
-            mb.stack[b] = stack_devs[b];
-            mb.halo[b] = halo_of(b);
-            mb.std_stack[b] = std_mode == CT_STD_EXPLICIT ? std_of(b) : nullptr;
-            mb.dark[b] = dark_devs[b];
-            mb.dark_std[b] = dark_std_of(b);
-            mb.dark_stride[b] = dark_batches[b] == 1 ? 0 : (int64_t)a.plane * geom->channels;
-            mb.batch[b] = batch_sizes[b];
-            mb.offset[b] = (int32_t)offset[b];
-        }
-        mb.n_batches = n;
-        return merge_dark_multi(a, mb, dtype, icrf->interp, weight_mode, has_std, s);
-    }
-    // the scales of all exposures do not fit the LDS beside the LUT, those of each batch do: one launch per batch
-    if ((flags & CT_MERGE_REQUIRE_ONE_LAUNCH) || !has_state) return CT_ERR_UNSUPPORTED;
-    const bool first = flags & CT_MERGE_FIRST_BATCH, finalize = flags & CT_MERGE_FINALIZE;
-    for (int b = 0; b < n; ++b) {
-        const uint32_t f = (single_flags & ~(CT_MERGE_FIRST_BATCH | CT_MERGE_FINALIZE)) | ((first && b == 0) ? CT_MERGE_FIRST_BATCH : 0u) |
-                           ((finalize && b == n - 1) ? CT_MERGE_FINALIZE : 0u);
-        const int rc = ct_hdr_merge_dark_batch(stack_devs[b], dtype, max_code, batch_sizes[b], geom, halo_of(b), std_of(b), std_mode,
-                                               std_value, dark_devs[b], dark_std_of(b), dark_batches[b], threshold, alpha,
-                                               exposure_dev + offset[b], icrf, weight_mode, mean_state_dev, sumw_state_dev, var_state_dev,
-                                               mean_out_dev, std_out_dev, f, stream);
-        if (rc != CT_OK) return rc;
-    }
-    return CT_OK;
+    return merge_batches(
+        batch_sizes, n, flags, c.has_state(has_std), kPolicy,
+        // FIRST_BATCH / FINALIZE: of the whole call, so that a state is needed unless the call is a whole merge
+        [&](int b, int64_t offset) {
+            return md_validate(c, stack_devs[b], batch_sizes[b], batch_item(halo_devs, b), batch_item(std_devs, b), dark_devs[b],
+                               batch_item(dark_std_devs, b), dark_batches[b], exposure_dev ? exposure_dev + offset : nullptr, norm);
+        },
+        [&](const MergeBatchList &list) {
+            // one launch: the scales of all exposures fit the LDS beside the LUT (those of each batch do: md_validate)
+            if (!merge_scales_fit(icrf, geom->channels, list.total)) return kMergePerBatch;
+            const MergeDarkArgs a = md_fill_args(c, has_std, norm, exposure_dev, (int32_t)list.total);
+            MergeDarkBatches mb = {};
+            for (int b = 0; b < n; ++b) {
+                mb.stack[b] = stack_devs[b];
+                mb.halo[b] = batch_item(halo_devs, b);
+                mb.std_stack[b] = std_mode == CT_STD_EXPLICIT ? batch_item(std_devs, b) : nullptr;
+                mb.dark[b] = dark_devs[b];
+                mb.dark_std[b] = batch_item(dark_std_devs, b);
+                mb.dark_stride[b] = dark_batches[b] == 1 ? 0 : (int64_t)a.plane * geom->channels;
+                mb.batch[b] = batch_sizes[b];
+                mb.offset[b] = (int32_t)list.offset[b];
+            }
+            mb.n_batches = n;
+            return merge_dark_multi(a, mb, dtype, icrf->interp, weight_mode, has_std, static_cast<hipStream_t>(stream));
+        },
+        single);
 }

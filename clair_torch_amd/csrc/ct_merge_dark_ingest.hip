@@ -44,7 +44,6 @@
 // against 1), and at these register counts the latency is not hidden.  The byte counts above did not decide it.  So
 // compute_hdr_image(fused_dark_ingest=...) is off by default; what it saves today is the float32 stack of a batch.  First
 // things to look at: the chain on a row shared through the LDS, or one division per tap replaced where the divisor allows.
-#include <algorithm>
 #include "ct_merge_dark_ingest_kernel.hpp"
 
 namespace ct {
@@ -53,7 +52,7 @@ static int merge_dark_ingest_launch(const MergeDarkIngestArgs &a, const MergeDar
                                     int weight_mode, bool has_std, hipStream_t s)
 {
     if (packed) return merge_dark_ingest_packed(a, mb, dtype, interp, weight_mode, has_std, s);
-    return mdi_dispatch_dtype<false>(a, mb, dtype, interp, weight_mode, has_std, s);
+    return mdi_dispatch<false>(a, mb, dtype, interp, weight_mode, has_std, s);
 }
 
 }  // namespace ct
@@ -71,23 +70,15 @@ extern "C" int ct_hdr_merge_dark_ingest_batches(const void *const *frames_devs, 
 {
     using namespace ct;
     // ---- the batch list itself ----
-    if (n_batches < 1 || n_batches > kMaxDarkBatches || !frames_devs || !batch_sizes || !dark_devs || !dark_batches || !geom)
-        return CT_ERR_INVALID_ARGUMENT;
+    if (!batch_list_ok(n_batches, batch_sizes, frames_devs, dark_devs, dark_batches, geom)) return CT_ERR_INVALID_ARGUMENT;
     const int n = n_batches;
-    auto halo_of = [&](int b) { return halo_devs ? halo_devs[b] : nullptr; };
-    auto std_of = [&](int b) { return std_devs ? std_devs[b] : nullptr; };
-    auto dark_std_of = [&](int b) { return dark_std_devs ? dark_std_devs[b] : nullptr; };
-    auto consts_of = [&](int b) { return consts_devs ? consts_devs[b] : nullptr; };
     // a dark std for every batch or for none (the kernels propagate an uncertainty or do not); likewise the halo rows and the
     // constants of a data-dependent stage
-    for (int b = 1; b < n; ++b)
-        if ((dark_std_of(b) != nullptr) != (dark_std_of(0) != nullptr) || (halo_of(b) != nullptr) != (halo_of(0) != nullptr) ||
-            (consts_of(b) != nullptr) != (consts_of(0) != nullptr))
-            return CT_ERR_INVALID_ARGUMENT;
+    if (!all_or_none(dark_std_devs, n) || !all_or_none(halo_devs, n) || !all_or_none(consts_devs, n)) return CT_ERR_INVALID_ARGUMENT;
     // ---- the stage list and the layout of the raw frames: a data-dependent stage needs constants, and there is one at most ----
     bool by_channel = false;
     if (int rc = ingest_validate(dtype, geom->layout, 1, geom->channels, geom->h_tile * geom->width, stages, n_stages, CT_INGEST_MAX_STAGES,
-                                 consts_of(0) ? 1 : 0, by_channel))
+                                 batch_item(consts_devs, 0) ? 1 : 0, by_channel))
         return rc;
     const bool packed = geom->layout != CT_LAYOUT_NCHW;
     if (packed && (geom->row_offset != 0 || geom->h_tile != geom->h_global)) return CT_ERR_UNSUPPORTED;  // no interleaved halo is built
@@ -95,24 +86,11 @@ extern "C" int ct_hdr_merge_dark_ingest_batches(const void *const *frames_devs, 
     //      is the stage list's matter; pointers are aligned to the raw element); FIRST_BATCH / FINALIZE: of the whole call ----
     ct_geometry planar = *geom;
     planar.layout = CT_LAYOUT_NCHW;
-    const uint32_t single_flags = flags & ~CT_MERGE_REQUIRE_ONE_LAUNCH;
     const MergeDarkCall c{dtype, 1.0f, &planar, std_mode, std_value, threshold, alpha, icrf, weight_mode, mean_state_dev,
-                          sumw_state_dev, var_state_dev, mean_out_dev, std_out_dev, single_flags};
-    NormConst norm;
-    int64_t offset[kMaxDarkBatches] = {}, total = 0;
-    for (int b = 0; b < n; ++b) {
-        offset[b] = total;
-        if (const int rc = md_validate(c, frames_devs[b], batch_sizes[b], halo_of(b), std_of(b), dark_devs[b], dark_std_of(b), dark_batches[b],
-                                       exposure_dev ? exposure_dev + total : nullptr, norm);
-            rc != CT_OK)
-            return rc;
-        if (!aligned(consts_of(b), sizeof(float))) return CT_ERR_INVALID_ARGUMENT;
-        total += batch_sizes[b];
-    }
-    const bool has_std = dark_std_of(0) != nullptr;
-    const bool has_state = mean_state_dev && sumw_state_dev && (!has_std || var_state_dev);
-    const int interp = icrf->interp;
+                          sumw_state_dev, var_state_dev, mean_out_dev, std_out_dev, flags & ~CT_MERGE_REQUIRE_ONE_LAUNCH};
+    const bool has_std = batch_item(dark_std_devs, 0) != nullptr;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    NormConst norm;
 
     MergeDarkIngestArgs a{};
     a.reversed = geom->layout == CT_LAYOUT_NHWC_BGR ? 1u : 0u;
@@ -121,35 +99,42 @@ extern "C" int ct_hdr_merge_dark_ingest_batches(const void *const *frames_devs, 
     for (int32_t k = 0; k < n_stages; ++k) a.stage[k] = stages[k];
     auto fill_batch = [&](MergeDarkIngestBatches &mb, int slot, int b, int32_t at) {
         mb.frames[slot] = frames_devs[b];
-        mb.halo[slot] = halo_of(b);
-        mb.std_stack[slot] = std_mode == CT_STD_EXPLICIT ? std_of(b) : nullptr;
+        mb.halo[slot] = batch_item(halo_devs, b);
+        mb.std_stack[slot] = std_mode == CT_STD_EXPLICIT ? batch_item(std_devs, b) : nullptr;
         mb.dark[slot] = dark_devs[b];
-        mb.dark_std[slot] = dark_std_of(b);
-        mb.consts[slot] = consts_of(b);
+        mb.dark_std[slot] = batch_item(dark_std_devs, b);
+        mb.consts[slot] = batch_item(consts_devs, b);
         mb.dark_stride[slot] = dark_batches[b] == 1 ? 0 : geom->h_tile * geom->width * geom->channels;
         mb.batch[slot] = batch_sizes[b];
         mb.offset[slot] = at;
     };
-    if (mi_lds_bytes(interp, geom->channels, icrf_points(icrf), total) <= kLdsBudget) {
-        a.d = md_fill_args(c, has_std, norm, exposure_dev, (int32_t)total);
-        MergeDarkIngestBatches mb = {};
-        for (int b = 0; b < n; ++b) fill_batch(mb, b, b, (int32_t)offset[b]);
-        mb.n_batches = n;
-        return merge_dark_ingest_launch(a, mb, dtype, packed, interp, weight_mode, has_std, s);
-    }
-    // the scales of all exposures do not fit the LDS beside the LUT, those of each batch do (md_validate): one launch per batch
-    if (flags & CT_MERGE_REQUIRE_ONE_LAUNCH) return CT_ERR_TOO_LARGE;
-    if (!has_state) return CT_ERR_UNSUPPORTED;
-    const bool first = flags & CT_MERGE_FIRST_BATCH, finalize = flags & CT_MERGE_FINALIZE;
-    for (int b = 0; b < n; ++b) {
-        MergeDarkCall cb = c;
-        cb.flags = (single_flags & ~(CT_MERGE_FIRST_BATCH | CT_MERGE_FINALIZE)) | ((first && b == 0) ? CT_MERGE_FIRST_BATCH : 0u) |
-                   ((finalize && b == n - 1) ? CT_MERGE_FINALIZE : 0u);
-        a.d = md_fill_args(cb, has_std, norm, exposure_dev + offset[b], batch_sizes[b]);
-        MergeDarkIngestBatches mb = {};
-        fill_batch(mb, 0, b, 0);
-        mb.n_batches = 1;
-        if (const int rc = merge_dark_ingest_launch(a, mb, dtype, packed, interp, weight_mode, has_std, s); rc != CT_OK) return rc;
-    }
-    return CT_OK;
+    // an empty batch is refused like any other fault of a batch; a list that is not one launch is "too large" under the flag
+    constexpr MergeBatchPolicy kPolicy{/*skip_empty*/ false, /*no_state*/ CT_ERR_UNSUPPORTED, /*require_one_launch*/ CT_ERR_TOO_LARGE};
+    return merge_batches(
+        batch_sizes, n, flags, c.has_state(has_std), kPolicy,
+        [&](int b, int64_t offset) {
+            if (const int rc = md_validate(c, frames_devs[b], batch_sizes[b], batch_item(halo_devs, b), batch_item(std_devs, b), dark_devs[b],
+                                           batch_item(dark_std_devs, b), dark_batches[b], exposure_dev ? exposure_dev + offset : nullptr, norm);
+                rc != CT_OK)
+                return rc;
+            return aligned(batch_item(consts_devs, b), sizeof(float)) ? (int)CT_OK : (int)CT_ERR_INVALID_ARGUMENT;
+        },
+        [&](const MergeBatchList &list) {
+            // one launch: the scales of all exposures fit the LDS beside the LUT (those of each batch do: md_validate)
+            if (!merge_scales_fit(icrf, geom->channels, list.total)) return kMergePerBatch;
+            a.d = md_fill_args(c, has_std, norm, exposure_dev, (int32_t)list.total);
+            MergeDarkIngestBatches mb = {};
+            for (int b = 0; b < n; ++b) fill_batch(mb, b, b, (int32_t)list.offset[b]);
+            mb.n_batches = n;
+            return merge_dark_ingest_launch(a, mb, dtype, packed, icrf->interp, weight_mode, has_std, s);
+        },
+        [&](int b, uint32_t f, int64_t offset) {  // a list of one
+            MergeDarkCall cb = c;
+            cb.flags = f;
+            a.d = md_fill_args(cb, has_std, norm, exposure_dev + offset, batch_sizes[b]);
+            MergeDarkIngestBatches mb = {};
+            fill_batch(mb, 0, b, 0);
+            mb.n_batches = 1;
+            return merge_dark_ingest_launch(a, mb, dtype, packed, icrf->interp, weight_mode, has_std, s);
+        });
 }

@@ -1,7 +1,7 @@
 // ct_merge_dark_ingest_kernel.hpp -- what ct_merge_dark_ingest.hip (the entry point and the planar kernels) and
 // ct_merge_dark_ingest_packed.hip (the interleaved kernels) share: the argument blocks, mdi_run -- the walk of one thread over
-// the batches of the elements it owns -- and the workgroup around it.  The head of ct_merge_dark_ingest.hip describes
-// ownership, the window and the byte counts.  mdi_run is md_run (ct_merge_dark_kernel.hpp) with the state always in registers
+// the batches of the elements it owns -- the workgroup around it and its dispatch.  The head of ct_merge_dark_ingest.hip
+// describes ownership, the window and the byte counts.  mdi_run is md_run (ct_merge_dark_kernel.hpp) with the state always in registers
 // (one batch is a list of one) and a sample step that sends the raw window taps through the chain before the blur.
 #pragma once
 #include "ct_merge_dark_kernel.hpp"
@@ -317,14 +317,6 @@ __device__ __forceinline__ void mdi_run(const MergeDarkIngestArgs &a, const Merg
     }
 }
 
-// groups per thread row: kMdGroup columns of a plane, or kMiPackedGroup interleaved pixels
-template <bool PACKED>
-static inline __host__ __device__ uint32_t mdi_groups_per_row(uint32_t width)
-{
-    constexpr uint32_t kG = PACKED ? kMiPackedGroup : kMdGroup;
-    return (width + kG - 1) / kG;
-}
-
 // merge_dark_multi_kernel's workgroup (ct_merge_dark_multi.hip): the LUT and the scales of all batches staged once, one slot
 // per group of every row; a workgroup row (blockIdx.y) is one channel plane, or with PACKED the whole frame
 template <typename T, bool PACKED, int INTERP, int WEIGHT, int STD>
@@ -349,7 +341,7 @@ __global__ __launch_bounds__(kBlock) void merge_dark_ingest_kernel(const MergeDa
     __syncthreads();
 
     const uint32_t W = (uint32_t)a.d.width;
-    const uint32_t gpr = mdi_groups_per_row<PACKED>(W);
+    const uint32_t gpr = groups_per_row<kG>(W);
     const uint64_t slot = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (slot >= (uint64_t)gpr * (uint32_t)a.d.h_tile) return;
     const uint32_t h = (uint32_t)(slot / gpr);
@@ -365,41 +357,18 @@ __global__ __launch_bounds__(kBlock) void merge_dark_ingest_kernel(const MergeDa
     for (uint32_t w = w0; w < W; ++w) mdi_run<T, NP, 1, PF, INTERP, WEIGHT, STD>(a, mb, lds, inv_t, cq, c0, h, w);
 }
 
-template <typename T, bool PACKED, int INTERP, int WEIGHT, int STD>
-static int mdi_launch(const MergeDarkIngestArgs &a, const MergeDarkIngestBatches &mb, hipStream_t s)
-{
-    if constexpr (INTERP == CT_INTERP_LOOKUP && WEIGHT == CT_WEIGHT_NONE && STD != CT_STD_NONE) {
-        return CT_ERR_NO_GRADIENT_PATH;  // (refused by the entry point before it gets here)
-    } else {
-        const size_t lds = mi_lds_bytes(INTERP, a.d.channels, a.d.n_points, a.d.batch);
-        if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;  // (the entry point walks such a call batch by batch instead)
-        const uint64_t slots = (uint64_t)mdi_groups_per_row<PACKED>((uint32_t)a.d.width) * (uint64_t)a.d.h_tile;
-        const dim3 grid((uint32_t)((slots + kBlock - 1) / kBlock), PACKED ? 1u : (uint32_t)a.d.channels);
-        hipLaunchKernelGGL((merge_dark_ingest_kernel<T, PACKED, INTERP, WEIGHT, STD>), grid, dim3(kBlock), lds, s, a, mb);
-        return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
-    }
-}
-
-template <typename T, bool PACKED>
-static int mdi_dispatch(const MergeDarkIngestArgs &a, const MergeDarkIngestBatches &mb, int interp, int weight_mode, bool has_std,
+// the launch of one layout, dispatched on dtype / interpolation / weight / dark std (has_std: CT_STD_EXPLICIT, else none)
+template <bool PACKED>
+static int mdi_dispatch(const MergeDarkIngestArgs &a, const MergeDarkIngestBatches &mb, int dtype, int interp, int weight_mode, bool has_std,
                         hipStream_t s)
 {
-    return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
-        return with_enum<CT_WEIGHT_NONE, CT_WEIGHT_GAUSS>(weight_mode, [&](auto W) {
-            return has_std ? mdi_launch<T, PACKED, I, W, CT_STD_EXPLICIT>(a, mb, s) : mdi_launch<T, PACKED, I, W, CT_STD_NONE>(a, mb, s);
+    constexpr int kG = PACKED ? kMiPackedGroup : kMdGroup;
+    return with_pixel_dtype(dtype, [&](auto t) {
+        return with_dark_merge_modes(interp, weight_mode, has_std, [&](auto I, auto W, auto S) {
+            return merge_fused_launch(merge_dark_ingest_kernel<decltype(t), PACKED, I, W, S>, md_grid<kG>(a.d, PACKED ? 1u : (uint32_t)a.d.channels), I,
+                                      a.d.channels, a.d.n_points, a.d.batch, s, a, mb);
         });
     });
-}
-
-template <bool PACKED>
-static int mdi_dispatch_dtype(const MergeDarkIngestArgs &a, const MergeDarkIngestBatches &mb, int dtype, int interp, int weight_mode,
-                              bool has_std, hipStream_t s)
-{
-    switch (dtype) {
-        case CT_DTYPE_U8: return mdi_dispatch<uint8_t, PACKED>(a, mb, interp, weight_mode, has_std, s);
-        case CT_DTYPE_U16: return mdi_dispatch<uint16_t, PACKED>(a, mb, interp, weight_mode, has_std, s);
-        default: return mdi_dispatch<float, PACKED>(a, mb, interp, weight_mode, has_std, s);
-    }
 }
 
 }  // namespace ct

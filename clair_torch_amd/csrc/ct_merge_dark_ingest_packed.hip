@@ -10,7 +10,7 @@ namespace ct {
 int merge_dark_ingest_packed(const MergeDarkIngestArgs &a, const MergeDarkIngestBatches &mb, int dtype, int interp, int weight_mode,
                              bool has_std, hipStream_t s)
 {
-    return mdi_dispatch_dtype<true>(a, mb, dtype, interp, weight_mode, has_std, s);
+    return mdi_dispatch<true>(a, mb, dtype, interp, weight_mode, has_std, s);
 }
 
 }  // namespace ct

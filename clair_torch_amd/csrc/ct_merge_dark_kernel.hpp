@@ -3,7 +3,8 @@
 // thread over the batch(es) of the columns it owns.  The head of ct_merge_dark.hip describes ownership, the window and the
 // packets.  MULTI is a template flag of that one body, as in ct_merge_ingest_kernel.hpp: everything it adds is behind
 // `if constexpr`, and the order of the text is kept so that the single-batch kernels compile to the instructions they had
-// without it.
+// without it.  Host side: MergeDarkCall, md_validate and md_fill_args, what the dark-field merge entry points and
+// ct_hdr_merge_dark_ingest_batches check and fill alike.
 #pragma once
 #include "ct_dark_window.hpp"
 #include "ct_merge_ingest_kernel.hpp"
@@ -42,7 +43,7 @@ struct MergeDarkArgs {
 // field and dark std of its own (dark_stride[b]: 0 for one shared dark field, C * H_tile * W for one per frame); its exposure
 // times start at offset[b] of MergeDarkArgs::exposure, where those of all batches follow each other, and MergeDarkArgs::batch
 // is their total.  MergeDarkArgs::stack, halo, std_stack, dark, dark_std and dark_stride are not read.
-constexpr int kMaxDarkBatches = 16;
+constexpr int kMaxDarkBatches = kMaxFusedBatches;
 struct MergeDarkBatches {
     const void *stack[kMaxDarkBatches];
     const void *halo[kMaxDarkBatches];
@@ -288,14 +289,27 @@ __device__ __forceinline__ void md_run(const MergeDarkArgs &a, const MergeDarkBa
     }
 }
 
-// groups of kMdGroup columns in a row, the last one possibly short
-static inline __host__ __device__ uint32_t md_groups_per_row(uint32_t width) { return (width + kMdGroup - 1) / kMdGroup; }
-
-// grid of a launch: one slot per group of every row, one plane per workgroup row
-static inline dim3 md_grid(const MergeDarkArgs &a)
+// groups of G columns (or pixels) in a row, the last one possibly short
+template <int G>
+static inline __host__ __device__ uint32_t groups_per_row(uint32_t width)
 {
-    const uint64_t slots = (uint64_t)md_groups_per_row((uint32_t)a.width) * (uint64_t)a.h_tile;
-    return dim3((uint32_t)((slots + kBlock - 1) / kBlock), (uint32_t)a.channels);
+    return (width + G - 1) / G;
+}
+
+// grid of a launch: one slot per group of G columns of every row, one workgroup row per plane
+template <int G>
+static inline dim3 md_grid(const MergeDarkArgs &a, uint32_t planes)
+{
+    const uint64_t slots = (uint64_t)groups_per_row<G>((uint32_t)a.width) * (uint64_t)a.h_tile;
+    return dim3((uint32_t)((slots + kBlock - 1) / kBlock), planes);
+}
+
+// The modes of a dark-field family: interpolation and weight as ever; has_std (a dark std comes with the call, sigma_eff is
+// propagated) is CT_STD_EXPLICIT, without one no uncertainty exists at all
+template <typename F>
+static int with_dark_merge_modes(int interp, int weight_mode, bool has_std, F &&f)
+{
+    return with_fused_merge_modes<CT_STD_NONE, CT_STD_EXPLICIT>(interp, weight_mode, has_std ? CT_STD_EXPLICIT : CT_STD_NONE, f);
 }
 
 // ---- host: the checks and the argument block the dark-field merge entry points share -------------------------------------
@@ -314,6 +328,8 @@ struct MergeDarkCall {
     void *mean_out;
     float *std_out;
     uint32_t flags;
+    // has_std: a dark std comes with the call, so the variance is part of the state
+    bool has_state(bool has_std) const { return mean_state && sumw_state && (!has_std || var_state); }
 };
 
 // One batch as ct_hdr_merge_dark_batch judges it, every check in its order; nothing is read.  FIRST_BATCH / FINALIZE in
@@ -339,14 +355,13 @@ static inline int md_validate(const MergeDarkCall &c, const void *stack_dev, int
     const int interp = icrf->interp;
     // hdr_merge.py:107-113: autograd.grad raises when nothing connects the mean to the image
     if (has_std && interp == CT_INTERP_LOOKUP && weight_mode == CT_WEIGHT_NONE) return CT_ERR_NO_GRADIENT_PATH;
-    const bool has_state = c.mean_state && c.sumw_state && (!has_std || c.var_state);
-    if (!has_state && !((flags & CT_MERGE_FIRST_BATCH) && (flags & CT_MERGE_FINALIZE))) return CT_ERR_INVALID_ARGUMENT;
+    if (!c.has_state(has_std) && !((flags & CT_MERGE_FIRST_BATCH) && (flags & CT_MERGE_FINALIZE))) return CT_ERR_INVALID_ARGUMENT;
     if ((flags & CT_MERGE_FINALIZE) && (!c.mean_out || (has_std && !c.std_out))) return CT_ERR_INVALID_ARGUMENT;
     if (!global_below_2_31(geom)) return CT_ERR_TOO_LARGE;
     // ---- what this entry point does not have: the routes of ct_hdr_merge_batch besides the closed-form float32 kernel ----
     if (flags & (CT_MERGE_F64_MOMENTS | CT_MERGE_REFERENCE_ORDER | CT_MERGE_OUT_AS_INPUT)) return CT_ERR_UNSUPPORTED;
     if ((interp == CT_INTERP_CATMULL || interp == CT_INTERP_LOOKUP) && has_std && !(flags & CT_MERGE_CLOSED_FORM)) return CT_ERR_UNSUPPORTED;
-    if (mi_lds_bytes(interp, geom->channels, icrf_points(icrf), batch) > kLdsBudget) return CT_ERR_TOO_LARGE;
+    if (!merge_scales_fit(icrf, geom->channels, batch)) return CT_ERR_TOO_LARGE;
     const size_t elem = dtype_bytes(c.dtype);
     if (!aligned(stack_dev, elem) || !aligned(halo_dev, elem) || !aligned(std_dev, sizeof(float)) || !aligned(dark_dev, sizeof(float)) ||
         !aligned(dark_std_dev, sizeof(float)) || !aligned(exposure_dev, sizeof(double)) || !aligned(c.mean_state, sizeof(double)) ||
@@ -360,7 +375,7 @@ static inline int md_validate(const MergeDarkCall &c, const void *stack_dev, int
 static inline MergeDarkArgs md_fill_args(const MergeDarkCall &c, bool has_std, NormConst norm, const double *exposure_dev, int32_t batch)
 {
     const ct_geometry *geom = c.geom;
-    const bool has_state = c.mean_state && c.sumw_state && (!has_std || c.var_state);
+    const bool has_state = c.has_state(has_std);
     const int64_t plane = geom->h_tile * geom->width;
     MergeDarkArgs a{};
     a.exposure = exposure_dev;

@@ -1,9 +1,9 @@
 // ct_merge_dark_multi.hip -- the several-batches-per-launch (MULTI) instantiations of the fused dark-field blur + merge kernel,
-// behind ct::merge_dark_multi (ct_hdr_merge_dark_batches).  The body is ct::md_run of ct_merge_dark_kernel.hpp with MULTI set:
-// one thread owns the same 4 columns of one image row for every batch and keeps (mean float64, sum of weights, variance) in
-// registers between them, so the 32 B of state per element and batch that one launch per batch moves shrink to one read (not
-// even that on a first batch) and one write per call.  A translation unit of its own, as ct_merge_ingest_multi.hip is for the
-// chain kernel: the instantiations compile next to ct_merge_dark.hip's instead of after them.
+// behind ct::merge_dark_multi (ct_hdr_merge_dark_batches).  The body is ct::md_run of ct_merge_dark_kernel.hpp
+// with MULTI set: one thread owns the same 4 columns of one image row for every batch and keeps (mean
+// float64, sum of weights, variance) in registers between them, so the 32 B of state per element and batch that one launch per
+// batch moves shrink to one read (not even that on a first batch) and one write per call.  A translation unit of its own, as
+// ct_merge_ingest_multi.hip is for the chain kernel: the instantiations compile next to ct_merge_dark.hip's instead of after them.
 #include "ct_merge_dark_kernel.hpp"
 
 namespace ct {
@@ -30,7 +30,7 @@ __global__ __launch_bounds__(kBlock) void merge_dark_multi_kernel(const MergeDar
     __syncthreads();
 
     const uint32_t W = (uint32_t)a.width;
-    const uint32_t gpr = md_groups_per_row(W);
+    const uint32_t gpr = groups_per_row<kMdGroup>(W);
     const uint64_t slot = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (slot >= (uint64_t)gpr * (uint32_t)a.h_tile) return;
     const uint32_t h = (uint32_t)(slot / gpr);
@@ -46,37 +46,15 @@ __global__ __launch_bounds__(kBlock) void merge_dark_multi_kernel(const MergeDar
     for (uint32_t w = w0; w < W; ++w) md_run<T, 1, INTERP, WEIGHT, STD, true>(a, &mb, lds, inv_t, cq, c0, h, w);
 }
 
-template <typename T, int INTERP, int WEIGHT, int STD>
-static int md_launch_multi(const MergeDarkArgs &a, const MergeDarkBatches &mb, hipStream_t s)
-{
-    if constexpr (INTERP == CT_INTERP_LOOKUP && WEIGHT == CT_WEIGHT_NONE && STD != CT_STD_NONE) {
-        return CT_ERR_NO_GRADIENT_PATH;  // (refused by the entry point before it gets here)
-    } else {
-        const size_t lds = mi_lds_bytes(INTERP, a.channels, a.n_points, a.batch);
-        if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;  // (the entry point walks such a call batch by batch instead)
-        hipLaunchKernelGGL((merge_dark_multi_kernel<T, INTERP, WEIGHT, STD>), md_grid(a), dim3(kBlock), lds, s, a, mb);
-        return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
-    }
-}
-
-template <typename T>
-static int md_dispatch_multi(const MergeDarkArgs &a, const MergeDarkBatches &mb, int interp, int weight_mode, bool has_std, hipStream_t s)
-{
-    return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
-        return with_enum<CT_WEIGHT_NONE, CT_WEIGHT_GAUSS>(weight_mode, [&](auto W) {
-            return has_std ? md_launch_multi<T, I, W, CT_STD_EXPLICIT>(a, mb, s) : md_launch_multi<T, I, W, CT_STD_NONE>(a, mb, s);
-        });
-    });
-}
-
 int merge_dark_multi(const MergeDarkArgs &a, const MergeDarkBatches &mb, int dtype, int interp, int weight_mode, bool has_std,
                      hipStream_t s)
 {
-    switch (dtype) {
-        case CT_DTYPE_U8: return md_dispatch_multi<uint8_t>(a, mb, interp, weight_mode, has_std, s);
-        case CT_DTYPE_U16: return md_dispatch_multi<uint16_t>(a, mb, interp, weight_mode, has_std, s);
-        default: return md_dispatch_multi<float>(a, mb, interp, weight_mode, has_std, s);
-    }
+    return with_pixel_dtype(dtype, [&](auto t) {
+        return with_dark_merge_modes(interp, weight_mode, has_std, [&](auto I, auto W, auto S) {
+            return merge_fused_launch(merge_dark_multi_kernel<decltype(t), I, W, S>, md_grid<kMdGroup>(a, (uint32_t)a.channels), I, a.channels,
+                                      a.n_points, a.batch, s, a, mb);
+        });
+    });
 }
 
 }  // namespace ct

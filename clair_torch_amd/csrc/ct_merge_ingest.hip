@@ -70,30 +70,11 @@ __global__ __launch_bounds__(kBlock) void merge_ingest_kernel(const MergeIngestA
     for (uint32_t k = 0; k < n; ++k) mi_run<T, PACKED, 1, INTERP, WEIGHT, STD, false>(a, nullptr, lds, inv_t, cq, c0, p0 + k, dsub, ddiv);
 }
 
-template <typename T, bool PACKED, int INTERP, int WEIGHT, int STD>
-static int mi_launch(const MergeIngestArgs &a, hipStream_t s)
-{
-    if constexpr (INTERP == CT_INTERP_LOOKUP && WEIGHT == CT_WEIGHT_NONE && STD != CT_STD_NONE) {
-        return CT_ERR_NO_GRADIENT_PATH;  // (refused by the entry point before it gets here)
-    } else {
-        const size_t lds = (INTERP == CT_INTERP_NONE ? 0 : (size_t)a.channels * a.n_points * lut_entry_bytes(INTERP)) +
-                           2 * sizeof(float) * (size_t)a.batch;
-        constexpr uint64_t kG = PACKED ? kMiPackedGroup : kMiGroup;
-        const uint64_t slots = 1 + ((uint64_t)a.plane + kG - 1) / kG;
-        const dim3 grid((uint32_t)((slots + kBlock - 1) / kBlock), PACKED ? 1u : (uint32_t)a.channels);
-        hipLaunchKernelGGL((merge_ingest_kernel<T, PACKED, INTERP, WEIGHT, STD>), grid, dim3(kBlock), lds, s, a);
-        return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
-    }
-}
-
 template <typename T, bool PACKED>
 static int mi_dispatch(const MergeIngestArgs &a, int interp, int weight_mode, int std_mode, hipStream_t s)
 {
-    return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
-        return with_enum<CT_WEIGHT_NONE, CT_WEIGHT_GAUSS>(weight_mode, [&](auto W) {
-            return with_enum<CT_STD_NONE, CT_STD_CONSTANT, CT_STD_MULTIPLIER, CT_STD_EXPLICIT>(
-                std_mode, [&](auto S) { return mi_launch<T, PACKED, I, W, S>(a, s); });
-        });
+    return with_fused_merge_modes(interp, weight_mode, std_mode, [&](auto I, auto W, auto S) {
+        return merge_fused_launch(merge_ingest_kernel<T, PACKED, I, W, S>, mi_grid<PACKED>(a), I, a.channels, a.n_points, a.batch, s, a);
     });
 }
 
@@ -140,8 +121,7 @@ static int mi_validate(const MergeIngestCall &c, int32_t batch, const float *con
     if (!c.has_state() && !((flags & CT_MERGE_FIRST_BATCH) && (flags & CT_MERGE_FINALIZE))) return CT_ERR_INVALID_ARGUMENT;
     if ((flags & CT_MERGE_FINALIZE) && (!c.mean_out || (std_mode != CT_STD_NONE && !c.std_out))) return CT_ERR_INVALID_ARGUMENT;
     if (!stride_holds_image(geom)) return CT_ERR_INVALID_ARGUMENT;
-    if (mi_lds_bytes(interp, geom->channels, c.n_points(), batch) > kLdsBudget) return CT_ERR_TOO_LARGE;
-    return CT_OK;
+    return merge_scales_fit(icrf, geom->channels, batch) ? CT_OK : CT_ERR_TOO_LARGE;
 }
 
 // the pointers of a call that has something to do: present and aligned to their element
@@ -194,12 +174,12 @@ extern "C" int ct_hdr_merge_ingest_batch(const void *frames_dev, int32_t dtype, 
     if (batch == 0 || c.plane() == 0) return CT_OK;
     if (!mi_pointers_ok(c, frames_dev, std_dev)) return CT_ERR_INVALID_ARGUMENT;
     const MergeIngestArgs a = mi_fill_args(c, frames_dev, std_dev, consts_dev, exposure_dev, batch, flags, by_channel);
-    const int interp = icrf->interp;
     const bool packed = geom->layout != CT_LAYOUT_NCHW;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == CT_DTYPE_U8)
-        return packed ? mi_dispatch<uint8_t, true>(a, interp, weight_mode, std_mode, s) : mi_dispatch<uint8_t, false>(a, interp, weight_mode, std_mode, s);
-    return packed ? mi_dispatch<uint16_t, true>(a, interp, weight_mode, std_mode, s) : mi_dispatch<uint16_t, false>(a, interp, weight_mode, std_mode, s);
+    return with_code_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return packed ? mi_dispatch<T, true>(a, icrf->interp, weight_mode, std_mode, s) : mi_dispatch<T, false>(a, icrf->interp, weight_mode, std_mode, s);
+    });
 }
 
 // Several consecutive batches of one merge behind one chain: ONE launch of the MULTI kernels (ct_merge_ingest_multi.hip) where
@@ -213,57 +193,45 @@ extern "C" int ct_hdr_merge_ingest_batches(const void *const *frames_devs, const
                                            float *std_out_dev, uint32_t flags, void *stream)
 {
     using namespace ct;
-    if (n_batches < 1 || n_batches > kMaxIngestBatches || !frames_devs || !batch_sizes) return CT_ERR_INVALID_ARGUMENT;
+    if (!batch_list_ok(n_batches, batch_sizes, frames_devs)) return CT_ERR_INVALID_ARGUMENT;
     const uint32_t single_flags = flags & ~CT_MERGE_REQUIRE_ONE_LAUNCH;
-    if (n_batches == 1)
-        return ct_hdr_merge_ingest_batch(frames_devs[0], dtype, batch_sizes[0], geom, stages, n_stages, consts_devs ? consts_devs[0] : nullptr,
-                                         std_devs ? std_devs[0] : nullptr, std_mode, std_value, exposure_dev, icrf, weight_mode,
-                                         mean_state_dev, sumw_state_dev, var_state_dev, mean_out_dev, std_out_dev, single_flags, stream);
+    auto single = [&](int b, const float *std_dev, uint32_t f, int64_t offset) {
+        return ct_hdr_merge_ingest_batch(frames_devs[b], dtype, batch_sizes[b], geom, stages, n_stages, batch_item(consts_devs, b), std_dev,
+                                         std_mode, std_value, exposure_dev + offset, icrf, weight_mode, mean_state_dev, sumw_state_dev,
+                                         var_state_dev, mean_out_dev, std_out_dev, f, stream);
+    };
+    if (n_batches == 1) return single(0, batch_item(std_devs, 0), single_flags, 0);
     const MergeIngestCall c{dtype, geom, stages, n_stages, std_mode, std_value, exposure_dev, icrf, weight_mode, mean_state_dev,
                             sumw_state_dev, var_state_dev, mean_out_dev, std_out_dev, single_flags};
-    // every batch as the single-batch entry point would judge it (FIRST_BATCH / FINALIZE: of the whole call, so that a state
-    // is needed unless the call is a whole merge); nothing has touched the device when one of them is refused
+    // the list reads explicit uncertainties only where the mode asks for them
+    auto std_of = [&](int b) { return std_mode == CT_STD_EXPLICIT ? batch_item(std_devs, b) : nullptr; };
+    // an empty batch is skipped (FIRST_BATCH is the first and FINALIZE the last of those with frames); a missing state is the
+    // caller's fault here, as in ct_hdr_merge_batches
+    constexpr MergeBatchPolicy kPolicy{/*skip_empty*/ true, /*no_state*/ CT_ERR_INVALID_ARGUMENT, /*require_one_launch*/ CT_ERR_UNSUPPORTED};
     bool by_channel = false;
-    for (int b = 0; b < n_batches; ++b)
-        if (const int rc = mi_validate(c, batch_sizes[b], consts_devs ? consts_devs[b] : nullptr, by_channel); rc != CT_OK) return rc;
-    // the batches that have something to do (an empty one is skipped: FIRST_BATCH is the first and FINALIZE the last of these)
-    MergeIngestBatches mb = {};
-    int64_t offset[kMaxIngestBatches] = {}, total = 0;
-    int n = 0, n_consts = 0;
-    for (int b = 0; b < n_batches; ++b) {
-        if (batch_sizes[b] > 0) {
-            mb.frames[n] = frames_devs[b];
-            mb.std_stack[n] = (std_mode == CT_STD_EXPLICIT && std_devs) ? std_devs[b] : nullptr;
-            mb.consts[n] = consts_devs ? consts_devs[b] : nullptr;
-            mb.batch[n] = batch_sizes[b];
-            offset[n] = total;
-            n_consts += mb.consts[n] ? 1 : 0;
-            ++n;
-        }
-        total += batch_sizes[b];
-    }
-    mb.n_batches = n;
-    if (n == 0 || c.plane() == 0) return CT_OK;
-    for (int b = 0; b < n; ++b)
-        if (!mi_pointers_ok(c, mb.frames[b], mb.std_stack[b])) return CT_ERR_INVALID_ARGUMENT;
-    const int interp = icrf->interp;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool one_launch = n >= 2 && (n_consts == 0 || n_consts == n) &&
-                            mi_lds_bytes(interp, geom->channels, c.n_points(), total) <= kLdsBudget;
-    if (one_launch) {
-        const MergeIngestArgs a = mi_fill_args(c, nullptr, nullptr, nullptr, exposure_dev, (int32_t)total, single_flags, by_channel);
-        return merge_ingest_multi(a, mb, dtype, geom->layout != CT_LAYOUT_NCHW, interp, weight_mode, std_mode, s);
-    }
-    if (n > 1 && (flags & CT_MERGE_REQUIRE_ONE_LAUNCH)) return CT_ERR_UNSUPPORTED;  // (tests: make the route explicit)
-    if (n > 1 && !c.has_state()) return CT_ERR_INVALID_ARGUMENT;
-    const bool first = flags & CT_MERGE_FIRST_BATCH, finalize = flags & CT_MERGE_FINALIZE;
-    for (int b = 0; b < n; ++b) {
-        const uint32_t f = (single_flags & ~(CT_MERGE_FIRST_BATCH | CT_MERGE_FINALIZE)) | ((first && b == 0) ? CT_MERGE_FIRST_BATCH : 0u) |
-                           ((finalize && b == n - 1) ? CT_MERGE_FINALIZE : 0u);
-        const int rc = ct_hdr_merge_ingest_batch(mb.frames[b], dtype, mb.batch[b], geom, stages, n_stages, mb.consts[b], mb.std_stack[b],
-                                                 std_mode, std_value, exposure_dev + offset[b], icrf, weight_mode, mean_state_dev,
-                                                 sumw_state_dev, var_state_dev, mean_out_dev, std_out_dev, f, stream);
-        if (rc != CT_OK) return rc;
-    }
-    return CT_OK;
+    return merge_batches(
+        batch_sizes, n_batches, flags, c.has_state(), kPolicy,
+        // FIRST_BATCH / FINALIZE: of the whole call, so that a state is needed unless the call is a whole merge
+        [&](int b, int64_t) { return mi_validate(c, batch_sizes[b], batch_item(consts_devs, b), by_channel); },
+        [&](const MergeBatchList &list) {
+            if (list.n == 0 || c.plane() == 0) return (int)CT_OK;
+            MergeIngestBatches mb = {};
+            int n_consts = 0;
+            for (int k = 0; k < list.n; ++k) {
+                const int b = list.index[k];
+                mb.frames[k] = frames_devs[b];
+                mb.std_stack[k] = std_of(b);
+                mb.consts[k] = batch_item(consts_devs, b);
+                mb.batch[k] = batch_sizes[b];
+                n_consts += mb.consts[k] ? 1 : 0;
+                if (!mi_pointers_ok(c, mb.frames[k], mb.std_stack[k])) return (int)CT_ERR_INVALID_ARGUMENT;
+            }
+            mb.n_batches = list.n;
+            // one launch: two batches or more, constants for all of them or for none (the MULTI kernels read them per batch,
+            // but a chain has a data-dependent stage or has none), and the scales of all exposures beside the LUT
+            if (list.n < 2 || (n_consts != 0 && n_consts != list.n) || !merge_scales_fit(icrf, geom->channels, list.total)) return kMergePerBatch;
+            const MergeIngestArgs a = mi_fill_args(c, nullptr, nullptr, nullptr, exposure_dev, (int32_t)list.total, single_flags, by_channel);
+            return merge_ingest_multi(a, mb, dtype, geom->layout != CT_LAYOUT_NCHW, icrf->interp, weight_mode, std_mode, static_cast<hipStream_t>(stream));
+        },
+        [&](int b, uint32_t f, int64_t offset) { return single(b, std_of(b), f, offset); });
 }

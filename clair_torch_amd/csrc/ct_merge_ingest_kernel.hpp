@@ -2,7 +2,11 @@
 // (several batches per launch, the streaming state in registers in between) share: the argument blocks and mi_run, the walk of
 // one thread over the batch(es) of the elements it owns.  The head of ct_merge_ingest.hip describes ownership, packets and
 // the element-by-element walk.  MULTI is a template flag of that one body; everything it adds is behind `if constexpr`, and
-// the order of the text is kept so that the single-batch kernels compile to the instructions they had without it.
+// the order of the text is kept so that the single-batch kernels compile to the instructions they had without it.  The
+// workgroups around mi_run are written out in the two .hip files: shared as a function they compile to other instructions
+// (profiles/merge_fused_refactor_ab.md).  Host side, what the three fused families (this one, ct_merge_dark_kernel.hpp and
+// ct_merge_dark_ingest_kernel.hpp) have in front of a launch, one copy each: the dtype and mode dispatch (with_code_dtype,
+// with_pixel_dtype, with_fused_merge_modes), the launch (merge_fused_launch) and the walk over a batch list (merge_batches).
 #pragma once
 #include "ct_args.hpp"
 #include "ct_ingest_stages.hpp"
@@ -39,7 +43,8 @@ struct MergeIngestArgs {
 // std_stack[b], the constants of a data-dependent Normalize at consts[b] or NULL); the exposure times of all batches follow
 // each other in MergeIngestArgs::exposure and MergeIngestArgs::batch is their total.  MergeIngestArgs::frames, std_stack and
 // consts are not read.
-constexpr int kMaxIngestBatches = 16;
+constexpr int kMaxFusedBatches = 16;  // of every fused family: the lists of the three entry points are one size
+constexpr int kMaxIngestBatches = kMaxFusedBatches;
 struct MergeIngestBatches {
     const void *frames[kMaxIngestBatches];
     const float *std_stack[kMaxIngestBatches];
@@ -374,6 +379,122 @@ inline dim3 mi_grid(const MergeIngestArgs &a)
     constexpr uint64_t kG = PACKED ? kMiPackedGroup : kMiGroup;
     const uint64_t slots = 1 + ((uint64_t)a.plane + kG - 1) / kG;
     return dim3((uint32_t)((slots + kBlock - 1) / kBlock), PACKED ? 1u : (uint32_t)a.channels);
+}
+
+// ---- host: dispatch and launch of the three fused families, one copy ----------------------------------------------------
+// f(T{}) for the element type of raw codes (validated: CT_DTYPE_U8 or CT_DTYPE_U16) ...
+template <typename F>
+static int with_code_dtype(int dtype, F &&f)
+{
+    return dtype == CT_DTYPE_U8 ? f(uint8_t{}) : f(uint16_t{});
+}
+
+// ... and of a stack that may also hold float32 pixels
+template <typename F>
+static int with_pixel_dtype(int dtype, F &&f)
+{
+    return dtype == CT_DTYPE_U8 || dtype == CT_DTYPE_U16 ? with_code_dtype(dtype, f) : f(float{});
+}
+
+// with_merge_modes for a fused family.  hdr_merge.py:107-113 (nothing connects the mean to the image) is refused HERE, not in
+// the launch: a kernel named as the launch's argument is instantiated whether or not it is launched, and no family has one
+// for that combination.  (The entry points refuse such a call before it gets here.)
+template <int... STDS, typename F>
+static int with_fused_merge_modes(int interp, int weight_mode, int std_mode, F &&f)
+{
+    return with_merge_modes<STDS...>(interp, weight_mode, std_mode, [&](auto I, auto W, auto S) {
+        if constexpr (I == CT_INTERP_LOOKUP && W == CT_WEIGHT_NONE && S != CT_STD_NONE)
+            return (int)CT_ERR_NO_GRADIENT_PATH;
+        else
+            return f(I, W, S);
+    });
+}
+
+// the scales of `exposures` exposures fit the LDS beside the LUT of a (validated) model
+static inline bool merge_scales_fit(const ct_icrf *icrf, int channels, int64_t exposures)
+{
+    return mi_lds_bytes(icrf->interp, channels, icrf_points(icrf), exposures) <= kLdsBudget;
+}
+
+// kernel(args...) on `grid` with the LUT and the scales of `batch` exposures in LDS.  (CT_ERR_TOO_LARGE cannot fire for one
+// batch, which validation has refused, nor for a list, which the entry points walk batch by batch instead.)
+template <typename Kernel, typename... Args>
+static int merge_fused_launch(Kernel kernel, dim3 grid, int interp, int channels, int n_points, int64_t batch, hipStream_t s,
+                              const Args &...args)
+{
+    const size_t lds = mi_lds_bytes(interp, channels, n_points, batch);
+    if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, s, args...);
+    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
+}
+
+// ---- host: the batch list of ct_hdr_merge_ingest_batches, ct_hdr_merge_dark_batches and ct_hdr_merge_dark_ingest_batches -------
+// element b of an optional list of pointers
+template <typename P>
+static inline P batch_item(P const *list, int b)
+{
+    return list ? list[b] : nullptr;
+}
+
+// ... which holds a pointer for every one of the n batches or for none
+template <typename P>
+static inline bool all_or_none(P const *list, int n)
+{
+    for (int b = 1; b < n; ++b)
+        if ((batch_item(list, b) != nullptr) != (batch_item(list, 0) != nullptr)) return false;
+    return true;
+}
+
+// the list itself: 1 to kMaxFusedBatches batches, their sizes and every array that is not optional
+template <typename... Lists>
+static inline bool batch_list_ok(int32_t n_batches, const int32_t *batch_sizes, Lists... required)
+{
+    return n_batches >= 1 && n_batches <= kMaxFusedBatches && batch_sizes && (... && (required != nullptr));
+}
+
+// the batches a call works on, in order: which batch of the arguments, and where its exposure times start
+struct MergeBatchList {
+    int n;
+    int index[kMaxFusedBatches];
+    int64_t offset[kMaxFusedBatches];
+    int64_t total;  // exposures of all batches
+};
+
+// What the three entry points do differently on purpose ("Host-side argument checks").
+struct MergeBatchPolicy {
+    bool skip_empty;         // a batch of size 0 is skipped and the list compacted; else the validator judges it like any other
+    int no_state;            // one launch per batch, but no state to carry between them
+    int require_one_launch;  // one launch per batch, but CT_MERGE_REQUIRE_ONE_LAUNCH
+};
+
+constexpr int kMergePerBatch = 1;  // one_launch's answer where the list is not one launch (no CT_* status is positive)
+
+// Every batch judged as the single-batch entry point would judge it -- nothing has touched the device when one of them is
+// refused -- then ONE launch where the list allows it, else one launch per batch with the state in memory, exactly what the
+// caller would have done.
+//   validate(b, offset)          the status of batch b of the arguments, whose exposure times start at `offset`
+//   one_launch(list)             the status of the call, or kMergePerBatch: what besides the validators' verdict stands
+//                                between the list and one launch is the entry point's, in its order
+//   single(b, flags, offset)     batch b alone, with merge_batch_flags of its place in the list
+template <typename Validate, typename OneLaunch, typename Single>
+static int merge_batches(const int32_t *batch_sizes, int32_t n_batches, uint32_t flags, bool has_state, MergeBatchPolicy policy,
+                         Validate &&validate, OneLaunch &&one_launch, Single &&single)
+{
+    MergeBatchList list = {};
+    for (int b = 0; b < n_batches; ++b) {
+        if (const int rc = validate(b, list.total); rc != CT_OK) return rc;
+        if (policy.skip_empty && batch_sizes[b] == 0) continue;
+        list.index[list.n] = b;
+        list.offset[list.n] = list.total;
+        ++list.n;
+        list.total += batch_sizes[b];
+    }
+    if (const int rc = one_launch(list); rc != kMergePerBatch) return rc;
+    if (list.n > 1 && (flags & CT_MERGE_REQUIRE_ONE_LAUNCH)) return policy.require_one_launch;  // (tests: make the route explicit)
+    if (list.n > 1 && !has_state) return policy.no_state;
+    for (int k = 0; k < list.n; ++k)
+        if (const int rc = single(list.index[k], merge_batch_flags(flags, k == 0, k == list.n - 1), list.offset[k]); rc != CT_OK) return rc;
+    return CT_OK;
 }
 
 }  // namespace ct

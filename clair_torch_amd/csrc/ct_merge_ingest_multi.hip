@@ -1,9 +1,9 @@
 // ct_merge_ingest_multi.hip -- the several-batches-per-launch (MULTI) instantiations of the fused chain + merge kernel, behind
-// ct::merge_ingest_multi (ct_hdr_merge_ingest_batches).  The body is ct::mi_block / ct::mi_run of ct_merge_ingest_kernel.hpp
-// with MULTI set: one thread owns the same elements for every batch and keeps (mean float64, sum of weights, variance) in
-// registers between them, so the 32 B of state per element and batch that one launch per batch moves shrink to one read (not
-// even that on a first batch) and one write per call.  A translation unit of its own, as ct_merge_multi.hip is for the pivot
-// kernel: the instantiations compile next to ct_merge_ingest.hip's instead of after them.
+// ct::merge_ingest_multi (ct_hdr_merge_ingest_batches).  The body is ct::mi_run of ct_merge_ingest_kernel.hpp
+// with MULTI set (the workgroup around it is merge_ingest_kernel's, written out below): one thread owns the same elements for every batch and keeps (mean float64, sum of
+// weights, variance) in registers between them, so the 32 B of state per element and batch that one launch per batch moves
+// shrink to one read (not even that on a first batch) and one write per call.  A translation unit of its own, as
+// ct_merge_multi.hip is for the pivot kernel: the instantiations compile next to ct_merge_ingest.hip's instead of after them.
 #include "ct_merge_ingest_kernel.hpp"
 
 namespace ct {
@@ -51,39 +51,23 @@ __global__ __launch_bounds__(kBlock) void merge_ingest_multi_kernel(const MergeI
     for (uint32_t k = 0; k < n; ++k) mi_run<T, PACKED, 1, INTERP, WEIGHT, STD, true>(a, &mb, lds, inv_t, cq, c0, p0 + k, 0.0f, 1.0f);
 }
 
-template <typename T, bool PACKED, int INTERP, int WEIGHT, int STD>
-static int mi_launch_multi(const MergeIngestArgs &a, const MergeIngestBatches &mb, hipStream_t s)
-{
-    if constexpr (INTERP == CT_INTERP_LOOKUP && WEIGHT == CT_WEIGHT_NONE && STD != CT_STD_NONE) {
-        return CT_ERR_NO_GRADIENT_PATH;  // (refused by the entry point before it gets here)
-    } else {
-        const size_t lds = mi_lds_bytes(INTERP, a.channels, a.n_points, a.batch);
-        if (lds > kLdsBudget) return CT_ERR_TOO_LARGE;  // (the entry point walks such a call batch by batch instead)
-        hipLaunchKernelGGL((merge_ingest_multi_kernel<T, PACKED, INTERP, WEIGHT, STD>), mi_grid<PACKED>(a), dim3(kBlock), lds, s, a, mb);
-        return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
-    }
-}
-
 template <typename T, bool PACKED>
 static int mi_dispatch_multi(const MergeIngestArgs &a, const MergeIngestBatches &mb, int interp, int weight_mode, int std_mode,
                              hipStream_t s)
 {
-    return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
-        return with_enum<CT_WEIGHT_NONE, CT_WEIGHT_GAUSS>(weight_mode, [&](auto W) {
-            return with_enum<CT_STD_NONE, CT_STD_CONSTANT, CT_STD_MULTIPLIER, CT_STD_EXPLICIT>(
-                std_mode, [&](auto S) { return mi_launch_multi<T, PACKED, I, W, S>(a, mb, s); });
-        });
+    return with_fused_merge_modes(interp, weight_mode, std_mode, [&](auto I, auto W, auto S) {
+        return merge_fused_launch(merge_ingest_multi_kernel<T, PACKED, I, W, S>, mi_grid<PACKED>(a), I, a.channels, a.n_points, a.batch, s, a, mb);
     });
 }
 
 int merge_ingest_multi(const MergeIngestArgs &a, const MergeIngestBatches &mb, int dtype, bool packed, int interp, int weight_mode,
                        int std_mode, hipStream_t s)
 {
-    if (dtype == CT_DTYPE_U8)
-        return packed ? mi_dispatch_multi<uint8_t, true>(a, mb, interp, weight_mode, std_mode, s)
-                      : mi_dispatch_multi<uint8_t, false>(a, mb, interp, weight_mode, std_mode, s);
-    return packed ? mi_dispatch_multi<uint16_t, true>(a, mb, interp, weight_mode, std_mode, s)
-                  : mi_dispatch_multi<uint16_t, false>(a, mb, interp, weight_mode, std_mode, s);
+    return with_code_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return packed ? mi_dispatch_multi<T, true>(a, mb, interp, weight_mode, std_mode, s)
+                      : mi_dispatch_multi<T, false>(a, mb, interp, weight_mode, std_mode, s);
+    });
 }
 
 }  // namespace ct

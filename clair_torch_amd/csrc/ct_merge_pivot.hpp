@@ -719,16 +719,7 @@ static size_t pivot_lds_bytes(const MergeArgs &a, const PivotArgs &x, int interp
     return table + 2 * sizeof(float) * (size_t)a.batch;
 }
 
-// f(INTERP, WEIGHT, STD) with the three run-time modes of a merge as compile-time constants.
-template <typename F>
-static int with_merge_modes(int interp, int weight_mode, int std_mode, F &&f)
-{
-    return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
-        return with_enum<CT_WEIGHT_NONE, CT_WEIGHT_GAUSS>(weight_mode, [&](auto W) {
-            return with_enum<CT_STD_NONE, CT_STD_CONSTANT, CT_STD_MULTIPLIER, CT_STD_EXPLICIT>(std_mode, [&](auto S) { return f(I, W, S); });
-        });
-    });
-}
+// (with_merge_modes, the dispatch on the three modes of a merge, is in ct_merge.hpp)
 
 // The several-batches launch of ct_hdr_merge_batches (ct_merge_multi.hip): packets of kPivotV, state-carrying instantiations.
 int merge_pivot_multi(const MergeArgs &a, const PivotArgs &px, int dtype, bool clamp, int interp, int weight_mode, int std_mode,

@@ -152,3 +152,35 @@ def test_compute_hdr_image_checks_the_keyword(bad):
     loader = DataLoader(StackDataset(torch.zeros((2, 1, 4, 4)), [1.0, 2.0]), batch_size=1, shuffle=False, collate_fn=custom_collate)
     with pytest.raises(ValueError, match="dark_batches_per_launch"):
         compute_hdr_image(loader, "cpu", dark_batches_per_launch=bad)
+
+
+def test_fallback_route_and_batch_order_statuses(lib):
+    """What the walk over the batch list answers where the scales of all batches do not fit the LDS and those of each batch do
+    (16 batches of 4, one channel, the table of LDS_EDGE_POINTS), without a launch."""
+    from clair_torch_amd import _native as nv
+    FIRST, FINAL, ONE = nv.MERGE_FIRST_BATCH, nv.MERGE_FINALIZE, nv.MERGE_REQUIRE_ONE_LAUNCH
+    fake = 0x1000
+    fakep = ctypes.c_void_p(fake)
+    edge = nv.Icrf(lut_dev=0x2000, n_points=LDS_EDGE_POINTS, interp=nv.INTERP_LINEAR)
+    state = (fakep,) * 3
+
+    def call(sizes=(4,) * 16, stacks=None, dark_batches=None, state=(None, None, None), flags=FIRST | FINAL):
+        k = len(sizes)
+        geom = _geom(c=1)
+        stacks = [fake] * k if stacks is None else stacks
+        dark_batches = list(sizes) if dark_batches is None else dark_batches
+        return lib.ct_hdr_merge_dark_batches(_pointers(stacks), (ctypes.c_int32 * k)(*sizes), k, nv.DTYPE_U16, 65535.0, ctypes.byref(geom),
+                                             None, None, nv.STD_MULTIPLIER, 0.05, _pointers([fake] * k), _pointers([fake] * k),
+                                             (ctypes.c_int32 * k)(*dark_batches), 0.05, 50.0, fakep, ctypes.byref(edge), nv.WEIGHT_GAUSS,
+                                             state[0], state[1], state[2], fakep, fakep, flags, None)
+
+    assert call(flags=FIRST | FINAL | ONE, state=state) == UNSUPPORTED
+    assert call(flags=FIRST | FINAL | ONE) == UNSUPPORTED
+    assert call(flags=FIRST | FINAL) == UNSUPPORTED                # a whole merge, but every launch but the last leaves a state
+    assert call(flags=0) == INVALID and call(flags=FIRST) == INVALID and call(flags=FINAL) == INVALID   # (every batch's own refusal)
+    # an empty batch is not skipped: the single-batch entry point refuses it
+    holed = (4,) * 7 + (0,) + (4,) * 8
+    assert call(sizes=holed, flags=FIRST | FINAL | ONE, state=state) == INVALID and call(sizes=holed, state=state) == INVALID
+    # the first batch's refusal before the second's, either way round
+    assert call(sizes=(4, 3), dark_batches=[1, 2]) == UNSUPPORTED and call(sizes=(4, 3), dark_batches=[2, 1]) == INVALID
+    assert call(sizes=(1 << 16, 2), stacks=[fake, None]) == TOO_LARGE and call(sizes=(2, 1 << 16), stacks=[None, fake]) == INVALID

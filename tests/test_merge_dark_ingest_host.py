@@ -447,3 +447,36 @@ def test_keywords_under_the_byte_cap(events, routed, monkeypatch):
     monkeypatch.setattr(routed.hdr_merge, "DARK_QUEUE_BYTES", 3 * (one + 2 * 3 * 4 * 6 * 2))
     assert events.run(existing=(), fused_dark_ingest=False, dark_batches_per_launch=16) == \
         [T, H] * 4 + [ST, _m("dark_batches", 3, 0, False)] + [T, H] * 2 + [_m("dark_batches", 3, 0, True)]
+
+
+def test_fallback_route_and_batch_order_statuses(lib):
+    """What the walk over the batch list answers where the scales of all batches do not fit the LDS and those of each batch do
+    (16 batches of 4, one channel, the table of LDS_EDGE_POINTS), without a launch."""
+    from clair_torch_amd import _native as nv
+    FIRST, FINAL, ONE = nv.MERGE_FIRST_BATCH, nv.MERGE_FINALIZE, nv.MERGE_REQUIRE_ONE_LAUNCH
+    fake = 0x1000
+    fakep = ctypes.c_void_p(fake)
+    edge = nv.Icrf(lut_dev=0x2000, n_points=LDS_EDGE_POINTS, interp=nv.INTERP_LINEAR)
+    state = (fakep,) * 3
+    stage = (nv.IngestStage * 1)(nv.IngestStage(kind=nv.INGEST_AFFINE, sub=64.0, div=1000.0, mul=1.0, add=0.0))
+
+    def call(sizes=(4,) * 16, frames=None, dark_batches=None, state=(None, None, None), flags=FIRST | FINAL):
+        k = len(sizes)
+        geom = _geom(c=1)
+        frames = [fake] * k if frames is None else frames
+        dark_batches = list(sizes) if dark_batches is None else dark_batches
+        return lib.ct_hdr_merge_dark_ingest_batches(
+            _pointers(frames), (ctypes.c_int32 * k)(*sizes), k, nv.DTYPE_U16, ctypes.byref(geom), stage, 1, None, None, None,
+            nv.STD_MULTIPLIER, 0.05, _pointers([fake] * k), _pointers([fake] * k), (ctypes.c_int32 * k)(*dark_batches), 0.05, 50.0, fakep,
+            ctypes.byref(edge), nv.WEIGHT_GAUSS, state[0], state[1], state[2], fakep, fakep, flags, None)
+
+    assert call(flags=FIRST | FINAL | ONE, state=state) == TOO_LARGE
+    assert call(flags=FIRST | FINAL | ONE) == TOO_LARGE            # the flag is looked at before the state
+    assert call(flags=FIRST | FINAL) == UNSUPPORTED                # a whole merge, but every launch but the last leaves a state
+    assert call(flags=0) == INVALID and call(flags=FIRST) == INVALID and call(flags=FINAL) == INVALID   # (every batch's own refusal)
+    # an empty batch is not skipped: ct_hdr_merge_dark_batch's judgement refuses it
+    holed = (4,) * 7 + (0,) + (4,) * 8
+    assert call(sizes=holed, flags=FIRST | FINAL | ONE, state=state) == INVALID and call(sizes=holed, state=state) == INVALID
+    # the first batch's refusal before the second's, either way round
+    assert call(sizes=(4, 3), dark_batches=[1, 2]) == UNSUPPORTED and call(sizes=(4, 3), dark_batches=[2, 1]) == INVALID
+    assert call(sizes=(1 << 16, 2), frames=[fake, None]) == TOO_LARGE and call(sizes=(2, 1 << 16), frames=[None, fake]) == INVALID

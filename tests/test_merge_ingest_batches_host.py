@@ -169,3 +169,38 @@ def test_front_end_without_a_device():
         ops.hdr_merge_ingest_batches(frames, stages, expo, lut=lut, consts=[None])
     with pytest.raises(ValueError, match="at most 16"):
         ops.hdr_merge_ingest_batches(frames * 9, stages, expo * 9, lut=lut)
+
+
+def test_fallback_route_and_batch_order_statuses(lib):
+    """What the walk over the batch list answers where the list cannot be one launch, without a launch: one channel and a LINEAR
+    table of 20470 points leave 80 B of the LDS, so the scales of one batch of 4 fit and those of the whole list do not."""
+    from clair_torch_amd import _native as nv
+    from test_merge_dark_batches_host import LDS_EDGE_POINTS
+    FIRST, FINAL, ONE = nv.MERGE_FIRST_BATCH, nv.MERGE_FINALIZE, nv.MERGE_REQUIRE_ONE_LAUNCH
+    fake = 0x1000
+    fakep = ctypes.c_void_p(fake)
+    edge = nv.Icrf(lut_dev=0x2000, n_points=LDS_EDGE_POINTS, interp=nv.INTERP_LINEAR)
+    linear = nv.Icrf(lut_dev=0x2000, n_points=256, interp=nv.INTERP_LINEAR)
+    one = _stages(nv.INGEST_AFFINE)
+    state = (fakep, fakep, None)   # no uncertainties: no variance state
+
+    def call(frames=(fake,) * 16, sizes=(4,) * 16, geom=None, model=edge, state=(None, None, None), flags=FIRST | FINAL):
+        geom = _geom(c=1) if geom is None else geom
+        return lib.ct_hdr_merge_ingest_batches((ctypes.c_void_p * len(frames))(*frames), (ctypes.c_int32 * len(sizes))(*sizes), len(sizes),
+                                               nv.DTYPE_U16, ctypes.byref(geom), one, 1, None, None, nv.STD_NONE, 0.05, fakep,
+                                               ctypes.byref(model), nv.WEIGHT_GAUSS, state[0], state[1], state[2], fakep, fakep, flags, None)
+
+    assert 8 * LDS_EDGE_POINTS + 8 * 4 <= 160 * 1024 < 8 * LDS_EDGE_POINTS + 8 * 60
+    # one launch per batch: refused with the flag, and without a state
+    assert call(flags=FIRST | FINAL | ONE, state=state) == UNSUPPORTED
+    assert call(flags=FIRST | FINAL | ONE) == UNSUPPORTED          # the flag is looked at before the state
+    assert call(flags=FIRST | FINAL) == INVALID                    # a whole merge, but every launch but the last leaves a state
+    assert call(flags=0) == INVALID and call(flags=FIRST) == INVALID and call(flags=FINAL) == INVALID   # (every batch's own refusal)
+    # an empty batch among batches with frames is skipped: its NULL frames are no fault, the other 15 are still too many
+    holed = dict(frames=(fake,) * 7 + (None,) + (fake,) * 8, sizes=(4,) * 7 + (0,) + (4,) * 8)
+    assert call(flags=FIRST | FINAL | ONE, state=state, **holed) == UNSUPPORTED and call(**holed) == INVALID
+    assert call(frames=(fake,) * 7 + (None,) + (fake,) * 8, flags=FIRST | FINAL | ONE, state=state) == INVALID   # ... with frames it is one
+    # every batch is judged before any pointer, the first batch's refusal before the second's
+    assert call(sizes=(1 << 20, -1), frames=(fake, fake), model=linear) == TOO_LARGE
+    assert call(sizes=(-1, 1 << 20), frames=(fake, fake), model=linear) == INVALID
+    assert call(sizes=(1 << 20, 2), frames=(None, None), model=linear) == TOO_LARGE
