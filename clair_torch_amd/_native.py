@@ -34,7 +34,8 @@ EXPORTS = ("ct_abi_version", "ct_error_string", "ct_hdr_merge_batch", "ct_hdr_me
            "ct_hdr_merge_ingest_batches", "ct_ingest_extrema_frames_workspace", "ct_ingest_extrema_frames",
            "ct_linearize_ingest_data", "ct_pair_residual_ingest_fwd", "ct_pair_residual_ingest_bwd", "ct_linearize_ingest_strided",
            "ct_video_stats_batches", "ct_video_stats_ingest_batches", "ct_hdr_merge_dark_batch", "ct_linearize_dark",
-           "ct_hdr_merge_dark_batches", "ct_linearize_dark_ingest", "ct_hdr_merge_dark_ingest_batches")
+           "ct_hdr_merge_dark_batches", "ct_linearize_dark_ingest", "ct_hdr_merge_dark_ingest_batches",
+           "ct_linearize_std_flat", "ct_linearize_ingest_flat", "ct_linearize_ingest_strided_flat")
 
 
 class Geometry(ctypes.Structure):
@@ -159,6 +160,14 @@ def load():
     lib.ct_linearize_ingest_data.argtypes = [vp, i32, i64, gp, ctypes.POINTER(IngestStage), i32, vp, i32, f32, ip, vp, vp, vp, vp]
     lib.ct_linearize_ingest_strided.restype = i32
     lib.ct_linearize_ingest_strided.argtypes = [vp, i32, i64, gp, i32, ctypes.POINTER(IngestStage), i32, vp, i32, f32, ip, vp, vp, vp, vp]
+    # ... _flat: the parent's arguments, then flat, flat std (or NULL) and the C channel means in front of the stream
+    lib.ct_linearize_std_flat.restype = i32
+    lib.ct_linearize_std_flat.argtypes = [vp, i32, f32, i64, gp, vp, i32, f32, ip, vp, vp, vp, vp, vp, vp]
+    lib.ct_linearize_ingest_flat.restype = i32
+    lib.ct_linearize_ingest_flat.argtypes = [vp, i32, i64, gp, ctypes.POINTER(IngestStage), i32, vp, i32, f32, ip, vp, vp, vp, vp, vp, vp, vp]
+    lib.ct_linearize_ingest_strided_flat.restype = i32
+    lib.ct_linearize_ingest_strided_flat.argtypes = [vp, i32, i64, gp, i32, ctypes.POINTER(IngestStage), i32, vp, i32, f32, ip, vp, vp, vp, vp,
+                                                     vp, vp, vp]
     lib.ct_hdr_merge_ingest_batch.restype = i32
     lib.ct_hdr_merge_ingest_batch.argtypes = [vp, i32, i32, gp, ctypes.POINTER(IngestStage), i32, vp, vp, i32, f32, vp, ip, i32, vp, vp,
                                               vp, vp, vp, u32, vp]

@@ -19,6 +19,7 @@
 // of four elements as floats; lin_dispatch / lin_launch / lin_launch_grid are the one host path of the four routes.
 #include <algorithm>
 #include "ct_args.hpp"
+#include "ct_linearize_ingest.hpp"  // the flat-field epilogue of the FLAT instantiations (LinFlat, WithFlat, li_flat1)
 
 namespace ct {
 
@@ -60,8 +61,11 @@ __device__ __forceinline__ void load_frame4(const void *frames, int64_t frame_of
 }
 
 // grid.x covers the packets of one frame, grid.y walks frames
-template <typename T, int V, int INTERP, int STD, bool WRITE_STD>
-__global__ __launch_bounds__(kBlock) void linearize_kernel(const LinArgs a)
+// FLAT (ct_linearize_std_flat; WRITE_STD): the flat-field correction of ct_flatfield_apply on every (lin, std) before its store.
+// The flat field is planar (C, H_tile, W) like an output frame, so the element's planar index is its index, and it does not
+// depend on the frame: every kernel loads what its thread needs once, in front of the frame loop.
+template <typename T, int V, int INTERP, int STD, bool WRITE_STD, bool FLAT>
+__global__ __launch_bounds__(kBlock) void linearize_kernel(const flat_args_t<LinArgs, FLAT> a)
 {
     extern __shared__ __align__(16) char lds[];
     constexpr bool kRanged = sizeof(T) != 4;
@@ -90,6 +94,16 @@ __global__ __launch_bounds__(kBlock) void linearize_kernel(const LinArgs a)
             uint32_t qg;
             a.tile.locate(a.tile.planar_index(q0 + e), ch, qg);
             row_off[e] = lut_row<INTERP>(qg, ch, C) * L * kEntry;
+        }
+    }
+    [[maybe_unused]] float fl[V], fls[V], fm[V];
+    if constexpr (FLAT) {
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const uint32_t pi = a.tile.planar_index(q0 + e);
+            fl[e] = a.ff.flat[pi];
+            fls[e] = a.ff.flat_std ? a.ff.flat_std[pi] : 0.0f;
+            fm[e] = a.ff.mean[pi / a.tile.plane_local];
         }
     }
     for (uint32_t f = blockIdx.y; f < a.n_frames; f += gridDim.y) {
@@ -149,6 +163,15 @@ __global__ __launch_bounds__(kBlock) void linearize_kernel(const LinArgs a)
                 }
             }
         }
+        if constexpr (FLAT) {
+            if (a.ff.flat_std) {  // (wave-uniform)
+#pragma unroll
+                for (int e = 0; e < V; ++e) li_flat1<true>(lo.v[e], so.v[e], fl[e], fls[e], fm[e]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < V; ++e) li_flat1<false>(lo.v[e], so.v[e], fl[e], 0.0f, fm[e]);
+            }
+        }
         // interleaved input -> planar outputs, element-wise stores (packets are interleaved input: no alignment asked of
         // out_stride)
         if (V > 1 || a.tile.layout != CT_LAYOUT_NCHW) {
@@ -172,8 +195,8 @@ __global__ __launch_bounds__(kBlock) void linearize_kernel(const LinArgs a)
 // store instructions; the pixel-owning RGB kernel below, whose stores are dense, ran the same C4 workload in 0.70 ms
 // against 0.84 ms (profiles/r03_layout_ingest.md) -- this kernel gives the planar layout the same access shape.
 // Per-element arithmetic is that of linearize_sample, spelled out (bit-identical results).  q_count: a multiple of 4.
-template <typename T, int K, int INTERP, int STD, bool WRITE_STD>
-__global__ __launch_bounds__(kBlock) void linearize_planar_kernel(const LinArgs a)
+template <typename T, int K, int INTERP, int STD, bool WRITE_STD, bool FLAT>
+__global__ __launch_bounds__(kBlock) void linearize_planar_kernel(const flat_args_t<LinArgs, FLAT> a)
 {
     extern __shared__ __align__(16) char lds[];
     constexpr bool kRanged = sizeof(T) != 4;
@@ -186,6 +209,7 @@ __global__ __launch_bounds__(kBlock) void linearize_planar_kernel(const LinArgs 
     uint32_t q0[K];
     bool live[K];
     int row_off[K][4];
+    [[maybe_unused]] float fl[K][4], fls[K][4], fm[K][4];  // FLAT: flat field, its uncertainty (or 0) and its mean per element
     const int skip_mod = (int)(a.tile.chan_skip % (uint32_t)C);
 #pragma unroll
     for (int k = 0; k < K; ++k) {
@@ -200,6 +224,7 @@ __global__ __launch_bounds__(kBlock) void linearize_planar_kernel(const LinArgs 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             row_off[k][e] = (INTERP == CT_INTERP_LOOKUP ? ch : r) * L * kEntry;
+            if constexpr (FLAT) fm[k][e] = a.ff.mean[ch];
             int inc = 1;
             if (++off == a.tile.plane_local) {
                 off = 0;
@@ -208,6 +233,10 @@ __global__ __launch_bounds__(kBlock) void linearize_planar_kernel(const LinArgs 
             }
             r += inc;
             r = r >= C ? r - C : r;
+        }
+        if constexpr (FLAT) {  // (q0[k] .. q0[k] + 3 lie inside the frame for a packet that is not live, too)
+            __builtin_memcpy(fl[k], a.ff.flat + q0[k], sizeof(fl[k]));
+            if (a.ff.flat_std) __builtin_memcpy(fls[k], a.ff.flat_std + q0[k], sizeof(fls[k]));
         }
     }
     if (!live[0]) return;
@@ -248,6 +277,19 @@ __global__ __launch_bounds__(kBlock) void linearize_planar_kernel(const LinArgs 
                         if (so[k].v[e] < 1e-18f && so[k].v[e] != 0.0f) so[k].v[e] = sqrtf(so[k].v[e] * so[k].v[e]);
             }
         }
+        if constexpr (FLAT) {
+            if (a.ff.flat_std) {  // (wave-uniform)
+#pragma unroll
+                for (int k = 0; k < K; ++k)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) li_flat1<true>(lo[k].v[e], so[k].v[e], fl[k][e], fls[k][e], fm[k][e]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < K; ++k)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) li_flat1<false>(lo[k].v[e], so[k].v[e], fl[k][e], 0.0f, fm[k][e]);
+            }
+        }
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             if (!live[k]) continue;
@@ -264,8 +306,8 @@ __global__ __launch_bounds__(kBlock) void linearize_planar_kernel(const LinArgs 
 // element-per-thread mapping of linearize_kernel scatters 4-byte stores over three planes and pays three runtime divisions
 // per element: 2.09 ms against 0.85 ms for the planar layout on C4 (profiles/r03_layout_ingest.md).  Per-element arithmetic
 // is linearize_sample, so results are bit-identical to the planar path.  q_begin / q_count are multiples of 12.
-template <typename T, int INTERP, int STD, bool WRITE_STD>
-__global__ __launch_bounds__(kBlock) void linearize_rgb_kernel(const LinArgs a)
+template <typename T, int INTERP, int STD, bool WRITE_STD, bool FLAT>
+__global__ __launch_bounds__(kBlock) void linearize_rgb_kernel(const flat_args_t<LinArgs, FLAT> a)
 {
     extern __shared__ __align__(16) char lds[];
     constexpr bool kRanged = sizeof(T) != 4;
@@ -295,6 +337,17 @@ __global__ __launch_bounds__(kBlock) void linearize_rgb_kernel(const LinArgs a)
     for (int k = 0; k < 12; ++k) {
         const uint32_t j = k / 3, cm = k % 3, c = bgr ? 2u - cm : cm;
         row_off[k] = (int)(INTERP == CT_INTERP_LOOKUP ? c : (c * pg + mrow + j) % 3u) * L * kEntry;
+    }
+    // FLAT: the four pixels of this thread in every plane of the flat field and of its uncertainty (lanes past the end own none)
+    [[maybe_unused]] float fl[3][4], fls[3][4];
+    if constexpr (FLAT) {
+        if (active) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                __builtin_memcpy(fl[c], a.ff.flat + (int64_t)c * a.tile.plane_local + pix0, sizeof(fl[c]));
+                if (a.ff.flat_std) __builtin_memcpy(fls[c], a.ff.flat_std + (int64_t)c * a.tile.plane_local + pix0, sizeof(fls[c]));
+            }
+        }
     }
     for (uint32_t f = blockIdx.y; f < a.n_frames; f += gridDim.y) {
         float xin[12];
@@ -342,6 +395,16 @@ __global__ __launch_bounds__(kBlock) void linearize_rgb_kernel(const LinArgs a)
                 lo.v[j] = lin[3 * j + cm];
                 so.v[j] = sd[3 * j + cm];
             }
+            if constexpr (FLAT) {
+                const float M = a.ff.mean[c];
+                if (a.ff.flat_std) {  // (wave-uniform)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) li_flat1<true>(lo.v[j], so.v[j], fl[c][j], fls[c][j], M);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) li_flat1<false>(lo.v[j], so.v[j], fl[c][j], 0.0f, M);
+                }
+            }
             store_stream(reinterpret_cast<LPacket<float, 4> *>(a.lin_out + obase + (int64_t)c * a.tile.plane_local), lo);
             if constexpr (WRITE_STD)
                 store_stream(reinterpret_cast<LPacket<float, 4> *>(a.std_out + obase + (int64_t)c * a.tile.plane_local), so);
@@ -355,8 +418,8 @@ constexpr int kLinV = 8;        // elements per thread of linearize_kernel's pac
 constexpr int kLinPackets = 3;  // packets per thread of linearize_planar_kernel (12 elements, like the RGB kernel)
 
 // What every launch shares; `per_block`: elements of one frame per workgroup (q_count is a multiple of a thread's share)
-template <typename Kernel>
-static int lin_launch_grid(Kernel kernel, const LinArgs &a, uint32_t per_block, size_t lds, hipStream_t s)
+template <typename Kernel, typename Args>
+static int lin_launch_grid(Kernel kernel, const Args &a, uint32_t per_block, size_t lds, hipStream_t s)
 {
     if (a.q_count == 0 || a.n_frames == 0) return CT_OK;
     const uint32_t gx = (uint32_t)(((uint64_t)a.q_count + per_block - 1) / per_block);
@@ -370,25 +433,32 @@ static int lin_launch_grid(Kernel kernel, const LinArgs &a, uint32_t per_block, 
     return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
 }
 
-template <typename T, int ROUTE, int INTERP, int STD, bool WRITE_STD>
-static int lin_launch(const LinArgs &a, hipStream_t s)
+// Args: LinArgs, or WithFlat<LinArgs> for the FLAT instantiations, which always write a std (ct_linearize_std_flat refuses a
+// call without one): no kernel for FLAT without WRITE_STD
+template <typename T, int ROUTE, int INTERP, int STD, bool WRITE_STD, typename Args>
+static int lin_launch(const Args &a, hipStream_t s)
 {
+    constexpr bool FLAT = !std::is_same_v<Args, LinArgs>;
+    if constexpr (FLAT && !WRITE_STD) {
+        return CT_ERR_INVALID_ARGUMENT;
+    } else {
     const size_t lut = lut_lds_bytes(INTERP, a.channels, a.n_points);
     if constexpr (ROUTE == kLinRgb) {  // (channels == 3)  LUT | 3 KB of exchange space per wavefront
         const size_t lds = (lut + 15 & ~(size_t)15) + (size_t)(kBlock / 64) * 768 * sizeof(float);
-        return lin_launch_grid(linearize_rgb_kernel<T, INTERP, STD, WRITE_STD>, a, 12 * kBlock, lds, s);
+        return lin_launch_grid(linearize_rgb_kernel<T, INTERP, STD, WRITE_STD, FLAT>, a, 12 * kBlock, lds, s);
     } else if constexpr (ROUTE == kLinPlanar) {
-        return lin_launch_grid(linearize_planar_kernel<T, kLinPackets, INTERP, STD, WRITE_STD>, a, 4 * kLinPackets * kBlock, lut, s);
+        return lin_launch_grid(linearize_planar_kernel<T, kLinPackets, INTERP, STD, WRITE_STD, FLAT>, a, 4 * kLinPackets * kBlock, lut, s);
     } else {
         constexpr int V = ROUTE == kLinPacket ? kLinV : 1;
-        return lin_launch_grid(linearize_kernel<T, V, INTERP, STD, WRITE_STD>, a, V * kBlock, lut, s);
+        return lin_launch_grid(linearize_kernel<T, V, INTERP, STD, WRITE_STD, FLAT>, a, V * kBlock, lut, s);
+    }
     }
 }
 
 // interp / std_mode / write_std -> template arguments.  The RGB kernel has no CT_STD_EXPLICIT (explicit std stacks with
 // interleaved frames go through the element-wise kernel, lin_typed): it answers CT_ERR_UNSUPPORTED for a mode it does not hold.
-template <typename T, int ROUTE>
-static int lin_dispatch(const LinArgs &a, int interp, int std_mode, bool write_std, hipStream_t s)
+template <typename T, int ROUTE, typename Args>
+static int lin_dispatch(const Args &a, int interp, int std_mode, bool write_std, hipStream_t s)
 {
     return with_enum<CT_INTERP_LOOKUP, CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
         auto launch = [&](auto S, auto W) { return lin_launch<T, ROUTE, I, S, W>(a, s); };
@@ -401,8 +471,8 @@ static int lin_dispatch(const LinArgs &a, int interp, int std_mode, bool write_s
     });
 }
 
-template <typename T>
-static int lin_typed(LinArgs a, uint32_t Q, int interp, int std_mode, bool write_std, hipStream_t s)
+template <typename T, typename Args>
+static int lin_typed(Args a, uint32_t Q, int interp, int std_mode, bool write_std, hipStream_t s)
 {
     // Elements per thread: 8 integer codes (two typed loads) or 8 float pixels (two 16-byte loads).  16 codes per thread was
     // measured 2.6x SLOWER on C4 (2.21 against 0.85 ms, profiles/r03_layout_ingest.md) although the pixel-owning RGB kernel
@@ -548,11 +618,13 @@ static int bwd_launch(const BwdArgs &a, hipStream_t s)
 
 extern "C" int ct_norm_constants(float max_code, float *hi, float *lo);
 
-extern "C" int ct_linearize_std(const void *frames_dev, int32_t dtype, float max_code, int64_t n_frames,
-                                const ct_geometry *geom, const float *std_dev, int32_t std_mode, float std_value,
-                                const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev, void *stream)
+namespace ct {
+
+// ff NULL: ct_linearize_std; else ct_linearize_std_flat, whose own refusals come behind every one of the parent's
+static int linearize_std(const void *frames_dev, int32_t dtype, float max_code, int64_t n_frames, const ct_geometry *geom,
+                         const float *std_dev, int32_t std_mode, float std_value, const ct_icrf *icrf, float *lin_out_dev,
+                         float *std_out_dev, void *stream, const LinFlat *ff)
 {
-    using namespace ct;
     if (!frames_dev || !icrf || !lin_out_dev || n_frames <= 0 || n_frames > 0x7fffffff) return CT_ERR_INVALID_ARGUMENT;
     int rc = geom ? check_stack_geometry(geom) : CT_ERR_INVALID_ARGUMENT;
     if (rc != CT_OK) return rc;
@@ -560,7 +632,7 @@ extern "C" int ct_linearize_std(const void *frames_dev, int32_t dtype, float max
     if (!icrf_ok(icrf) || !std_mode_ok(std_mode, std_dev)) return CT_ERR_INVALID_ARGUMENT;
     // linearization.py:100-105: autograd.grad raises for LOOKUP (no gradient path) when stds are present
     if (std_mode != CT_STD_NONE && interp == CT_INTERP_LOOKUP) return CT_ERR_NO_GRADIENT_PATH;
-    LinArgs a{};
+    WithFlat<LinArgs> a{};
     a.frames = frames_dev;
     a.std_stack = std_mode == CT_STD_EXPLICIT ? std_dev : nullptr;
     a.lut = icrf->lut_dev;
@@ -576,16 +648,43 @@ extern "C" int ct_linearize_std(const void *frames_dev, int32_t dtype, float max
     const uint32_t Q = (uint32_t)local_elements(geom);
     const bool write_std = std_out_dev != nullptr;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    auto typed = [&](auto zero) {
+        using T = decltype(zero);
+        if (!ff) return lin_typed<T, LinArgs>(a, Q, interp, std_mode, write_std, s);
+        if (!li_flat_ok(*ff, std_out_dev)) return (int)CT_ERR_INVALID_ARGUMENT;
+        a.ff = *ff;
+        return lin_typed<T, WithFlat<LinArgs>>(a, Q, interp, std_mode, true, s);
+    };
     switch (dtype) {
         case CT_DTYPE_U8:
             if (ct_norm_constants(max_code, &a.norm.hi, &a.norm.lo) != CT_OK) return CT_ERR_UNSUPPORTED;
-            return lin_typed<uint8_t>(a, Q, interp, std_mode, write_std, s);
+            return typed(uint8_t{});
         case CT_DTYPE_U16:
             if (ct_norm_constants(max_code, &a.norm.hi, &a.norm.lo) != CT_OK) return CT_ERR_UNSUPPORTED;
-            return lin_typed<uint16_t>(a, Q, interp, std_mode, write_std, s);
-        case CT_DTYPE_F32: return lin_typed<float>(a, Q, interp, std_mode, write_std, s);
+            return typed(uint16_t{});
+        case CT_DTYPE_F32: return typed(float{});
     }
     return CT_ERR_UNSUPPORTED;
+}
+
+}  // namespace ct
+
+extern "C" int ct_linearize_std(const void *frames_dev, int32_t dtype, float max_code, int64_t n_frames,
+                                const ct_geometry *geom, const float *std_dev, int32_t std_mode, float std_value,
+                                const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev, void *stream)
+{
+    return ct::linearize_std(frames_dev, dtype, max_code, n_frames, geom, std_dev, std_mode, std_value, icrf, lin_out_dev, std_out_dev,
+                             stream, nullptr);
+}
+
+extern "C" int ct_linearize_std_flat(const void *frames_dev, int32_t dtype, float max_code, int64_t n_frames,
+                                     const ct_geometry *geom, const float *std_dev, int32_t std_mode, float std_value,
+                                     const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev, const float *flat_dev,
+                                     const float *flat_std_dev, const float *flat_mean_dev, void *stream)
+{
+    const ct::LinFlat ff = {flat_dev, flat_std_dev, flat_mean_dev};
+    return ct::linearize_std(frames_dev, dtype, max_code, n_frames, geom, std_dev, std_mode, std_value, icrf, lin_out_dev, std_out_dev,
+                             stream, &ff);
 }
 
 extern "C" int ct_linearize_fwd(const float *x_dev, int64_t n_images, const ct_geometry *geom, const ct_icrf *icrf,

@@ -33,8 +33,8 @@
 
 namespace ct {
 
-template <typename T, int INTERP, int STD, bool WRITE_STD>
-__global__ __launch_bounds__(kBlock) void linearize_ingest_planar_kernel(const LinIngestArgs a)
+template <typename T, int INTERP, int STD, bool WRITE_STD, bool FLAT>
+__global__ __launch_bounds__(kBlock) void linearize_ingest_planar_kernel(const flat_args_t<LinIngestArgs, FLAT> a)
 {
     extern __shared__ __align__(16) char lds[];
     const int C = (int)a.channels, L = (int)a.n_points;
@@ -49,6 +49,14 @@ __global__ __launch_bounds__(kBlock) void linearize_ingest_planar_kernel(const L
     const int64_t head = (int64_t)(((0 - reinterpret_cast<uintptr_t>(lin)) & 15u) / sizeof(float));
     const uint32_t row0 = c * a.plane_global + a.base;  // global flat index of this plane's first local element (< 2^31)
     const float dsub = a.consts ? a.consts[4 * (int64_t)f] : 0.0f, ddiv = a.consts ? a.consts[4 * (int64_t)f + 1] : 1.0f;
+    // FLAT: this plane of the flat field, of its uncertainty (or NULL) and its mean -- wave-uniform
+    [[maybe_unused]] const float *fl = nullptr, *fls = nullptr;
+    [[maybe_unused]] float M = 0.0f;
+    if constexpr (FLAT) {
+        fl = a.ff.flat + (int64_t)c * a.plane;
+        fls = a.ff.flat_std ? a.ff.flat_std + (int64_t)c * a.plane : nullptr;
+        M = a.ff.mean[c];
+    }
 #pragma unroll 1
     for (int k = 0; k < kLiSlots; ++k) {
         const int64_t slot = ((int64_t)blockIdx.x * kLiSlots + k) * kBlock + threadIdx.x;
@@ -71,13 +79,14 @@ __global__ __launch_bounds__(kBlock) void linearize_ingest_planar_kernel(const L
         const int r = C == 3 ? (int)(qg % 3u) : (int)(qg % a.channels);
         LinIngestPacket lo, so;
         li_sample4<INTERP, STD, WRITE_STD>(v, sg, lds, L, C, (int)c, r, a.std_value, lo, so);
+        if constexpr (FLAT) li_flat4(lo, so, fl, fls, p0, n, M);
         li_store(lin + p0, lo, n);
         if constexpr (WRITE_STD) li_store(sdo + p0, so, n);
     }
 }
 
-template <typename T, int INTERP, int STD, bool WRITE_STD>
-__global__ __launch_bounds__(kBlock) void linearize_ingest_packed3_kernel(const LinIngestArgs a)
+template <typename T, int INTERP, int STD, bool WRITE_STD, bool FLAT>
+__global__ __launch_bounds__(kBlock) void linearize_ingest_packed3_kernel(const flat_args_t<LinIngestArgs, FLAT> a)
 {
     extern __shared__ __align__(16) char lds[];
     constexpr int C = 3;
@@ -119,6 +128,7 @@ __global__ __launch_bounds__(kBlock) void linearize_ingest_packed3_kernel(const 
             const int r = (int)((c * pg3 + m3) % 3u);
             LinIngestPacket lo, so;
             li_sample4<INTERP, STD, WRITE_STD>(v, sg, lds, L, C, (int)c, r, a.std_value, lo, so);
+            if constexpr (FLAT) li_flat4(lo, so, a.ff.flat, a.ff.flat_std, po, n, a.ff.mean[c]);  // (C, plane): po of plane 0
             li_store(lin + po, lo, n);
             if constexpr (WRITE_STD) li_store(sdo + po, so, n);
         }
@@ -129,16 +139,27 @@ template <typename T, int INTERP, int STD, bool WRITE_STD>
 struct LinIngestLaunch {
     static int run(const LinIngestArgs &a, bool packed, int64_t rows, hipStream_t s)
     {
-        return li_launch_rows(packed ? linearize_ingest_packed3_kernel<T, INTERP, STD, WRITE_STD>
-                                     : linearize_ingest_planar_kernel<T, INTERP, STD, WRITE_STD>,
+        return li_launch_rows(packed ? linearize_ingest_packed3_kernel<T, INTERP, STD, WRITE_STD, false>
+                                     : linearize_ingest_planar_kernel<T, INTERP, STD, WRITE_STD, false>,
                               a, INTERP, rows, s);
+    }
+    // the flat-field epilogue always writes a std (li_flat_ok): no kernel without one
+    static int run(const WithFlat<LinIngestArgs> &a, bool packed, int64_t rows, hipStream_t s)
+    {
+        if constexpr (WRITE_STD)
+            return li_launch_rows(packed ? linearize_ingest_packed3_kernel<T, INTERP, STD, true, true>
+                                         : linearize_ingest_planar_kernel<T, INTERP, STD, true, true>,
+                                  a, INTERP, rows, s);
+        return CT_ERR_INVALID_ARGUMENT;
     }
 };
 
-// consts_dev NULL: the constant chains of ct_linearize_ingest (no AFFINE_DATA stage); else ct_linearize_ingest_data
+// consts_dev NULL: the constant chains of ct_linearize_ingest (no AFFINE_DATA stage); else ct_linearize_ingest_data.
+// ff NULL: no flat field; else ct_linearize_ingest_flat
 static int linearize_ingest(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
                             const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode, float std_value,
-                            const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev, const float *consts_dev, void *stream)
+                            const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev, const float *consts_dev, void *stream,
+                            const LinFlat *ff = nullptr)
 {
     // everything that needs no pointer into device memory first: geometry (check_ingest_geometry, no empty plane), then the
     // stack, the stage list, the model and the uncertainty mode (li_check_call)
@@ -153,7 +174,8 @@ static int linearize_ingest(const void *frames_dev, int32_t dtype, int64_t n_fra
     if (rc != CT_OK) return rc;
     if (n_frames == 0) return CT_OK;
     if (!li_pointers_ok(frames_dev, dtype, std_dev, lin_out_dev, std_out_dev)) return CT_ERR_INVALID_ARGUMENT;
-    LinIngestArgs a = {};
+    if (ff && !li_flat_ok(*ff, std_out_dev)) return CT_ERR_INVALID_ARGUMENT;
+    WithFlat<LinIngestArgs> a = {};
     a.src = frames_dev;
     a.std_in = std_mode == CT_STD_EXPLICIT ? std_dev : nullptr;
     a.lut = icrf->lut_dev;
@@ -162,11 +184,25 @@ static int linearize_ingest(const void *frames_dev, int32_t dtype, int64_t n_fra
     a.std_out = std_out_dev;
     fill_ingest_args(a, geom, icrf_points(icrf), by_channel, stages, n_stages);
     a.std_value = std_value;
-    return li_dispatch<LinIngestLaunch>(a, dtype, geom->layout != CT_LAYOUT_NCHW, rows, icrf->interp, std_mode, std_out_dev != nullptr,
-                                        static_cast<hipStream_t>(stream));
+    const bool packed = geom->layout != CT_LAYOUT_NCHW;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!ff) return li_dispatch<LinIngestLaunch>(static_cast<const LinIngestArgs &>(a), dtype, packed, rows, icrf->interp, std_mode, std_out_dev != nullptr, s);
+    a.ff = *ff;
+    return li_dispatch<LinIngestLaunch>(a, dtype, packed, rows, icrf->interp, std_mode, true, s);
 }
 
 }  // namespace ct
+
+extern "C" int ct_linearize_ingest_flat(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
+                                        const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,
+                                        float std_value, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev,
+                                        const float *consts_dev, const float *flat_dev, const float *flat_std_dev,
+                                        const float *flat_mean_dev, void *stream)
+{
+    const ct::LinFlat ff = {flat_dev, flat_std_dev, flat_mean_dev};
+    return ct::linearize_ingest(frames_dev, dtype, n_frames, geom, stages, n_stages, std_dev, std_mode, std_value, icrf, lin_out_dev,
+                                std_out_dev, consts_dev, stream, &ff);
+}
 
 extern "C" int ct_linearize_ingest(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
                                    const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,

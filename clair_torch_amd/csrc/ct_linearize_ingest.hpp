@@ -1,10 +1,12 @@
 // ct_linearize_ingest.hpp -- what the fused chain + linearization kernels share (ct_linearize_ingest.hip on dense frames,
 // ct_linearize_ingest_strided.hip on every step-th row and column of them): the argument block, the slot / span scheme of
 // a thread's 4 output elements, the sample step behind the chain (li_sample4: four linearize_sample of ct_device.hpp, the
-// step ct_linearize.hip runs, and their `tiny` fix-up), the packet store, and the host-side launch loop and dispatch over
+// step ct_linearize.hip runs, and their `tiny` fix-up), the flat-field epilogue of the FLAT instantiations behind it (li_flat1 /
+// li_flat4, which ct_linearize.hip shares), the packet store, and the host-side launch loop and dispatch over
 // element type, interpolation and uncertainty mode (with_enum, with_linearize_std).  One copy of each: the outputs of the
 // two files agree bit for bit because they run the same device functions.
 #pragma once
+#include <type_traits>
 #include "ct_args.hpp"
 #include "ct_ingest_stages.hpp"
 
@@ -34,6 +36,23 @@ struct LinIngestArgs {
 struct alignas(16) LinIngestPacket {
     float v[4];
 };
+
+// The flat field of the FLAT instantiations (ct_linearize*_flat): planar (C, plane) float32 of the OUTPUT's shape -- the
+// downscaled one behind a step, the band's rows for a row band -- and the C channel means, a constant of the run
+struct LinFlat {
+    const float *flat;
+    const float *flat_std;  // or NULL
+    const float *mean;      // (C) float32 in device memory
+};
+
+// The argument block of a kernel family with the flat field BEHIND it: the FLAT = false instantiations take the family's own
+// block, unchanged, so every offset they load from is the one they had
+template <typename Base>
+struct WithFlat : Base {
+    LinFlat ff;
+};
+template <typename Base, bool FLAT>
+using flat_args_t = std::conditional_t<FLAT, WithFlat<Base>, Base>;
 
 constexpr int kLiGroup = 4;     // output elements per packet
 constexpr int kLiSlots = 4;     // slots per thread
@@ -104,6 +123,44 @@ __device__ __forceinline__ void li_load_std(const float *sp, int n, float (&sg)[
     for (int k = 0; k < kLiGroup; ++k) sg[k] = k < n ? sp[k] : 0.0f;
 }
 
+// ---- the flat-field epilogue ------------------------------------------------------------------------------------------------
+// linearization.py:48-57,118-130 on one sample the unfused launch would have stored (behind the `tiny` fix-up): exactly the
+// expressions of flatfield_apply_kernel<float, false> (ct_flatfield.hip) with the mean a constant -- same float32 types, same
+// order, every operation rounded on its own (-ffp-contract=off) -- so the results are those of ct_flatfield_apply on the
+// stored pair, bit for bit.  `fs` is read with WITH_STD only.
+template <bool WITH_STD>
+__device__ __forceinline__ void li_flat1(float &lin, float &sd, float flat, float fs, float M)
+{
+    const float den = flat + 1e-6f;
+    const float v = lin;
+    lin = (v / den) * M;
+    float var = sd * sd;
+    if constexpr (WITH_STD) {
+        const float grad = -(M * v) / (den * den);
+        const float gs = grad * fs;
+        var = var + gs * gs;
+    }
+    sd = sqrtf(var);
+}
+
+// ... on the n <= 4 (lin, sd) of a packet at element p0 of a channel plane whose flat field starts at `flat` (`flat_std`: its
+// uncertainty or NULL, a wave-uniform branch) and whose mean is M.  The loads are li_load_std's: one 16-byte packet for a
+// whole group, element by element otherwise; lanes k >= n compute on zeros and are never stored.
+__device__ __forceinline__ void li_flat4(LinIngestPacket &lo, LinIngestPacket &so, const float *flat, const float *flat_std, int64_t p0,
+                                         int n, float M)
+{
+    float fl[kLiGroup], fs[kLiGroup];
+    li_load_std(flat + p0, n, fl);
+    if (flat_std) {
+        li_load_std(flat_std + p0, n, fs);
+#pragma unroll
+        for (int e = 0; e < kLiGroup; ++e) li_flat1<true>(lo.v[e], so.v[e], fl[e], fs[e], M);
+    } else {
+#pragma unroll
+        for (int e = 0; e < kLiGroup; ++e) li_flat1<false>(lo.v[e], so.v[e], fl[e], 0.0f, M);
+    }
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------------
 // `rows` workgroup rows (planes or frames) of `kernel`, at most kLiMaxRows per launch; Args is LinIngestArgs or derives from it
 template <typename Args>
@@ -171,6 +228,14 @@ static inline bool li_pointers_ok(const void *frames_dev, int32_t dtype, const f
 {
     return frames_dev && lin_out_dev && aligned(frames_dev, dtype_bytes(dtype)) && aligned(lin_out_dev, sizeof(float)) &&
            aligned(std_out_dev, sizeof(float)) && aligned(std_dev, sizeof(float));
+}
+
+// ... and behind those, in the _flat entry points: the flat field and its means are required, everything is aligned to its
+// element, and the correction writes a std
+static inline bool li_flat_ok(const LinFlat &ff, const float *std_out_dev)
+{
+    return ff.flat && ff.mean && std_out_dev && aligned(ff.flat, sizeof(float)) && aligned(ff.flat_std, sizeof(float)) &&
+           aligned(ff.mean, sizeof(float));
 }
 
 }  // namespace ct

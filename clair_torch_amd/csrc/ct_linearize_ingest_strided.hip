@@ -34,8 +34,8 @@ struct LinIngestStridedArgs : LinIngestArgs {  // plane, plane_global, base: of 
     uint32_t src_plane;  // planar: source elements per plane, H * W
 };
 
-template <typename T, int INTERP, int STD, bool WRITE_STD, bool PACKED>
-__global__ __launch_bounds__(kBlock) void linearize_ingest_strided_kernel(const LinIngestStridedArgs a)
+template <typename T, int INTERP, int STD, bool WRITE_STD, bool PACKED, bool FLAT>
+__global__ __launch_bounds__(kBlock) void linearize_ingest_strided_kernel(const flat_args_t<LinIngestStridedArgs, FLAT> a)
 {
     extern __shared__ __align__(16) char lds[];
     constexpr int PE = PACKED ? 3 : 1;  // elements of a source pixel = output planes of a workgroup row
@@ -101,6 +101,8 @@ __global__ __launch_bounds__(kBlock) void linearize_ingest_strided_kernel(const 
             }
             LinIngestPacket lo, so;
             li_sample4<INTERP, STD, WRITE_STD>(v, sg, lds, L, C, (int)c, r, a.std_value, lo, so);
+            // the flat field is (C, plane) of the OUTPUT: element po of plane c0 (interleaved: c0 = 0, po holds the plane)
+            if constexpr (FLAT) li_flat4(lo, so, a.ff.flat + (int64_t)c0 * a.plane, a.ff.flat_std ? a.ff.flat_std + (int64_t)c0 * a.plane : nullptr, po, n, a.ff.mean[c]);
             li_store(lin + po, lo, n);
             if constexpr (WRITE_STD) li_store(sdo + po, so, n);
         }
@@ -111,20 +113,27 @@ template <typename T, int INTERP, int STD, bool WRITE_STD>
 struct LinIngestStridedLaunch {
     static int run(const LinIngestStridedArgs &a, bool packed, int64_t rows, hipStream_t s)
     {
-        return li_launch_rows(packed ? linearize_ingest_strided_kernel<T, INTERP, STD, WRITE_STD, true>
-                                     : linearize_ingest_strided_kernel<T, INTERP, STD, WRITE_STD, false>,
+        return li_launch_rows(packed ? linearize_ingest_strided_kernel<T, INTERP, STD, WRITE_STD, true, false>
+                                     : linearize_ingest_strided_kernel<T, INTERP, STD, WRITE_STD, false, false>,
                               a, INTERP, rows, s);
+    }
+    // the flat-field epilogue always writes a std (li_flat_ok): no kernel without one
+    static int run(const WithFlat<LinIngestStridedArgs> &a, bool packed, int64_t rows, hipStream_t s)
+    {
+        if constexpr (WRITE_STD)
+            return li_launch_rows(packed ? linearize_ingest_strided_kernel<T, INTERP, STD, true, true, true>
+                                         : linearize_ingest_strided_kernel<T, INTERP, STD, true, false, true>,
+                                  a, INTERP, rows, s);
+        return CT_ERR_INVALID_ARGUMENT;
     }
 };
 
-}  // namespace ct
-
-extern "C" int ct_linearize_ingest_strided(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
-                                           int32_t step, const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev,
-                                           int32_t std_mode, float std_value, const ct_icrf *icrf, float *lin_out_dev,
-                                           float *std_out_dev, const float *consts_dev, void *stream)
+// ff NULL: ct_linearize_ingest_strided; else ct_linearize_ingest_strided_flat
+static int linearize_ingest_strided(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom, int32_t step,
+                                    const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,
+                                    float std_value, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev,
+                                    const float *consts_dev, void *stream, const LinFlat *ff)
 {
-    using namespace ct;
     // everything that needs no pointer into device memory first, as in ct_linearize_ingest: the step, the geometry of the
     // SOURCE frames (no empty plane), no row band behind a downscale, then li_check_call on the output plane
     if (!geom || !icrf || step < 1) return CT_ERR_INVALID_ARGUMENT;
@@ -139,7 +148,8 @@ extern "C" int ct_linearize_ingest_strided(const void *frames_dev, int32_t dtype
     if (rc != CT_OK) return rc;
     if (n_frames == 0) return CT_OK;
     if (!li_pointers_ok(frames_dev, dtype, std_dev, lin_out_dev, std_out_dev)) return CT_ERR_INVALID_ARGUMENT;
-    LinIngestStridedArgs a = {};
+    if (ff && !li_flat_ok(*ff, std_out_dev)) return CT_ERR_INVALID_ARGUMENT;
+    WithFlat<LinIngestStridedArgs> a = {};
     a.src = frames_dev;
     a.std_in = std_mode == CT_STD_EXPLICIT ? std_dev : nullptr;
     a.lut = icrf->lut_dev;
@@ -157,6 +167,32 @@ extern "C" int ct_linearize_ingest_strided(const void *frames_dev, int32_t dtype
     a.wo = (uint32_t)wo;
     a.row_in = (uint32_t)(geom->width * (packed ? 3 : 1));
     a.src_plane = (uint32_t)(geom->h_tile * geom->width);
-    return li_dispatch<LinIngestStridedLaunch>(a, dtype, packed, rows, icrf->interp, std_mode, std_out_dev != nullptr,
-                                               static_cast<hipStream_t>(stream));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!ff)
+        return li_dispatch<LinIngestStridedLaunch>(static_cast<const LinIngestStridedArgs &>(a), dtype, packed, rows, icrf->interp, std_mode,
+                                                   std_out_dev != nullptr, s);
+    a.ff = *ff;
+    return li_dispatch<LinIngestStridedLaunch>(a, dtype, packed, rows, icrf->interp, std_mode, true, s);
+}
+
+}  // namespace ct
+
+extern "C" int ct_linearize_ingest_strided(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
+                                           int32_t step, const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev,
+                                           int32_t std_mode, float std_value, const ct_icrf *icrf, float *lin_out_dev,
+                                           float *std_out_dev, const float *consts_dev, void *stream)
+{
+    return ct::linearize_ingest_strided(frames_dev, dtype, n_frames, geom, step, stages, n_stages, std_dev, std_mode, std_value, icrf,
+                                        lin_out_dev, std_out_dev, consts_dev, stream, nullptr);
+}
+
+extern "C" int ct_linearize_ingest_strided_flat(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
+                                                int32_t step, const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev,
+                                                int32_t std_mode, float std_value, const ct_icrf *icrf, float *lin_out_dev,
+                                                float *std_out_dev, const float *consts_dev, const float *flat_dev,
+                                                const float *flat_std_dev, const float *flat_mean_dev, void *stream)
+{
+    const ct::LinFlat ff = {flat_dev, flat_std_dev, flat_mean_dev};
+    return ct::linearize_ingest_strided(frames_dev, dtype, n_frames, geom, step, stages, n_stages, std_dev, std_mode, std_value, icrf,
+                                        lin_out_dev, std_out_dev, consts_dev, stream, &ff);
 }

@@ -84,11 +84,18 @@ FUSED_DARK_DEFAULT = True
 # run (81 ms) ahead of the fastest frame-by-frame run (139 ms); planar black level 1042 [1022 .. 1044] against 460 [313 .. 461],
 # 2.27x, 63 ms ahead of 139 ms: True.
 FUSED_DARK_INGEST_DEFAULT = True
+# linearize_dataset_generator(fused_flat=...).  The rule, set before measuring (profiles/linearize_flat.md): True only if every
+# fused run was faster than every run of the pair of launches, in every comparison made there.  Measured: per group of 16
+# 1080p frames the fused launch takes 0.41 to 0.51 of the time of linearize + flatfield_correct in all five comparisons, every
+# fused run faster (uint16 MULTIPLIER LINEAR 0.235 ms against 0.560 ms); end to end on 64 uint16 1080p frames from pinned
+# memory, which the copy-out bounds, 1029 [1004 .. 1041] frames/s against 1019 [997 .. 1035]: the ranges overlap: False.
+FUSED_FLAT_DEFAULT = False
 
 
 def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRFModelBase, flatfield_dataset=None,
                                 gpu_transforms=None, dark_field_dataset=None, output_layout: str = "planar",
-                                fused_dark: bool = FUSED_DARK_DEFAULT, fused_dark_ingest: bool = FUSED_DARK_INGEST_DEFAULT):
+                                fused_dark: bool = FUSED_DARK_DEFAULT, fused_dark_ingest: bool = FUSED_DARK_INGEST_DEFAULT,
+                                fused_flat: bool = FUSED_FLAT_DEFAULT):
     """``fused_dark`` (extension; only read with a ``dark_field_dataset``): True lets inputs that
     ``DarkField.fuses_with_linearize`` accepts take the streamed pipeline with ct_linearize_dark; False is the frame-by-frame
     route through ct_dark_field_blur and ct_linearize_std.  The yielded values are the same bit for bit.  The default and the
@@ -104,7 +111,20 @@ def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRF
     through those three.  The yielded values are the same bit for bit.  The default and the measurement behind it:
     FUSED_DARK_INGEST_DEFAULT above (True: 2.26x the frames/s of the frame-by-frame route on 64 uint16 1080p raw BGR frames
     and 2.27x on planar frames behind a black level, every fused run faster than every frame-by-frame run; the kernel alone
-    takes 0.55 to 0.63 of the time of the three launches; profiles/linearize_dark_ingest.md)."""
+    takes 0.55 to 0.63 of the time of the three launches; profiles/linearize_dark_ingest.md).
+
+    ``fused_flat`` (extension; only read with a ``flatfield_dataset``, on the streamed pipeline): True computes the flat field's
+    mean once per run (``ops.flatfield_mean``) and lets every launch without dark-field pairs -- ct_linearize_std,
+    ct_linearize_ingest / _data, ct_linearize_ingest_strided -- apply the correction to each (lin, std) before it is stored
+    (their _flat entry points: 10 + 8/F bytes per uint16 sample with derived uncertainties and F frames per launch, where the
+    launch followed by ct_flatfield_sums and ct_flatfield_apply moves 26 + 8/F; byte counts from the shapes); runs of
+    dark-matched frames keep their launch and ct_flatfield_apply, with that mean.  False is the pair of launches per group, as
+    ever; so are the frame-by-frame route and a flat field whose shape is not the outputs'.  The yielded values are the same bit
+    for bit.  The default and the measurement behind it: FUSED_FLAT_DEFAULT above (False: the fused launch takes 0.41 to 0.51 of
+    the pair's time per group, but end to end the copy-out bounds the run and the two ranges of frames/s overlap;
+    profiles/linearize_flat.md)."""
+    if not isinstance(fused_flat, bool):
+        raise TypeError(f"fused_flat must be a bool, got {type(fused_flat).__qualname__}")
     if output_layout not in ("planar", "cv"):
         raise ValueError(f"unknown output_layout {output_layout!r} (planar, cv)")
     expect(dataloader, DataLoader, "dataloader")
@@ -134,7 +154,8 @@ def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRF
         yield from _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat, flat_std, dark,
                                    output_layout == "cv")
     else:  # (a dark field only ever comes with the plan its own decisions accepted)
-        yield from _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan, output_layout == "cv", dark)
+        yield from _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan, output_layout == "cv", dark,
+                              fused_flat)
 
 
 def _pipeline_plan(probe, with_std, transforms, dev, interp, dark, fused_dark, fused_dark_ingest):
@@ -242,7 +263,7 @@ class _Slot:
         self.busy = False
 
 
-def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan, cv, dark=None):
+def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan, cv, dark=None, fused_flat=False):
     # Memory note for consumers: the yielded CPU tensors of one group (up to _GROUP_BYTES = 256 MB of output, 5 frames of
     # 1080p RGB) are views of two pinned host tensors, so keeping ONE frame alive keeps its group's pinned pages, and
     # list(generator) page-locks the whole output.  The reference hands out independent pageable .cpu() copies; copying
@@ -270,6 +291,13 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
         # gpu_transforms are applied to the value images only: explicit uncertainties arrive at the downscaled size
         raise ValueError(f"uncertainty images must have the downscaled shape {chw}, got {tuple(std_probe.shape[1:])}")
     slots = [_Slot(group, frame_shape, probe.dtype, std_shape, chw, dev, cv, data) for _ in range(_SLOTS)]
+    # fused_flat: (flat, flat std | None, flat mean) as the _flat entry points read them, the mean computed once for the run.  A
+    # flat field of another shape than the outputs is left to flatfield_correct, which refuses it
+    flat_fused = None
+    if flat is not None and fused_flat:
+        images = [None if t is None else ops._flat_image(t, dev) for t in (flat, flat_std)]
+        if tuple(images[0].shape) == tuple(chw) and (images[1] is None or images[1].shape == images[0].shape):
+            flat_fused = (images[0], images[1], ops.flatfield_mean(images[0]))
     compute = torch.cuda.current_stream(dev)
     h2d, d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
     in_flight = deque()  # (slot, n frames, pinned lin, pinned std, metas, device dark fields the group's launches read)
@@ -326,15 +354,15 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
         compute.wait_event(slot.copied_out)  # the slot's output buffers were last read by its previous copy-out
         if dark is not None:
             lin, lin_std = _linearize_dark_runs(slot, k, pairs, with_std, lut, interp, std_mode, std_value, max_code,
-                                                (stages, layout) if fused else None)
+                                                (stages, layout) if fused else None, flat_fused)
         else:
             consts = None
             if data:  # two launches for the group's k sets of constants, into the slot's own buffers
                 consts = ops.ingest_extrema_frames(slot.frames[:k], plan.prefix, layout, plan.min_val, plan.max_val,
                                                    out=slot.consts[:k], workspace=slot.workspace)
             lin, lin_std = _linearize_run(slot, 0, k, with_std, lut, interp, std_mode, std_value, max_code,
-                                          stages if fused else None, layout, step, consts)
-        if flat is not None:  # linearization.py:118-130
+                                          stages if fused else None, layout, step, consts, flat=flat_fused)
+        if flat is not None and flat_fused is None:  # linearization.py:118-130
             ops.flatfield_correct(lin, lin_std, flat, flat_std, input_is_variance=False, through_mean=False)
         if cv:
             lin = ops.export_cv(lin, out=slot.lin_cv[:k])
@@ -358,12 +386,14 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
 
 
 def _linearize_run(slot, a, b, with_std, lut, interp, std_mode, std_value, max_code, stages=None, layout="nchw", step=1,
-                   consts=None, pairs=None):
+                   consts=None, pairs=None, flat=None):
     """Frames [a:b] of ``slot`` into the same range of its output buffers, in ONE launch of the kernel they belong to.
     ``stages``: the chain of a plan whose slot holds the RAW frames in ``layout`` (explicit uncertainties planar), None for
     frames ct_linearize_std reads as they are; ``step``: a StridedDownscale the kernel applies; ``consts``: the per-frame
     constants of a data-dependent Normalize; ``pairs``: the device (dark, dark std) matched to each frame of the run, None for a
-    run without dark fields.
+    run without dark fields; ``flat``: the (flat, flat std | None, flat mean) of ``fused_flat``, applied by the launch itself on a
+    run without dark fields (ct_linearize_std_flat, ct_linearize_ingest_flat, ct_linearize_ingest_strided_flat) and by
+    ct_flatfield_apply with that mean behind the launch of a run with them.
 
         pairs   stages  step    front
         None    None    1       linearize_frames                 (ct_linearize_std)
@@ -377,9 +407,19 @@ def _linearize_run(slot, a, b, with_std, lut, interp, std_mode, std_value, max_c
     if pairs is not None:
         darks, dark_stds = [p[0] for p in pairs], [p[1] for p in pairs]
         if stages is None:
-            return ops.linearize_dark_frames(frames, darks, dark_stds, lut, interp, max_code=max_code, **args)
-        return ops.linearize_dark_ingest_frames(frames, stages, darks, dark_stds, lut, interp, layout=layout, **args)
+            lin, lin_std = ops.linearize_dark_frames(frames, darks, dark_stds, lut, interp, max_code=max_code, **args)
+        else:
+            lin, lin_std = ops.linearize_dark_ingest_frames(frames, stages, darks, dark_stds, lut, interp, layout=layout, **args)
+        if flat is not None:
+            ops.flatfield_correct(lin, lin_std, flat[0], flat[1], input_is_variance=False, through_mean=False, flat_mean=flat[2])
+        return lin, lin_std
     args.update(want_std=True, layout=layout)
+    if flat is not None:  # the same three fronts with the correction in their launch
+        if stages is None:
+            return ops.linearize_frames_flat(frames, lut, interp, flat=flat, max_code=max_code, **args)
+        if step > 1:
+            return ops.linearize_ingest_frames_strided_flat(frames, step, stages, lut, interp, flat=flat, consts=consts, **args)
+        return ops.linearize_ingest_frames_flat(frames, stages, lut, interp, flat=flat, consts=consts, **args)
     if stages is None:
         return ops.linearize_frames(frames, lut, interp, max_code=max_code, **args)
     if step > 1:
@@ -387,7 +427,7 @@ def _linearize_run(slot, a, b, with_std, lut, interp, std_mode, std_value, max_c
     return ops.linearize_ingest_frames(frames, stages, lut, interp, consts=consts, **args)
 
 
-def _linearize_dark_runs(slot, k, pairs, with_std, lut, interp, std_mode, std_value, max_code, chain=None):
+def _linearize_dark_runs(slot, k, pairs, with_std, lut, interp, std_mode, std_value, max_code, chain=None, flat=None):
     """The first ``k`` frames of ``slot`` into its output buffers, cut into maximal runs of frames with a matched dark
     field (``pairs[i]``: its device (dark, dark std)) and without one (None: MissingValMode.SKIP_BATCH leaves the frame
     uncorrected), one ``_linearize_run`` each.  ``chain`` = (stages, layout) of a route "ingest" plan: the slot holds the raw
@@ -399,6 +439,6 @@ def _linearize_dark_runs(slot, k, pairs, with_std, lut, interp, std_mode, std_va
         while b < k and (pairs[b] is None) == (pairs[a] is None):
             b += 1
         _linearize_run(slot, a, b, with_std, lut, interp, std_mode, std_value, max_code, stages, layout,
-                       pairs=None if pairs[a] is None else pairs[a:b])
+                       pairs=None if pairs[a] is None else pairs[a:b], flat=flat)
         a = b
     return slot.lin_out[:k], slot.std_out[:k]

@@ -173,6 +173,35 @@ def _lin_std_out(out, shape, device, want_std: bool, lin_required: bool):
     return lin, (std_out if want_std else None)
 
 
+def _flat_arguments(flat, shape, device, want_std: bool):
+    """``flat`` of the linearize_*_flat fronts as the _flat entry points read it: (flat, flat std | None, flat mean), the images
+    float32 and planar (C,H,W) like one frame of the outputs (``shape``: (F,C,H,W); a leading batch dimension of 1 is dropped),
+    the mean (C,) float32 -- ``flatfield_mean(flat)`` -- all on ``device``.  The correction writes a std."""
+    if not isinstance(flat, (tuple, list)) or len(flat) != 3:
+        raise ValueError("flat must be (flat, flat_std or None, flat_mean)")
+    if not want_std:
+        raise ValueError("flat needs want_std: the flat-field correction writes a std")
+    chw = tuple(shape[1:])
+    images = []
+    for name, t in (("flat[0]", flat[0]), ("flat[1]", flat[1])):
+        if t is None:
+            if name == "flat[0]":
+                raise ValueError("flat[0], the flat field, is required")
+            images.append(None)
+            continue
+        _require_device(t, name)
+        if t.ndim == 4 and t.shape[0] == 1:
+            t = t[0]
+        if t.dtype != torch.float32 or tuple(t.shape) != chw or t.device != device:
+            raise ValueError(f"{name} must be a float32 tensor of shape {chw} (planar, like a frame of the outputs) on {device}")
+        images.append(t.contiguous())
+    mean = flat[2]
+    _require_device(mean, "flat[2]")
+    if mean.dtype != torch.float32 or tuple(mean.shape) != chw[:1] or mean.device != device:
+        raise ValueError(f"flat[2] must be the float32 tensor of {chw[0]} channel means on {device} (flatfield_mean)")
+    return images[0], images[1], mean.contiguous()
+
+
 def _check_stats_state(mean_state, m2_state, shape, device=None):
     """The running (mean, m2) state: contiguous float32 ``shape``; on ``device`` where the caller names one."""
     what = "(C,H,W) tensor" if device is None else f"(C,H,W) = {shape} tensor on {device}"
@@ -442,6 +471,23 @@ def linearize_frames(frames: torch.Tensor, lut: torch.Tensor, interp: str = "lin
     ``layout`` "nhwc" / "nhwc_bgr": frames are (F,H,W,C); the outputs are planar (F,C,H,W).
     ``out`` = (lin, std | None): caller-owned contiguous float32 (F,C,H,W) device buffers to write into (the streamed
     pipeline re-uses its ring slots instead of allocating per launch)."""
+    return _linearize_std(frames, lut, interp, std, std_mode, std_value, max_code, want_std, tile, layout, out, None)
+
+
+def linearize_frames_flat(frames: torch.Tensor, lut: torch.Tensor, interp: str = "linear", *, flat,
+                          std: Optional[torch.Tensor] = None, std_mode: str = "none", std_value: float = 0.0,
+                          max_code: Optional[float] = None, want_std: bool = True, tile: Optional[TileGeometry] = None,
+                          layout: str = "nchw", out=None):
+    """ct_linearize_std_flat: ``linearize_frames`` followed by ``flatfield_correct(lin, std, flat, flat_std,
+    input_is_variance=False, through_mean=False, flat_mean=flat_mean)``, bit for bit and in the same launch.
+    ``flat`` = (flat, flat_std | None, flat_mean): ``flat`` / ``flat_std`` float32 (C,H,W) like a frame of the outputs (the
+    rows of the band with ``tile``), ``flat_mean`` = ``flatfield_mean(flat)``.  Needs ``want_std``: the correction writes a
+    std.  Everything else as ``linearize_frames``."""
+    return _linearize_std(frames, lut, interp, std, std_mode, std_value, max_code, want_std, tile, layout, out, flat)
+
+
+def _linearize_std(frames, lut, interp, std, std_mode, std_value, max_code, want_std, tile, layout, out, flat):
+    """The two fronts above: ct_linearize_std, with ``flat`` ct_linearize_std_flat."""
     _check_stack(frames, "frames")
     f = frames.shape[0]
     c, h, w = _chw(frames, layout)
@@ -452,8 +498,13 @@ def linearize_frames(frames: torch.Tensor, lut: torch.Tensor, interp: str = "lin
     frames = frames.contiguous()
     geom = _geometry(frames, tile, layout)
     lin, std_out = _lin_std_out(out, (f, c, h, w), dev, want_std, lin_required=False)
-    _call("ct_linearize_std", dev, _ptr(frames), _DTYPE[frames.dtype], float(max_code or 1.0), f, ctypes.byref(geom), _ptr(std),
-          _STD[std_mode], float(std_value), ctypes.byref(icrf), _ptr(lin), _ptr(std_out))
+    args = (_ptr(frames), _DTYPE[frames.dtype], float(max_code or 1.0), f, ctypes.byref(geom), _ptr(std), _STD[std_mode],
+            float(std_value), ctypes.byref(icrf), _ptr(lin), _ptr(std_out))
+    if flat is None:
+        _call("ct_linearize_std", dev, *args)
+    else:
+        flat = _flat_arguments(flat, (f, c, h, w), dev, want_std)
+        _call("ct_linearize_std_flat", dev, *args, *map(_ptr, flat))
     return lin, std_out
 
 
@@ -640,17 +691,43 @@ def band_stats(mean: torch.Tensor, std: Optional[torch.Tensor] = None) -> torch.
 
 
 # ---- flat-field correction epilogues ----------------------------------------------------------------------------
+def _flat_image(flat: torch.Tensor, device) -> torch.Tensor:
+    """A flat field (or its uncertainty) as the kernels read it: float32, contiguous (C,H,W) on ``device``."""
+    flat = flat.to(device=device, dtype=torch.float32).contiguous()
+    return flat[0] if flat.ndim == 4 else flat
+
+
+def _flatfield_means(value, is_f64: bool, flat: torch.Tensor, global_pixels, reduce):
+    """ct_flatfield_sums on a ``_flat_image`` (and on ``value``, or None), the division and the cast: ((C,) float32 spatial
+    mean of the flat field, (C,) float64 mean of value / (flat + eps) | None)."""
+    c, plane, dev = flat.shape[0], flat.shape[1] * flat.shape[2], flat.device
+    sums = torch.zeros((c, 2), dtype=torch.float64, device=dev)
+    _call("ct_flatfield_sums", dev, _ptr(value), int(is_f64), _ptr(flat), c, plane, _ptr(sums))
+    if reduce is not None:
+        reduce(sums)
+    n_px = float(global_pixels if global_pixels is not None else plane)
+    return (sums[:, 0] / n_px).to(torch.float32).contiguous(), ((sums[:, 1] / n_px).contiguous() if value is not None else None)
+
+
+def flatfield_mean(flat: torch.Tensor, *, global_pixels: Optional[int] = None, reduce=None) -> torch.Tensor:
+    """The (C,) float32 spatial mean of a (C,H,W) flat field as ``flatfield_correct`` computes it (flat_field_mean with a
+    mid-area of 1.0, common/general_functions.py:182-210; ct_flatfield_sums without a value): the constant of a linearization
+    run, computed once and handed to ``flatfield_correct(flat_mean=...)`` or, in ``flat``, to the linearize_*_flat fronts.
+    ``reduce`` / ``global_pixels`` as there."""
+    _require_device(flat, "flat")
+    return _flatfield_means(None, False, _flat_image(flat, flat.device), global_pixels, reduce)[0]
+
+
 def flatfield_correct(value: torch.Tensor, var_or_std: Optional[torch.Tensor], flat: torch.Tensor,
                       flat_std: Optional[torch.Tensor], *, input_is_variance: bool, through_mean: bool,
-                      global_pixels: Optional[int] = None, reduce=None):
+                      global_pixels: Optional[int] = None, reduce=None, flat_mean: Optional[torch.Tensor] = None):
     """In-place flat-field correction of ``value`` ((C,H,W) float64 merged mean or (F,C,H,W) float32 frames) and of
     its uncertainty (ct_flatfield_sums + ct_flatfield_apply).  ``through_mean``: the gradient also flows through the
     flat field's spatial mean (compute_hdr_image) or not (linearize).  ``reduce`` all-reduces the (C,2) sums across
-    ranks holding row bands; ``global_pixels`` is then the pixel count of the whole image plane."""
+    ranks holding row bands; ``global_pixels`` is then the pixel count of the whole image plane.  ``flat_mean`` (without
+    ``through_mean`` only): the (C,) float32 ``flatfield_mean(flat)`` computed before; ct_flatfield_sums is then skipped."""
     _require_device(value, "value")
-    flat = flat.to(device=value.device, dtype=torch.float32).contiguous()
-    if flat.ndim == 4:
-        flat = flat[0]
+    flat = _flat_image(flat, value.device)
     c, h, w = flat.shape
     plane = h * w
     if tuple(value.shape[-3:]) != (c, h, w):
@@ -666,17 +743,16 @@ def flatfield_correct(value: torch.Tensor, var_or_std: Optional[torch.Tensor], f
     if value.dtype not in (torch.float64, torch.float32):
         raise TypeError("value must be float32 or float64")
     if flat_std is not None:
-        flat_std = flat_std.to(device=value.device, dtype=torch.float32).contiguous()
-        if flat_std.ndim == 4:
-            flat_std = flat_std[0]
+        flat_std = _flat_image(flat_std, value.device)
     dev = value.device
-    sums = torch.zeros((c, 2), dtype=torch.float64, device=dev)
-    _call("ct_flatfield_sums", dev, _ptr(value) if through_mean else None, int(is_f64), _ptr(flat), c, plane, _ptr(sums))
-    if reduce is not None:
-        reduce(sums)
-    n_px = float(global_pixels if global_pixels is not None else plane)
-    flat_mean = (sums[:, 0] / n_px).to(torch.float32).contiguous()
-    through = (sums[:, 1] / n_px).contiguous() if through_mean else None
+    if flat_mean is None:
+        flat_mean, through = _flatfield_means(value if through_mean else None, is_f64, flat, global_pixels, reduce)
+    else:
+        if through_mean:
+            raise ValueError("flat_mean is a constant of the run: not with through_mean=True")
+        if flat_mean.dtype != torch.float32 or tuple(flat_mean.shape) != (c,) or flat_mean.device != dev:
+            raise ValueError(f"flat_mean must be the float32 tensor of {c} channel means on {dev} (flatfield_mean)")
+        flat_mean, through = flat_mean.contiguous(), None
     _call("ct_flatfield_apply", dev, _ptr(value), int(is_f64), frames, _ptr(var_or_std), int(input_is_variance), _ptr(flat),
           _ptr(flat_std), _ptr(flat_mean), _ptr(through), c, plane)
     return value, var_or_std
@@ -1099,8 +1175,10 @@ def ingest_transform(stack: torch.Tensor, stages, layout: str = "nchw", out: Opt
 
 
 # ---- such a chain and the linearization in one pass ----------------------------------------------------------------------
-def _linearize_ingest(strided, frames, step, stages, lut, interp, std, std_mode, std_value, want_std, tile, layout, out, consts):
-    """The two fronts below: ct_linearize_ingest_strided with ``strided``, else ct_linearize_ingest / ct_linearize_ingest_data."""
+def _linearize_ingest(strided, frames, step, stages, lut, interp, std, std_mode, std_value, want_std, tile, layout, out, consts,
+                      flat=None):
+    """The two fronts below: ct_linearize_ingest_strided with ``strided``, else ct_linearize_ingest / ct_linearize_ingest_data;
+    with ``flat`` their _flat forms (``linearize_frames_flat``; the images have the shape of a frame of the OUTPUTS)."""
     _check_ingest_stack(frames, layout)
     if strided and (isinstance(step, bool) or not isinstance(step, int) or step < 1):
         raise ValueError(f"step must be an int >= 1, got {step!r}")
@@ -1115,11 +1193,17 @@ def _linearize_ingest(strided, frames, step, stages, lut, interp, std, std_mode,
     icrf, lut_keep = _icrf_struct(lut, interp, c)
     geom = _ingest_geometry(src_shape, tile, layout)
     lin, std_out = _lin_std_out(out, shape, dev, want_std, lin_required=True)
+    if flat is not None:
+        flat = _flat_arguments(flat, shape, dev, want_std)
     if frames.numel() == 0:
         return lin, std_out
     head = (_ptr(frames), _DTYPE[frames.dtype], f, ctypes.byref(geom))
     tail = (arr, n_stages, _ptr(std), _STD[std_mode], float(std_value), ctypes.byref(icrf), _ptr(lin), _ptr(std_out))
-    if strided:
+    if flat is not None:
+        step_arg = (min(step, 0x7fffffff),) if strided else ()
+        _call("ct_linearize_ingest_strided_flat" if strided else "ct_linearize_ingest_flat", dev, *head, *step_arg, *tail, _ptr(consts),
+              *map(_ptr, flat))
+    elif strided:
         _call("ct_linearize_ingest_strided", dev, *head, min(step, 0x7fffffff), *tail, _ptr(consts))
     elif consts is None:
         _call("ct_linearize_ingest", dev, *head, *tail)
@@ -1147,6 +1231,17 @@ def linearize_ingest_frames(frames: torch.Tensor, stages, lut: Optional[torch.Te
     return _linearize_ingest(False, frames, 1, stages, lut, interp, std, std_mode, std_value, want_std, tile, layout, out, consts)
 
 
+def linearize_ingest_frames_flat(frames: torch.Tensor, stages, lut: Optional[torch.Tensor], interp: Optional[str] = "linear", *, flat,
+                                 std: Optional[torch.Tensor] = None, std_mode: str = "none", std_value: float = 0.0,
+                                 want_std: bool = True, tile: Optional[TileGeometry] = None, layout: str = "nchw", out=None,
+                                 consts: Optional[torch.Tensor] = None):
+    """ct_linearize_ingest_flat: ``linearize_ingest_frames`` (with ``consts``: its data-dependent form) and the flat-field
+    correction of ``linearize_frames_flat`` in the same launch, bit for bit.  ``flat`` = (flat, flat_std | None, flat_mean) as
+    there; everything else as ``linearize_ingest_frames``."""
+    return _linearize_ingest(False, frames, 1, stages, lut, interp, std, std_mode, std_value, want_std, tile, layout, out, consts,
+                             flat)
+
+
 def linearize_ingest_frames_strided(frames: torch.Tensor, step: int, stages, lut: Optional[torch.Tensor],
                                     interp: Optional[str] = "linear", *, std: Optional[torch.Tensor] = None,
                                     std_mode: str = "none", std_value: float = 0.0, want_std: bool = True,
@@ -1161,6 +1256,18 @@ def linearize_ingest_frames_strided(frames: torch.Tensor, step: int, stages, lut
     ``out`` = (lin, std | None): contiguous float32 (F,C,ho,wo) device buffers.  ``tile``: with ``step == 1`` only (a row
     band behind a downscale is refused: the phase of the band is not carried)."""
     return _linearize_ingest(True, frames, step, stages, lut, interp, std, std_mode, std_value, want_std, tile, layout, out, consts)
+
+
+def linearize_ingest_frames_strided_flat(frames: torch.Tensor, step: int, stages, lut: Optional[torch.Tensor],
+                                         interp: Optional[str] = "linear", *, flat, std: Optional[torch.Tensor] = None,
+                                         std_mode: str = "none", std_value: float = 0.0, want_std: bool = True,
+                                         tile: Optional[TileGeometry] = None, layout: str = "nchw", out=None,
+                                         consts: Optional[torch.Tensor] = None):
+    """ct_linearize_ingest_strided_flat: ``linearize_ingest_frames_strided`` and the flat-field correction of
+    ``linearize_frames_flat`` in the same launch, bit for bit.  ``flat`` = (flat, flat_std | None, flat_mean) as there, the
+    images float32 (C,ho,wo) like a frame of the outputs; everything else as ``linearize_ingest_frames_strided``."""
+    return _linearize_ingest(True, frames, step, stages, lut, interp, std, std_mode, std_value, want_std, tile, layout, out, consts,
+                             flat)
 
 
 # ---- such a chain, the dark-field blur and the linearization in one pass ------------------------------------------------------

@@ -35,6 +35,16 @@ and pair lists are passed as their component tensors / scalars.
     torch.ops.clair_hip.linearize_ingest_data(frames, stages, consts, lut, interp, std?, std_mode, std_value, layout,
                                   h_global, row_offset) -> (lin, std)   (linearize_ingest whose chain may hold one stage of
                                   kind 2, the data-dependent Normalize with per-frame sub / div = consts[f, 0:2])
+    torch.ops.clair_hip.flatfield_mean(flat) -> Tensor   ((C,) float32 spatial mean of a (C,H,W) flat field)
+    torch.ops.clair_hip.linearize_std_flat(frames, lut, interp, std?, std_mode, std_value, max_code, flat, flat_std?,
+                                  flat_mean, layout) -> (lin, std)
+    torch.ops.clair_hip.linearize_ingest_flat(frames, stages, lut, interp, std?, std_mode, std_value, flat, flat_std?,
+                                  flat_mean, layout, h_global, row_offset, consts?) -> (lin, std)
+    torch.ops.clair_hip.linearize_ingest_strided_flat(frames, step, stages, lut, interp, std?, std_mode, std_value, flat,
+                                  flat_std?, flat_mean, layout, consts?) -> (lin, std)   (linearize_std, linearize_ingest /
+                                  _data and linearize_ingest_strided with the linearization's flat-field correction -- the
+                                  mean a constant, ``flatfield_mean(flat)`` -- on every (lin, std) before it is stored; flat
+                                  and flat_std are (C,H,W) float32 like a frame of the outputs)
     torch.ops.clair_hip.hdr_merge_ingest_batch(frames, stages, exposures, lut?, interp, gaussian, std?, std_mode, std_value,
                                   layout, h_global, row_offset, closed_form, consts?) -> (mean float64, std float32)   (such
                                   a chain and hdr_merge in one pass over the raw frames; with ``consts`` a stage of kind 2 is
@@ -357,6 +367,70 @@ def linearize_ingest_data(frames: torch.Tensor, stages: Sequence[float], consts:
 @linearize_ingest_data.register_fake
 def _(frames, stages, consts, lut, interp, std, std_mode, std_value, layout="nchw", h_global=0, row_offset=0):
     shape = ops.ingest_shape(tuple(frames.shape), layout)
+    return frames.new_empty(shape, dtype=torch.float32), frames.new_empty(shape, dtype=torch.float32)
+
+
+@torch.library.custom_op(f"{_LIB}::flatfield_mean", mutates_args=())
+def flatfield_mean(flat: torch.Tensor) -> torch.Tensor:
+    """ct_flatfield_sums without a value, the division and the cast: the (C,) float32 mean the _flat ops below take."""
+    return ops.flatfield_mean(flat)
+
+
+@flatfield_mean.register_fake
+def _(flat):
+    return flat.new_empty((flat.shape[-3],), dtype=torch.float32)
+
+
+@torch.library.custom_op(f"{_LIB}::linearize_std_flat", mutates_args=())
+def linearize_std_flat(frames: torch.Tensor, lut: torch.Tensor, interp: str, std: Optional[torch.Tensor], std_mode: str,
+                       std_value: float, max_code: float, flat: torch.Tensor, flat_std: Optional[torch.Tensor],
+                       flat_mean: torch.Tensor, layout: str = "nchw") -> Tuple[torch.Tensor, torch.Tensor]:
+    """ct_linearize_std_flat: linearize_std followed by the flat-field correction of its outputs, bit for bit, in one launch."""
+    return ops.linearize_frames_flat(frames, lut, interp, std=std, std_mode=std_mode, std_value=std_value,
+                                     max_code=max_code if max_code > 0 else None, want_std=True, layout=layout,
+                                     flat=(flat, flat_std, flat_mean))
+
+
+@linearize_std_flat.register_fake
+def _(frames, lut, interp, std, std_mode, std_value, max_code, flat, flat_std, flat_mean, layout="nchw"):
+    shape = (frames.shape[0],) + tuple(_chw(frames, layout))
+    return frames.new_empty(shape, dtype=torch.float32), frames.new_empty(shape, dtype=torch.float32)
+
+
+@torch.library.custom_op(f"{_LIB}::linearize_ingest_flat", mutates_args=())
+def linearize_ingest_flat(frames: torch.Tensor, stages: Sequence[float], lut: torch.Tensor, interp: str, std: Optional[torch.Tensor],
+                          std_mode: str, std_value: float, flat: torch.Tensor, flat_std: Optional[torch.Tensor],
+                          flat_mean: torch.Tensor, layout: str = "nchw", h_global: int = 0, row_offset: int = 0,
+                          consts: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ct_linearize_ingest_flat: linearize_ingest (with ``consts``: linearize_ingest_data) followed by the flat-field correction
+    of its outputs, bit for bit, in one launch."""
+    return ops.linearize_ingest_frames_flat(frames, _listed_ingest_stages(frames, stages, layout), lut, interp, std=std,
+                                            std_mode=std_mode, std_value=std_value, want_std=True, tile=_tile(h_global, row_offset),
+                                            layout=layout, consts=consts, flat=(flat, flat_std, flat_mean))
+
+
+@linearize_ingest_flat.register_fake
+def _(frames, stages, lut, interp, std, std_mode, std_value, flat, flat_std, flat_mean, layout="nchw", h_global=0, row_offset=0,
+      consts=None):
+    shape = ops.ingest_shape(tuple(frames.shape), layout)
+    return frames.new_empty(shape, dtype=torch.float32), frames.new_empty(shape, dtype=torch.float32)
+
+
+@torch.library.custom_op(f"{_LIB}::linearize_ingest_strided_flat", mutates_args=())
+def linearize_ingest_strided_flat(frames: torch.Tensor, step: int, stages: Sequence[float], lut: torch.Tensor, interp: str,
+                                  std: Optional[torch.Tensor], std_mode: str, std_value: float, flat: torch.Tensor,
+                                  flat_std: Optional[torch.Tensor], flat_mean: torch.Tensor, layout: str = "nchw",
+                                  consts: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ct_linearize_ingest_strided_flat: linearize_ingest_strided followed by the flat-field correction of its outputs, bit for
+    bit, in one launch; flat and flat_std have the downscaled shape."""
+    return ops.linearize_ingest_frames_strided_flat(frames, step, _listed_ingest_stages(frames, stages, layout), lut, interp,
+                                                    std=std, std_mode=std_mode, std_value=std_value, want_std=True, layout=layout,
+                                                    consts=consts, flat=(flat, flat_std, flat_mean))
+
+
+@linearize_ingest_strided_flat.register_fake
+def _(frames, step, stages, lut, interp, std, std_mode, std_value, flat, flat_std, flat_mean, layout="nchw", consts=None):
+    shape = ops.downscaled_shape(ops.ingest_shape(tuple(frames.shape), layout), step)
     return frames.new_empty(shape, dtype=torch.float32), frames.new_empty(shape, dtype=torch.float32)
 
 

@@ -583,6 +583,36 @@ int ct_linearize_ingest_strided(const void *frames_dev, int32_t dtype, int64_t n
                                 const float *consts_dev /* may be NULL */, void *stream);
 
 /*
+ * ct_linearize_std_flat / ct_linearize_ingest_flat / ct_linearize_ingest_strided_flat -- ct_linearize_std, ct_linearize_ingest
+ * (consts_dev NULL) or ct_linearize_ingest_data, and ct_linearize_ingest_strided with the flat-field correction of
+ * linearize_dataset_generator (linearization.py:48-57,118-130; the mean a constant) applied to every (lin, std) before it is
+ * stored: bit for bit the parent followed by ct_flatfield_apply(value float32, std in, through_mean NULL) with the same
+ * flat_mean_dev, without the second trip of both outputs through memory.  Per element, float32, every operation rounded on
+ * its own:  den = flat + 1e-6;  lin' = (lin / den) * M;  grad = -(M * lin) / (den * den);  var = sd * sd
+ * (+ (grad * flat_std)^2 with a flat_std);  sd' = sqrt(var).
+ *   flat_dev       planar (C, plane) float32 of the OUTPUT's shape: (C, H_tile, W) -- the rows of the band for a row band --
+ *                  and (C, ho, wo) behind a step; dense, aligned to 4 bytes
+ *   flat_std_dev   its uncertainty, same shape, or NULL (no flat-field term in sd')
+ *   flat_mean_dev  M: C floats in device memory, read when the kernel runs
+ * Every other argument, and every refusal in its order, as the parent.  Behind them: flat_dev or flat_mean_dev NULL, or one of
+ * the three misaligned, is CT_ERR_INVALID_ARGUMENT, and so is std_out_dev NULL -- the correction writes a std.
+ */
+int ct_linearize_std_flat(const void *frames_dev, int32_t dtype, float max_code, int64_t n_frames, const ct_geometry *geom,
+                          const float *std_dev, int32_t std_mode, float std_value, const ct_icrf *icrf, float *lin_out_dev,
+                          float *std_out_dev, const float *flat_dev, const float *flat_std_dev /* may be NULL */,
+                          const float *flat_mean_dev, void *stream);
+int ct_linearize_ingest_flat(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
+                             const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,
+                             float std_value, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev,
+                             const float *consts_dev /* may be NULL */, const float *flat_dev,
+                             const float *flat_std_dev /* may be NULL */, const float *flat_mean_dev, void *stream);
+int ct_linearize_ingest_strided_flat(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom, int32_t step,
+                                     const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,
+                                     float std_value, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev,
+                                     const float *consts_dev /* may be NULL */, const float *flat_dev,
+                                     const float *flat_std_dev /* may be NULL */, const float *flat_mean_dev, void *stream);
+
+/*
  * ct_linearize_dark_ingest -- ct_linearize_dark on RAW frames behind a recognised gpu_transforms chain (the stage list of
  * ct_ingest_transform, declared above): for every frame lin_out and std_out are bit for bit those of
  * ct_ingest_transform on it into a planar float32 image x, ct_dark_field_blur on x (batch = 1, dark_batch = 1) into xb and
