@@ -35,7 +35,8 @@ EXPORTS = ("ct_abi_version", "ct_error_string", "ct_hdr_merge_batch", "ct_hdr_me
            "ct_linearize_ingest_data", "ct_pair_residual_ingest_fwd", "ct_pair_residual_ingest_bwd", "ct_linearize_ingest_strided",
            "ct_video_stats_batches", "ct_video_stats_ingest_batches", "ct_hdr_merge_dark_batch", "ct_linearize_dark",
            "ct_hdr_merge_dark_batches", "ct_linearize_dark_ingest", "ct_hdr_merge_dark_ingest_batches",
-           "ct_linearize_std_flat", "ct_linearize_ingest_flat", "ct_linearize_ingest_strided_flat")
+           "ct_linearize_std_flat", "ct_linearize_ingest_flat", "ct_linearize_ingest_strided_flat",
+           "ct_linearize_dark_ingest_data")
 
 
 class Geometry(ctypes.Structure):
@@ -133,6 +134,10 @@ def load():
     lib.ct_linearize_dark_ingest.restype = i32
     lib.ct_linearize_dark_ingest.argtypes = [vp, i32, i64, gp, ctypes.POINTER(IngestStage), i32, vp, i32, f32, vp, vp, f32, f32, ip, vp,
                                              vp, vp]
+    # ... _data: the parent's arguments, then the (n_frames, 4) per-frame constants in front of the stream
+    lib.ct_linearize_dark_ingest_data.restype = i32
+    lib.ct_linearize_dark_ingest_data.argtypes = [vp, i32, i64, gp, ctypes.POINTER(IngestStage), i32, vp, i32, f32, vp, vp, f32, f32, ip,
+                                                  vp, vp, vp, vp]
     lib.ct_band_stats_workspace.restype = i64
     lib.ct_band_stats_workspace.argtypes = [i32]
     lib.ct_band_stats.restype = i32

@@ -32,8 +32,12 @@ and float32 batches with an empty list (inference/linearization.py::pipeline_rou
 downscale or a dark field; ``pipeline_data_route``): every frame is a batch of its own there, so ct_ingest_extrema_frames
 takes the extrema of each frame of a group in one launch pair and ct_linearize_ingest_data reads the constants per frame.
 With a dark field, planar frames on route 2 without a downscale and bare float32 batches keep the pipeline
-(``DarkField.fuses_with_linearize``: ct_linearize_dark blurs and linearizes the matched frames in one pass).
-Everything else goes frame by frame.
+(``DarkField.fuses_with_linearize``: ct_linearize_dark blurs and linearizes the matched frames in one pass), and so does
+route 3 without a downscale (``DarkField.fuses_with_linearize_ingest``: ct_linearize_dark_ingest runs the chain as well).
+Route 4 without a downscale joins them only on request (``linearize_dataset_generator(fused_dark_ingest_data=True)``,
+``DarkField.fuses_with_linearize_ingest_data``: ct_ingest_extrema_frames per group, then ct_linearize_dark_ingest_data with
+each frame's own constants); by default it goes frame by frame.  So does everything else: with a dark field any
+``StridedDownscale`` and LOOKUP, and on every run route 5.
 
 A leading ``CvToTorch`` on (B,H,W,3) uint8 / uint16 frames is never executed on routes 1-4: the code-route kernels read the
 interleaved frames as they are (layout "nhwc_bgr") and the fused ingest reads them itself.  A caller that needs a planar

@@ -29,14 +29,25 @@
 // layout of the frames.  A workgroup walks kLdiSlots groups per thread, a workgroup apart, so one staging of the LUT
 // (stage_lut) serves kLdiSlots * 1024 samples per plane.  Outputs are one packet where the group is 16-byte aligned in
 // memory (li_store), else elements.  No atomics, no LDS tile; frames, dark fields and uncertainties are read only.  No row
-// bands (no halo is built here), no CT_INGEST_AFFINE_DATA stage, no LOOKUP (no gradient path: refused, no kernel).
+// bands (no halo is built here), no LOOKUP (no gradient path: refused, no kernel).
 //
-// Resources (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage; scratch is 0 bytes for all 18 kernels),
+// ct_linearize_dark_ingest_data: the chain may hold one CT_INGEST_AFFINE_DATA stage -- a data-dependent Normalize -- whose sub
+// and div are PER FRAME: consts[4 f], consts[4 f + 1] as ct_ingest_extrema_frames left them and as ct_linearize_ingest_data reads
+// them.  The frame of a workgroup row is known before the slot loop (blockIdx.y), so the two floats are one wave-uniform load per
+// workgroup row; ingest_stages<true> takes them for all 9 taps of a window -- a reflected border tap is an element of the same
+// frame.  The walks are the same templates with DATA = true (18 more kernels, their block the constant chains' with the pointer
+// behind it); the DATA = false instantiations are the kernels of ct_linearize_dark_ingest, instruction for instruction
+// (profiles/linearize_dark_ingest_data.md), and a call whose chain has no such stage launches those whether or not it brought
+// constants.  ct_linearize_dark_ingest itself still refuses the kind.  Per uint16 sample the extrema pass adds 2 B to the 18.
+//
+// Resources (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage; scratch is 0 bytes for all 36 kernels),
 // VGPRs for LINEAR / CATMULL / no LUT:
-//   planar   uint8, uint16, float32: 73 / 73 / 71 each (6 to 7 wavefronts per SIMD)
-//   packed3  uint8 111 / 111 / 109, uint16 115 / 115 / 114 (4 wavefronts per SIMD), float32 148 / 148 / 147 (3)
+//   planar   uint8, uint16, float32: 73 / 73 / 71 each (6 to 7 wavefronts per SIMD); DATA the same
+//   packed3  uint8 111 / 111 / 109, uint16 115 / 115 / 114 (4 wavefronts per SIMD), float32 148 / 148 / 147 (3);
+//            DATA the same but uint16 116 / 116 / 114 (4 wavefronts per SIMD still)
 // Measured on 16 x 3 x 1080 x 1920 (profiles/linearize_dark_ingest.md): 0.55 to 0.63 of the time of the three launches, 2.8 to
-// 3.5 TB/s of the bytes counted above; the packed3 walk's occupancy is the first thing to look at for more.
+// 3.5 TB/s of the bytes counted above; the packed3 walk's occupancy is the first thing to look at for more.  DATA, with the
+// extrema pass in front (profiles/linearize_dark_ingest_data.md): 0.48 to 0.55 of the time of the four launches, 3.1 to 3.8 TB/s.
 #include <algorithm>
 #include "ct_dark_window.hpp"
 #include "ct_linearize_ingest.hpp"
@@ -65,6 +76,15 @@ struct LinDarkIngestArgs {
     ct_ingest_stage stage[CT_INGEST_MAX_STAGES];
 };
 
+// The argument block of the DATA instantiations: the constants pointer appended BEHIND the block, so every member keeps its
+// offset, and in a derived block (as WithFlat of ct_linearize_ingest.hpp), so the constant-chain instantiations take their own
+// block unchanged -- a member more in it moves the hidden arguments behind the block, one s_load_dword offset in 12 of them
+struct LinDarkIngestDataArgs : LinDarkIngestArgs {
+    const float *consts;     // (frames of this launch, 4) per-frame {sub, div, min, max} of the CT_INGEST_AFFINE_DATA stage
+};
+template <bool DATA>
+using ldi_args_t = std::conditional_t<DATA, LinDarkIngestDataArgs, LinDarkIngestArgs>;
+
 constexpr int kLdiGroup = kLiGroup;  // columns / pixels per thread
 constexpr int kLdiSlots = 4;         // groups per thread
 
@@ -72,9 +92,10 @@ static inline __host__ __device__ uint32_t ldi_groups_per_row(uint32_t width) { 
 
 // PLANAR: xb and sigma_eff of columns w0 .. w0 + G - 1 of row h of plane c0 of the frame at `frame` (its dark field: dark,
 // dark_std; its explicit sigma: sigma or NULL, planar like the dark field)
-template <typename T, int G>
+template <typename T, int G, bool DATA>
 __device__ __forceinline__ void ldi_planar(const LinDarkIngestArgs &a, const T *frame, const float *sigma, const float *dark,
-                                           const float *dark_std, uint32_t c0, uint32_t h, uint32_t w0, float *xb, float *sig)
+                                           const float *dark_std, uint32_t c0, uint32_t h, uint32_t w0, float dsub, float ddiv,
+                                           float *xb, float *sig)
 {
     constexpr int N = G + 2;
     const uint32_t q = c0 * a.plane + h * a.width + w0;  // first element inside the (C, H, W) frame
@@ -89,12 +110,12 @@ __device__ __forceinline__ void ldi_planar(const LinDarkIngestArgs &a, const T *
         v[N + j] = (float)raw.mid[j];
         v[2 * N + j] = (float)raw.dn[j];
     }
-    ingest_stages<false>(v, a, a.by_channel ? c0 : 0u);
+    ingest_stages<DATA>(v, a, a.by_channel ? c0 : 0u, dsub, ddiv);  // all 9 taps: reflected ones are the frame's own
     dark_blur_staged<G, true>(a, v, v + N, v + 2 * N, raw.d, raw.ds, raw.sg, explicit_sigma, xb, sig);
 }
 
-template <typename T, int INTERP>
-__global__ __launch_bounds__(kBlock) void linearize_dark_ingest_planar_kernel(const LinDarkIngestArgs a)
+template <typename T, int INTERP, bool DATA>
+__global__ __launch_bounds__(kBlock) void linearize_dark_ingest_planar_kernel(const ldi_args_t<DATA> a)
 {
     extern __shared__ __align__(16) char lds[];
     const int C = (int)a.channels, L = (int)a.n_points;
@@ -105,6 +126,12 @@ __global__ __launch_bounds__(kBlock) void linearize_dark_ingest_planar_kernel(co
     const int64_t out0 = (int64_t)f * C * a.plane;  // the frame inside the dense planar arrays
     const float *sigma = a.std_in ? a.std_in + out0 : nullptr;
     const float *dark = a.dark[f], *dark_std = a.dark_std[f];
+    // DATA: the frame's pair, one wave-uniform load per workgroup row (f comes from blockIdx.y)
+    [[maybe_unused]] float dsub = 0.0f, ddiv = 1.0f;
+    if constexpr (DATA) {
+        dsub = a.consts[4 * (int64_t)f];
+        ddiv = a.consts[4 * (int64_t)f + 1];
+    }
     const uint32_t W = a.width;
     const uint32_t gpr = ldi_groups_per_row(W);
     const uint64_t n_slots = (uint64_t)gpr * a.h_tile;
@@ -117,14 +144,14 @@ __global__ __launch_bounds__(kBlock) void linearize_dark_ingest_planar_kernel(co
         float xb[kLdiGroup] = {0.0f, 0.0f, 0.0f, 0.0f}, sig[kLdiGroup] = {0.0f, 0.0f, 0.0f, 0.0f};
         int n = kLdiGroup;
         if (W - w0 >= (uint32_t)kLdiGroup) {
-            ldi_planar<T, kLdiGroup>(a, frame, sigma, dark, dark_std, c0, h, w0, xb, sig);
+            ldi_planar<T, kLdiGroup, DATA>(a, frame, sigma, dark, dark_std, c0, h, w0, dsub, ddiv, xb, sig);
         } else {
             // the end of a row whose width is no multiple of the group (at most kLdiGroup - 1 elements): one lane, one element
             // after the other, each with its own window
             n = (int)(W - w0);
 #pragma unroll
             for (int e = 0; e < kLdiGroup - 1; ++e)
-                if (e < n) ldi_planar<T, 1>(a, frame, sigma, dark, dark_std, c0, h, w0 + e, &xb[e], &sig[e]);
+                if (e < n) ldi_planar<T, 1, DATA>(a, frame, sigma, dark, dark_std, c0, h, w0 + e, dsub, ddiv, &xb[e], &sig[e]);
         }
         // the frame is batch element 0 of its own batch: the LINEAR / CATMULL row is the flat (C, H, W) index modulo C
         const uint32_t q = c0 * a.plane + h * W + w0;
@@ -138,10 +165,10 @@ __global__ __launch_bounds__(kBlock) void linearize_dark_ingest_planar_kernel(co
 
 // PACKED3: xb and sigma_eff of pixels w0 .. w0 + G - 1 of row h of the interleaved frame at `frame`, all 3 channels, into
 // elements E0 .. E0 + G - 1 of xb[cm] / sig[cm] (cm: the MEMORY channel; its plane is 2 - cm with a.reversed)
-template <typename T, int G, int E0>
+template <typename T, int G, int E0, bool DATA>
 __device__ __forceinline__ void ldi_packed3(const LinDarkIngestArgs &a, const T *frame, const float *sigma, const float *dark,
-                                            const float *dark_std, uint32_t h, uint32_t w0, float (&xb)[3][kLdiGroup],
-                                            float (&sig)[3][kLdiGroup])
+                                            const float *dark_std, uint32_t h, uint32_t w0, float dsub, float ddiv,
+                                            float (&xb)[3][kLdiGroup], float (&sig)[3][kLdiGroup])
 {
     constexpr int C = 3, N = G + 2;
     const uint32_t W = a.width, H = a.h_tile;
@@ -166,7 +193,7 @@ __device__ __forceinline__ void ldi_packed3(const LinDarkIngestArgs &a, const T 
         for (int k = 0; k < 3; ++k)
 #pragma unroll
             for (int j = 0; j < N; ++j) v[k * N + j] = (float)raw[k][j * C + cm];
-        ingest_stages<false>(v, a, a.by_channel ? c : 0u);
+        ingest_stages<DATA>(v, a, a.by_channel ? c : 0u, dsub, ddiv);
         float d[G], ds[G], sg[G];
         __builtin_memcpy(d, dark + q, sizeof(d));
         __builtin_memcpy(ds, dark_std + q, sizeof(ds));
@@ -177,8 +204,8 @@ __device__ __forceinline__ void ldi_packed3(const LinDarkIngestArgs &a, const T 
     }
 }
 
-template <typename T, int INTERP>
-__global__ __launch_bounds__(kBlock) void linearize_dark_ingest_packed3_kernel(const LinDarkIngestArgs a)
+template <typename T, int INTERP, bool DATA>
+__global__ __launch_bounds__(kBlock) void linearize_dark_ingest_packed3_kernel(const ldi_args_t<DATA> a)
 {
     extern __shared__ __align__(16) char lds[];
     constexpr int C = 3;
@@ -190,6 +217,11 @@ __global__ __launch_bounds__(kBlock) void linearize_dark_ingest_packed3_kernel(c
     const int64_t out0 = (int64_t)f * C * a.plane;
     const float *sigma = a.std_in ? a.std_in + out0 : nullptr;
     const float *dark = a.dark[f], *dark_std = a.dark_std[f];
+    [[maybe_unused]] float dsub = 0.0f, ddiv = 1.0f;  // DATA: the frame's pair, as in the planar kernel
+    if constexpr (DATA) {
+        dsub = a.consts[4 * (int64_t)f];
+        ddiv = a.consts[4 * (int64_t)f + 1];
+    }
     const uint32_t W = a.width;
     const uint32_t gpr = ldi_groups_per_row(W);
     const uint64_t n_slots = (uint64_t)gpr * a.h_tile;
@@ -202,13 +234,13 @@ __global__ __launch_bounds__(kBlock) void linearize_dark_ingest_packed3_kernel(c
         float xb[C][kLdiGroup] = {}, sig[C][kLdiGroup] = {};
         int n = kLdiGroup;
         if (W - w0 >= (uint32_t)kLdiGroup) {
-            ldi_packed3<T, kLdiGroup, 0>(a, frame, sigma, dark, dark_std, h, w0, xb, sig);
+            ldi_packed3<T, kLdiGroup, 0, DATA>(a, frame, sigma, dark, dark_std, h, w0, dsub, ddiv, xb, sig);
         } else {
             // the end of a row whose width is no multiple of the group (1 to 3 pixels): one pixel after the other
             n = (int)(W - w0);
-            ldi_packed3<T, 1, 0>(a, frame, sigma, dark, dark_std, h, w0, xb, sig);
-            if (n > 1) ldi_packed3<T, 1, 1>(a, frame, sigma, dark, dark_std, h, w0 + 1, xb, sig);
-            if (n > 2) ldi_packed3<T, 1, 2>(a, frame, sigma, dark, dark_std, h, w0 + 2, xb, sig);
+            ldi_packed3<T, 1, 0, DATA>(a, frame, sigma, dark, dark_std, h, w0, dsub, ddiv, xb, sig);
+            if (n > 1) ldi_packed3<T, 1, 1, DATA>(a, frame, sigma, dark, dark_std, h, w0 + 1, dsub, ddiv, xb, sig);
+            if (n > 2) ldi_packed3<T, 1, 2, DATA>(a, frame, sigma, dark, dark_std, h, w0 + 2, dsub, ddiv, xb, sig);
         }
 #pragma unroll
         for (int cm = 0; cm < C; ++cm) {
@@ -222,37 +254,35 @@ __global__ __launch_bounds__(kBlock) void linearize_dark_ingest_packed3_kernel(c
     }
 }
 
-template <typename T, int INTERP>
-static int ldi_launch(const LinDarkIngestArgs &a, bool packed, int n_frames, hipStream_t s)
+template <typename T, int INTERP, bool DATA>
+static int ldi_launch(const ldi_args_t<DATA> &a, bool packed, int n_frames, hipStream_t s)
 {
     const size_t lds = lut_lds_bytes(INTERP, (int)a.channels, (int)a.n_points);
     const uint64_t slots = (uint64_t)ldi_groups_per_row(a.width) * a.h_tile;
     const uint64_t per_block = (uint64_t)kBlock * kLdiSlots;
     const dim3 grid((uint32_t)((slots + per_block - 1) / per_block), (uint32_t)n_frames * (packed ? 1u : a.channels));
     if (packed)
-        hipLaunchKernelGGL((linearize_dark_ingest_packed3_kernel<T, INTERP>), grid, dim3(kBlock), lds, s, a);
+        hipLaunchKernelGGL((linearize_dark_ingest_packed3_kernel<T, INTERP, DATA>), grid, dim3(kBlock), lds, s, a);
     else
-        hipLaunchKernelGGL((linearize_dark_ingest_planar_kernel<T, INTERP>), grid, dim3(kBlock), lds, s, a);
+        hipLaunchKernelGGL((linearize_dark_ingest_planar_kernel<T, INTERP, DATA>), grid, dim3(kBlock), lds, s, a);
     return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
 }
 
 template <typename T>
-static int ldi_dispatch(const LinDarkIngestArgs &a, bool packed, int interp, int n_frames, hipStream_t s)
+static int ldi_dispatch(const LinDarkIngestDataArgs &a, bool packed, int interp, int n_frames, hipStream_t s)
 {
-    // (LOOKUP has no gradient path: refused by the entry point, no kernel)
-    return with_enum<CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp,
-                                                                          [&](auto I) { return ldi_launch<T, I>(a, packed, n_frames, s); });
+    // (LOOKUP has no gradient path: refused by the entry point, no kernel).  a.consts: the DATA instantiations
+    return with_enum<CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
+        return a.consts ? ldi_launch<T, I, true>(a, packed, n_frames, s) : ldi_launch<T, I, false>(a, packed, n_frames, s);
+    });
 }
 
-}  // namespace ct
-
-extern "C" int ct_linearize_dark_ingest(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
-                                        const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,
-                                        float std_value, const float *const *dark_devs, const float *const *dark_std_devs,
-                                        float threshold, float alpha, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev,
-                                        void *stream)
+// consts_dev NULL: the constant chains of ct_linearize_dark_ingest (no AFFINE_DATA stage); else ct_linearize_dark_ingest_data
+static int linearize_dark_ingest(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
+                                 const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode, float std_value,
+                                 const float *const *dark_devs, const float *const *dark_std_devs, float threshold, float alpha,
+                                 const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev, const float *consts_dev, void *stream)
 {
-    using namespace ct;
     // ---- what ct_linearize_dark refuses first: pointers, the frame count, a dark field per frame ----
     if (!frames_dev || !geom || !dark_devs || !dark_std_devs || !lin_out_dev || !std_out_dev || n_frames <= 0 || n_frames > 0x7fffffff)
         return CT_ERR_INVALID_ARGUMENT;
@@ -264,11 +294,15 @@ extern "C" int ct_linearize_dark_ingest(const void *frames_dev, int32_t dtype, i
     if (int rc = check_dark_frames(&planar, 1, 1, true, std_mode, std_dev)) return rc;
     if (geom->row_offset != 0 || geom->h_tile != geom->h_global) return CT_ERR_UNSUPPORTED;  // a row band: no halo is built here
     if (int rc = check_dark_band(&planar, nullptr)) return rc;  // (the whole image: what is left of it is the stride)
-    // ---- the stack and the stage list: constant chains only ----
+    // ---- the stack and the stage list: one AFFINE_DATA stage at most, and only with constants (li_check_call's rule) ----
     bool by_channel = false;
     if (int rc = ingest_validate(dtype, geom->layout, n_frames, geom->channels, geom->h_tile * geom->width, stages, n_stages,
-                                 CT_INGEST_MAX_STAGES, 0, by_channel))
+                                 CT_INGEST_MAX_STAGES, consts_dev ? 1 : 0, by_channel))
         return rc;
+    if (!aligned(consts_dev, sizeof(float))) return CT_ERR_INVALID_ARGUMENT;
+    // constants without a data stage are not read: the constant chain's kernels
+    bool data = false;
+    for (int32_t k = 0; k < n_stages; ++k) data |= stages[k].kind == CT_INGEST_AFFINE_DATA;
     // ---- the model: float32 pixels with explicit uncertainties, as ct_linearize_std sees (xb, sigma_eff) ----
     if (!icrf || !icrf_ok(icrf)) return CT_ERR_INVALID_ARGUMENT;
     const int interp = icrf->interp;
@@ -286,7 +320,7 @@ extern "C" int ct_linearize_dark_ingest(const void *frames_dev, int32_t dtype, i
 
     const int64_t plane = geom->h_tile * geom->width;
     const size_t elem = dtype_bytes(dtype);
-    LinDarkIngestArgs a{};
+    LinDarkIngestDataArgs a{};
     a.lut = icrf->lut_dev;
     a.image_stride = geom->image_stride;
     a.plane = (uint32_t)plane;
@@ -306,6 +340,7 @@ extern "C" int ct_linearize_dark_ingest(const void *frames_dev, int32_t dtype, i
         a.std_in = std_mode == CT_STD_EXPLICIT ? std_dev + first * geom->channels * plane : nullptr;
         a.lin_out = lin_out_dev + first * geom->channels * plane;
         a.std_out = std_out_dev + first * geom->channels * plane;
+        a.consts = data ? consts_dev + 4 * first : nullptr;
         for (int k = 0; k < nf; ++k) {
             a.dark[k] = dark_devs[first + k];
             a.dark_std[k] = dark_std_devs[first + k];
@@ -319,4 +354,26 @@ extern "C" int ct_linearize_dark_ingest(const void *frames_dev, int32_t dtype, i
         if (rc != CT_OK) return rc;
     }
     return CT_OK;
+}
+
+}  // namespace ct
+
+extern "C" int ct_linearize_dark_ingest(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
+                                        const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,
+                                        float std_value, const float *const *dark_devs, const float *const *dark_std_devs,
+                                        float threshold, float alpha, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev,
+                                        void *stream)
+{
+    return ct::linearize_dark_ingest(frames_dev, dtype, n_frames, geom, stages, n_stages, std_dev, std_mode, std_value, dark_devs,
+                                     dark_std_devs, threshold, alpha, icrf, lin_out_dev, std_out_dev, nullptr, stream);
+}
+
+extern "C" int ct_linearize_dark_ingest_data(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
+                                             const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,
+                                             float std_value, const float *const *dark_devs, const float *const *dark_std_devs,
+                                             float threshold, float alpha, const ct_icrf *icrf, float *lin_out_dev,
+                                             float *std_out_dev, const float *consts_dev, void *stream)
+{
+    return ct::linearize_dark_ingest(frames_dev, dtype, n_frames, geom, stages, n_stages, std_dev, std_mode, std_value, dark_devs,
+                                     dark_std_devs, threshold, alpha, icrf, lin_out_dev, std_out_dev, consts_dev, stream);
 }

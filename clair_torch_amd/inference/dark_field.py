@@ -154,6 +154,24 @@ class DarkField:
         return t.dtype in (torch.uint8, torch.uint16, torch.float32) and plan.source_layout in ("nchw", "nhwc_bgr")
 
     @staticmethod
+    def fuses_with_linearize_ingest_data(probe, plan, interp) -> bool:
+        """The third route decision of linearize_dataset_generator with a dark-field dataset, asked for what the two above
+        declined (``fused_dark_ingest_data``): True = the streamed pipeline with ct_ingest_extrema_frames once per group and
+        ct_linearize_dark_ingest_data on the matched frames (the chain with the frame's own constants, blur and ICRF in one pass
+        over the slot's raw frames).  ``probe``: as above; ``plan``: its ``plan_staging`` plan with ``planar=True`` and
+        ``on_device=True`` (route "ingest_data" exists only there).  Fused are 4-D uint8 / uint16 / float32 frames on route
+        "ingest_data" -- the fused-ingest grammar with ONE data-dependent Normalize, ``Normalize()`` above all; planar frames or
+        raw (H,W,3) BGR frames behind a leading ``CvToTorch`` -- without a StridedDownscale on either side of that Normalize
+        (the blur would run on the compacted image: another window walk), LINEAR / CATMULL.  Constant chains (the two
+        decisions above), LOOKUP and lists that run as torch ops are declined."""
+        t = probe
+        if not isinstance(t, torch.Tensor) or t.ndim != 4 or interp not in ("linear", "catmull"):
+            return False
+        if plan.route != "ingest_data" or plan.step != 1:
+            return False
+        return t.dtype in (torch.uint8, torch.uint16, torch.float32) and plan.source_layout in ("nchw", "nhwc_bgr")
+
+    @staticmethod
     def cache_key(dark, dark_std):
         """What identifies the contents of a matched host pair: address, in-place version counter, shape and dtype of both
         (an in-place edit bumps ``_version``; the cache holds the host tensors, so an address is not re-used while its

@@ -48,8 +48,17 @@ route "ingest" without a StridedDownscale -- a black level, a target range, ``Cl
 (explicit uncertainty images planar): matched runs go to ct_linearize_dark_ingest -- chain, blur and ICRF in one pass, bit for
 bit what ct_ingest_transform, ct_dark_field_blur and ct_linearize_std give frame by frame; 18 B per uint16 sample (22 with
 explicit uncertainties) against 42 (46), from the shapes; measured in profiles/linearize_dark_ingest.md -- and unmatched ones
-to ct_linearize_ingest.  Everything else with a dark field (a data-dependent Normalize, a StridedDownscale, LOOKUP, torch
-lists), and ``fused_dark=False``, goes frame by frame as ever.
+to ct_linearize_ingest.  What both declined goes to ``DarkField.fuses_with_linearize_ingest_data`` when
+``fused_dark_ingest_data=True`` (opt-in; the default is False): route "ingest_data" -- ONE data-dependent Normalize,
+``Normalize()`` above all -- without a StridedDownscale takes the pipeline too: ONE ct_ingest_extrema_frames launch pair per
+group leaves every frame's constants in the slot BEFORE the dark runs, matched runs go to ct_linearize_dark_ingest_data with
+their slice of the constants (chain, blur and ICRF in one pass: bit for bit what ct_ingest_extrema, ct_ingest_transform_data,
+ct_dark_field_blur and ct_linearize_std give frame by frame; 18 + 2 B per uint16 sample from the shapes;
+profiles/linearize_dark_ingest_data.md) and unmatched ones to ct_linearize_ingest_data; the constants ride the device-to-host
+stage and the zero-range ValueError is raised where the frame-by-frame route raises it, as without a dark field.  A frame whose
+match raises is staged BEFORE it is matched on the frame-by-frame route, so a zero range of that frame wins: its constants
+alone are taken once the queue has drained.  Everything else with a dark field (a data-dependent Normalize with the keyword
+off, a StridedDownscale, LOOKUP, torch lists), and ``fused_dark=False``, goes frame by frame as ever.
 
 ``output_layout="cv"`` (extension): every yielded pair is in the order the reference's ``save_image`` writes -- (H,W,C),
 a 3-channel frame reversed to BGR -- made by two ct_export_cv launches per group before the device-to-host copy, which
@@ -84,6 +93,15 @@ FUSED_DARK_DEFAULT = True
 # run (81 ms) ahead of the fastest frame-by-frame run (139 ms); planar black level 1042 [1022 .. 1044] against 460 [313 .. 461],
 # 2.27x, 63 ms ahead of 139 ms: True.
 FUSED_DARK_INGEST_DEFAULT = True
+# linearize_dataset_generator(fused_dark_ingest_data=...).  The rule for a later flip, set before measuring
+# (profiles/linearize_dark_ingest_data.md), is the standing one: True only if, end to end on 64 uint16 1080p frames from pinned
+# memory, every fused run was faster than every frame-by-frame run in BOTH comparisons -- raw (H,W,3) BGR frames behind
+# [CvToTorch, CastTo, Normalize()] and planar frames behind [CastTo, Normalize()].  Measured: BGR 1035 [734 .. 1039] frames/s fused
+# against 444 [288 .. 455] frame by frame, 2.33x at the medians, the slowest fused run (87 ms) ahead of the fastest frame-by-frame
+# run (141 ms); planar 1033 [1032 .. 1038] against 386 [368 .. 454], 2.68x, 62 ms ahead of 141 ms: the rule is met.  The default
+# stays False all the same: the route is opt-in, tests/test_gpu_linearize_dark_ingest.py documents the frame-by-frame route as
+# today's behaviour for these lists, and changing a default is a decision of its own.
+FUSED_DARK_INGEST_DATA_DEFAULT = False
 # linearize_dataset_generator(fused_flat=...).  The rule, set before measuring (profiles/linearize_flat.md): True only if every
 # fused run was faster than every run of the pair of launches, in every comparison made there.  Measured: per group of 16
 # 1080p frames the fused launch takes 0.41 to 0.51 of the time of linearize + flatfield_correct in all five comparisons, every
@@ -95,7 +113,8 @@ FUSED_FLAT_DEFAULT = False
 def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRFModelBase, flatfield_dataset=None,
                                 gpu_transforms=None, dark_field_dataset=None, output_layout: str = "planar",
                                 fused_dark: bool = FUSED_DARK_DEFAULT, fused_dark_ingest: bool = FUSED_DARK_INGEST_DEFAULT,
-                                fused_flat: bool = FUSED_FLAT_DEFAULT):
+                                fused_flat: bool = FUSED_FLAT_DEFAULT,
+                                fused_dark_ingest_data: bool = FUSED_DARK_INGEST_DATA_DEFAULT):
     """``fused_dark`` (extension; only read with a ``dark_field_dataset``): True lets inputs that
     ``DarkField.fuses_with_linearize`` accepts take the streamed pipeline with ct_linearize_dark; False is the frame-by-frame
     route through ct_dark_field_blur and ct_linearize_std.  The yielded values are the same bit for bit.  The default and the
@@ -122,9 +141,25 @@ def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRF
     ever; so are the frame-by-frame route and a flat field whose shape is not the outputs'.  The yielded values are the same bit
     for bit.  The default and the measurement behind it: FUSED_FLAT_DEFAULT above (False: the fused launch takes 0.41 to 0.51 of
     the pair's time per group, but end to end the copy-out bounds the run and the two ranges of frames/s overlap;
-    profiles/linearize_flat.md)."""
-    if not isinstance(fused_flat, bool):
-        raise TypeError(f"fused_flat must be a bool, got {type(fused_flat).__qualname__}")
+    profiles/linearize_flat.md).
+
+    ``fused_dark_ingest_data`` (extension, opt-in; only read with a ``dark_field_dataset``, ``fused_dark=True`` and
+    ``fused_dark_ingest=True``): True lets inputs that both decisions above declined and
+    ``DarkField.fuses_with_linearize_ingest_data`` accepts -- ``plan_staging`` route "ingest_data": the fused-ingest grammar with
+    ONE data-dependent ``Normalize`` (``Normalize()``, the reference's default transform, above all; per-frame bounds, since every
+    frame is its own batch here) on 4-D uint8 / uint16 / float32 frames, planar or raw (H,W,3) BGR behind a leading ``CvToTorch``,
+    LINEAR / CATMULL -- take the streamed pipeline: ct_ingest_extrema_frames once per group, ct_linearize_dark_ingest_data on the
+    runs of matched frames and ct_linearize_ingest_data on the others (18 + 2 B per uint16 sample with derived uncertainties
+    where the four launches of the frame-by-frame route move 2 + 42; byte counts from the shapes).  Not fused: a
+    ``StridedDownscale`` on either side of that Normalize, LOOKUP, two data-dependent stages.  The yielded values, and the
+    place, type and message of every error (a zero range, a failing match, both in one frame: the zero range), are those of the
+    frame-by-frame route.  False, the default, is that route.  The rule for a later flip and the measurement behind it:
+    FUSED_DARK_INGEST_DATA_DEFAULT above (2.33x the frames/s of the frame-by-frame route on 64 uint16 1080p raw BGR frames and
+    2.68x on planar ones, every fused run faster than every frame-by-frame run; per group of 16 frames the extrema call and the
+    fused launch take 0.48 to 0.55 of the time of the four launches; profiles/linearize_dark_ingest_data.md)."""
+    for name, flag in (("fused_flat", fused_flat), ("fused_dark_ingest_data", fused_dark_ingest_data)):
+        if not isinstance(flag, bool):
+            raise TypeError(f"{name} must be a bool, got {type(flag).__qualname__}")
     if output_layout not in ("planar", "cv"):
         raise ValueError(f"unknown output_layout {output_layout!r} (planar, cv)")
     expect(dataloader, DataLoader, "dataloader")
@@ -149,7 +184,8 @@ def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRF
     first = next(items, None)
     if first is None:
         return
-    plan = _pipeline_plan(first[1], first[2] is not None, transforms, dev, interp, dark, fused_dark, fused_dark_ingest)
+    plan = _pipeline_plan(first[1], first[2] is not None, transforms, dev, interp, dark, fused_dark, fused_dark_ingest,
+                          fused_dark_ingest_data)
     if plan is None:
         yield from _frame_by_frame(first, items, dataloader, dev, transforms, lut, interp, flat, flat_std, dark,
                                    output_layout == "cv")
@@ -158,7 +194,7 @@ def linearize_dataset_generator(dataloader: DataLoader, device, icrf_model: ICRF
                               fused_flat)
 
 
-def _pipeline_plan(probe, with_std, transforms, dev, interp, dark, fused_dark, fused_dark_ingest):
+def _pipeline_plan(probe, with_std, transforms, dev, interp, dark, fused_dark, fused_dark_ingest, fused_dark_ingest_data=False):
     """The plan the streamed pipeline runs with for a run whose first value batch is ``probe`` (``with_std``: it comes with an
     explicit uncertainty image), or None for the frame-by-frame route.  Every decision is asked here, each on the plan made
     for it."""
@@ -172,6 +208,12 @@ def _pipeline_plan(probe, with_std, transforms, dev, interp, dark, fused_dark, f
         if dark.fuses_with_linearize(probe, dark_plan, interp) or (
                 fused_dark_ingest and dark.fuses_with_linearize_ingest(probe, dark_plan, interp)):
             return dark_plan
+        if fused_dark_ingest and fused_dark_ingest_data:
+            # ... and for what both declined, the data-dependent chain's: planned as for the batch on the device (route
+            # "ingest_data" exists only there); the slot keeps the raw frames and their constants (ct_linearize_dark_ingest_data)
+            data_plan = plan_staging(probe, transforms, planar=True, on_device=dev.type == "cuda")
+            if dark.fuses_with_linearize_ingest_data(probe, data_plan, interp):
+                return data_plan
     if route == "pipelined":
         return plan
     # the second, separate decision: a data-dependent Normalize with per-frame constants.  The probe is a host tensor;
@@ -210,8 +252,9 @@ def pipeline_data_route(probe: torch.Tensor, plan, has_dark: bool) -> str:
     Normalize keeps it when the plan says ``step_in_kernel`` (see ``pipeline_route``): the extrema are those of the full
     frames and ct_linearize_ingest_strided takes the constants.  One in
     FRONT of it (``plan.step_first``) needs the extrema of the selected pixels, which no kernel here reduces from the raw
-    frames, and stays frame by frame.  A dark field always does here: ``DarkField.fuses_with_linearize``, the only decision
-    that sends a dark-field run to the pipeline, declines every data-dependent Normalize.  Measured against the frame-by-frame route in profiles/linearize_ingest_data.md;
+    frames, and stays frame by frame.  A dark field always does here: of the decisions that send a dark-field run to the
+    pipeline only ``DarkField.fuses_with_linearize_ingest_data`` takes a data-dependent Normalize, and the generator asks it
+    itself (``fused_dark_ingest_data``), in front of this function.  Measured against the frame-by-frame route in profiles/linearize_ingest_data.md;
     everything else stays frame by frame."""
     if has_dark or probe.ndim != 4 or plan.route != "ingest_data":
         return "frame_by_frame"
@@ -302,6 +345,7 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
     h2d, d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
     in_flight = deque()  # (slot, n frames, pinned lin, pinned std, metas, device dark fields the group's launches read)
     pending = None       # what dark.match raised for a frame: raised once the frames in front of it have been yielded
+    pending_frame = None  # ... and, with per-frame constants, that frame: its zero range is raised in place of ``pending``
 
     def drain_one():
         slot, k, lin_host, std_host, metas, _ = in_flight.popleft()
@@ -331,7 +375,7 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
                     try:
                         matched = dark.match(index_batch, std_batch, std_mode)
                     except Exception as exc:  # stop queueing here; the frames in front are still handed over first
-                        pending, item = exc, None
+                        pending, pending_frame, item = exc, val_batch if data else None, None
                         break
                     # (uploaded on this copy stream when the cache does not hold the pair)
                     pairs.append(None if matched is None else dark.device_pair(*matched))
@@ -352,14 +396,14 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
             break
         compute.wait_event(slot.copied_in)
         compute.wait_event(slot.copied_out)  # the slot's output buffers were last read by its previous copy-out
+        consts = None
+        if data:  # two launches for the group's k sets of constants, into the slot's own buffers (in front of the dark runs)
+            consts = ops.ingest_extrema_frames(slot.frames[:k], plan.prefix, layout, plan.min_val, plan.max_val,
+                                               out=slot.consts[:k], workspace=slot.workspace)
         if dark is not None:
             lin, lin_std = _linearize_dark_runs(slot, k, pairs, with_std, lut, interp, std_mode, std_value, max_code,
-                                                (stages, layout) if fused else None, flat_fused)
+                                                (stages, layout) if fused else None, flat_fused, consts=consts)
         else:
-            consts = None
-            if data:  # two launches for the group's k sets of constants, into the slot's own buffers
-                consts = ops.ingest_extrema_frames(slot.frames[:k], plan.prefix, layout, plan.min_val, plan.max_val,
-                                                   out=slot.consts[:k], workspace=slot.workspace)
             lin, lin_std = _linearize_run(slot, 0, k, with_std, lut, interp, std_mode, std_value, max_code,
                                           stages if fused else None, layout, step, consts, flat=flat_fused)
         if flat is not None and flat_fused is None:  # linearization.py:118-130
@@ -382,6 +426,11 @@ def _pipelined(first, items, dataloader, dev, lut, interp, flat, flat_std, plan,
     while in_flight:
         yield from drain_one()
     if pending is not None:
+        if pending_frame is not None:
+            # the frame-by-frame route stages a frame before it matches it: a zero range of the frame whose match raised wins.
+            # Its constants alone, now that every frame in front has been handed over (one 16-byte readback)
+            frame = pending_frame.to(device=dev, non_blocking=True).contiguous()
+            ops.check_ingest_consts(ops.ingest_extrema(frame, plan.prefix, layout, plan.min_val, plan.max_val))
         raise pending
 
 
@@ -390,7 +439,7 @@ def _linearize_run(slot, a, b, with_std, lut, interp, std_mode, std_value, max_c
     """Frames [a:b] of ``slot`` into the same range of its output buffers, in ONE launch of the kernel they belong to.
     ``stages``: the chain of a plan whose slot holds the RAW frames in ``layout`` (explicit uncertainties planar), None for
     frames ct_linearize_std reads as they are; ``step``: a StridedDownscale the kernel applies; ``consts``: the per-frame
-    constants of a data-dependent Normalize; ``pairs``: the device (dark, dark std) matched to each frame of the run, None for a
+    constants of a data-dependent Normalize, rows [a:b] of the group's; ``pairs``: the device (dark, dark std) matched to each frame of the run, None for a
     run without dark fields; ``flat``: the (flat, flat std | None, flat mean) of ``fused_flat``, applied by the launch itself on a
     run without dark fields (ct_linearize_std_flat, ct_linearize_ingest_flat, ct_linearize_ingest_strided_flat) and by
     ct_flatfield_apply with that mean behind the launch of a run with them.
@@ -400,7 +449,8 @@ def _linearize_run(slot, a, b, with_std, lut, interp, std_mode, std_value, max_c
         None    given   1       linearize_ingest_frames          (ct_linearize_ingest / _data with ``consts``)
         None    given   > 1     linearize_ingest_frames_strided  (ct_linearize_ingest_strided)
         given   None    1       linearize_dark_frames            (ct_linearize_dark)
-        given   given   1       linearize_dark_ingest_frames     (ct_linearize_dark_ingest)"""
+        given   given   1       linearize_dark_ingest_frames     (ct_linearize_dark_ingest)
+        given   given   1       linearize_dark_ingest_frames_data   with ``consts`` (ct_linearize_dark_ingest_data)"""
     frames = slot.frames[a:b]
     args = dict(std=slot.std[a:b] if with_std else None, std_mode=std_mode, std_value=std_value,
                 out=(slot.lin_out[a:b], slot.std_out[a:b]))
@@ -408,8 +458,11 @@ def _linearize_run(slot, a, b, with_std, lut, interp, std_mode, std_value, max_c
         darks, dark_stds = [p[0] for p in pairs], [p[1] for p in pairs]
         if stages is None:
             lin, lin_std = ops.linearize_dark_frames(frames, darks, dark_stds, lut, interp, max_code=max_code, **args)
-        else:
+        elif consts is None:
             lin, lin_std = ops.linearize_dark_ingest_frames(frames, stages, darks, dark_stds, lut, interp, layout=layout, **args)
+        else:
+            lin, lin_std = ops.linearize_dark_ingest_frames_data(frames, stages, darks, dark_stds, lut, interp, consts=consts,
+                                                                 layout=layout, **args)
         if flat is not None:
             ops.flatfield_correct(lin, lin_std, flat[0], flat[1], input_is_variance=False, through_mean=False, flat_mean=flat[2])
         return lin, lin_std
@@ -427,11 +480,12 @@ def _linearize_run(slot, a, b, with_std, lut, interp, std_mode, std_value, max_c
     return ops.linearize_ingest_frames(frames, stages, lut, interp, consts=consts, **args)
 
 
-def _linearize_dark_runs(slot, k, pairs, with_std, lut, interp, std_mode, std_value, max_code, chain=None, flat=None):
+def _linearize_dark_runs(slot, k, pairs, with_std, lut, interp, std_mode, std_value, max_code, chain=None, flat=None, consts=None):
     """The first ``k`` frames of ``slot`` into its output buffers, cut into maximal runs of frames with a matched dark
     field (``pairs[i]``: its device (dark, dark std)) and without one (None: MissingValMode.SKIP_BATCH leaves the frame
-    uncorrected), one ``_linearize_run`` each.  ``chain`` = (stages, layout) of a route "ingest" plan: the slot holds the raw
-    frames in that layout."""
+    uncorrected), one ``_linearize_run`` each.  ``chain`` = (stages, layout) of a route "ingest" / "ingest_data" plan: the slot
+    holds the raw frames in that layout; ``consts``: the (k, 4) per-frame constants of an "ingest_data" plan, made for the whole
+    group before the runs -- every run gets its rows."""
     stages, layout = chain if chain is not None else (None, "nchw")
     a = 0
     while a < k:
@@ -439,6 +493,6 @@ def _linearize_dark_runs(slot, k, pairs, with_std, lut, interp, std_mode, std_va
         while b < k and (pairs[b] is None) == (pairs[a] is None):
             b += 1
         _linearize_run(slot, a, b, with_std, lut, interp, std_mode, std_value, max_code, stages, layout,
-                       pairs=None if pairs[a] is None else pairs[a:b], flat=flat)
+                       consts=None if consts is None else consts[a:b], pairs=None if pairs[a] is None else pairs[a:b], flat=flat)
         a = b
     return slot.lin_out[:k], slot.std_out[:k]

@@ -936,16 +936,16 @@ def _dark_per_frame(frames, darks, dark_stds):
     return out
 
 
-def _linearize_dark(entry, planar, head, geom, middle, darks, dark_stds, threshold, alpha, lut, interp, out):
-    """What linearize_dark_frames and linearize_dark_ingest_frames share behind their own checks: the per-frame dark fields, the
-    ICRF, the (lin, std) outputs and ``entry``(*head, geometry, *middle, dark pointers, threshold, alpha, ICRF, outputs).
-    ``planar``: the frames, or a view without memory that has their planar shape (F,C,H,W) and device."""
+def _linearize_dark(entry, planar, head, geom, middle, darks, dark_stds, threshold, alpha, lut, interp, out, tail=()):
+    """What linearize_dark_frames and linearize_dark_ingest_frames (_data) share behind their own checks: the per-frame dark
+    fields, the ICRF, the (lin, std) outputs and ``entry``(*head, geometry, *middle, dark pointers, threshold, alpha, ICRF, outputs,
+    *tail).  ``planar``: the frames, or a view without memory that has their planar shape (F,C,H,W) and device."""
     shape, dev = tuple(planar.shape), planar.device
     dark_list, dark_std_list = _dark_per_frame(planar, darks, dark_stds)
     icrf, lut_keep = _icrf_struct(lut, interp, shape[1])
     lin, std_out = _lin_std_out(out, shape, dev, True, lin_required=True)
     _call(entry, dev, *head, ctypes.byref(geom), *middle, _pointers(dark_list), _pointers(dark_std_list), float(threshold),
-          float(alpha), ctypes.byref(icrf), _ptr(lin), _ptr(std_out))
+          float(alpha), ctypes.byref(icrf), _ptr(lin), _ptr(std_out), *tail)
     return lin, std_out
 
 
@@ -1287,19 +1287,46 @@ def linearize_dark_ingest_frames(frames: torch.Tensor, stages, darks, dark_stds,
     and PLANAR (F,C,H,W) whatever the layout of the frames.  ``out`` = (lin, std): contiguous float32 (F,C,H,W) device
     buffers to write into.  LOOKUP has no gradient path to the image (RuntimeError, as ``linearize_frames`` with
     uncertainties)."""
+    return _linearize_dark_ingest(frames, stages, darks, dark_stds, lut, interp, std, std_mode, std_value, layout, out, threshold,
+                                  alpha, None)
+
+
+def linearize_dark_ingest_frames_data(frames: torch.Tensor, stages, darks, dark_stds, lut: Optional[torch.Tensor],
+                                      interp: Optional[str] = "linear", *, consts: torch.Tensor, std: Optional[torch.Tensor] = None,
+                                      std_mode: str = "none", std_value: float = 0.0, layout: str = "nchw", out=None,
+                                      threshold: float = 0.05, alpha: float = 50.0):
+    """ct_linearize_dark_ingest_data: ``linearize_dark_ingest_frames`` whose chain may hold one ("affine_data", mul, add) stage -- a
+    data-dependent Normalize with PER-FRAME bounds, whose sub and div for frame k the kernel reads from ``consts[k, 0:2]`` when
+    it runs.  ``consts``: the (F, 4) tensor ``ingest_extrema_frames`` returned for these frames.  For every frame k, bit for bit
+    ``x = ingest_transform(frames[k:k+1], stages, layout, consts=consts[k])``, ``xb, sig = dark_field_blur(x, darks[k],
+    dark_stds[k], ...)`` and ``linearize_frames(xb, lut, interp, std=sig)``, in one launch per MAX_LINEARIZE_DARK_FRAMES frames.
+    No zero-range check happens here (``consts[k, 1] == 0``).  Everything else as ``linearize_dark_ingest_frames``."""
+    if consts is None:
+        raise TypeError("linearize_dark_ingest_frames_data takes the (F, 4) consts of ingest_extrema_frames "
+                        "(constant chains: linearize_dark_ingest_frames)")
+    return _linearize_dark_ingest(frames, stages, darks, dark_stds, lut, interp, std, std_mode, std_value, layout, out, threshold,
+                                  alpha, consts)
+
+
+def _linearize_dark_ingest(frames, stages, darks, dark_stds, lut, interp, std, std_mode, std_value, layout, out, threshold, alpha,
+                           consts):
+    """The two fronts above: ct_linearize_dark_ingest, or with ``consts`` ct_linearize_dark_ingest_data."""
     _check_ingest_stack(frames, layout)
     shape = ingest_shape(tuple(frames.shape), layout)
     f, c = shape[:2]
     dev = frames.device
     if f < 1:
         raise ValueError("no frames")
-    arr, n_stages = _ingest_stages(stages, c)
+    arr, n_stages = _ingest_stages(stages, c, data=consts is not None)
+    if consts is not None:
+        _check_frame_consts(consts, f, dev)
     std, std_mode = _std_arguments(std, std_mode, lambda sd: _planar_std(sd, shape, dev, "outputs"))
     # the dark fields are checked against the planar shape (of the stack only shape and device are read: a view without memory)
     planar = frames if layout == "nchw" else frames.new_empty((1, 1, 1, 1)).expand(shape)
-    return _linearize_dark("ct_linearize_dark_ingest", planar, (_ptr(frames), _DTYPE[frames.dtype], f),
+    entry, tail = ("ct_linearize_dark_ingest", ()) if consts is None else ("ct_linearize_dark_ingest_data", (_ptr(consts),))
+    return _linearize_dark(entry, planar, (_ptr(frames), _DTYPE[frames.dtype], f),
                            _ingest_geometry(shape, None, layout), (arr, n_stages, _ptr(std), _STD[std_mode], float(std_value)),
-                           darks, dark_stds, threshold, alpha, lut, interp, out)
+                           darks, dark_stds, threshold, alpha, lut, interp, out, tail)
 
 
 # ---- such a chain and one batch of the HDR merge in one pass ---------------------------------------------------------------

@@ -646,6 +646,25 @@ int ct_linearize_dark_ingest(const void *frames_dev, int32_t dtype, int64_t n_fr
                              void *stream);
 
 /*
+ * ct_linearize_dark_ingest_data -- ct_linearize_dark_ingest whose chain may hold at most one CT_INGEST_AFFINE_DATA stage with
+ * PER-FRAME constants, as ct_linearize_ingest_data reads them: sub and div of frame f are consts_dev[4 f] and
+ * consts_dev[4 f + 1] (consts_dev: (n_frames, 4) floats as ct_ingest_extrema_frames leaves them, 4-byte aligned, read when the
+ * kernel runs).  For every frame the outputs are bit for bit those of ct_ingest_transform_data on that frame with its four
+ * constants, ct_dark_field_blur on the result and ct_linearize_std on (xb, sigma_eff).  All nine taps of a sample's window take
+ * the frame's own pair (the reflected border taps belong to the same frame).  No zero-range check happens here
+ * (consts_dev[4 f + 1] == 0 divides by zero, as ct_ingest_transform_data does).
+ * consts_dev NULL: ct_linearize_dark_ingest, which refuses that kind.  With constants, a second CT_INGEST_AFFINE_DATA stage and a
+ * consts_dev not aligned to 4 bytes are CT_ERR_INVALID_ARGUMENT, checked with the stage list (in front of the model); constants
+ * beside a chain without such a stage are not read.  Everything else, and every other refusal in its order, as
+ * ct_linearize_dark_ingest: no row band (CT_ERR_UNSUPPORTED), no LOOKUP (CT_ERR_NO_GRADIENT_PATH).
+ */
+int ct_linearize_dark_ingest_data(const void *frames_dev, int32_t dtype, int64_t n_frames, const ct_geometry *geom,
+                                  const ct_ingest_stage *stages, int32_t n_stages, const float *std_dev, int32_t std_mode,
+                                  float std_value, const float *const *dark_devs, const float *const *dark_std_devs,
+                                  float threshold, float alpha, const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev,
+                                  const float *consts_dev, void *stream);
+
+/*
  * ct_hdr_merge_ingest_batch -- such a chain and one batch of compute_hdr_image's loop body in ONE pass over B raw frames:
  * state and outputs are bit for bit those of ct_ingest_transform (with consts_dev: ct_ingest_transform_data) into a dense
  * planar float32 (B, C, H_tile, W) stack followed by ct_hdr_merge_batch on that stack with CT_DTYPE_F32, the same geometry
