@@ -650,7 +650,20 @@ static int validate_merge(const MergeCall &c)
     if (!c.state_ok()) return CT_ERR_INVALID_ARGUMENT;
     if ((c.flags & CT_MERGE_FINALIZE) && (!c.mean_out || (c.std_mode != CT_STD_NONE && !c.std_out))) return CT_ERR_INVALID_ARGUMENT;
     if (!global_below_2_31(geom)) return CT_ERR_TOO_LARGE;
-    return stride_holds_image(geom) ? CT_OK : CT_ERR_INVALID_ARGUMENT;
+    if (!stride_holds_image(geom)) return CT_ERR_INVALID_ARGUMENT;
+    // last, as the fused forms do (ct_merge_dark_kernel.hpp, ct_merge_ingest.hip): every pointer at a multiple of its element --
+    // the one-element launches that packets_aligned leaves to any other address still load and store whole elements
+    return aligned(c.exposure, sizeof(double)) && aligned(c.mean_state, sizeof(double)) && aligned(c.sumw_state, sizeof(float)) &&
+                   aligned(c.var_state, sizeof(float)) &&
+                   aligned(c.mean_out, (c.flags & CT_MERGE_MEAN_OUT_F32) ? sizeof(float) : sizeof(double)) && aligned(c.std_out, sizeof(float))
+               ? CT_OK
+               : CT_ERR_INVALID_ARGUMENT;
+}
+
+// ... and the stack of a batch with its explicit uncertainties (a null pointer is not used, hence aligned)
+static bool batch_pointers_aligned(const void *stack, const float *std_stack, int32_t dtype)
+{
+    return ct::aligned(stack, ct::dtype_bytes(dtype)) && ct::aligned(std_stack, sizeof(float));
 }
 
 // The kernels' argument block for `batch` exposures at `stack` (explicit uncertainties at `std_stack`).  q_begin / q_count
@@ -693,6 +706,7 @@ extern "C" int ct_hdr_merge_batch(const void *stack_dev, int32_t dtype, float ma
                       mean_out_dev, std_out_dev, flags};
     if (!stack_dev || batch <= 0 || (std_mode == CT_STD_EXPLICIT && !std_dev)) return CT_ERR_INVALID_ARGUMENT;
     if (const int rc = validate_merge(c); rc != CT_OK) return rc;
+    if (!batch_pointers_aligned(stack_dev, std_mode == CT_STD_EXPLICIT ? std_dev : nullptr, dtype)) return CT_ERR_INVALID_ARGUMENT;
     MergeArgs a = fill_merge_args(c, stack_dev, std_dev, batch);
     const uint32_t Ql = (uint32_t)local_elements(geom);
     const int interp = icrf->interp;
@@ -734,6 +748,9 @@ extern "C" int ct_hdr_merge_batches(const void *const *stack_devs, const float *
     const MergeCall c{geom, std_mode, std_value, exposure_dev, icrf, weight_mode, mean_state_dev, sumw_state_dev, var_state_dev,
                       mean_out_dev, std_out_dev, flags};
     const int valid = validate_merge(c);  // of the whole sequence (FIRST: before its first batch, FINALIZE: after its last)
+    // a batch off its element is refused here, before the first batch is launched (a one-launch route would read it as it is)
+    for (int b = 0; valid == CT_OK && b < n_batches; ++b)
+        if (!batch_pointers_aligned(stack_devs[b], std_mode == CT_STD_EXPLICIT ? std_devs[b] : nullptr, dtype)) return CT_ERR_INVALID_ARGUMENT;
     const int interp = icrf->interp;
     const int64_t Ql = local_elements(geom);
     hipStream_t s = static_cast<hipStream_t>(stream);
