@@ -36,7 +36,7 @@ EXPORTS = ("ct_abi_version", "ct_error_string", "ct_hdr_merge_batch", "ct_hdr_me
            "ct_video_stats_batches", "ct_video_stats_ingest_batches", "ct_hdr_merge_dark_batch", "ct_linearize_dark",
            "ct_hdr_merge_dark_batches", "ct_linearize_dark_ingest", "ct_hdr_merge_dark_ingest_batches",
            "ct_linearize_std_flat", "ct_linearize_ingest_flat", "ct_linearize_ingest_strided_flat",
-           "ct_linearize_dark_ingest_data")
+           "ct_linearize_dark_ingest_data", "ct_hdr_merge_ingest_strided_batches")
 
 
 class Geometry(ctypes.Structure):
@@ -179,6 +179,10 @@ def load():
     lib.ct_hdr_merge_ingest_batches.restype = i32
     lib.ct_hdr_merge_ingest_batches.argtypes = [vp, vp, i32, i32, gp, ctypes.POINTER(IngestStage), i32, vp, vp, i32, f32, vp, ip, i32, vp,
                                                 vp, vp, vp, vp, u32, vp]
+    # ... _strided: the parent's arguments with the step behind the geometry
+    lib.ct_hdr_merge_ingest_strided_batches.restype = i32
+    lib.ct_hdr_merge_ingest_strided_batches.argtypes = [vp, vp, i32, i32, gp, i32, ctypes.POINTER(IngestStage), i32, vp, vp, i32, f32, vp,
+                                                        ip, i32, vp, vp, vp, vp, vp, u32, vp]
     lib.ct_video_stats_ingest_batch.restype = i32
     lib.ct_video_stats_ingest_batch.argtypes = [vp, i32, i32, gp, ctypes.POINTER(IngestStage), i32, vp, ip, f32, vp, vp, vp]
     stages = ctypes.POINTER(IngestStage)

@@ -235,3 +235,75 @@ extern "C" int ct_hdr_merge_ingest_batches(const void *const *frames_devs, const
         },
         [&](int b, uint32_t f, int64_t offset) { return single(b, std_of(b), f, offset); });
 }
+
+// ... behind a StridedDownscale(step) that the load applies (ct_merge_ingest_strided.hip): `geom` is the SOURCE frames', the state,
+// the outputs and explicit uncertainties are (C, ho, wo).  One kernel family serves one batch and sixteen, so the list in one
+// launch and the list walked batch by batch differ in the MergeIngestBatches block alone.
+extern "C" int ct_hdr_merge_ingest_strided_batches(const void *const *frames_devs, const int32_t *batch_sizes, int32_t n_batches,
+                                                   int32_t dtype, const ct_geometry *geom, int32_t step, const ct_ingest_stage *stages,
+                                                   int32_t n_stages, const float *const *consts_devs, const float *const *std_devs,
+                                                   int32_t std_mode, float std_value, const double *exposure_dev, const ct_icrf *icrf,
+                                                   int32_t weight_mode, double *mean_state_dev, float *sumw_state_dev,
+                                                   float *var_state_dev, void *mean_out_dev, float *std_out_dev, uint32_t flags,
+                                                   void *stream)
+{
+    using namespace ct;
+    if (step < 1) return CT_ERR_INVALID_ARGUMENT;
+    if (step == 1)
+        return ct_hdr_merge_ingest_batches(frames_devs, batch_sizes, n_batches, dtype, geom, stages, n_stages, consts_devs, std_devs, std_mode,
+                                           std_value, exposure_dev, icrf, weight_mode, mean_state_dev, sumw_state_dev, var_state_dev,
+                                           mean_out_dev, std_out_dev, flags, stream);
+    if (!batch_list_ok(n_batches, batch_sizes, frames_devs)) return CT_ERR_INVALID_ARGUMENT;
+    const uint32_t single_flags = flags & ~CT_MERGE_REQUIRE_ONE_LAUNCH;
+    const MergeIngestCall c{dtype, geom, stages, n_stages, std_mode, std_value, exposure_dev, icrf, weight_mode, mean_state_dev,
+                            sumw_state_dev, var_state_dev, mean_out_dev, std_out_dev, single_flags};
+    auto std_of = [&](int b) { return std_mode == CT_STD_EXPLICIT ? batch_item(std_devs, b) : nullptr; };
+    bool by_channel = false;
+    // `batches` exposures (of the batches in mb, times at `exposure`) in one launch, on the output plane
+    auto launch = [&](const MergeIngestBatches &mb, const double *exposure, int32_t batches, uint32_t f) {
+        const bool packed = geom->layout != CT_LAYOUT_NCHW;
+        const int64_t ho = (geom->h_tile + step - 1) / step, wo = (geom->width + step - 1) / step;
+        MergeIngestArgs a = mi_fill_args(c, nullptr, nullptr, nullptr, exposure, batches, f, by_channel);  // plane, base: of step 1
+        a.plane = (uint32_t)(ho * wo);  // untiled (validated): the downscaled frame is the whole image
+        a.plane_global = a.plane;
+        const uint32_t pe = packed ? 3u : 1u;
+        const MergeIngestStride sd{(uint32_t)wo, (uint32_t)(step * geom->width * pe), (uint32_t)step * pe, (uint32_t)(geom->h_tile * geom->width)};
+        return merge_ingest_strided(a, mb, sd, dtype, packed, icrf->interp, weight_mode, std_mode, static_cast<hipStream_t>(stream));
+    };
+    constexpr MergeBatchPolicy kPolicy{/*skip_empty*/ true, /*no_state*/ CT_ERR_INVALID_ARGUMENT, /*require_one_launch*/ CT_ERR_UNSUPPORTED};
+    return merge_batches(
+        batch_sizes, n_batches, flags, c.has_state(), kPolicy,
+        // every batch as ct_hdr_merge_ingest_batch judges it on the source geometry (a stride that holds a SOURCE frame holds
+        // the selected elements), then: no row band behind a downscale -- its phase, row_offset % step, is not carried
+        [&](int b, int64_t) {
+            if (const int rc = mi_validate(c, batch_sizes[b], batch_item(consts_devs, b), by_channel); rc != CT_OK) return rc;
+            return geom->row_offset != 0 || geom->h_tile != geom->h_global ? (int)CT_ERR_INVALID_ARGUMENT : (int)CT_OK;
+        },
+        [&](const MergeBatchList &list) {
+            if (list.n == 0 || c.plane() == 0) return (int)CT_OK;
+            MergeIngestBatches mb = {};
+            int n_consts = 0;
+            for (int k = 0; k < list.n; ++k) {
+                const int b = list.index[k];
+                mb.frames[k] = frames_devs[b];
+                mb.std_stack[k] = std_of(b);
+                mb.consts[k] = batch_item(consts_devs, b);
+                mb.batch[k] = batch_sizes[b];
+                n_consts += mb.consts[k] ? 1 : 0;
+                if (!mi_pointers_ok(c, mb.frames[k], mb.std_stack[k])) return (int)CT_ERR_INVALID_ARGUMENT;
+            }
+            mb.n_batches = list.n;
+            // one launch: constants for all batches or for none, and the scales of all exposures beside the LUT
+            if ((n_consts != 0 && n_consts != list.n) || !merge_scales_fit(icrf, geom->channels, list.total)) return kMergePerBatch;
+            return launch(mb, exposure_dev, (int32_t)list.total, single_flags);
+        },
+        [&](int b, uint32_t f, int64_t offset) {
+            MergeIngestBatches mb = {};
+            mb.frames[0] = frames_devs[b];
+            mb.std_stack[0] = std_of(b);
+            mb.consts[0] = batch_item(consts_devs, b);
+            mb.batch[0] = batch_sizes[b];
+            mb.n_batches = 1;
+            return launch(mb, exposure_dev + offset, batch_sizes[b], f);
+        });
+}

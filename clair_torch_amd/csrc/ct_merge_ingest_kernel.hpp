@@ -2,7 +2,8 @@
 // (several batches per launch, the streaming state in registers in between) share: the argument blocks and mi_run, the walk of
 // one thread over the batch(es) of the elements it owns.  The head of ct_merge_ingest.hip describes ownership, packets and
 // the element-by-element walk.  MULTI is a template flag of that one body; everything it adds is behind `if constexpr`, and
-// the order of the text is kept so that the single-batch kernels compile to the instructions they had without it.  The
+// the order of the text is kept so that the single-batch kernels compile to the instructions they had without it; STRIDED
+// (ct_merge_ingest_strided.hip: a StridedDownscale applied by the load) is a second such flag, under the same rule.  The
 // workgroups around mi_run are written out in the two .hip files: shared as a function they compile to other instructions
 // (profiles/merge_fused_refactor_ab.md).  Host side, what the three fused families (this one, ct_merge_dark_kernel.hpp and
 // ct_merge_dark_ingest_kernel.hpp) have in front of a launch, one copy each: the dtype and mode dispatch (with_code_dtype,
@@ -64,6 +65,19 @@ inline size_t mi_lds_bytes(int interp, int channels, int n_points, int64_t batch
     return lut_lds_bytes(interp, channels, n_points) + 2 * sizeof(float) * (size_t)batch;
 }
 
+// ct_merge_ingest_strided.hip: a StridedDownscale(step) in front of the chain, applied by the load.  MergeIngestArgs then
+// describes the OUTPUT (plane = plane_global = ho * wo, base = 0; image_stride stays the source's) and this block the source.
+struct MergeIngestStride {
+    uint32_t wo;            // output columns
+    uint32_t row_stride;    // source elements between selected rows: step * W (interleaved: step * 3 W)
+    uint32_t pixel_stride;  // ... between selected pixels of a row: step (interleaved: 3 step)
+    uint32_t src_plane;     // planar: source elements per plane, H * W
+};
+
+// ct_merge_ingest_strided.hip: 1 .. kMaxIngestBatches batches behind a downscale in one launch of the STRIDED kernels
+int merge_ingest_strided(const MergeIngestArgs &a, const MergeIngestBatches &mb, const MergeIngestStride &sd, int dtype, bool packed,
+                         int interp, int weight_mode, int std_mode, hipStream_t stream);
+
 constexpr int kMiGroup = 4;        // PLANAR: output elements per thread, one 16-byte packet
 constexpr int kMiPackedGroup = 2;  // PACKED3: pixels per thread (see the head of ct_merge_ingest.hip)
 constexpr int kMiPF = 2;     // samples in flight ahead of the one being reduced
@@ -116,9 +130,13 @@ __device__ __forceinline__ void mi_store(X *p, const X (&v)[G])
 // epilogue, conditioning test and one repeat -- with (mean, sum of weights, variance) in registers in between: the state
 // arrays are read once, before batch 0 (unless it starts the merge), and written once, after the last batch; FIRST_BATCH
 // is batch 0's and FINALIZE the last one's.  inv_t and cq hold the scales of all batches, concatenated.
-template <typename T, bool PACKED, int G, int INTERP, int WEIGHT, int STD, bool MULTI>
+// STRIDED (ct_merge_ingest_strided.hip): p0 and everything in `a` but image_stride are OUTPUT coordinates of a downscale; the
+// source of output element p = i * wo + j is row i * step, column j * step of the same plane (frame), so the one dense load
+// per exposure becomes one load per selected element (pixel) from offsets computed once -- nothing else changes.
+template <typename T, bool PACKED, int G, int INTERP, int WEIGHT, int STD, bool MULTI, bool STRIDED = false>
 __device__ __forceinline__ void mi_run(const MergeIngestArgs &a, const MergeIngestBatches *mb, const char *lds, const float *inv_t,
-                                       const float *cq, uint32_t c0, uint32_t p0, float dsub, float ddiv)
+                                       const float *cq, uint32_t c0, uint32_t p0, float dsub, float ddiv,
+                                       const MergeIngestStride *sd = nullptr)
 {
     constexpr int NP = PACKED ? 3 : 1;  // planes per thread
     constexpr int NE = NP * G;
@@ -151,14 +169,33 @@ __device__ __forceinline__ void mi_run(const MergeIngestArgs &a, const MergeInge
             r = r >= C ? r - C : r;
         }
     }
-    const int64_t src_off = PACKED ? (int64_t)p0 * NP : (int64_t)c0 * a.plane + p0;
+    // STRIDED: (i, j) of element p0 with one division, carried over the end of an output row; i < ho and j < wo for all G
+    // elements (the caller hands over whole groups inside the plane), so every offset lies inside the source plane (frame)
+    [[maybe_unused]] uint32_t off[STRIDED ? G : 1];
+    if constexpr (STRIDED) {
+        uint32_t i = p0 / sd->wo, j = p0 - i * sd->wo;
+#pragma unroll
+        for (int e = 0; e < G; ++e) {
+            off[e] = i * sd->row_stride + j * sd->pixel_stride;
+            if (++j == sd->wo) {
+                j = 0;
+                ++i;
+            }
+        }
+    }
+    const int64_t src_off = STRIDED ? (PACKED ? (int64_t)0 : (int64_t)c0 * sd->src_plane) : PACKED ? (int64_t)p0 * NP : (int64_t)c0 * a.plane + p0;
     const T *src = static_cast<const T *>(a.frames) + src_off;
     const float *std_multi = nullptr;  // MULTI: the batch's explicit uncertainties
     const int64_t std_stride = (int64_t)C * a.plane;  // the explicit uncertainties are planar and dense
 
     auto load_raw = [&](int64_t frame_offset) {
         MiRaw<T, NE> r;
-        __builtin_memcpy(&r, src + frame_offset, sizeof(r));  // any alignment: planes are only element-aligned in general
+        if constexpr (STRIDED) {
+#pragma unroll
+            for (int e = 0; e < G; ++e) __builtin_memcpy(&r.v[e * NP], src + frame_offset + off[e], NP * sizeof(T));  // one selected pixel
+        } else {
+            __builtin_memcpy(&r, src + frame_offset, sizeof(r));  // any alignment: planes are only element-aligned in general
+        }
         return r;
     };
     // the G pixels of plane j behind the chain

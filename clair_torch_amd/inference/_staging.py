@@ -31,15 +31,25 @@ class DeferredIngest:
     """A batch on routes "ingest" / "ingest_data" whose chain has NOT been executed (``stage_images(defer_ingest=True)``): the
     raw device ``frames`` (behind the StridedDownscale compaction where the plan has one), the ``stages`` as
     ``ops.ingest_transform`` takes them, the ``layout`` of the frames, and for "ingest_data" the ``consts`` of
-    ``ops.ingest_extrema`` (already checked for a zero range), else None.  ``ops.hdr_merge_ingest_batch`` takes all four."""
+    ``ops.ingest_extrema`` (already checked for a zero range), else None.  ``ops.hdr_merge_ingest_batch`` takes all four.
+    ``step`` (``stage_images(step_in_kernel=True)``): above 1 the StridedDownscale has NOT been applied either -- ``frames`` are
+    the raw full-size ones and the consumer's kernel selects every ``step``-th row and column (``ops.hdr_merge_ingest_batches_strided``),
+    or ``materialise`` compacts them first."""
     frames: torch.Tensor
     stages: tuple
     layout: str
     consts: Optional[torch.Tensor] = None
+    step: int = 1
+
+    def materialise(self) -> torch.Tensor:
+        """The float32 planar pixels the staging would have returned without ``defer_ingest``: the downscale where it is still
+        owed, then ct_ingest_transform(_data)."""
+        frames = ops.strided_downscale(self.frames, self.step, layout=self.layout) if self.step > 1 else self.frames
+        return ops.ingest_transform(frames, self.stages, layout=self.layout, consts=self.consts)
 
 
 def stage_images(val_batch: torch.Tensor, device: torch.device, transforms: list, planar: bool = False,
-                 defer_ingest: bool = False):
+                 defer_ingest: bool = False, step_in_kernel: bool = False):
     """Move the value batch to the device and run / fuse the device transforms: (images, max_code, layout).
 
     ``plan_staging`` picks the route (the table in common/transforms.py); what each of them does here and returns:
@@ -61,14 +71,24 @@ def stage_images(val_batch: torch.Tensor, device: torch.device, transforms: list
     ``planar``: the caller holds explicit std or dark-field images, which are planar: the layout is then always "nchw".
     ``defer_ingest`` (opt-in): routes "ingest" and "ingest_data" do everything but ct_ingest_transform(_data) and return a
     ``DeferredIngest`` in place of the float32 pixels, for a kernel that evaluates the chain itself; the other routes
-    return what they always do."""
+    return what they always do.
+    ``step_in_kernel`` (opt-in, read with ``defer_ingest`` only): the caller's kernel applies a StridedDownscale itself.  Route
+    "ingest" then skips the compaction and returns the raw full-size frames with ``DeferredIngest.step`` = the plan's step;
+    route "ingest_data" does the same when the Normalize stands IN FRONT of the downscale (the extrema are those of the full
+    stack, as ever); with the downscale in front (``step_first``) it compacts as before and the step is 1.  Route "code" with
+    a downscale, and everything without ``defer_ingest``, is staged as without the flag."""
     images = val_batch.to(device=device, non_blocking=True)  # the ONE host-to-device copy of the batch (a plain DMA when pinned)
-    plan = plan_staging(images, transforms, planar)
+    # (a caller that passes nothing new plans exactly as before: the call itself is the old one)
+    plan = plan_staging(images, transforms, planar, step_in_kernel=True) if step_in_kernel and defer_ingest else \
+        plan_staging(images, transforms, planar)
+    keep_step = plan.step_in_kernel and plan.route in ("ingest", "ingest_data") and not plan.step_first
     if plan.route == "code":
         if plan.step > 1:
             images = ops.strided_downscale(images, plan.step, layout=plan.layout)
         return images, plan.max_code, plan.layout
     if plan.route == "ingest":
+        if keep_step:
+            return DeferredIngest(images, plan.stages, plan.source_layout, step=plan.step), None, "nchw"
         images = ops.strided_downscale(images, plan.step, layout=plan.source_layout)
         if defer_ingest:
             return DeferredIngest(images, plan.stages, plan.source_layout), None, "nchw"
@@ -77,6 +97,9 @@ def stage_images(val_batch: torch.Tensor, device: torch.device, transforms: list
         if plan.step_first:
             images = ops.strided_downscale(images, plan.step, layout=plan.source_layout)
         consts = ops.ingest_extrema(images, plan.prefix, plan.source_layout, plan.min_val, plan.max_val)
+        if keep_step:
+            ops.check_ingest_consts(consts)
+            return DeferredIngest(images, plan.stages, plan.source_layout, consts, step=plan.step), None, "nchw"
         if not plan.step_first:
             images = ops.strided_downscale(images, plan.step, layout=plan.source_layout)
         if defer_ingest:

@@ -25,6 +25,11 @@ DARK_QUEUE_BYTES = 8 << 30
 # measured shape -- the rule ``fused_dark`` was decided by.
 FUSED_DARK_INGEST_DEFAULT = False
 
+# compute_hdr_image(fused_downscale=...).  The same rule, set before measuring (profiles/merge_ingest_strided.md): True only if
+# every timed run of the fused launch (ops.hdr_merge_ingest_batches_strided) is faster than every timed run of
+# ops.strided_downscale + ops.hdr_merge_ingest_batches at every measured shape -- and only if no existing test notices the route.
+FUSED_DOWNSCALE_DEFAULT = False
+
 
 class _QueueKind(NamedTuple):
     """What the queued batches of compute_hdr_image have in common, and what tells one launch of them from the next."""
@@ -47,7 +52,7 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
                       dark_field_dataset=None, tile: Optional[ops.TileGeometry] = None, group=None,
                       output_layout: str = "planar", reference_order: Optional[bool] = None, fused_ingest: bool = True,
                       fused_dark: bool = True, dark_batches_per_launch: int = 1,
-                      fused_dark_ingest: bool = FUSED_DARK_INGEST_DEFAULT):
+                      fused_dark_ingest: bool = FUSED_DARK_INGEST_DEFAULT, fused_downscale: bool = FUSED_DOWNSCALE_DEFAULT):
     """Merge the exposure stack served by ``dataloader`` into an HDR image and its standard uncertainty.
 
     Returns ``(mean float64 (C,H,W), std float32 (C,H,W) | None)`` on ``device`` (squeezed like the reference).
@@ -104,6 +109,16 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
     are materialised with ct_ingest_transform and go on as without this keyword.  The results are the same bit for bit.
     False = ct_ingest_transform when the batch is staged, as before this keyword existed.  Measured: see
     profiles/merge_dark_ingest.md for the numbers and for the default, which follows the rule stated there.
+    ``fused_downscale`` (extension; only read without a ``dark_field_dataset`` and with ``fused_ingest=True``): a ``gpu_transforms``
+    list on route "ingest" / "ingest_data" that holds a ``StridedDownscale``.  True = the staging does not compact the batch
+    (ct_strided_downscale: a copy written once to be read once); the queued batches stay the raw full-size frames and one launch
+    of ct_hdr_merge_ingest_strided_batches selects every step-th row and column while it merges them.  The results are the same
+    bit for bit.  These keep today's route whatever the keyword says: route "code" with a downscale (the pivoted code-domain
+    kernel is other arithmetic, so bit-identity with it cannot be promised), a data-dependent Normalize BEHIND the downscale (its
+    extrema are those of the selected pixels: the staging compacts first), dark-field batches, row bands (``tile`` with a
+    downscale is refused as ever), float32 frames and the reference-order modes (compacted, then the float32 stack), and the
+    video-statistics and pair kernels.  Measured: see profiles/merge_ingest_strided.md for the numbers and for the default,
+    which follows the rule stated there.
     """
     if type(dark_batches_per_launch) is not int or not 1 <= dark_batches_per_launch <= ops.MAX_MERGE_BATCHES:
         raise ValueError(f"dark_batches_per_launch must be an int in 1 .. {ops.MAX_MERGE_BATCHES}, got {dark_batches_per_launch!r}")
@@ -186,9 +201,11 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
         # and the streaming state stays in registers between the batches, as on the code route
         d = k0["images"]
         consts = None if d.consts is None else [q["images"].consts for q in queue]
-        return ops.hdr_merge_ingest_batches([q["images"].frames for q in queue], d.stages, column("exposure"), stds=column("std"),
-                                            std_mode=k0["std_mode"], std_value=k0["std_value"], tile=tile, layout=d.layout, consts=consts,
-                                            **args)
+        kw = dict(stds=column("std"), std_mode=k0["std_mode"], std_value=k0["std_value"], tile=tile, layout=d.layout, consts=consts, **args)
+        frames = [q["images"].frames for q in queue]
+        if d.step > 1:  # ... and so is the StridedDownscale: the load selects every step-th row and column of the raw frames
+            return ops.hdr_merge_ingest_batches_strided(frames, d.step, d.stages, column("exposure"), **kw)
+        return ops.hdr_merge_ingest_batches(frames, d.stages, column("exposure"), **kw)
 
     def launch_plain(k0, **args):
         return ops.hdr_merge_batches(column("images"), column("exposure"), stds=column("std"), std_mode=k0["std_mode"],
@@ -201,7 +218,8 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
         last = pending is None
         planar = std_batch is not None or dark is not None  # explicit std / dark images are planar
         defer = fused_ingest if dark is None else (fused_dark and fused_dark_ingest)
-        images, max_code, layout = stage_images(val_batch, dev, transforms, planar, defer_ingest=defer)
+        images, max_code, layout = stage_images(val_batch, dev, transforms, planar, defer_ingest=defer,
+                                                step_in_kernel=dark is None and fused_downscale)
         std, std_mode, std_value = std_arguments(std_batch, dataloader.dataset, dev)
         exposure = meta_batch["exposure_time"]
         fused = isinstance(images, DeferredIngest)
@@ -218,12 +236,12 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
                         images=images, exposure=exposure, std=std, std_mode=std_mode, std_value=std_value, matched=matched, halo=halo)
                 continue
             if matched is not None:  # declined: the float32 stack, then as without the keyword
-                images = ops.ingest_transform(images.frames, images.stages, layout=images.layout, consts=images.consts)
+                images = images.materialise()
                 fused = False
         if fused and (images.frames.dtype == torch.float32 or reference_order is True or
                       (interp in ("lookup", "catmull") and std_mode != "none" and reference_order is None)):
             # float32 frames have no copy to save, and the reference-order kernel is not fused: they get the float32 stack
-            images = ops.ingest_transform(images.frames, images.stages, layout=images.layout, consts=images.consts)
+            images = images.materialise()
             fused = False
         if dark is not None:
             if not asked:
@@ -250,9 +268,9 @@ def compute_hdr_image(dataloader: DataLoader, device, icrf_model: Optional[ICRFM
                 images, max_code, std, std_mode, std_value = xb, None, sig, "explicit", 0.0
         if fused:  # one dtype, shape, layout and chain per call; every batch with constants of its own, or none
             key = ("ingest", images.frames.dtype, tuple(images.frames.shape[1:]), images.layout, images.stages, std_mode, std_value,
-                   std is None, images.consts is None)
-            enqueue(_QueueKind(key, ops.MAX_MERGE_BATCHES, 0, ops.ingest_shape(tuple(images.frames.shape), images.layout)[1:],
-                               std_mode != "none", launch_ingest),
+                   std is None, images.consts is None, images.step)
+            chw = ops.downscaled_shape(ops.ingest_shape(tuple(images.frames.shape), images.layout), images.step)[1:]
+            enqueue(_QueueKind(key, ops.MAX_MERGE_BATCHES, 0, chw, std_mode != "none", launch_ingest),
                     images=images, exposure=exposure, std=std, std_mode=std_mode, std_value=std_value)
         else:
             key = (images.dtype, tuple(images.shape[1:]), max_code, layout, std_mode, std_value, std is None)

@@ -1421,6 +1421,75 @@ def hdr_merge_ingest_batches(frames_list, stages, exposures_list, *, lut: Option
                          probe_one_launch=True)
 
 
+# ---- a StridedDownscale, such a chain and several batches of the HDR merge in one pass over the raw frames -----------------------
+def hdr_merge_ingest_batches_strided(frames_list, step: int, stages, exposures_list, *, lut: Optional[torch.Tensor] = None,
+                                     interp: Optional[str] = "linear", gaussian_weight: bool = True, stds=None,
+                                     std_mode: str = "none", std_value: float = 0.0, state: Optional[MergeState] = None,
+                                     finalize: bool = True, tile: Optional[TileGeometry] = None,
+                                     mean_dtype: torch.dtype = torch.float64, layout: str = "nchw",
+                                     reference_order: Optional[bool] = None, consts=None, require_one_launch: bool = False):
+    """ct_hdr_merge_ingest_strided_batches: ``hdr_merge_ingest_batches([strided_downscale(f, step, layout) for f in
+    frames_list], stages, exposures_list, ...)`` bit for bit, in one launch over the raw full-size frames and without the
+    compacted copies in between.  Returns (mean, std|None), planar (C,ho,wo) with ho = ceil(H/step), wo = ceil(W/step), when
+    ``finalize`` else None.
+
+    ``frames_list``, ``stages``, ``exposures_list``, ``layout`` and every keyword as ``hdr_merge_ingest_batches`` takes them.
+    ``consts`` are those of the frames as given (``ingest_extrema`` on the full batch: a data-dependent Normalize in FRONT of
+    the downscale).  ``stds``: explicit uncertainties, float32 and planar (B_k,C,ho,wo) -- already of the downscaled shape,
+    because gpu_transforms are applied to the value images only.  ``state``: a MergeState of shape (C,ho,wo).  ``step == 1``
+    is ``hdr_merge_ingest_batches`` itself.  ``tile``: with ``step == 1`` only (a row band behind a downscale is refused: the
+    phase of the band is not carried).  One kernel family serves one batch and sixteen."""
+    if isinstance(step, bool) or not isinstance(step, int) or step < 1:
+        raise ValueError(f"step must be an int >= 1, got {step!r}")
+    if step == 1:
+        return hdr_merge_ingest_batches(frames_list, stages, exposures_list, lut=lut, interp=interp, gaussian_weight=gaussian_weight,
+                                        stds=stds, std_mode=std_mode, std_value=std_value, state=state, finalize=finalize, tile=tile,
+                                        mean_dtype=mean_dtype, layout=layout, reference_order=reference_order, consts=consts,
+                                        require_one_launch=require_one_launch)
+    if tile is not None:
+        raise ValueError("tile= cannot be combined with step > 1: which rows of a band a downscale selects depends on "
+                         "row_offset % step, a phase that is not carried")
+
+    def check_stack(t):
+        _check_ingest_stack(t, layout, codes_only="hdr_merge_ingest_batches_strided takes uint8 / uint16 codes (float32 pixels: "
+                                                  "strided_downscale + ingest_transform + hdr_merge_batches)")
+
+    _check_batch_list(frames_list, (exposures_list, stds, consts), "frames / exposures / stds / consts", check_stack)
+    k = len(frames_list)
+    f0 = frames_list[0]
+    dev = f0.device
+    shape0 = ingest_shape(tuple(f0.shape), layout)
+    _, c, ho, wo = downscaled_shape(shape0, step)
+    has_consts = consts is not None and any(t is not None for t in consts)
+    arr, n_stages = _ingest_stages(stages, c, data=has_consts)
+    if consts is not None:
+        for t in consts:
+            if t is not None:
+                _check_consts(t, dev)
+    stds, std_mode = _std_arguments(stds, std_mode, lambda sds: [_planar_std(sd, (int(t.shape[0]), c, ho, wo), dev, "state")
+                                                                 for sd, t in zip(sds, frames_list)])
+    sizes = [int(t.shape[0]) for t in frames_list]
+    exposure_dev = _exposure_list_to_device(exposures_list, sizes, dev)
+    icrf, lut_keep = _icrf_struct(lut, interp, c)
+    geom = _ingest_geometry(shape0, None, layout)  # of the SOURCE frames
+    flags, mean_out, std_out = _merge_setup((c, ho, wo), dev, "planar", state, finalize, std_mode != "none", mean_dtype, reference_order,
+                                            nv.MERGE_REQUIRE_ONE_LAUNCH if require_one_launch else 0, "call")
+    head = (_pointers(frames_list), (ctypes.c_int32 * k)(*sizes), k, _DTYPE[f0.dtype], ctypes.byref(geom), min(step, 0x7fffffff), arr,
+            n_stages, _pointers(consts), _pointers(stds), _STD[std_mode], float(std_value), _ptr(exposure_dev), ctypes.byref(icrf),
+            _weight(gaussian_weight))
+    return _launch_merge("ct_hdr_merge_ingest_strided_batches", dev, head, state, flags, k, mean_out, std_out, retry_with_state=True,
+                         probe_one_launch=True)
+
+
+def hdr_merge_ingest_batch_strided(frames: torch.Tensor, step: int, stages, exposures: torch.Tensor, *,
+                                   std: Optional[torch.Tensor] = None, consts: Optional[torch.Tensor] = None, **kw):
+    """One batch of ``hdr_merge_ingest_batches_strided``: ``hdr_merge_ingest_batch(strided_downscale(frames, step, layout),
+    stages, exposures, ...)`` bit for bit.  ``std`` (planar (B,C,ho,wo)) and ``consts`` are the batch's own; every other keyword
+    as ``hdr_merge_ingest_batch`` takes it."""
+    return hdr_merge_ingest_batches_strided([frames], step, stages, [exposures], stds=None if std is None else [std],
+                                            consts=None if consts is None else [consts], **kw)
+
+
 # ---- such a chain, the dark-field blur and several batches of the HDR merge in one pass ---------------------------------------
 def hdr_merge_dark_ingest_batches(frames_list, stages, exposures_list, darks, dark_stds, *, consts=None, stds=None,
                                   std_mode: str = "none", std_value: float = 0.0, lut: Optional[torch.Tensor] = None,

@@ -54,6 +54,13 @@ and pair lists are passed as their component tensors / scalars.
                                   std float32)   (such a chain, the dark-field blur and 1 to 16 consecutive batches of one
                                   whole merge in one pass over the raw frames; lists hold one tensor per batch, the last
                                   three may be empty)
+    torch.ops.clair_hip.hdr_merge_ingest_batches_strided(frames[], step, stages, exposures[], consts[], stds[], lut?, interp,
+                                  gaussian, std_mode, std_value, layout, closed_form) -> (mean float64, std float32)
+                                  (strided_downscale of every batch, such a chain and 1 to 16 consecutive batches of one
+                                  whole merge in one pass over the raw full-size frames; results and explicit stds have the
+                                  downscaled shape; the last two lists may be empty)
+    torch.ops.clair_hip.hdr_merge_ingest_batch_strided(frames, step, stages, exposures, lut?, interp, gaussian, std?, std_mode,
+                                  std_value, layout, closed_form, consts?) -> (mean float64, std float32)   (its single-batch form)
 
 CPU tensors are refused by the kernels' front-end exactly as through ``ops`` (there is no CPU path).
 """
@@ -478,3 +485,47 @@ def _(frames, stages, exposures, darks, dark_stds, consts, stds, lut, interp, ga
       closed_form=False):
     chw = ops.ingest_shape(tuple(frames[0].shape), layout)[1:]
     return frames[0].new_empty(chw, dtype=torch.float64), frames[0].new_empty(chw if len(dark_stds) else (0,), dtype=torch.float32)
+
+
+@torch.library.custom_op(f"{_LIB}::hdr_merge_ingest_batches_strided", mutates_args=())
+def hdr_merge_ingest_batches_strided(frames: Sequence[torch.Tensor], step: int, stages: Sequence[float],
+                                     exposures: Sequence[torch.Tensor], consts: Sequence[torch.Tensor], stds: Sequence[torch.Tensor],
+                                     lut: Optional[torch.Tensor], interp: str, gaussian: bool, std_mode: str, std_value: float,
+                                     layout: str = "nchw", closed_form: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ct_hdr_merge_ingest_strided_batches: per batch strided_downscale followed by the fused chain + merge, bit for bit, in one
+    pass over the raw full-size frames (a whole merge: first and final).  One tensor per batch in every list; ``consts`` and
+    ``stds`` may be empty (none); explicit stds are planar and of the downscaled shape (B_k,C,ho,wo)."""
+    mean, sd = ops.hdr_merge_ingest_batches_strided(list(frames), step, _listed_ingest_stages(frames[0], stages, layout),
+                                                    list(exposures), lut=lut, interp=interp if lut is not None else None,
+                                                    gaussian_weight=gaussian, stds=list(stds) or None, std_mode=std_mode,
+                                                    std_value=std_value, layout=layout, reference_order=False if closed_form else None,
+                                                    consts=list(consts) or None)
+    return mean, (sd if sd is not None else mean.new_zeros(0, dtype=torch.float32))
+
+
+@hdr_merge_ingest_batches_strided.register_fake
+def _(frames, step, stages, exposures, consts, stds, lut, interp, gaussian, std_mode, std_value, layout="nchw", closed_form=False):
+    chw = ops.downscaled_shape(ops.ingest_shape(tuple(frames[0].shape), layout), step)[1:]
+    has_std = len(stds) > 0 or std_mode != "none"
+    return frames[0].new_empty(chw, dtype=torch.float64), frames[0].new_empty(chw if has_std else (0,), dtype=torch.float32)
+
+
+@torch.library.custom_op(f"{_LIB}::hdr_merge_ingest_batch_strided", mutates_args=())
+def hdr_merge_ingest_batch_strided(frames: torch.Tensor, step: int, stages: Sequence[float], exposures: torch.Tensor,
+                                   lut: Optional[torch.Tensor], interp: str, gaussian: bool, std: Optional[torch.Tensor],
+                                   std_mode: str, std_value: float, layout: str = "nchw", closed_form: bool = False,
+                                   consts: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The single-batch form of hdr_merge_ingest_batches_strided (strided_downscale followed by hdr_merge_ingest_batch, bit for
+    bit, in one pass); an explicit std is planar (B,C,ho,wo)."""
+    mean, sd = ops.hdr_merge_ingest_batch_strided(frames, step, _listed_ingest_stages(frames, stages, layout), exposures, lut=lut,
+                                                  interp=interp if lut is not None else None, gaussian_weight=gaussian, std=std,
+                                                  std_mode=std_mode, std_value=std_value, layout=layout,
+                                                  reference_order=False if closed_form else None, consts=consts)
+    return mean, (sd if sd is not None else mean.new_zeros(0, dtype=torch.float32))
+
+
+@hdr_merge_ingest_batch_strided.register_fake
+def _(frames, step, stages, exposures, lut, interp, gaussian, std, std_mode, std_value, layout="nchw", closed_form=False, consts=None):
+    chw = ops.downscaled_shape(ops.ingest_shape(tuple(frames.shape), layout), step)[1:]
+    has_std = std is not None or std_mode != "none"
+    return frames.new_empty(chw, dtype=torch.float64), frames.new_empty(chw if has_std else (0,), dtype=torch.float32)

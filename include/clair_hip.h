@@ -732,6 +732,37 @@ int ct_hdr_merge_ingest_batches(const void *const *frames_devs, const int32_t *b
                                 uint32_t flags, void *stream);
 
 /*
+ * ct_hdr_merge_ingest_strided_batches -- StridedDownscale(step), such a chain and n_batches consecutive batches of one merge in
+ * ONE pass over the RAW full-size frames: state and outputs are bit for bit those of ct_strided_downscale on every batch
+ * followed by ct_hdr_merge_ingest_batches on the compacted frames, without the compacted copies.  With ho = ceil(H / step) and
+ * wo = ceil(W / step), output element (c, i, j) reads row i * step, column j * step of plane c of every frame.
+ *   geom         of the SOURCE frames (layout, H, W, image_stride) as ct_hdr_merge_ingest_batch takes it.  With step > 1 a row
+ *                band (row_offset != 0 or h_tile != h_global) is CT_ERR_INVALID_ARGUMENT: which rows of a band a downscale
+ *                selects depends on row_offset % step, a phase that is not carried
+ *   step         >= 1, else CT_ERR_INVALID_ARGUMENT (tested first).  step == 1 is ct_hdr_merge_ingest_batches itself, row band
+ *                included
+ *   std_devs     CT_STD_EXPLICIT: each planar (B_b, C, ho, wo) float32, dense -- already of the OUTPUT shape: gpu_transforms are
+ *                applied to the value images only
+ *   consts_devs  as ct_hdr_merge_ingest_batches: per batch, computed by the caller on the frames as given (ct_ingest_extrema on
+ *                the FULL batch: a Normalize in front of the downscale)
+ *   state, outputs   planar (C, ho, wo)
+ * The LINEAR / CATMULL LUT row is the flat NCHW index of the DOWNSCALED frame modulo C, (c * ho * wo + i * wo + j) % C.
+ * With step > 1: the list is checked (n_batches outside 1 .. 16: CT_ERR_INVALID_ARGUMENT), then every batch is judged as
+ * ct_hdr_merge_ingest_batch judges it ON THE SOURCE GEOMETRY, in its order (image_stride must hold a source frame), then for
+ * the row band, before anything touches the device.  CT_DTYPE_F32, CT_MERGE_REFERENCE_ORDER, CT_MERGE_F64_MOMENTS,
+ * CT_MERGE_OUT_AS_INPUT and the reference-order modes are CT_ERR_UNSUPPORTED as there.  One launch takes 1 .. 16 batches; the
+ * conditions of one launch, the walk batch by batch with the state in memory otherwise and CT_MERGE_REQUIRE_ONE_LAUNCH are
+ * those of ct_hdr_merge_ingest_batches.  Reads only selected elements of the frames, never writes them, touches nothing
+ * outside C*ho*wo elements of the state and the outputs.
+ */
+int ct_hdr_merge_ingest_strided_batches(const void *const *frames_devs, const int32_t *batch_sizes, int32_t n_batches, int32_t dtype,
+                                        const ct_geometry *geom, int32_t step, const ct_ingest_stage *stages, int32_t n_stages,
+                                        const float *const *consts_devs, const float *const *std_devs, int32_t std_mode,
+                                        float std_value, const double *exposure_dev, const ct_icrf *icrf, int32_t weight_mode,
+                                        double *mean_state_dev, float *sumw_state_dev, float *var_state_dev, void *mean_out_dev,
+                                        float *std_out_dev, uint32_t flags, void *stream);
+
+/*
  * ct_hdr_merge_dark_ingest_batches -- n_batches consecutive dark-field batches of one merge behind one chain in one call, on
  * the RAW frames: for every batch the state and the outputs are bit for bit those of ct_ingest_transform (with constants:
  * ct_ingest_transform_data) into a dense planar float32 (B_b, C, H_tile, W) stack followed by ct_hdr_merge_dark_batch on that
