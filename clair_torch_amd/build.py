@@ -20,7 +20,7 @@ OBJ_DIR = os.path.join(LIB_DIR, "obj")   # per-source objects (git-ignored), so 
 SOURCES = ["ct_merge.hip", "ct_merge_multi.hip", "ct_merge_exact.hip", "ct_linearize.hip", "ct_pairs.hip", "ct_flatfield.hip", "ct_stats.hip", "ct_stats_multi.hip", "ct_darkfield.hip", "ct_merge_dark.hip", "ct_merge_dark_multi.hip", "ct_merge_dark_ingest.hip", "ct_merge_dark_ingest_packed.hip", "ct_linearize_dark.hip", "ct_linearize_dark_ingest.hip", "ct_bandstats.hip",
            "ct_downscale.hip", "ct_export.hip", "ct_ingest.hip", "ct_extrema.hip", "ct_linearize_ingest.hip", "ct_linearize_ingest_strided.hip", "ct_merge_ingest.hip", "ct_merge_ingest_multi.hip", "ct_merge_ingest_strided.hip", "ct_stats_ingest.hip", "ct_stats_ingest_multi.hip", "ct_pairs_ingest.hip",
            "ct_api.cpp"]
-HEADERS = ["ct_device.hpp", "ct_args.hpp", "ct_dark_window.hpp", "ct_merge.hpp", "ct_merge_pivot.hpp", "ct_ingest_stages.hpp", "ct_merge_ingest.hpp", "ct_merge_ingest_kernel.hpp", "ct_merge_dark_kernel.hpp", "ct_merge_dark_ingest_kernel.hpp", "ct_stats_merge.hpp", "ct_stats_kernel.hpp", "ct_pairs_kernel.hpp", "ct_linearize_ingest.hpp", os.path.join("..", "..", "include", "clair_hip.h")]
+HEADERS = ["ct_device.hpp", "ct_args.hpp", "ct_dark_window.hpp", "ct_merge.hpp", "ct_merge_pivot.hpp", "ct_ingest_stages.hpp", "ct_merge_ingest.hpp", "ct_merge_ingest_kernel.hpp", "ct_merge_dark_kernel.hpp", "ct_merge_dark_ingest_kernel.hpp", "ct_stats_merge.hpp", "ct_stats_kernel.hpp", "ct_pairs_kernel.hpp", "ct_linearize_ingest.hpp", "ct_linearize_dark_launch.hpp", os.path.join("..", "..", "include", "clair_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fno-slp-vectorize", "-Wall", "-Wno-unused-function", "-Wno-pass-failed"]
 

@@ -15,23 +15,16 @@
 // the linearization: a uint16 frame with derived uncertainties costs 18 B per sample where the pair moves 34, and the two
 // float32 stacks of a group never exist.  (Byte counts from the shapes; see profiles/linearize_dark.md for what was timed.)
 //
-// Ownership: a workgroup row (blockIdx.y) is one (frame, channel) plane, so the frame -- its dark field pointers, which
-// travel in the argument block: at most CT_LINEARIZE_DARK_MAX_FRAMES frames per launch -- and the channel are wave-uniform.
-// A thread owns 4 consecutive columns of ONE image row: 3 x (1 + 4 + 1) window loads (the column left of the group or the
-// reflected one, the group, the column right of it).  What is left of a row whose width is no multiple of 4 goes through the
-// same code one element after the other.  A workgroup walks kLdSlots groups per thread, a workgroup apart, so one staging of
-// the LUT (stage_lut) serves kLdSlots * 1024 elements.  Outputs are one packet where the group is 16-byte aligned in memory
-// (li_store), else elements.  No atomics, no LDS tile; the frames and the dark fields are read only.  No row bands: the
-// generator that calls this has no tile=, so no halo is built here.
-#include <algorithm>
-#include "ct_dark_window.hpp"
-#include "ct_linearize_ingest.hpp"
+// Ownership: the walk of ct_linearize_dark_launch.hpp with one (frame, channel) plane per workgroup row.  A thread's 4
+// columns cost 3 x (1 + 4 + 1) window loads (the column left of the group or the reflected one, the group, the column right
+// of it).  The frames and the dark fields are read only.
+#include "ct_linearize_dark_launch.hpp"
 
 namespace ct {
 
 struct LinDarkArgs {
     const void *frames;      // (F, C, H, W) T, image_stride between frames
-    const float *std_stack;  // explicit sigma of the raw image, laid out like the frames, or NULL
+    const float *std_in;     // explicit sigma of the raw image, laid out like the frames, or NULL
     const float *lut;
     float *lin_out;          // (F, C, H, W) dense
     float *std_out;
@@ -47,9 +40,6 @@ struct LinDarkArgs {
     float k0, k1;            // the two distinct taps of the normalised 1-D kernel: k0 (centre), k1 (sides)
 };
 
-constexpr int kLdGroup = kLiGroup;  // columns per thread
-constexpr int kLdSlots = 4;         // groups per thread
-
 // xb and sigma_eff of columns w0 .. w0 + G - 1 of row h of plane c0 of the frame at `frame` (its dark field: dark, dark_std;
 // its explicit sigma: sigma or NULL): the window of ct_dark_window.hpp for one frame that is the whole image (no halo).
 template <typename T, int G>
@@ -64,9 +54,6 @@ __device__ __forceinline__ void ld_blur(const LinDarkArgs &a, const T *frame, co
     dark_blur<T, G, true>(a, raw, explicit_sigma, xb, sig);
 }
 
-// groups of kLdGroup columns in a row, the last one possibly short
-static inline __host__ __device__ uint32_t ld_groups_per_row(uint32_t width) { return (width + kLdGroup - 1) / kLdGroup; }
-
 template <typename T, int INTERP>
 __global__ __launch_bounds__(kBlock) void linearize_dark_kernel(const LinDarkArgs a)
 {
@@ -76,7 +63,7 @@ __global__ __launch_bounds__(kBlock) void linearize_dark_kernel(const LinDarkArg
     __syncthreads();
     const uint32_t f = blockIdx.y / a.channels, c0 = blockIdx.y - f * a.channels;  // frame of this launch, channel
     const T *frame = static_cast<const T *>(a.frames) + (int64_t)f * a.image_stride;
-    const float *sigma = a.std_stack ? a.std_stack + (int64_t)f * a.image_stride : nullptr;
+    const float *sigma = a.std_in ? a.std_in + (int64_t)f * a.image_stride : nullptr;
     const float *dark = a.dark[f], *dark_std = a.dark_std[f];
     const int64_t out0 = (int64_t)f * C * a.plane;  // the frame inside the dense outputs
     const uint32_t W = a.width;
@@ -110,24 +97,6 @@ __global__ __launch_bounds__(kBlock) void linearize_dark_kernel(const LinDarkArg
     }
 }
 
-template <typename T, int INTERP>
-static int ld_launch(const LinDarkArgs &a, int n_frames, hipStream_t s)
-{
-    const size_t lds = lut_lds_bytes(INTERP, (int)a.channels, (int)a.n_points);
-    const uint64_t slots = (uint64_t)ld_groups_per_row(a.width) * a.h_tile;
-    const uint64_t per_block = (uint64_t)kBlock * kLdSlots;
-    const dim3 grid((uint32_t)((slots + per_block - 1) / per_block), (uint32_t)n_frames * a.channels);
-    hipLaunchKernelGGL((linearize_dark_kernel<T, INTERP>), grid, dim3(kBlock), lds, s, a);
-    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
-}
-
-template <typename T>
-static int ld_dispatch(const LinDarkArgs &a, int interp, int n_frames, hipStream_t s)
-{
-    // (LOOKUP has no gradient path: refused by the entry point, no kernel)
-    return with_enum<CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) { return ld_launch<T, I>(a, n_frames, s); });
-}
-
 }  // namespace ct
 
 extern "C" int ct_linearize_dark(const void *frames_dev, int32_t dtype, float max_code, int64_t n_frames, const ct_geometry *geom,
@@ -136,15 +105,8 @@ extern "C" int ct_linearize_dark(const void *frames_dev, int32_t dtype, float ma
                                  float *lin_out_dev, float *std_out_dev, void *stream)
 {
     using namespace ct;
-    // ---- what ct_dark_field_blur refuses for each frame as a batch of one, in its order (ct_darkfield.hip) ----
-    if (!frames_dev || !geom || !dark_devs || !dark_std_devs || !lin_out_dev || !std_out_dev || n_frames <= 0 || n_frames > 0x7fffffff)
-        return CT_ERR_INVALID_ARGUMENT;
-    for (int64_t k = 0; k < n_frames; ++k)
-        if (!dark_devs[k] || !dark_std_devs[k]) return CT_ERR_INVALID_ARGUMENT;
-    if (int rc = check_dark_frames(geom, 1, 1, true, std_mode, std_dev)) return rc;
-    // a row band would need the rows above and below it; the streamed generator has no tile=, so no halo is built here
-    if (geom->row_offset != 0 || geom->h_tile != geom->h_global) return CT_ERR_UNSUPPORTED;
-    if (int rc = check_dark_band(geom, nullptr)) return rc;  // (the whole image: what is left of it is the stride)
+    if (!ld_pointers_present(frames_dev, geom, dark_devs, dark_std_devs, lin_out_dev, std_out_dev, n_frames)) return CT_ERR_INVALID_ARGUMENT;
+    if (int rc = ld_check_geometry(geom, std_mode, std_dev)) return rc;
     NormConst norm;
     if (norm_for_dtype(dtype, max_code, &norm) != CT_OK) return CT_ERR_UNSUPPORTED;
     // ---- what ct_linearize_std refuses for (xb, sigma_eff): float32 pixels with explicit uncertainties ----
@@ -155,44 +117,20 @@ extern "C" int ct_linearize_dark(const void *frames_dev, int32_t dtype, float ma
     if (!global_below_2_31(geom)) return CT_ERR_TOO_LARGE;
     const int n_points = icrf_points(icrf);
     if (lut_lds_bytes(interp, geom->channels, n_points) > kLdsBudget) return CT_ERR_TOO_LARGE;
-    // frames per launch: what the argument block holds, and a grid's y extent (65535) in (frame, channel) planes
-    const int64_t per_launch = std::min<int64_t>(CT_LINEARIZE_DARK_MAX_FRAMES, (int64_t)kLiMaxRows / geom->channels);
+    const int64_t per_launch = ld_frames_per_launch(geom->channels);  // a workgroup row is one (frame, channel) plane
     if (per_launch < 1) return CT_ERR_TOO_LARGE;
-    const size_t elem = dtype_bytes(dtype);
-    if (!aligned(frames_dev, elem) || !aligned(std_dev, sizeof(float)) || !aligned(lin_out_dev, sizeof(float)) ||
-        !aligned(std_out_dev, sizeof(float)))
+    if (!aligned(frames_dev, dtype_bytes(dtype)) || !aligned(std_dev, sizeof(float)) || !aligned(lin_out_dev, sizeof(float)) ||
+        !aligned(std_out_dev, sizeof(float)) || !ld_darks_aligned(dark_devs, dark_std_devs, n_frames))
         return CT_ERR_INVALID_ARGUMENT;
-    for (int64_t k = 0; k < n_frames; ++k)
-        if (!aligned(dark_devs[k], sizeof(float)) || !aligned(dark_std_devs[k], sizeof(float))) return CT_ERR_INVALID_ARGUMENT;
 
-    const int64_t plane = geom->h_tile * geom->width;
     LinDarkArgs a{};
-    a.lut = icrf->lut_dev;
-    a.image_stride = geom->image_stride;
-    a.plane = (uint32_t)plane;
-    a.width = (uint32_t)geom->width;
-    a.h_tile = (uint32_t)geom->h_tile;
-    a.channels = (uint32_t)geom->channels;
-    a.n_points = (uint32_t)n_points;
-    fill_blur_args(a, norm, std_mode, std_value, threshold, alpha);
+    ld_fill_args(a, icrf, geom, n_points, norm, std_mode, std_value, threshold, alpha);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    for (int64_t first = 0; first < n_frames; first += per_launch) {
-        const int nf = (int)std::min<int64_t>(per_launch, n_frames - first);
-        a.frames = static_cast<const char *>(frames_dev) + first * geom->image_stride * (int64_t)elem;
-        a.std_stack = std_mode == CT_STD_EXPLICIT ? std_dev + first * geom->image_stride : nullptr;
-        a.lin_out = lin_out_dev + first * geom->channels * plane;
-        a.std_out = std_out_dev + first * geom->channels * plane;
-        for (int k = 0; k < nf; ++k) {
-            a.dark[k] = dark_devs[first + k];
-            a.dark_std[k] = dark_std_devs[first + k];
-        }
-        int rc;
-        switch (dtype) {
-            case CT_DTYPE_U8: rc = ld_dispatch<uint8_t>(a, interp, nf, s); break;
-            case CT_DTYPE_U16: rc = ld_dispatch<uint16_t>(a, interp, nf, s); break;
-            default: rc = ld_dispatch<float>(a, interp, nf, s); break;
-        }
-        if (rc != CT_OK) return rc;
-    }
-    return CT_OK;
+    // the explicit sigma is laid out like the frames.  (LOOKUP: refused above, no kernel)
+    return ld_launch_frames(a, frames_dev, dtype, std_mode == CT_STD_EXPLICIT ? std_dev : nullptr, geom->image_stride, lin_out_dev,
+                            std_out_dev, dark_devs, dark_std_devs, n_frames, per_launch, [&](auto t, LinDarkArgs &b, int64_t, int nf) {
+                                return with_enum<CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
+                                    return ld_launch(linearize_dark_kernel<decltype(t), I>, b, I, (uint32_t)nf * b.channels, s);
+                                });
+                            });
 }

@@ -13,11 +13,10 @@
 // where the three launches move 2 + 4, then 4 + 8 + 8, then 8 + 8 = 42 (46), and the three float32 stacks of a group never
 // exist.  (Byte counts from the shapes; what was timed: profiles/linearize_dark_ingest.md.)
 //
-// Ownership.  At most CT_LINEARIZE_DARK_MAX_FRAMES frames per launch: their dark-field pointers travel in the argument block,
-// like the stage list; the stage loop is wave-uniform.
-// PLANAR (CT_LAYOUT_NCHW, any C): the walk of linearize_dark_kernel (ct_linearize_dark.hip).  A workgroup row (blockIdx.y) is
-//   one (frame, channel) plane, so the clamp pair is wave-uniform; a thread owns 4 consecutive columns of ONE image row,
-//   3 x (1 + 4 + 1) window loads; the end of a row whose width is no multiple of 4 goes one element after the other.
+// Ownership: the slot walk of ct_linearize_dark_launch.hpp.  The stage list travels in the argument block like the frames'
+// dark-field pointers; the stage loop is wave-uniform.
+// PLANAR (CT_LAYOUT_NCHW, any C): a workgroup row (blockIdx.y) is one (frame, channel) plane, so the clamp pair is
+//   wave-uniform; 3 x (1 + 4 + 1) window loads per thread.
 // PACKED3 (CT_LAYOUT_NHWC / NHWC_BGR, raw (F, H, W, 3) frames): a workgroup row is one frame.  A thread owns 4 consecutive
 //   PIXELS of one image row with all 3 channels: on each of the three rows the 12 contiguous elements of its pixels and the
 //   3 of the pixel left and of the pixel right of them (or the reflected ones) -- neighbours of a sample lie 3 elements apart
@@ -26,10 +25,8 @@
 //   interleaved walk built: three stride-3 walks, one per plane, would read every frame three times through the caches and
 //   were neither built nor timed.
 // The dark field, its std and explicit image uncertainties are planar (C, H, W) float32 in plane (RGB) order whatever the
-// layout of the frames.  A workgroup walks kLdiSlots groups per thread, a workgroup apart, so one staging of the LUT
-// (stage_lut) serves kLdiSlots * 1024 samples per plane.  Outputs are one packet where the group is 16-byte aligned in
-// memory (li_store), else elements.  No atomics, no LDS tile; frames, dark fields and uncertainties are read only.  No row
-// bands (no halo is built here), no LOOKUP (no gradient path: refused, no kernel).
+// layout of the frames; frames, dark fields and uncertainties are read only.  No LOOKUP (no gradient path: refused, no
+// kernel).
 //
 // ct_linearize_dark_ingest_data: the chain may hold one CT_INGEST_AFFINE_DATA stage -- a data-dependent Normalize -- whose sub
 // and div are PER FRAME: consts[4 f], consts[4 f + 1] as ct_ingest_extrema_frames left them and as ct_linearize_ingest_data reads
@@ -48,9 +45,7 @@
 // Measured on 16 x 3 x 1080 x 1920 (profiles/linearize_dark_ingest.md): 0.55 to 0.63 of the time of the three launches, 2.8 to
 // 3.5 TB/s of the bytes counted above; the packed3 walk's occupancy is the first thing to look at for more.  DATA, with the
 // extrema pass in front (profiles/linearize_dark_ingest_data.md): 0.48 to 0.55 of the time of the four launches, 3.1 to 3.8 TB/s.
-#include <algorithm>
-#include "ct_dark_window.hpp"
-#include "ct_linearize_ingest.hpp"
+#include "ct_linearize_dark_launch.hpp"
 
 namespace ct {
 
@@ -84,11 +79,6 @@ struct LinDarkIngestDataArgs : LinDarkIngestArgs {
 };
 template <bool DATA>
 using ldi_args_t = std::conditional_t<DATA, LinDarkIngestDataArgs, LinDarkIngestArgs>;
-
-constexpr int kLdiGroup = kLiGroup;  // columns / pixels per thread
-constexpr int kLdiSlots = 4;         // groups per thread
-
-static inline __host__ __device__ uint32_t ldi_groups_per_row(uint32_t width) { return (width + kLdiGroup - 1) / kLdiGroup; }
 
 // PLANAR: xb and sigma_eff of columns w0 .. w0 + G - 1 of row h of plane c0 of the frame at `frame` (its dark field: dark,
 // dark_std; its explicit sigma: sigma or NULL, planar like the dark field)
@@ -133,24 +123,24 @@ __global__ __launch_bounds__(kBlock) void linearize_dark_ingest_planar_kernel(co
         ddiv = a.consts[4 * (int64_t)f + 1];
     }
     const uint32_t W = a.width;
-    const uint32_t gpr = ldi_groups_per_row(W);
+    const uint32_t gpr = ld_groups_per_row(W);
     const uint64_t n_slots = (uint64_t)gpr * a.h_tile;
 #pragma unroll 1
-    for (int k = 0; k < kLdiSlots; ++k) {
-        const uint64_t slot = ((uint64_t)blockIdx.x * kLdiSlots + k) * kBlock + threadIdx.x;
+    for (int k = 0; k < kLdSlots; ++k) {
+        const uint64_t slot = ((uint64_t)blockIdx.x * kLdSlots + k) * kBlock + threadIdx.x;
         if (slot >= n_slots) break;
         const uint32_t h = (uint32_t)(slot / gpr);
-        const uint32_t w0 = ((uint32_t)slot - h * gpr) * kLdiGroup;
-        float xb[kLdiGroup] = {0.0f, 0.0f, 0.0f, 0.0f}, sig[kLdiGroup] = {0.0f, 0.0f, 0.0f, 0.0f};
-        int n = kLdiGroup;
-        if (W - w0 >= (uint32_t)kLdiGroup) {
-            ldi_planar<T, kLdiGroup, DATA>(a, frame, sigma, dark, dark_std, c0, h, w0, dsub, ddiv, xb, sig);
+        const uint32_t w0 = ((uint32_t)slot - h * gpr) * kLdGroup;
+        float xb[kLdGroup] = {0.0f, 0.0f, 0.0f, 0.0f}, sig[kLdGroup] = {0.0f, 0.0f, 0.0f, 0.0f};
+        int n = kLdGroup;
+        if (W - w0 >= (uint32_t)kLdGroup) {
+            ldi_planar<T, kLdGroup, DATA>(a, frame, sigma, dark, dark_std, c0, h, w0, dsub, ddiv, xb, sig);
         } else {
-            // the end of a row whose width is no multiple of the group (at most kLdiGroup - 1 elements): one lane, one element
+            // the end of a row whose width is no multiple of the group (at most kLdGroup - 1 elements): one lane, one element
             // after the other, each with its own window
             n = (int)(W - w0);
 #pragma unroll
-            for (int e = 0; e < kLdiGroup - 1; ++e)
+            for (int e = 0; e < kLdGroup - 1; ++e)
                 if (e < n) ldi_planar<T, 1, DATA>(a, frame, sigma, dark, dark_std, c0, h, w0 + e, dsub, ddiv, &xb[e], &sig[e]);
         }
         // the frame is batch element 0 of its own batch: the LINEAR / CATMULL row is the flat (C, H, W) index modulo C
@@ -168,7 +158,7 @@ __global__ __launch_bounds__(kBlock) void linearize_dark_ingest_planar_kernel(co
 template <typename T, int G, int E0, bool DATA>
 __device__ __forceinline__ void ldi_packed3(const LinDarkIngestArgs &a, const T *frame, const float *sigma, const float *dark,
                                             const float *dark_std, uint32_t h, uint32_t w0, float dsub, float ddiv,
-                                            float (&xb)[3][kLdiGroup], float (&sig)[3][kLdiGroup])
+                                            float (&xb)[3][kLdGroup], float (&sig)[3][kLdGroup])
 {
     constexpr int C = 3, N = G + 2;
     const uint32_t W = a.width, H = a.h_tile;
@@ -223,18 +213,18 @@ __global__ __launch_bounds__(kBlock) void linearize_dark_ingest_packed3_kernel(c
         ddiv = a.consts[4 * (int64_t)f + 1];
     }
     const uint32_t W = a.width;
-    const uint32_t gpr = ldi_groups_per_row(W);
+    const uint32_t gpr = ld_groups_per_row(W);
     const uint64_t n_slots = (uint64_t)gpr * a.h_tile;
 #pragma unroll 1
-    for (int k = 0; k < kLdiSlots; ++k) {
-        const uint64_t slot = ((uint64_t)blockIdx.x * kLdiSlots + k) * kBlock + threadIdx.x;
+    for (int k = 0; k < kLdSlots; ++k) {
+        const uint64_t slot = ((uint64_t)blockIdx.x * kLdSlots + k) * kBlock + threadIdx.x;
         if (slot >= n_slots) break;
         const uint32_t h = (uint32_t)(slot / gpr);
-        const uint32_t w0 = ((uint32_t)slot - h * gpr) * kLdiGroup;
-        float xb[C][kLdiGroup] = {}, sig[C][kLdiGroup] = {};
-        int n = kLdiGroup;
-        if (W - w0 >= (uint32_t)kLdiGroup) {
-            ldi_packed3<T, kLdiGroup, 0, DATA>(a, frame, sigma, dark, dark_std, h, w0, dsub, ddiv, xb, sig);
+        const uint32_t w0 = ((uint32_t)slot - h * gpr) * kLdGroup;
+        float xb[C][kLdGroup] = {}, sig[C][kLdGroup] = {};
+        int n = kLdGroup;
+        if (W - w0 >= (uint32_t)kLdGroup) {
+            ldi_packed3<T, kLdGroup, 0, DATA>(a, frame, sigma, dark, dark_std, h, w0, dsub, ddiv, xb, sig);
         } else {
             // the end of a row whose width is no multiple of the group (1 to 3 pixels): one pixel after the other
             n = (int)(W - w0);
@@ -257,24 +247,8 @@ __global__ __launch_bounds__(kBlock) void linearize_dark_ingest_packed3_kernel(c
 template <typename T, int INTERP, bool DATA>
 static int ldi_launch(const ldi_args_t<DATA> &a, bool packed, int n_frames, hipStream_t s)
 {
-    const size_t lds = lut_lds_bytes(INTERP, (int)a.channels, (int)a.n_points);
-    const uint64_t slots = (uint64_t)ldi_groups_per_row(a.width) * a.h_tile;
-    const uint64_t per_block = (uint64_t)kBlock * kLdiSlots;
-    const dim3 grid((uint32_t)((slots + per_block - 1) / per_block), (uint32_t)n_frames * (packed ? 1u : a.channels));
-    if (packed)
-        hipLaunchKernelGGL((linearize_dark_ingest_packed3_kernel<T, INTERP, DATA>), grid, dim3(kBlock), lds, s, a);
-    else
-        hipLaunchKernelGGL((linearize_dark_ingest_planar_kernel<T, INTERP, DATA>), grid, dim3(kBlock), lds, s, a);
-    return hipGetLastError() == hipSuccess ? CT_OK : CT_ERR_LAUNCH;
-}
-
-template <typename T>
-static int ldi_dispatch(const LinDarkIngestDataArgs &a, bool packed, int interp, int n_frames, hipStream_t s)
-{
-    // (LOOKUP has no gradient path: refused by the entry point, no kernel).  a.consts: the DATA instantiations
-    return with_enum<CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
-        return a.consts ? ldi_launch<T, I, true>(a, packed, n_frames, s) : ldi_launch<T, I, false>(a, packed, n_frames, s);
-    });
+    if (packed) return ld_launch(linearize_dark_ingest_packed3_kernel<T, INTERP, DATA>, a, INTERP, (uint32_t)n_frames, s);
+    return ld_launch(linearize_dark_ingest_planar_kernel<T, INTERP, DATA>, a, INTERP, (uint32_t)n_frames * a.channels, s);
 }
 
 // consts_dev NULL: the constant chains of ct_linearize_dark_ingest (no AFFINE_DATA stage); else ct_linearize_dark_ingest_data
@@ -284,16 +258,11 @@ static int linearize_dark_ingest(const void *frames_dev, int32_t dtype, int64_t 
                                  const ct_icrf *icrf, float *lin_out_dev, float *std_out_dev, const float *consts_dev, void *stream)
 {
     // ---- what ct_linearize_dark refuses first: pointers, the frame count, a dark field per frame ----
-    if (!frames_dev || !geom || !dark_devs || !dark_std_devs || !lin_out_dev || !std_out_dev || n_frames <= 0 || n_frames > 0x7fffffff)
-        return CT_ERR_INVALID_ARGUMENT;
-    for (int64_t k = 0; k < n_frames; ++k)
-        if (!dark_devs[k] || !dark_std_devs[k]) return CT_ERR_INVALID_ARGUMENT;
+    if (!ld_pointers_present(frames_dev, geom, dark_devs, dark_std_devs, lin_out_dev, std_out_dev, n_frames)) return CT_ERR_INVALID_ARGUMENT;
     // ---- the dark geometry, of the planar image the chain yields (the layout of the raw frames is the stage list's matter) ----
     ct_geometry planar = *geom;
     planar.layout = CT_LAYOUT_NCHW;
-    if (int rc = check_dark_frames(&planar, 1, 1, true, std_mode, std_dev)) return rc;
-    if (geom->row_offset != 0 || geom->h_tile != geom->h_global) return CT_ERR_UNSUPPORTED;  // a row band: no halo is built here
-    if (int rc = check_dark_band(&planar, nullptr)) return rc;  // (the whole image: what is left of it is the stride)
+    if (int rc = ld_check_geometry(&planar, std_mode, std_dev)) return rc;
     // ---- the stack and the stage list: one AFFINE_DATA stage at most, and only with constants (li_check_call's rule) ----
     bool by_channel = false;
     if (int rc = ingest_validate(dtype, geom->layout, n_frames, geom->channels, geom->h_tile * geom->width, stages, n_stages,
@@ -311,49 +280,29 @@ static int linearize_dark_ingest(const void *frames_dev, int32_t dtype, int64_t 
     if (lut_lds_bytes(interp, geom->channels, n_points) > kLdsBudget) return CT_ERR_TOO_LARGE;
     if (!global_below_2_31(geom)) return CT_ERR_TOO_LARGE;
     const bool packed = geom->layout != CT_LAYOUT_NCHW;
-    // frames per launch: what the argument block holds, and a grid's y extent (65535) in workgroup rows
-    const int64_t per_launch = std::min<int64_t>(CT_LINEARIZE_DARK_MAX_FRAMES, (int64_t)kLiMaxRows / (packed ? 1 : geom->channels));
+    const int64_t per_launch = ld_frames_per_launch(packed ? 1 : geom->channels);  // a workgroup row: a frame, or one of its planes
     if (per_launch < 1) return CT_ERR_TOO_LARGE;
-    if (!li_pointers_ok(frames_dev, dtype, std_dev, lin_out_dev, std_out_dev)) return CT_ERR_INVALID_ARGUMENT;
-    for (int64_t k = 0; k < n_frames; ++k)
-        if (!aligned(dark_devs[k], sizeof(float)) || !aligned(dark_std_devs[k], sizeof(float))) return CT_ERR_INVALID_ARGUMENT;
+    if (!li_pointers_ok(frames_dev, dtype, std_dev, lin_out_dev, std_out_dev) || !ld_darks_aligned(dark_devs, dark_std_devs, n_frames))
+        return CT_ERR_INVALID_ARGUMENT;
 
-    const int64_t plane = geom->h_tile * geom->width;
-    const size_t elem = dtype_bytes(dtype);
     LinDarkIngestDataArgs a{};
-    a.lut = icrf->lut_dev;
-    a.image_stride = geom->image_stride;
-    a.plane = (uint32_t)plane;
-    a.width = (uint32_t)geom->width;
-    a.h_tile = (uint32_t)geom->h_tile;
-    a.channels = (uint32_t)geom->channels;
-    a.n_points = (uint32_t)n_points;
+    ld_fill_args(a, icrf, geom, n_points, NormConst{1.0f, 0.0f}, std_mode, std_value, threshold, alpha);
     a.reversed = geom->layout == CT_LAYOUT_NHWC_BGR ? 1u : 0u;
     a.by_channel = by_channel ? 1u : 0u;
     a.n_stages = (uint32_t)n_stages;
     for (int32_t k = 0; k < n_stages; ++k) a.stage[k] = stages[k];
-    fill_blur_args(a, NormConst{1.0f, 0.0f}, std_mode, std_value, threshold, alpha);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    for (int64_t first = 0; first < n_frames; first += per_launch) {
-        const int nf = (int)std::min<int64_t>(per_launch, n_frames - first);
-        a.frames = static_cast<const char *>(frames_dev) + first * geom->image_stride * (int64_t)elem;
-        a.std_in = std_mode == CT_STD_EXPLICIT ? std_dev + first * geom->channels * plane : nullptr;
-        a.lin_out = lin_out_dev + first * geom->channels * plane;
-        a.std_out = std_out_dev + first * geom->channels * plane;
-        a.consts = data ? consts_dev + 4 * first : nullptr;
-        for (int k = 0; k < nf; ++k) {
-            a.dark[k] = dark_devs[first + k];
-            a.dark_std[k] = dark_std_devs[first + k];
-        }
-        int rc;
-        switch (dtype) {
-            case CT_DTYPE_U8: rc = ldi_dispatch<uint8_t>(a, packed, interp, nf, s); break;
-            case CT_DTYPE_U16: rc = ldi_dispatch<uint16_t>(a, packed, interp, nf, s); break;
-            default: rc = ldi_dispatch<float>(a, packed, interp, nf, s); break;
-        }
-        if (rc != CT_OK) return rc;
-    }
-    return CT_OK;
+    // the explicit sigma is dense and planar, like the outputs.  (LOOKUP: refused above, no kernel).  b.consts: the DATA
+    // instantiations, with the launch's rows of the constants
+    return ld_launch_frames(a, frames_dev, dtype, std_mode == CT_STD_EXPLICIT ? std_dev : nullptr, geom->channels * (int64_t)a.plane,
+                            lin_out_dev, std_out_dev, dark_devs, dark_std_devs, n_frames, per_launch,
+                            [&](auto t, LinDarkIngestDataArgs &b, int64_t first, int nf) {
+                                using T = decltype(t);
+                                b.consts = data ? consts_dev + 4 * first : nullptr;
+                                return with_enum<CT_INTERP_LINEAR, CT_INTERP_CATMULL, CT_INTERP_NONE>(interp, [&](auto I) {
+                                    return b.consts ? ldi_launch<T, I, true>(b, packed, nf, s) : ldi_launch<T, I, false>(b, packed, nf, s);
+                                });
+                            });
 }
 
 }  // namespace ct
